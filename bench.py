@@ -10,7 +10,8 @@ out as `--layout` says: auto = wave-striped slots (C ABI 8) for rANS / tANS batc
 the same streams at the same logical bit positions either way (`config.slot_layout` names what ran).
 value = (bytes of all ranks * steps) / wall time of the timed region / 1e6, i.e. N / (t_enc + t_dec).
 
-    python bench.py                      # 1 GPU, finishes in a few minutes incl. the CPU baselines and other_configs
+    python bench.py --gpus 1 --steps K --warmup W    # the headline alone: set-up, warm-up, K timed steps, one line
+    python bench.py --full                           # + everything else below; finishes in a few minutes
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -27,11 +28,18 @@ no data-path collective); the only communication is the barrier / max-reduction 
 `--gather` additionally times the optional final gather of the compacted streams to rank 0
 (BASELINE.json configs[4]) and reports it separately; it never enters `value`.
 
-The ONE line printed is the COMPACT contract line (< 6 KB: the contract keys, roofline{,_encode,_decode,_dense}, both CPU
-baselines, `summary` last -- round 5's 21.6 KB line left the driver's record unparsed); the full record goes to
-gpurun_out/bench_full.json (`--full-json`), `--full-line` prints it instead.
+A plain run does only what the headline figure needs: it sets up, warms up, times the steps, checks their round trip,
+writes their outputs if `--dump-outputs DIR` is given (a fixed sample where the batch is larger than 64 MB allows) and
+prints the line.  `--full` adds everything else: both CPU baselines, the decode kernel behind another decode, the
+compaction and the pipelined dense encode (`value_dense`, `roofline_dense`), rank 0's solo run of a multi-GPU line
+(`scaling_efficiency`), the configurations and the file path below, and the full record.
 
-The default 1-GPU run (no workload flags) also measures BASELINE.json's other single-GPU configurations and attaches them
+The ONE line printed is the COMPACT contract line (< 6 KB: the contract keys, roofline{,_encode,_decode,_dense}, both CPU
+baselines, `summary` last -- round 5's 21.6 KB line left the driver's record unparsed; what a run did not measure is
+null); with `--full` the full record goes to the file `--full-json` names (a default under the repository root
+otherwise), and `--full-line` prints it instead of the compact line.
+
+The `--full` 1-GPU run (no workload flags) also measures BASELINE.json's other single-GPU configurations and attaches them
 as `other_configs` to the full record (their numbers ride in the line's `summary`): configs[1] at its literal size (65 536 chunks), configs[2] (range coder, 1 GiB
 of uniform bytes), configs[3] (order-1 adaptive arithmetic coder on a Markov-1 source: K = 16 at 1 GiB, K = 256 at 256 MiB)
 -- each with kernel times, `roofline` (frac + PMC traffic where a stamped pass exists) and both CPU baselines.
@@ -100,6 +108,15 @@ def parse_args(argv=None):
                     help="slot layout of the rANS / tANS batches: wave-striped slots (ABI 8: four waves per SIMD in the "
                          "encoder, row-by-row stores) for batches that fill the chip, linear slots otherwise (auto); the "
                          "other coders have linear slots only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: both CPU baselines, the decode "
+                         "behind a decode, the compaction and the pipelined dense encode (value_dense, roofline_dense), the "
+                         "other BASELINE configurations, the file path, the solo-rank run of a multi-GPU line, and the full "
+                         "record (--full-json); a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (encoded streams, lengths, offsets, "
+                         "statuses; decoded symbols) as DIR/<name>.npy in float32 / float64, a fixed sample of chunks where "
+                         "the batch is larger than 64 MB allows (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dense-pipeline", action="store_true",
                     help="skip the two-sub-batch pipelined dense encode (roofline_dense.pipelined_ms): it launches the encode "
@@ -414,6 +431,59 @@ def linear_slots(enc, n):
     return torch.cat([body[: n * enc.stride], body.new_zeros(16)])
 
 
+DUMP_SCALARS_BYTES = 24 << 20  # --dump-outputs: per-chunk figures (7 float64 per chunk, the chunk index included)
+DUMP_ROWS_BYTES = 36 << 20     # --dump-outputs: stream bytes + decoded symbols of the sampled chunks (float32)
+
+
+def dump_outputs(path, enc, dec_out, chunk_len):
+    """--dump-outputs: what a caller of the timed step receives from its last step, as path/<name>.npy (64 MB at most).
+    Per chunk (all chunks, or a fixed sample of them when more than DUMP_SCALARS_BYTES would be needed): stream length,
+    bit offset and status of the encode; length, bits consumed and status of the decode.  For a fixed sample of at most
+    1024 chunks: the stream bytes (left-aligned, zero past the stream: the same bytes in either slot layout) and the decoded
+    symbols.  The samples depend on the batch shape only (seed 0), so two builds can be compared file by file."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    n, stride, dev = enc.n_chunks, enc.stride, enc.nbits.device
+    dec_sym, dec_lens, dec_used, dec_status = dec_out
+    rng = np.random.default_rng(0)
+    n_scalar = min(n, DUMP_SCALARS_BYTES // (7 * 8))
+    chunks = np.arange(n) if n_scalar == n else np.sort(rng.choice(n, n_scalar, replace=False))
+    n_rows = max(1, min(n, 1024, DUMP_ROWS_BYTES // (4 * (stride + chunk_len))))
+    rows = np.sort(rng.choice(n, n_rows, replace=False))
+    cols = max(stride, chunk_len)
+    if 4 * n_rows * (stride + chunk_len) > DUMP_ROWS_BYTES:  # one chunk of several MB: its first `cols` bytes and symbols
+        cols = DUMP_ROWS_BYTES // (8 * n_rows)
+
+    out = {"chunk_index": chunks, "sample_index": rows}
+    ci = torch.from_numpy(chunks).to(dev)
+    for name, t in (("encoded_nbits", enc.nbits), ("encoded_bit_offset", enc.bit_offset), ("encoded_status", enc.status),
+                    ("decoded_lens", dec_lens), ("decoded_bits_used", dec_used), ("decoded_status", dec_status)):
+        out[name] = t[ci].cpu().numpy()
+
+    # stream bytes of the sampled chunks: stride + 1 bytes from the byte that holds the first bit (logical positions;
+    # EncodedBatch gives the striped permutation), then the nbits bits from the stream's bit phase
+    ri = torch.from_numpy(rows).to(dev)
+    bo = enc.bit_offset[ri]
+    pos = (bo // 8)[:, None] + torch.arange(stride + 1, dtype=torch.int64, device=dev)[None, :]
+    if enc.layout == "striped":
+        c, b = pos // stride, pos % stride
+        pos = (c // 64) * 64 * stride + (b // 16) * 1024 + 16 * (c % 64) + b % 16
+    raw = enc.data[pos.clamp_(max=enc.data.numel() - 1)].cpu().numpy()
+    phase, nbits = (bo % 8).cpu().numpy(), enc.nbits[ri].cpu().numpy().astype(np.int64)
+    assert (nbits >= 0).all() and (nbits <= 8 * stride).all(), "a stream longer than its slot"
+    streams = np.zeros((n_rows, stride), dtype=np.uint8)
+    for i in range(n_rows):
+        s = np.packbits(np.unpackbits(raw[i])[phase[i]:phase[i] + nbits[i]])
+        streams[i, :s.size] = s
+    out["encoded_stream_bytes"] = streams[:, :cols]
+    out["decoded_symbols"] = dec_sym[ri, :min(chunk_len, cols)].cpu().numpy()
+
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.ndim == 2 else np.float64))
+
+
 def rocprof_kernel_names(w, model, layout="linear"):
     """the names rocprofv3 prints for the two kernels of the timed step, from the library itself (C ABI 6:
     scl_rans_kernel_names / scl_tans_kernel_names report the instantiation the launch code picks for this model and batch
@@ -526,8 +596,9 @@ def payload_checksum(t):
     return [int(n), int(wds.sum().item()), int((wds * idx).sum().item())]
 
 
-def measure(w, D, wd, steps, warmup, min_warm_ms, with_cpu, with_restatement, with_dense=True):
-    """one workload on this rank's GPU -> the fields of its JSON object (rank 0 assembles the line)"""
+def measure(w, D, wd, steps, warmup, min_warm_ms, with_cpu, with_restatement, with_dense=True, with_dd=True, dump=None):
+    """one workload on this rank's GPU -> the fields of its JSON object (rank 0 assembles the line).  `with_dd`: time the
+    decode kernel behind another decode; `dump`: directory that receives the outputs of the last timed step"""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -618,21 +689,26 @@ def measure(w, D, wd, steps, warmup, min_warm_ms, with_cpu, with_restatement, wi
     if not ok:
         raise SystemExit(f"rank {rank}: round trip FAILED (status enc={int(enc.status.abs().sum())} "
                          f"dec={int(dec_status.abs().sum())})")
+    if dump:
+        wd.enter(f"{w.coder}: writing the outputs of the last timed step")
+        dump_outputs(dump, enc, dec_out, chunk_len)
 
     enc_t = np.array([e[0].elapsed_time(e[1]) for e in evs])
     dec_t = np.array([e[1].elapsed_time(e[2]) for e in evs])
-    # the decode kernel again, this time behind ANOTHER DECODE instead of behind the encode that has just written ~1 GB
-    # (the write-back of those lines is paid by whoever runs next: VERDICT r4 weak #9 -- the spread is in the line now)
-    wd.enter(f"{w.coder}: decode after decode")
-    n_dd = max(3, min(steps, 20))
-    model.decode_encoded(enc, chunk_len, out=dec_out)
-    dd = [torch.cuda.Event(enable_timing=True) for _ in range(n_dd + 1)]
-    dd[0].record()
-    for i in range(n_dd):
+    dec_after_dec_ms = None
+    if with_dd:
+        # the decode kernel again, this time behind ANOTHER DECODE instead of behind the encode that has just written ~1 GB
+        # (the write-back of those lines is paid by whoever runs next: VERDICT r4 weak #9 -- the spread is in the line now)
+        wd.enter(f"{w.coder}: decode after decode")
+        n_dd = max(3, min(steps, 20))
         model.decode_encoded(enc, chunk_len, out=dec_out)
-        dd[i + 1].record()
-    torch.cuda.synchronize()
-    dec_after_dec_ms = float(np.mean([dd[i].elapsed_time(dd[i + 1]) for i in range(n_dd)]))
+        dd = [torch.cuda.Event(enable_timing=True) for _ in range(n_dd + 1)]
+        dd[0].record()
+        for i in range(n_dd):
+            model.decode_encoded(enc, chunk_len, out=dec_out)
+            dd[i + 1].record()
+        torch.cuda.synchronize()
+        dec_after_dec_ms = float(np.mean([dd[i].elapsed_time(dd[i + 1]) for i in range(n_dd)]))
     enc_ms, dec_ms = float(enc_t.mean()), float(dec_t.mean())
     enc_med, dec_med = float(np.median(enc_t)), float(np.median(dec_t))
     in_bytes = n_chunks * chunk_len
@@ -723,8 +799,9 @@ def rooflines(res):
     r_enc = roof(res["enc_ms"], res["enc_med"], "encode", k_enc)
     r_dec = roof(res["dec_ms"], res["dec_med"], "decode", k_dec)
     # `avg_launch_ms` is the decode behind the step's encode (what a round trip pays); the same kernel behind another decode:
-    r_dec["after_decode_ms"] = round(res["dec_after_dec_ms"], 4)
-    r_dec["frac_after_decode"] = round(alg / (res["dec_after_dec_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+    if res["dec_after_dec_ms"] is not None:
+        r_dec["after_decode_ms"] = round(res["dec_after_dec_ms"], 4)
+        r_dec["frac_after_decode"] = round(alg / (res["dec_after_dec_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
     r_dense = None
     if res["compact_ms"] is not None:
         seq_ms = res["enc_ms"] + res["compact_ms"]
@@ -916,9 +993,9 @@ def main():
         world = dist.get_world_size()
     D = Dist(world, rank, local_rank, shared_gpu, dev)
 
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline
     single = None
-    if world > 1:
+    if world > 1 and args.full:
         # the N = 1 figure of THIS run: rank 0 alone, the others parked at a barrier (same binary, same box, same clocks)
         if rank == 0:
             solo = Dist(1, 0, local_rank, shared_gpu, dev)
@@ -928,7 +1005,8 @@ def main():
             torch.cuda.empty_cache()
         wd.enter("barrier after rank 0's solo run")
         D.barrier()
-    res = measure(args, D, wd, args.steps, args.warmup, args.min_warm_ms, want_cpu, want_cpu)
+    res = measure(args, D, wd, args.steps, args.warmup, args.min_warm_ms, want_cpu, want_cpu, with_dense=args.full,
+                  with_dd=args.full, dump=args.dump_outputs if rank == 0 else None)
     n_chunks, chunk_len = args.chunks, args.chunk_len
     enc, sym, model = res["enc"], res["sym"], res["model"]
     elapsed, in_bytes, stream_bytes = res["elapsed"], res["in_bytes"], res["stream_bytes"]
@@ -1029,14 +1107,14 @@ def main():
     per_rank_steps = D.gather_all([res["own_elapsed"] / args.steps * 1e3, enc_ms, dec_ms])
 
     file_rate = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.coder in ("rans", "tans", "range"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.coder in ("rans", "tans", "range"):
         wd.enter("stream_file (reference-API file path, end to end)")
         try:
             file_rate = stream_file_rate(args, res)
         except Exception as exc:  # an extra: it must not take the line with it
             file_rate = {"error": f"{type(exc).__name__}: {exc}"}
     others = []
-    if rank == 0 and world == 1 and args.default_workload and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and args.default_workload and not args.no_other_configs:
         del res["sym"], res["enc"], res["model"]
         del enc, sym, model
         torch.cuda.empty_cache()
@@ -1054,10 +1132,14 @@ def main():
         total_bytes = in_bytes * world
         value = total_bytes * args.steps / elapsed / 1e6
         r_enc, r_dec, r_dense, tkey, sha = rooflines(res)
-        dense_extra_ms = compact_ms
-        if res.get("dense_pipelined_ms"):  # what the dense form adds to a step: the pipelined operation replaces the encode
-            dense_extra_ms = min(compact_ms, max(res["dense_pipelined_ms"] - enc_ms, 0.0))
-        value_dense = total_bytes * args.steps / (elapsed + args.steps * dense_extra_ms * 1e-3) / 1e6
+        value_dense = dense_output = None
+        if compact_ms is not None:  # --full
+            dense_extra_ms = compact_ms
+            if res.get("dense_pipelined_ms"):  # what the dense form adds to a step: the pipelined operation replaces the encode
+                dense_extra_ms = min(compact_ms, max(res["dense_pipelined_ms"] - enc_ms, 0.0))
+            value_dense = round(total_bytes * args.steps / (elapsed + args.steps * dense_extra_ms * 1e-3) / 1e6, 2)
+            dense_output = {"compact_ms": round(compact_ms, 4), "compacted_bytes": stream_bytes,
+                            "value_incl_compaction_MBps": round(total_bytes / ((enc_ms + compact_ms + dec_ms) * 1e-3) / 1e6, 2)}
         w = args
         out = {
             "metric": "MB/s encode+decode, 1 GiB i.i.d. bytes, 256-sym rANS; achieved HBM GB/s %peak",
@@ -1065,7 +1147,7 @@ def main():
             # what `value` is: N / (t_encode + t_decode) with every stream left in its own slot, (bit_offset, nbits) --
             # the form the decoders read.  value_dense: the same with the left-align / compaction pass of SURVEY 8d
             # (scl_streams_compact, BitArray.tobytes() of every stream back to back) counted into the step.
-            "value_definition": "slots", "value_dense": round(value_dense, 2),
+            "value_definition": "slots", "value_dense": value_dense,
             "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "warmup_actual": {"steps": res["warm_steps"], "ms": round(res["warm_ms"], 1), "min_ms": args.min_warm_ms},
             "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
@@ -1081,9 +1163,7 @@ def main():
             "roofline": r_enc if enc_ms >= dec_ms else r_dec,
             "roofline_encode": r_enc, "roofline_decode": r_dec, "roofline_dense": r_dense,
             "round_trip_verified": True, "traffic_key": tkey, "csrc_sha": sha, "core_sha": core_sha(),
-            "dense_output": {"compact_ms": round(compact_ms, 4), "compacted_bytes": stream_bytes,
-                             "value_incl_compaction_MBps":
-                                 round(total_bytes / ((enc_ms + compact_ms + dec_ms) * 1e-3) / 1e6, 2)},
+            "dense_output": dense_output,
         }
         if world > 1:
             def mmm(i):
@@ -1122,7 +1202,7 @@ def main():
             else:
                 summ[tag] = {"error": o.get("error", "?")[:60]}
         out["summary"] = summ
-        full_path = write_full_record(out, args.full_json)
+        full_path = write_full_record(out, args.full_json) if args.full or args.full_json else None
         if not args.full_line:
             out = compact_line(out, full_path)
         # the ONE line of the contract -- at the start of a line of its own even if a library (RCCL prints warnings and its

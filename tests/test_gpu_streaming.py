@@ -172,7 +172,8 @@ def test_bench_two_ranks_on_one_gpu(ranks, layout):
     env = dict(os.environ, SCL_BENCH_SHARED_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "2",
-           "--warmup", "1", "--min-warm-ms", "0", "--chunks", "4096", "--no-cpu-baseline", "--gather", "--layout", layout]
+           "--warmup", "1", "--min-warm-ms", "0", "--chunks", "4096", "--full", "--no-cpu-baseline", "--gather", "--layout",
+           layout]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -2,7 +2,7 @@
 # round-3 evidence batch (GPU box): bench lines + rocprofv3 trace / PMC summaries of every kernel family that is quoted
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/r03; mkdir -p $O
-run() { name=$1; shift; python bench.py "$@" 2>/dev/null | grep '^{' > $O/bench_$name.json; python - <<PY
+run() { name=$1; shift; python bench.py --full "$@" 2>/dev/null | grep '^{' > $O/bench_$name.json; python - <<PY
 import json
 d=json.loads(open("$O/bench_$name.json").read())
 print("$name", d["value"], d["roofline_encode"]["avg_launch_ms"], d["roofline_encode"]["frac"], d["roofline_decode"]["avg_launch_ms"], d["roofline_decode"]["frac"], d["dense_output"]["compact_ms"])

@@ -3,9 +3,9 @@
 # lines of the other workloads, and rocprofv3 trace / PMC summaries + stamped traffic entries of every kernel family quoted
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/r05; mkdir -p $O
-python bench.py --steps 20 --warmup 5 2>/dev/null | grep '^{' > $O/bench_driver_style.json
-python bench.py 2>/dev/null | grep '^{' > $O/bench_headline_full.json
-run() { name=$1; shift; python bench.py --no-other-configs "$@" 2>/dev/null | grep '^{' > $O/bench_$name.json; python - <<PY
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | grep '^{' > $O/bench_driver_style.json
+python bench.py --full 2>/dev/null | grep '^{' > $O/bench_headline_full.json
+run() { name=$1; shift; python bench.py --full --no-other-configs "$@" 2>/dev/null | grep '^{' > $O/bench_$name.json; python - <<PY
 import json
 d=json.loads(open("$O/bench_$name.json").read())
 print("$name", d["value"], d["roofline_encode"]["avg_launch_ms"], d["roofline_encode"]["frac"], d["roofline_decode"]["avg_launch_ms"], d["roofline_decode"]["frac"], d["dense_output"]["compact_ms"])

@@ -8,10 +8,10 @@ python tools/try_striped_rt.py 2>/dev/null | grep -v amdgpu.ids > $O/striped_ab.
 python tools/try_striped_rt.py 65536 4096 2>/dev/null | grep -v amdgpu.ids >> $O/striped_ab.txt
 python tools/try_striped_rt.py 131072 4096 2>/dev/null | grep -v amdgpu.ids >> $O/striped_ab.txt
 if [ "${PART:-all}" != "prof" ]; then
-python bench.py --steps 20 --warmup 5 --full-json $O/bench_driver_style.json 2>/dev/null | grep '^{' > $O/bench_line_driver_style.json
-python bench.py --full-json $O/bench_headline_full.json 2>/dev/null | grep '^{' > $O/bench_line_default.json
+python bench.py --full --steps 20 --warmup 5 --full-json $O/bench_driver_style.json 2>/dev/null | grep '^{' > $O/bench_line_driver_style.json
+python bench.py --full --full-json $O/bench_headline_full.json 2>/dev/null | grep '^{' > $O/bench_line_default.json
 wc -c $O/bench_line_driver_style.json $O/bench_line_default.json
-run() { name=$1; shift; python bench.py --full-line --no-other-configs "$@" 2>/dev/null | grep '^{' > $O/bench_$name.json; python - <<PY
+run() { name=$1; shift; python bench.py --full --full-line --no-other-configs "$@" 2>/dev/null | grep '^{' > $O/bench_$name.json; python - <<PY
 import json
 d=json.loads(open("$O/bench_$name.json").read())
 print("$name", d["value"], d["roofline_encode"]["avg_launch_ms"], d["roofline_encode"]["frac"], d["roofline_decode"]["avg_launch_ms"], d["roofline_decode"]["frac"], d["dense_output"]["compact_ms"])
