@@ -304,7 +304,9 @@ int scl_streams_compact_at(const uint8_t *d_in, const uint64_t *d_bit_offset, co
  *   scl_*_striped_ok              1 if the striped entry points serve this model (= the tuned kernels do: fast_path with
  *                                 NUM_BITS_OUT = 1 or in {4, 8, 16}, alphabet <= 256), else 0 -- they then fail with
  *                                 SCL_E_PARAM, as they do while the calling thread keeps the tuned kernels out;
- *   scl_*_encode_batch_striped    arguments of scl_rans_encode_batch; out_stride >= scl_*_slot_bytes(chunk_len), < 2^24;
+ *   scl_*_encode_batch_striped    arguments of scl_rans_encode_batch; out_stride < 2^24 and, for rANS / tANS,
+ *                                 >= scl_*_slot_bytes(chunk_len) (the range coder takes shorter slots: a stream that
+ *                                 does not fit gets SCL_ST_CAPACITY, as on linear slots);
  *   scl_*_decode_batch_striped    arguments of scl_rans_decode_batch with in_stride (the encoder's out_stride) in place of
  *                                 in_size_bytes; stream c must lie inside logical slot c;
  *   scl_streams_compact_striped   scl_streams_compact_at on striped slots: the SAME dense / framed bytes as the linear

@@ -33,6 +33,7 @@
 
 #include <vector>
 
+#include "scl_entry.h"
 #include "scl_aec_internal.h"
 
 // Per-lane frequency model (one of the three kinds); the coders only see counts through rd()/wr().
@@ -609,16 +610,44 @@ static int aec_prepare_scratch(const scl_aec_model *m, u64 n_chunks, void *d_scr
     return SCL_OK;
 }
 
+// the any-parameter kernels: a lane's model in LDS (lds: byte symbols only, aec_use_lds) or in `cells` (scratch, or the
+// state a *_resume call carries on, with its contexts in ctx_state), 64-bit arithmetic for PRECISION above 32
+template <class SYM>
+static int aec_encode_any(const scl_aec_model *m, bool lds, const SYM *d_sym, u64 sym_stride, const u32 *d_lens,
+                          u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
+                          u32 *d_status, u32 *cells, u64 *ctx_state, hipStream_t st) {
+    const bool wide = m->dev.P > 32;
+    auto kernel = wide ? aec_encode_kernel<false, true, SYM> : aec_encode_kernel<false, false, SYM>;
+    if constexpr (sizeof(SYM) == 1)
+        if (lds) kernel = wide ? aec_encode_kernel<true, true> : aec_encode_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_sym, sym_stride, d_lens,
+                       chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status, cells, ctx_state);
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+template <class SYM>
+static int aec_decode_any(const scl_aec_model *m, bool lds, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_off,
+                          const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride, u32 out_cap,
+                          u32 *d_out_lens, u32 *d_consumed, u32 *d_status, u32 *cells, u64 *ctx_state, hipStream_t st) {
+    const bool wide = m->dev.P > 32;
+    auto kernel = wide ? aec_decode_kernel<false, true, SYM> : aec_decode_kernel<false, false, SYM>;
+    if constexpr (sizeof(SYM) == 1)
+        if (lds) kernel = wide ? aec_decode_kernel<true, true> : aec_decode_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_in, in_size_bytes,
+                       d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status,
+                       cells, ctx_state);
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
 extern "C" int scl_aec_encode_batch(const scl_aec_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                     const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                     uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                     uint32_t *d_status, void *d_scratch, uint64_t scratch_bytes, void *stream) {
-    SCL_REQUIRE(m && d_sym && d_out && d_out_bit_offset && d_out_nbits, "aec_encode_batch: null pointer argument");
-    SCL_REQUIRE(m->dev.K <= 256, "aec_encode_batch: alphabet of %u symbols: use scl_aec_encode_batch_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "aec_encode_batch")) return rc_dev;
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && out_stride * 8 < (1ull << 32),
-                "aec_encode_batch: bad out_stride %llu", (unsigned long long)out_stride);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0, "aec_encode_batch: d_out must be 16-byte aligned");
+    if (int rc = scl_check_encode("aec_encode_batch", SCL_ROWS_U8, m, d_sym, d_out, d_out_bit_offset, d_out_nbits,
+                                  out_stride))
+        return rc;
     if (n_chunks == 0) return SCL_OK;
     hipStream_t st = (hipStream_t)stream;
     const bool tuned = !scl_force_generic();
@@ -673,32 +702,8 @@ extern "C" int scl_aec_encode_batch(const scl_aec_model *m, const uint8_t *d_sym
         SCL_HIP_TRY(hipGetLastError());
         return SCL_OK;
     }
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    if (aec_use_lds(m, chunk_len))
-        do {
-        if (m->dev.P > 32)
-            hipLaunchKernelGGL((aec_encode_kernel<true, true>), dim3(blocks), dim3(threads), 0, st, m->dev, d_sym, sym_stride,
-                           d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status,
-                           (u32 *)d_scratch, (u64 *)nullptr);
-        else
-            hipLaunchKernelGGL((aec_encode_kernel<true, false>), dim3(blocks), dim3(threads), 0, st, m->dev, d_sym, sym_stride,
-                           d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status,
-                           (u32 *)d_scratch, (u64 *)nullptr);
-    } while (0);
-    else
-        do {
-        if (m->dev.P > 32)
-            hipLaunchKernelGGL((aec_encode_kernel<false, true>), dim3(blocks), dim3(threads), 0, st, m->dev, d_sym, sym_stride,
-                           d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status,
-                           (u32 *)d_scratch, (u64 *)nullptr);
-        else
-            hipLaunchKernelGGL((aec_encode_kernel<false, false>), dim3(blocks), dim3(threads), 0, st, m->dev, d_sym, sym_stride,
-                           d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status,
-                           (u32 *)d_scratch, (u64 *)nullptr);
-    } while (0);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return aec_encode_any(m, aec_use_lds(m, chunk_len), d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
+                          out_stride, d_out_bit_offset, d_out_nbits, d_status, (u32 *)d_scratch, nullptr, st);
 }
 
 extern "C" int scl_aec_decode_batch(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -706,11 +711,9 @@ extern "C" int scl_aec_decode_batch(const scl_aec_model *m, const uint8_t *d_in,
                                     uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
                                     uint32_t *d_consumed, uint32_t *d_status, void *d_scratch, uint64_t scratch_bytes,
                                     void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "aec_decode_batch: null pointer argument");
-    SCL_REQUIRE(m->dev.K <= 256, "aec_decode_batch: alphabet of %u symbols: use scl_aec_decode_batch_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "aec_decode_batch")) return rc_dev;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0, "aec_decode_batch: d_in must be 4-byte aligned");
+    if (int rc = scl_check_decode("aec_decode_batch", SCL_ROWS_U8, m, d_in, d_bit_offset, d_in_nbits, d_out_sym,
+                                  d_out_lens, d_consumed))
+        return rc;
     if (n_chunks == 0) return SCL_OK;
     hipStream_t st = (hipStream_t)stream;
     const bool tuned = !scl_force_generic() && in_size_bytes >= 4;  // the tuned readers load whole 32-bit words
@@ -760,31 +763,10 @@ extern "C" int scl_aec_decode_batch(const scl_aec_model *m, const uint8_t *d_in,
         SCL_HIP_TRY(hipGetLastError());
         return relay.out_end(d_out_lens);
     }
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    if (aec_use_lds(m, out_cap))
-        do {
-        if (m->dev.P > 32)
-            hipLaunchKernelGGL((aec_decode_kernel<true, true>), dim3(blocks), dim3(threads), 0, st, m->dev, d_in, in_size_bytes,
-                           d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
-                           d_consumed, d_status, (u32 *)d_scratch, (u64 *)nullptr);
-        else
-            hipLaunchKernelGGL((aec_decode_kernel<true, false>), dim3(blocks), dim3(threads), 0, st, m->dev, d_in, in_size_bytes,
-                           d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
-                           d_consumed, d_status, (u32 *)d_scratch, (u64 *)nullptr);
-    } while (0);
-    else
-        do {
-        if (m->dev.P > 32)
-            hipLaunchKernelGGL((aec_decode_kernel<false, true>), dim3(blocks), dim3(threads), 0, st, m->dev, d_in, in_size_bytes,
-                           d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
-                           d_consumed, d_status, (u32 *)d_scratch, (u64 *)nullptr);
-        else
-            hipLaunchKernelGGL((aec_decode_kernel<false, false>), dim3(blocks), dim3(threads), 0, st, m->dev, d_in, in_size_bytes,
-                           d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
-                           d_consumed, d_status, (u32 *)d_scratch, (u64 *)nullptr);
-    } while (0);
-    SCL_HIP_TRY(hipGetLastError());
+    if (int rc = aec_decode_any(m, aec_use_lds(m, out_cap), d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
+                                d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, (u32 *)d_scratch,
+                                nullptr, st))
+        return rc;
     return relay.out_end(d_out_lens);
 }
 
@@ -917,43 +899,76 @@ extern "C" int scl_aec_state_download(const scl_aec_model *m, const void *d_stat
     return SCL_OK;
 }
 
+// ---- uint16 symbols (alphabets up to 65536: the any-parameter kernels, counts in device memory) and the *_resume forms
+// of both widths: chunk c continues coder c of a state d_state reset with n_coders coders; the layout of d_state is a
+// function of n_coders (the context array follows the cells of ALL coders), so a batch may be shorter, never longer.
+// A FIXED model has nothing to carry: its *_resume calls are the plain batch calls.
+static int aec_resume_state(const char *what, const scl_aec_model *m, u64 n_chunks, void *d_state, u64 state_bytes,
+                            u64 n_coders, u32 *&cells, u64 *&ctx_state) {
+    SCL_REQUIRE(d_state, "%s: null pointer argument", what);
+    SCL_REQUIRE(((uintptr_t)d_state & 255) == 0, "%s: d_state must be 256-byte aligned", what);
+    SCL_REQUIRE(n_chunks <= n_coders, "%s: %llu chunks but the state holds %llu coders", what,
+                (unsigned long long)n_chunks, (unsigned long long)n_coders);
+    SCL_REQUIRE(state_bytes >= scl_aec_state_bytes(m, n_coders), "%s: state of %llu bytes required", what,
+                (unsigned long long)scl_aec_state_bytes(m, n_coders));
+    cells = (u32 *)d_state;
+    ctx_state = (u64 *)((u8 *)d_state + aec_state_cells_bytes(m, n_coders));
+    return SCL_OK;
+}
+
+template <class SYM>
+static int aec_encode_cells(const char *what, const scl_aec_model *m, const SYM *d_sym, u64 sym_stride,
+                            const u32 *d_lens, u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off,
+                            u32 *d_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes, bool resume,
+                            void *d_state, u64 state_bytes, u64 n_coders, hipStream_t st) {
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, d_sym, d_out, d_bit_off, d_nbits, out_stride)) return rc;
+    u32 *cells = (u32 *)d_scratch;
+    u64 *ctx_state = nullptr;
+    if (resume && m->dev.kind != SCL_MODEL_FIXED)
+        if (int rc = aec_resume_state(what, m, n_chunks, d_state, state_bytes, n_coders, cells, ctx_state)) return rc;
+    if constexpr (sizeof(SYM) == 1)
+        if (!ctx_state)
+            return scl_aec_encode_batch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
+                                        d_nbits, d_status, d_scratch, scratch_bytes, st);
+    if (n_chunks == 0) return SCL_OK;
+    if (!ctx_state)
+        if (int rc = aec_prepare_scratch(m, n_chunks, d_scratch, scratch_bytes, st)) return rc;
+    return aec_encode_any(m, false, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
+                          d_nbits, d_status, cells, ctx_state, st);
+}
+
+template <class SYM>
+static int aec_decode_cells(const char *what, const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes,
+                            const u64 *d_bit_off, const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride,
+                            u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, void *d_scratch,
+                            u64 scratch_bytes, bool resume, void *d_state, u64 state_bytes, u64 n_coders,
+                            hipStream_t st) {
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, d_in, d_bit_off, d_in_nbits, d_out_sym, d_out_lens,
+                                  d_consumed))
+        return rc;
+    u32 *cells = (u32 *)d_scratch;
+    u64 *ctx_state = nullptr;
+    if (resume && m->dev.kind != SCL_MODEL_FIXED)
+        if (int rc = aec_resume_state(what, m, n_chunks, d_state, state_bytes, n_coders, cells, ctx_state)) return rc;
+    if constexpr (sizeof(SYM) == 1)
+        if (!ctx_state)
+            return scl_aec_decode_batch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
+                                        out_cap, d_out_lens, d_consumed, d_status, d_scratch, scratch_bytes, st);
+    if (n_chunks == 0) return SCL_OK;
+    if (!ctx_state)
+        if (int rc = aec_prepare_scratch(m, n_chunks, d_scratch, scratch_bytes, st)) return rc;
+    return aec_decode_any(m, false, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
+                          d_out_lens, d_consumed, d_status, cells, ctx_state, st);
+}
+
 extern "C" int scl_aec_encode_batch_resume(const scl_aec_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                            const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                            uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                            uint32_t *d_out_nbits, uint32_t *d_status, void *d_state,
                                            uint64_t state_bytes, uint64_t n_coders, void *stream) {
-    SCL_REQUIRE(m, "aec_encode_batch_resume: null model");
-    SCL_REQUIRE(m->dev.K <= 256, "aec_encode_batch_resume: alphabet of %u symbols: use scl_aec_encode_batch_resume_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "aec_encode_batch_resume")) return rc_dev;
-    if (m->dev.kind == SCL_MODEL_FIXED)  // nothing to carry
-        return scl_aec_encode_batch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                                    d_out_bit_offset, d_out_nbits, d_status, nullptr, 0, stream);
-    SCL_REQUIRE(d_sym && d_out && d_out_bit_offset && d_out_nbits && d_state,
-                "aec_encode_batch_resume: null pointer argument");
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && out_stride * 8 < (1ull << 32),
-                "aec_encode_batch_resume: bad out_stride %llu", (unsigned long long)out_stride);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0 && ((uintptr_t)d_state & 255) == 0,
-                "aec_encode_batch_resume: d_out must be 16-byte, d_state 256-byte aligned");
-    // the layout of d_state is a function of the n_coders it was reset with (the context array follows the cells of
-    // ALL coders): chunk c continues coder c, so a batch may be shorter than the state, never longer
-    SCL_REQUIRE(n_chunks <= n_coders, "aec_encode_batch_resume: %llu chunks but the state holds %llu coders",
-                (unsigned long long)n_chunks, (unsigned long long)n_coders);
-    SCL_REQUIRE(state_bytes >= scl_aec_state_bytes(m, n_coders), "aec_encode_batch_resume: state of %llu bytes required",
-                (unsigned long long)scl_aec_state_bytes(m, n_coders));
-    if (n_chunks == 0) return SCL_OK;
-    u64 *ctx_state = (u64 *)((u8 *)d_state + aec_state_cells_bytes(m, n_coders));
-    do {
-        if (m->dev.P > 32)
-            hipLaunchKernelGGL((aec_encode_kernel<false, true>), dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       m->dev, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                       d_out_nbits, d_status, (u32 *)d_state, ctx_state);
-        else
-            hipLaunchKernelGGL((aec_encode_kernel<false, false>), dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       m->dev, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                       d_out_nbits, d_status, (u32 *)d_state, ctx_state);
-    } while (0);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return aec_encode_cells("aec_encode_batch_resume", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
+                            out_stride, d_out_bit_offset, d_out_nbits, d_status, nullptr, 0, true, d_state, state_bytes,
+                            n_coders, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_decode_batch_resume(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -961,121 +976,18 @@ extern "C" int scl_aec_decode_batch_resume(const scl_aec_model *m, const uint8_t
                                            uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap,
                                            uint32_t *d_out_lens, uint32_t *d_consumed, uint32_t *d_status,
                                            void *d_state, uint64_t state_bytes, uint64_t n_coders, void *stream) {
-    SCL_REQUIRE(m, "aec_decode_batch_resume: null model");
-    SCL_REQUIRE(m->dev.K <= 256, "aec_decode_batch_resume: alphabet of %u symbols: use scl_aec_decode_batch_resume_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "aec_decode_batch_resume")) return rc_dev;
-    if (m->dev.kind == SCL_MODEL_FIXED)
-        return scl_aec_decode_batch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                    out_cap, d_out_lens, d_consumed, d_status, nullptr, 0, stream);
-    SCL_REQUIRE(d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed && d_state,
-                "aec_decode_batch_resume: null pointer argument");
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0 && ((uintptr_t)d_state & 255) == 0,
-                "aec_decode_batch_resume: d_in must be 4-byte, d_state 256-byte aligned");
-    // the layout of d_state is a function of the n_coders it was reset with (the context array follows the cells of
-    // ALL coders): chunk c continues coder c, so a batch may be shorter than the state, never longer
-    SCL_REQUIRE(n_chunks <= n_coders, "aec_decode_batch_resume: %llu chunks but the state holds %llu coders",
-                (unsigned long long)n_chunks, (unsigned long long)n_coders);
-    SCL_REQUIRE(state_bytes >= scl_aec_state_bytes(m, n_coders), "aec_decode_batch_resume: state of %llu bytes required",
-                (unsigned long long)scl_aec_state_bytes(m, n_coders));
-    if (n_chunks == 0) return SCL_OK;
-    u64 *ctx_state = (u64 *)((u8 *)d_state + aec_state_cells_bytes(m, n_coders));
-    do {
-        if (m->dev.P > 32)
-            hipLaunchKernelGGL((aec_decode_kernel<false, true>), dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       m->dev, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                       d_out_lens, d_consumed, d_status, (u32 *)d_state, ctx_state);
-        else
-            hipLaunchKernelGGL((aec_decode_kernel<false, false>), dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       m->dev, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                       d_out_lens, d_consumed, d_status, (u32 *)d_state, ctx_state);
-    } while (0);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
-}
-
-
-// ---- uint16 symbol indices: alphabets up to 65536 (any model; the any-parameter kernels, counts in device memory) ----
-// d_state != nullptr: the *_resume form (chunk c continues coder c of a state reset with n_coders coders)
-static int aec_encode_u16(const char *what, const scl_aec_model *m, const u16 *d_sym, u64 sym_stride, const u32 *d_lens,
-                          u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset,
-                          u32 *d_out_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes, void *d_state,
-                          u64 state_bytes, u64 n_coders, hipStream_t st) {
-    SCL_REQUIRE(m && d_sym && d_out && d_out_bit_offset && d_out_nbits, "%s: null pointer argument", what);
-    if (int rc_dev = scl_check_device(m->device, what)) return rc_dev;
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && out_stride * 8 < (1ull << 32), "%s: bad out_stride %llu", what,
-                (unsigned long long)out_stride);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0 && ((uintptr_t)d_sym & 1) == 0,
-                "%s: d_out must be 16-byte aligned, d_sym 2-byte aligned", what);
-    u32 *cells = (u32 *)d_scratch;
-    u64 *ctx_state = nullptr;
-    if (d_state && m->dev.kind != SCL_MODEL_FIXED) {
-        SCL_REQUIRE(((uintptr_t)d_state & 255) == 0, "%s: d_state must be 256-byte aligned", what);
-        SCL_REQUIRE(n_chunks <= n_coders, "%s: %llu chunks but the state holds %llu coders", what,
-                    (unsigned long long)n_chunks, (unsigned long long)n_coders);
-        SCL_REQUIRE(state_bytes >= scl_aec_state_bytes(m, n_coders), "%s: state of %llu bytes required", what,
-                    (unsigned long long)scl_aec_state_bytes(m, n_coders));
-        cells = (u32 *)d_state;
-        ctx_state = (u64 *)((u8 *)d_state + aec_state_cells_bytes(m, n_coders));
-    }
-    if (n_chunks == 0) return SCL_OK;
-    if (!ctx_state)
-        if (int rc = aec_prepare_scratch(m, n_chunks, d_scratch, scratch_bytes, st)) return rc;
-    const dim3 grid((u32)((n_chunks + 255) / 256)), block(256);
-    if (m->dev.P > 32)
-        hipLaunchKernelGGL((aec_encode_kernel<false, true, u16>), grid, block, 0, st, m->dev, d_sym, sym_stride, d_lens,
-                           chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status, cells,
-                           ctx_state);
-    else
-        hipLaunchKernelGGL((aec_encode_kernel<false, false, u16>), grid, block, 0, st, m->dev, d_sym, sym_stride, d_lens,
-                           chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status, cells,
-                           ctx_state);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
-}
-
-static int aec_decode_u16(const char *what, const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes,
-                          const u64 *d_bit_offset, const u32 *d_in_nbits, u64 n_chunks, u16 *d_out_sym, u64 out_stride,
-                          u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, void *d_scratch,
-                          u64 scratch_bytes, void *d_state, u64 state_bytes, u64 n_coders, hipStream_t st) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "%s: null pointer argument", what);
-    if (int rc_dev = scl_check_device(m->device, what)) return rc_dev;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0 && ((uintptr_t)d_out_sym & 1) == 0,
-                "%s: d_in must be 4-byte aligned, d_out_sym 2-byte aligned", what);
-    u32 *cells = (u32 *)d_scratch;
-    u64 *ctx_state = nullptr;
-    if (d_state && m->dev.kind != SCL_MODEL_FIXED) {
-        SCL_REQUIRE(((uintptr_t)d_state & 255) == 0, "%s: d_state must be 256-byte aligned", what);
-        SCL_REQUIRE(n_chunks <= n_coders, "%s: %llu chunks but the state holds %llu coders", what,
-                    (unsigned long long)n_chunks, (unsigned long long)n_coders);
-        SCL_REQUIRE(state_bytes >= scl_aec_state_bytes(m, n_coders), "%s: state of %llu bytes required", what,
-                    (unsigned long long)scl_aec_state_bytes(m, n_coders));
-        cells = (u32 *)d_state;
-        ctx_state = (u64 *)((u8 *)d_state + aec_state_cells_bytes(m, n_coders));
-    }
-    if (n_chunks == 0) return SCL_OK;
-    if (!ctx_state)
-        if (int rc = aec_prepare_scratch(m, n_chunks, d_scratch, scratch_bytes, st)) return rc;
-    const dim3 grid((u32)((n_chunks + 255) / 256)), block(256);
-    if (m->dev.P > 32)
-        hipLaunchKernelGGL((aec_decode_kernel<false, true, u16>), grid, block, 0, st, m->dev, d_in, in_size_bytes,
-                           d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed,
-                           d_status, cells, ctx_state);
-    else
-        hipLaunchKernelGGL((aec_decode_kernel<false, false, u16>), grid, block, 0, st, m->dev, d_in, in_size_bytes,
-                           d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed,
-                           d_status, cells, ctx_state);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return aec_decode_cells("aec_decode_batch_resume", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
+                            d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, nullptr, 0, true, d_state,
+                            state_bytes, n_coders, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_encode_batch_u16(const scl_aec_model *m, const uint16_t *d_sym, uint64_t sym_stride,
                                         const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                         uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                         uint32_t *d_status, void *d_scratch, uint64_t scratch_bytes, void *stream) {
-    return aec_encode_u16("aec_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                          d_out_bit_offset, d_out_nbits, d_status, d_scratch, scratch_bytes, nullptr, 0, 0,
-                          (hipStream_t)stream);
+    return aec_encode_cells("aec_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                            d_out_bit_offset, d_out_nbits, d_status, d_scratch, scratch_bytes, false, nullptr, 0, 0,
+                            (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_decode_batch_u16(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -1083,9 +995,9 @@ extern "C" int scl_aec_decode_batch_u16(const scl_aec_model *m, const uint8_t *d
                                         uint16_t *d_out_sym, uint64_t out_stride, uint32_t out_cap,
                                         uint32_t *d_out_lens, uint32_t *d_consumed, uint32_t *d_status, void *d_scratch,
                                         uint64_t scratch_bytes, void *stream) {
-    return aec_decode_u16("aec_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
-                          out_stride, out_cap, d_out_lens, d_consumed, d_status, d_scratch, scratch_bytes, nullptr, 0, 0,
-                          (hipStream_t)stream);
+    return aec_decode_cells("aec_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
+                            d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, d_scratch, scratch_bytes,
+                            false, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_encode_batch_resume_u16(const scl_aec_model *m, const uint16_t *d_sym, uint64_t sym_stride,
@@ -1093,10 +1005,9 @@ extern "C" int scl_aec_encode_batch_resume_u16(const scl_aec_model *m, const uin
                                                uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                                uint32_t *d_out_nbits, uint32_t *d_status, void *d_state,
                                                uint64_t state_bytes, uint64_t n_coders, void *stream) {
-    SCL_REQUIRE(m && (d_state || m->dev.kind == SCL_MODEL_FIXED), "aec_encode_batch_resume_u16: null model or state");
-    return aec_encode_u16("aec_encode_batch_resume_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
-                          out_stride, d_out_bit_offset, d_out_nbits, d_status, nullptr, 0, d_state, state_bytes, n_coders,
-                          (hipStream_t)stream);
+    return aec_encode_cells("aec_encode_batch_resume_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
+                            out_stride, d_out_bit_offset, d_out_nbits, d_status, nullptr, 0, true, d_state, state_bytes,
+                            n_coders, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_decode_batch_resume_u16(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -1105,46 +1016,42 @@ extern "C" int scl_aec_decode_batch_resume_u16(const scl_aec_model *m, const uin
                                                uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                                uint32_t *d_status, void *d_state, uint64_t state_bytes,
                                                uint64_t n_coders, void *stream) {
-    SCL_REQUIRE(m && (d_state || m->dev.kind == SCL_MODEL_FIXED), "aec_decode_batch_resume_u16: null model or state");
-    return aec_decode_u16("aec_decode_batch_resume_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
-                          d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, nullptr, 0, d_state,
-                          state_bytes, n_coders, (hipStream_t)stream);
+    return aec_decode_cells("aec_decode_batch_resume_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
+                            d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, nullptr, 0, true, d_state,
+                            state_bytes, n_coders, (hipStream_t)stream);
 }
 
 // ---- single-chunk host drivers --------------------------------------------------------------------------
-static int aec_run_enc(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                       u32 *d_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes) {
-    return scl_aec_encode_batch((const scl_aec_model *)model, d_sym, n, nullptr, n, 1, d_out, out_stride, d_bit_off,
-                                d_nbits, d_status, d_scratch, scratch_bytes, nullptr);
-}
-static u64 aec_slot(const void *model, u64 n) { return scl_aec_slot_bytes((const scl_aec_model *)model, n); }
-static u64 aec_scratch(const void *model) { return scl_aec_scratch_bytes((const scl_aec_model *)model, 1); }
-static int aec_run_dec(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-                       u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *d_scratch,
-                       u64 scratch_bytes) {
-    return scl_aec_decode_batch((const scl_aec_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1, d_out_sym,
-                                scl_round_up((u64)out_cap + 1, 16), out_cap, d_out_len, d_consumed, d_status,
-                                d_scratch, scratch_bytes, nullptr);
-}
-
 extern "C" int scl_aec_encode_host(const scl_aec_model *m, const uint8_t *h_sym, uint64_t n, uint8_t *h_out,
                                    uint64_t out_cap_bytes, uint64_t *nbits) {
-    HostEncodeCall call = {aec_run_enc, aec_slot, aec_scratch};
-    return scl_host_encode_one(call, m, h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(scl_host_encode_call<scl_aec_encode_batch, scl_aec_slot_bytes, scl_aec_scratch_bytes>(),
+                               m, h_sym, n, h_out, out_cap_bytes, nbits);
 }
 
 extern "C" int scl_aec_decode_host(const scl_aec_model *m, const uint8_t *h_in, uint64_t in_nbits, uint8_t *h_out_sym,
                                    uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
-    HostDecodeCall call = {aec_run_dec, aec_scratch};
-    return scl_host_decode_one(call, m, h_in, in_nbits, h_out_sym, out_cap, n_out, consumed);
+    return scl_host_decode_one(scl_host_decode_call<scl_aec_decode_batch, scl_aec_scratch_bytes>(), m, h_in, in_nbits,
+                               h_out_sym, out_cap, n_out, consumed);
+}
+
+extern "C" int scl_aec_encode_host_u16(const scl_aec_model *m, const uint16_t *h_sym, uint64_t n, uint8_t *h_out,
+                                       uint64_t out_cap_bytes, uint64_t *nbits) {
+    return scl_host_encode_one(
+        scl_host_encode_call<scl_aec_encode_batch_u16, scl_aec_slot_bytes, scl_aec_scratch_bytes>(), m,
+        (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
+}
+
+extern "C" int scl_aec_decode_host_u16(const scl_aec_model *m, const uint8_t *h_in, uint64_t in_nbits,
+                                       uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
+    return scl_host_decode_one(scl_host_decode_call<scl_aec_decode_batch_u16, scl_aec_scratch_bytes>(), m, h_in,
+                               in_nbits, (u8 *)h_out_sym, out_cap, n_out, consumed);
 }
 
 // one block of a coder whose model state lives on the host between calls (what the drop-in classes do with the
-// caller's freq_model object): upload -> code one block -> download
+// caller's freq_model object): upload -> code one block (the *_resume batch call on a one-coder state) -> download
 struct AecHostState {
     uint32_t *counts, *past_k;
 };
-static u64 aec_state1(const void *model) { return scl_aec_state_bytes((const scl_aec_model *)model, 1); }
 static int aec_state_pre(const void *model, void *d_scratch, void *user) {
     const AecHostState *hs = (const AecHostState *)user;
     return scl_aec_state_upload((const scl_aec_model *)model, d_scratch, 1, 0, hs->counts, hs->past_k, nullptr);
@@ -1153,17 +1060,12 @@ static int aec_state_post(const void *model, const void *d_scratch, void *user) 
     const AecHostState *hs = (const AecHostState *)user;
     return scl_aec_state_download((const scl_aec_model *)model, d_scratch, 1, 0, hs->counts, hs->past_k, nullptr);
 }
-static int aec_run_enc_resume(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                              u32 *d_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes) {
-    return scl_aec_encode_batch_resume((const scl_aec_model *)model, d_sym, n, nullptr, n, 1, d_out, out_stride,
-                                       d_bit_off, d_nbits, d_status, d_scratch, scratch_bytes, 1, nullptr);
-}
-static int aec_run_dec_resume(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off,
-                              const u32 *d_in_nbits, u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed,
-                              u32 *d_status, void *d_scratch, u64 scratch_bytes) {
-    return scl_aec_decode_batch_resume((const scl_aec_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1,
-                                       d_out_sym, scl_round_up((u64)out_cap + 1, 16), out_cap, d_out_len, d_consumed,
-                                       d_status, d_scratch, scratch_bytes, 1, nullptr);
+template <class CALL>
+static CALL aec_with_state(CALL call, AecHostState *hs) {
+    call.pre = aec_state_pre;
+    call.post = aec_state_post;
+    call.user = hs;
+    return call;
 }
 
 extern "C" int scl_aec_encode_host_resume(const scl_aec_model *m, const uint8_t *h_sym, uint64_t n, uint8_t *h_out,
@@ -1173,8 +1075,9 @@ extern "C" int scl_aec_encode_host_resume(const scl_aec_model *m, const uint8_t 
     if (m->dev.kind == SCL_MODEL_FIXED) return scl_aec_encode_host(m, h_sym, n, h_out, out_cap_bytes, nbits);
     SCL_REQUIRE(h_counts && (m->dev.k == 0 || h_past_k), "aec_encode_host_resume: null state arrays");
     AecHostState hs = {h_counts, h_past_k};
-    HostEncodeCall call = {aec_run_enc_resume, aec_slot, aec_state1, aec_state_pre, aec_state_post, &hs};
-    return scl_host_encode_one(call, m, h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(
+        aec_with_state(scl_host_encode_call<scl_aec_encode_batch_resume, scl_aec_slot_bytes, scl_aec_state_bytes>(), &hs),
+        m, h_sym, n, h_out, out_cap_bytes, nbits);
 }
 
 extern "C" int scl_aec_decode_host_resume(const scl_aec_model *m, const uint8_t *h_in, uint64_t in_nbits,
@@ -1184,49 +1087,9 @@ extern "C" int scl_aec_decode_host_resume(const scl_aec_model *m, const uint8_t 
     if (m->dev.kind == SCL_MODEL_FIXED) return scl_aec_decode_host(m, h_in, in_nbits, h_out_sym, out_cap, n_out, consumed);
     SCL_REQUIRE(h_counts && (m->dev.k == 0 || h_past_k), "aec_decode_host_resume: null state arrays");
     AecHostState hs = {h_counts, h_past_k};
-    HostDecodeCall call = {aec_run_dec_resume, aec_state1, aec_state_pre, aec_state_post, &hs};
-    return scl_host_decode_one(call, m, h_in, in_nbits, h_out_sym, out_cap, n_out, consumed);
-}
-
-// ---- single-chunk host drivers, uint16 symbol indices --------------------------------------------------------
-static int aec_run_enc16(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                         u32 *d_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes) {
-    return scl_aec_encode_batch_u16((const scl_aec_model *)model, (const u16 *)d_sym, n, nullptr, n, 1, d_out, out_stride,
-                                    d_bit_off, d_nbits, d_status, d_scratch, scratch_bytes, nullptr);
-}
-static int aec_run_dec16(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-                         u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *d_scratch,
-                         u64 scratch_bytes) {
-    return scl_aec_decode_batch_u16((const scl_aec_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1,
-                                    (u16 *)d_out_sym, (u64)out_cap + 1, out_cap, d_out_len, d_consumed, d_status,
-                                    d_scratch, scratch_bytes, nullptr);
-}
-static int aec_run_enc_resume16(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                                u32 *d_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes) {
-    return scl_aec_encode_batch_resume_u16((const scl_aec_model *)model, (const u16 *)d_sym, n, nullptr, n, 1, d_out,
-                                           out_stride, d_bit_off, d_nbits, d_status, d_scratch, scratch_bytes, 1,
-                                           nullptr);
-}
-static int aec_run_dec_resume16(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off,
-                                const u32 *d_in_nbits, u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed,
-                                u32 *d_status, void *d_scratch, u64 scratch_bytes) {
-    return scl_aec_decode_batch_resume_u16((const scl_aec_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1,
-                                           (u16 *)d_out_sym, (u64)out_cap + 1, out_cap, d_out_len, d_consumed, d_status,
-                                           d_scratch, scratch_bytes, 1, nullptr);
-}
-
-extern "C" int scl_aec_encode_host_u16(const scl_aec_model *m, const uint16_t *h_sym, uint64_t n, uint8_t *h_out,
-                                       uint64_t out_cap_bytes, uint64_t *nbits) {
-    HostEncodeCall call = {aec_run_enc16, aec_slot, aec_scratch};
-    call.sym_bytes = 2;
-    return scl_host_encode_one(call, m, (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
-}
-
-extern "C" int scl_aec_decode_host_u16(const scl_aec_model *m, const uint8_t *h_in, uint64_t in_nbits,
-                                       uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
-    HostDecodeCall call = {aec_run_dec16, aec_scratch};
-    call.sym_bytes = 2;
-    return scl_host_decode_one(call, m, h_in, in_nbits, (u8 *)h_out_sym, out_cap, n_out, consumed);
+    return scl_host_decode_one(
+        aec_with_state(scl_host_decode_call<scl_aec_decode_batch_resume, scl_aec_state_bytes>(), &hs), m, h_in,
+        in_nbits, h_out_sym, out_cap, n_out, consumed);
 }
 
 extern "C" int scl_aec_encode_host_resume_u16(const scl_aec_model *m, const uint16_t *h_sym, uint64_t n,
@@ -1236,9 +1099,10 @@ extern "C" int scl_aec_encode_host_resume_u16(const scl_aec_model *m, const uint
     if (m->dev.kind == SCL_MODEL_FIXED) return scl_aec_encode_host_u16(m, h_sym, n, h_out, out_cap_bytes, nbits);
     SCL_REQUIRE(h_counts && (m->dev.k == 0 || h_past_k), "aec_encode_host_resume_u16: null state arrays");
     AecHostState hs = {h_counts, h_past_k};
-    HostEncodeCall call = {aec_run_enc_resume16, aec_slot, aec_state1, aec_state_pre, aec_state_post, &hs};
-    call.sym_bytes = 2;
-    return scl_host_encode_one(call, m, (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(
+        aec_with_state(scl_host_encode_call<scl_aec_encode_batch_resume_u16, scl_aec_slot_bytes, scl_aec_state_bytes>(),
+                       &hs),
+        m, (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
 }
 
 extern "C" int scl_aec_decode_host_resume_u16(const scl_aec_model *m, const uint8_t *h_in, uint64_t in_nbits,
@@ -1249,7 +1113,7 @@ extern "C" int scl_aec_decode_host_resume_u16(const scl_aec_model *m, const uint
         return scl_aec_decode_host_u16(m, h_in, in_nbits, h_out_sym, out_cap, n_out, consumed);
     SCL_REQUIRE(h_counts && (m->dev.k == 0 || h_past_k), "aec_decode_host_resume_u16: null state arrays");
     AecHostState hs = {h_counts, h_past_k};
-    HostDecodeCall call = {aec_run_dec_resume16, aec_state1, aec_state_pre, aec_state_post, &hs};
-    call.sym_bytes = 2;
-    return scl_host_decode_one(call, m, h_in, in_nbits, (u8 *)h_out_sym, out_cap, n_out, consumed);
+    return scl_host_decode_one(
+        aec_with_state(scl_host_decode_call<scl_aec_decode_batch_resume_u16, scl_aec_state_bytes>(), &hs), m, h_in,
+        in_nbits, (u8 *)h_out_sym, out_cap, n_out, consumed);
 }

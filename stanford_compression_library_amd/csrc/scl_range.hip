@@ -13,6 +13,7 @@
 
 #include <vector>
 
+#include "scl_entry.h"
 #include "scl_range_internal.h"
 
 template <typename ST>
@@ -238,39 +239,99 @@ extern "C" uint64_t scl_range_slot_bytes(const scl_range_model *m, uint64_t n_sy
     return scl_round_up(bytes + 4, 128);
 }
 
-extern "C" int scl_range_encode_batch(const scl_range_model *m, const uint8_t *d_sym, uint64_t sym_stride,
-                                      const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
-                                      uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
-                                      uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_sym && d_out && d_out_bit_offset && d_out_nbits, "range_encode_batch: null pointer argument");
-    SCL_REQUIRE(m->dev.K <= 256, "range_encode_batch: alphabet of %u symbols: use scl_range_encode_batch_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "range_encode_batch")) return rc_dev;
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && out_stride * 8 < (1ull << 32),
-                "range_encode_batch: bad out_stride %llu", (unsigned long long)out_stride);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0, "range_encode_batch: d_out must be 16-byte aligned");
+// ---- batch entry points: one body for uint8 symbols (the tuned kernels first) and uint16 symbols (alphabets up to
+// 65536: the any-parameter kernels) --------------------------------------------------------------------------------------
+template <class SYM>
+static int range_encode(const char *what, const scl_range_model *m, const SYM *d_sym, u64 sym_stride, const u32 *d_lens,
+                        u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
+                        u32 *d_status, hipStream_t st) {
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, d_sym, d_out, d_bit_off, d_nbits, out_stride)) return rc;
     if (n_chunks == 0) return SCL_OK;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    const bool tuned = !scl_force_generic();
     RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
-    if (tuned && m->fast)
-        if (int rc_r = relay.in(d_sym, sym_stride, chunk_len, n_chunks, (hipStream_t)stream)) return rc_r;
-    if (tuned && m->fast && ((uintptr_t)d_sym & 15) == 0 && (sym_stride & 15) == 0)
-        range_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                                 d_out_nbits, d_status, (hipStream_t)stream);
-    else if (m->dev.P <= 32)
-        hipLaunchKernelGGL(range_encode_kernel<u32>, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, m->dev,
-                           d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                           d_out_nbits, d_status);
-    else
-        hipLaunchKernelGGL(range_encode_kernel<u64>, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, m->dev,
-                           d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                           d_out_nbits, d_status);
+    if constexpr (sizeof(SYM) == 1) {
+        const bool tuned = !scl_force_generic();
+        if (tuned && m->fast)
+            if (int rc = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc;
+        if (tuned && m->fast && scl_rows_aligned(d_sym, sym_stride)) {
+            range_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
+                                     d_nbits, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return SCL_OK;
+        }
+    }
+    auto kernel = m->dev.P <= 32 ? range_encode_kernel<u32, SYM> : range_encode_kernel<u64, SYM>;
+    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_sym, sym_stride, d_lens,
+                       chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status);
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
+template <class SYM>
+static int range_decode(const char *what, const scl_range_model *m, const u8 *d_in, u64 in_size_bytes,
+                        const u64 *d_bit_off, const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride,
+                        u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, d_in, d_bit_off, d_in_nbits, d_out_sym, d_out_lens,
+                                  d_consumed))
+        return rc;
+    if (n_chunks == 0) return SCL_OK;
+    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
+    RangeDev dev = m->dev;
+    if constexpr (sizeof(SYM) == 1) {
+        const bool tuned = !scl_force_generic();
+        const bool in_ok = ((uintptr_t)d_in & 15) == 0;
+        if (tuned && m->fast && in_ok)
+            if (int rc = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc;
+        if (tuned && m->fast && in_ok && scl_rows_aligned(d_out_sym, out_stride)) {
+            range_fast_decode_launch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
+                                     out_cap, d_out_lens, d_consumed, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return relay.out_end(d_out_lens);
+        }
+    } else {
+        dev.d_slot2sym = nullptr;  // a table of BYTES: the u16 kernels search the cumulative counts
+    }
+    auto kernel = m->dev.P <= 32 ? range_decode_kernel<u32, SYM> : range_decode_kernel<u64, SYM>;
+    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, dev, d_in, in_size_bytes,
+                       d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status);
+    SCL_HIP_TRY(hipGetLastError());
+    return relay.out_end(d_out_lens);
+}
+
+extern "C" int scl_range_encode_batch(const scl_range_model *m, const uint8_t *d_sym, uint64_t sym_stride,
+                                      const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
+                                      uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
+                                      uint32_t *d_status, void *stream) {
+    return range_encode("range_encode_batch", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                        d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+}
+
+extern "C" int scl_range_decode_batch(const scl_range_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
+                                      const uint64_t *d_bit_offset, const uint32_t *d_in_nbits, uint64_t n_chunks,
+                                      uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
+                                      uint32_t *d_consumed, uint32_t *d_status, void *stream) {
+    return range_decode("range_decode_batch", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                        out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+}
+
+extern "C" int scl_range_encode_batch_u16(const scl_range_model *m, const uint16_t *d_sym, uint64_t sym_stride,
+                                          const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
+                                          uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
+                                          uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
+    return range_encode("range_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                        d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+}
+
+extern "C" int scl_range_decode_batch_u16(const scl_range_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
+                                          const uint64_t *d_bit_offset, const uint32_t *d_in_nbits,
+                                          uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
+                                          uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
+                                          uint32_t *d_status, void *stream) {
+    return range_decode("range_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
+                        d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+}
+
 // ---- wave-striped slots (ABI version 8; scl_range_fast.hip: RgOutT, scl_ans_fast_io.h: AnsBitReaderT) ------------------------
+// No lower bound on out_stride: a slot too short for its stream gives SCL_ST_CAPACITY, as on linear slots.
 extern "C" int scl_range_striped_ok(const scl_range_model *m) {
     return (m && m->dev.K <= 256 && range_fast_striped_ok(m)) ? 1 : 0;
 }
@@ -279,23 +340,15 @@ extern "C" int scl_range_encode_batch_striped(const scl_range_model *m, const ui
                                               const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                               uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                               uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_sym && d_out && d_out_bit_offset && d_out_nbits, "range_encode_batch_striped: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "range_encode_batch_striped")) return rc_dev;
-    SCL_REQUIRE(scl_range_striped_ok(m), "range_encode_batch_striped: this model is not served by the striped kernels");
-    SCL_REQUIRE(!scl_force_generic(), "range_encode_batch_striped: the calling thread keeps the tuned kernels out");
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && out_stride < (1ull << 24) && ((uintptr_t)d_out & 15) == 0,
-                "range_encode_batch_striped: d_out must be 16-byte aligned and out_stride a multiple of 16 below 2^24");
-    if (n_chunks == 0) return SCL_OK;
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid
-    if (int rc_r = relay.in(d_sym, sym_stride, chunk_len, n_chunks, (hipStream_t)stream)) return rc_r;
-    if (!scl_rows_aligned(d_sym, sym_stride)) {
-        scl_set_error("range_encode_batch_striped: out of device memory re-laying unaligned symbol rows");
-        return SCL_E_ALLOC;
-    }
-    range_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                             d_out_nbits, d_status, (hipStream_t)stream, true);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    const char *what = "range_encode_batch_striped";
+    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride))
+        return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    return scl_striped_encode(what, scl_range_striped_ok(m), 0, d_sym, sym_stride, chunk_len, n_chunks, d_out,
+                              out_stride, st, [&](const u8 *sym, u64 stride) {
+                                  range_fast_encode_launch(m, sym, stride, d_lens, chunk_len, n_chunks, d_out,
+                                                           out_stride, d_out_bit_offset, d_out_nbits, d_status, st, true);
+                              });
 }
 
 extern "C" int scl_range_decode_batch_striped(const scl_range_model *m, const uint8_t *d_in, uint64_t in_stride,
@@ -303,160 +356,39 @@ extern "C" int scl_range_decode_batch_striped(const scl_range_model *m, const ui
                                               uint64_t n_chunks, uint8_t *d_out_sym, uint64_t out_stride,
                                               uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                               uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "range_decode_batch_striped: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "range_decode_batch_striped")) return rc_dev;
-    SCL_REQUIRE(scl_range_striped_ok(m), "range_decode_batch_striped: this model is not served by the striped kernels");
-    SCL_REQUIRE(!scl_force_generic(), "range_decode_batch_striped: the calling thread keeps the tuned kernels out");
-    SCL_REQUIRE(((uintptr_t)d_in & 15) == 0 && in_stride % 16 == 0 && in_stride > 0 && in_stride < (1ull << 24),
-                "range_decode_batch_striped: d_in must be 16-byte aligned and in_stride a multiple of 16 below 2^24");
-    if (n_chunks == 0) return SCL_OK;
-    RowRelay relay;  // output rows the kernels cannot store to go through aligned scratch and are copied back
-    if (int rc_r = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, (hipStream_t)stream)) return rc_r;
-    if (!scl_rows_aligned(d_out_sym, out_stride)) {
-        scl_set_error("range_decode_batch_striped: out of device memory re-laying unaligned output rows");
-        return SCL_E_ALLOC;
-    }
-    range_fast_decode_launch(m, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                             d_out_lens, d_consumed, d_status, (hipStream_t)stream, true);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
-}
-
-extern "C" int scl_range_decode_batch(const scl_range_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
-                                      const uint64_t *d_bit_offset, const uint32_t *d_in_nbits, uint64_t n_chunks,
-                                      uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
-                                      uint32_t *d_consumed, uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "range_decode_batch: null pointer argument");
-    SCL_REQUIRE(m->dev.K <= 256, "range_decode_batch: alphabet of %u symbols: use scl_range_decode_batch_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "range_decode_batch")) return rc_dev;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0, "range_decode_batch: d_in must be 4-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    const bool tuned = !scl_force_generic();
-    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
-    if (tuned && m->fast && ((uintptr_t)d_in & 15) == 0)
-        if (int rc_r = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, (hipStream_t)stream)) return rc_r;
-    if (tuned && m->fast && ((uintptr_t)d_in & 15) == 0 && ((uintptr_t)d_out_sym & 15) == 0 && (out_stride & 15) == 0)
-        range_fast_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                 out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
-    else if (m->dev.P <= 32)
-        hipLaunchKernelGGL(range_decode_kernel<u32>, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, m->dev,
-                           d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
-    else
-        hipLaunchKernelGGL(range_decode_kernel<u64>, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, m->dev,
-                           d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
-}
-
-// ---- uint16 symbol indices: alphabets up to 65536 (any model; the any-parameter kernels) ---------------------
-extern "C" int scl_range_encode_batch_u16(const scl_range_model *m, const uint16_t *d_sym, uint64_t sym_stride,
-                                          const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
-                                          uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
-                                          uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_sym && d_out && d_out_bit_offset && d_out_nbits,
-                "range_encode_batch_u16: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "range_encode_batch_u16")) return rc_dev;
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && out_stride * 8 < (1ull << 32),
-                "range_encode_batch_u16: bad out_stride %llu", (unsigned long long)out_stride);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0 && ((uintptr_t)d_sym & 1) == 0,
-                "range_encode_batch_u16: d_out must be 16-byte aligned, d_sym 2-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    if (m->dev.P <= 32)
-        hipLaunchKernelGGL((range_encode_kernel<u32, u16>), dim3(blocks), dim3(threads), 0, (hipStream_t)stream, m->dev,
-                           d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                           d_out_nbits, d_status);
-    else
-        hipLaunchKernelGGL((range_encode_kernel<u64, u16>), dim3(blocks), dim3(threads), 0, (hipStream_t)stream, m->dev,
-                           d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                           d_out_nbits, d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
-}
-
-extern "C" int scl_range_decode_batch_u16(const scl_range_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
-                                          const uint64_t *d_bit_offset, const uint32_t *d_in_nbits,
-                                          uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
-                                          uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
-                                          uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "range_decode_batch_u16: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "range_decode_batch_u16")) return rc_dev;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0 && ((uintptr_t)d_out_sym & 1) == 0,
-                "range_decode_batch_u16: d_in must be 4-byte aligned, d_out_sym 2-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    RangeDev dev = m->dev;
-    dev.d_slot2sym = nullptr;  // a table of BYTES: the u16 kernels search the cumulative counts
-    if (m->dev.P <= 32)
-        hipLaunchKernelGGL((range_decode_kernel<u32, u16>), dim3(blocks), dim3(threads), 0, (hipStream_t)stream, dev,
-                           d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
-    else
-        hipLaunchKernelGGL((range_decode_kernel<u64, u16>), dim3(blocks), dim3(threads), 0, (hipStream_t)stream, dev,
-                           d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    const char *what = "range_decode_batch_striped";
+    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, d_in, d_bit_offset, d_in_nbits, d_out_sym, d_out_lens,
+                                  d_consumed))
+        return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    return scl_striped_decode(what, scl_range_striped_ok(m), d_in, in_stride, n_chunks, d_out_sym, out_stride, out_cap,
+                              d_out_lens, st, [&](u8 *out, u64 stride) {
+                                  range_fast_decode_launch(m, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, out,
+                                                           stride, out_cap, d_out_lens, d_consumed, d_status, st, true);
+                              });
 }
 
 // ---- single-chunk host drivers --------------------------------------------------------------------------
-static int range_run_enc(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                         u32 *d_nbits, u32 *d_status, void *, u64) {
-    return scl_range_encode_batch((const scl_range_model *)model, d_sym, n, nullptr, n, 1, d_out, out_stride,
-                                  d_bit_off, d_nbits, d_status, nullptr);
-}
-static u64 range_slot(const void *model, u64 n) { return scl_range_slot_bytes((const scl_range_model *)model, n); }
-static int range_run_dec(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-                         u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *, u64) {
-    return scl_range_decode_batch((const scl_range_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1, d_out_sym,
-                                  scl_round_up((u64)out_cap + 1, 16), out_cap, d_out_len, d_consumed, d_status,
-                                  nullptr);
-}
-
 extern "C" int scl_range_encode_host(const scl_range_model *m, const uint8_t *h_sym, uint64_t n, uint8_t *h_out,
                                      uint64_t out_cap_bytes, uint64_t *nbits) {
-    HostEncodeCall call = {range_run_enc, range_slot, nullptr};
-    return scl_host_encode_one(call, m, h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(scl_host_encode_call<scl_range_encode_batch, scl_range_slot_bytes>(), m, h_sym, n, h_out,
+                               out_cap_bytes, nbits);
 }
 
 extern "C" int scl_range_decode_host(const scl_range_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                      uint8_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
-    HostDecodeCall call = {range_run_dec, nullptr};
-    return scl_host_decode_one(call, m, h_in, in_nbits, h_out_sym, out_cap, n_out, consumed);
-}
-
-static int range_run_enc16(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                           u32 *d_nbits, u32 *d_status, void *, u64) {
-    return scl_range_encode_batch_u16((const scl_range_model *)model, (const u16 *)d_sym, n, nullptr, n, 1, d_out,
-                                      out_stride, d_bit_off, d_nbits, d_status, nullptr);
-}
-static int range_run_dec16(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off,
-                           const u32 *d_in_nbits, u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed,
-                           u32 *d_status, void *, u64) {
-    return scl_range_decode_batch_u16((const scl_range_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1,
-                                      (u16 *)d_out_sym, (u64)out_cap + 1, out_cap, d_out_len, d_consumed, d_status,
-                                      nullptr);
+    return scl_host_decode_one(scl_host_decode_call<scl_range_decode_batch>(), m, h_in, in_nbits, h_out_sym, out_cap,
+                               n_out, consumed);
 }
 
 extern "C" int scl_range_encode_host_u16(const scl_range_model *m, const uint16_t *h_sym, uint64_t n, uint8_t *h_out,
                                          uint64_t out_cap_bytes, uint64_t *nbits) {
-    HostEncodeCall call = {range_run_enc16, range_slot, nullptr};
-    call.sym_bytes = 2;
-    return scl_host_encode_one(call, m, (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(scl_host_encode_call<scl_range_encode_batch_u16, scl_range_slot_bytes>(), m,
+                               (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
 }
 
 extern "C" int scl_range_decode_host_u16(const scl_range_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                          uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
-    HostDecodeCall call = {range_run_dec16, nullptr};
-    call.sym_bytes = 2;
-    return scl_host_decode_one(call, m, h_in, in_nbits, (u8 *)h_out_sym, out_cap, n_out, consumed);
+    return scl_host_decode_one(scl_host_decode_call<scl_range_decode_batch_u16>(), m, h_in, in_nbits,
+                               (u8 *)h_out_sym, out_cap, n_out, consumed);
 }

@@ -20,7 +20,7 @@
 
 #include <vector>
 
-#include "scl_common.h"
+#include "scl_entry.h"
 
 #include "scl_rans_internal.h"
 
@@ -293,131 +293,131 @@ extern "C" uint64_t scl_rans_slot_bytes(const scl_rans_model *m, uint64_t n_symb
     return scl_round_up((bits + 7) / 8 + 4, 128);
 }
 
-static int check_batch_args(const char *what, const void *m, const void *a, const void *b, const void *c,
-                            const void *d, u64 stride) {
-    SCL_REQUIRE(m && a && b && c && d, "%s: null pointer argument", what);
-    SCL_REQUIRE(stride % 16 == 0 && stride > 0, "%s: stream stride %llu is not a positive multiple of 16", what,
-                (unsigned long long)stride);
+// ---- batch entry points: one body for uint8 symbols (the tuned kernels first) and uint16 symbols (alphabets up to
+// 65536: the any-parameter kernels) --------------------------------------------------------------------------------------
+template <class SYM>
+static int rans_encode(const char *what, const scl_rans_model *m, const SYM *d_sym, u64 sym_stride, const u32 *d_lens,
+                       u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
+                       u32 *d_status, hipStream_t st) {
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, d_sym, d_out, d_bit_off, d_nbits, out_stride)) return rc;
+    if (n_chunks == 0) return SCL_OK;
+    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
+    if constexpr (sizeof(SYM) == 1) {
+        const bool tuned = !scl_force_generic();
+        const bool fits = out_stride >= scl_rans_slot_bytes(m, chunk_len);  // the tuned kernels have no capacity check
+        if (tuned && (m->fast || m->fastb) && fits)
+            if (int rc = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc;
+        const bool rows_ok = scl_rows_aligned(d_sym, sym_stride);
+        if (tuned && m->fast && rows_ok && fits && out_stride < (1ull << 24)) {  // 256 slots within 32-bit offsets
+            rans_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
+                                    d_nbits, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return SCL_OK;
+        }
+        if (tuned && m->fastb && rows_ok && fits) {
+            rans_fastb_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
+                                     d_nbits, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return SCL_OK;
+        }
+    }
+    auto kernel = m->state32 ? rans_encode_generic<u32, SYM> : rans_encode_generic<u64, SYM>;
+    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_sym, sym_stride, d_lens,
+                       chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status);
+    SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
+}
+
+template <class SYM>
+static int rans_decode(const char *what, const scl_rans_model *m, const u8 *d_in, u64 in_size_bytes,
+                       const u64 *d_bit_off, const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride,
+                       u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, d_in, d_bit_off, d_in_nbits, d_out_sym, d_out_lens,
+                                  d_consumed))
+        return rc;
+    if (n_chunks == 0) return SCL_OK;
+    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
+    if constexpr (sizeof(SYM) == 1) {
+        const bool tuned = !scl_force_generic();
+        const bool in_ok = ((uintptr_t)d_in & 15) == 0;
+        if (tuned && (m->fast || m->fastb) && in_ok)
+            if (int rc = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc;
+        const bool rows_ok = in_ok && scl_rows_aligned(d_out_sym, out_stride);
+        if (tuned && m->fast && rows_ok) {
+            rans_fast_decode_launch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
+                                    out_cap, d_out_lens, d_consumed, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return relay.out_end(d_out_lens);
+        }
+        if (tuned && m->fastb && rows_ok) {
+            rans_fastb_decode_launch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
+                                     out_cap, d_out_lens, d_consumed, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return relay.out_end(d_out_lens);
+        }
+    }
+    auto kernel = m->state32 ? rans_decode_generic<u32, SYM> : rans_decode_generic<u64, SYM>;
+    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_in, in_size_bytes,
+                       d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status);
+    SCL_HIP_TRY(hipGetLastError());
+    return relay.out_end(d_out_lens);
 }
 
 extern "C" int scl_rans_encode_batch(const scl_rans_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                      const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                      uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                      uint32_t *d_status, void *stream) {
-    int rc = check_batch_args("rans_encode_batch", m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride);
-    if (rc) return rc;
-    SCL_REQUIRE(m->dev.K <= 256, "rans_encode_batch: alphabet of %u symbols: use scl_rans_encode_batch_u16", m->dev.K);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0, "rans_encode_batch: d_out must be 16-byte aligned");
-    if (int rc_dev = scl_check_device(m->device, "rans_encode_batch")) return rc_dev;
-    SCL_REQUIRE(out_stride * 8 < (1ull << 32), "rans_encode_batch: slot larger than 512 MiB");
-    if (n_chunks == 0) return SCL_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    const bool tuned = !scl_force_generic();
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
-    if (tuned && (m->fast || m->fastb) && out_stride >= scl_rans_slot_bytes(m, chunk_len))
-        if (int rc_r = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc_r;
-    // fast path: qualifying model, 16-byte aligned rows, and slots that cannot overflow (it has no capacity check)
-    if (tuned && m->fast && ((uintptr_t)d_sym & 15) == 0 && (sym_stride & 15) == 0 &&
-        out_stride >= scl_rans_slot_bytes(m, chunk_len) && out_stride < (1ull << 24))  // 256 slots within 32-bit offsets
-        rans_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                                d_out_bit_offset, d_out_nbits, d_status, st);
-    else if (tuned && m->fastb && ((uintptr_t)d_sym & 15) == 0 && (sym_stride & 15) == 0 &&
-             out_stride >= scl_rans_slot_bytes(m, chunk_len))
-        rans_fastb_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                                 d_out_bit_offset, d_out_nbits, d_status, st);
-    else if (m->state32)
-        hipLaunchKernelGGL(rans_encode_generic<u32>, dim3(blocks), dim3(threads), 0, st, m->dev, d_sym, sym_stride,
-                           d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status);
-    else
-        hipLaunchKernelGGL(rans_encode_generic<u64>, dim3(blocks), dim3(threads), 0, st, m->dev, d_sym, sym_stride,
-                           d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return rans_encode("rans_encode_batch", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                       d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
 }
 
 extern "C" int scl_rans_decode_batch(const scl_rans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
                                      const uint64_t *d_bit_offset, const uint32_t *d_in_nbits, uint64_t n_chunks,
                                      uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
                                      uint32_t *d_consumed, uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "rans_decode_batch: null pointer argument");
-    SCL_REQUIRE(m->dev.K <= 256, "rans_decode_batch: alphabet of %u symbols: use scl_rans_decode_batch_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "rans_decode_batch")) return rc_dev;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0, "rans_decode_batch: d_in must be 4-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    const bool tuned = !scl_force_generic();
-    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
-    if (tuned && (m->fast || m->fastb) && ((uintptr_t)d_in & 15) == 0)
-        if (int rc_r = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc_r;
-    if (tuned && m->fast && ((uintptr_t)d_in & 15) == 0 && ((uintptr_t)d_out_sym & 15) == 0 && (out_stride & 15) == 0)
-        rans_fast_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                out_cap, d_out_lens, d_consumed, d_status, st);
-    else if (tuned && m->fastb && ((uintptr_t)d_in & 15) == 0 && ((uintptr_t)d_out_sym & 15) == 0 && (out_stride & 15) == 0)
-        rans_fastb_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                 out_cap, d_out_lens, d_consumed, d_status, st);
-    else if (m->state32)
-        hipLaunchKernelGGL(rans_decode_generic<u32>, dim3(blocks), dim3(threads), 0, st, m->dev, d_in, in_size_bytes,
-                           d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed,
-                           d_status);
-    else
-        hipLaunchKernelGGL(rans_decode_generic<u64>, dim3(blocks), dim3(threads), 0, st, m->dev, d_in, in_size_bytes,
-                           d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed,
-                           d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
+    return rans_decode("rans_decode_batch", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                       out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
 }
 
-// ---- uint16 symbol indices: alphabets up to 65536 (any model; the any-parameter kernels) -------------------
+extern "C" int scl_rans_encode_batch_u16(const scl_rans_model *m, const uint16_t *d_sym, uint64_t sym_stride,
+                                         const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
+                                         uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
+                                         uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
+    return rans_encode("rans_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                       d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+}
+
+extern "C" int scl_rans_decode_batch_u16(const scl_rans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
+                                         const uint64_t *d_bit_offset, const uint32_t *d_in_nbits,
+                                         uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
+                                         uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
+                                         uint32_t *d_status, void *stream) {
+    return rans_decode("rans_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                       out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+}
+
 // ---- wave-striped slots (ABI version 8; scl_ans_fast_io.h: AnsBackWriterT / AnsBitReaderT) -----------------------------
 // The same streams at the same LOGICAL bit positions, the 64 slots of a wave interleaved in 16-byte pieces in memory.
-// Only the tuned kernels have a striped form: a model they do not serve is refused (scl_rans_striped_ok says so up front),
-// and so is a call made while the calling thread keeps the tuned kernels out (scl_set_any_parameter_kernels).
+// Only the tuned kernels have a striped form (scl_entry.h: scl_striped_encode / scl_striped_decode).  These two bodies
+// serve the rANS entry points and the tANS models the table-free rANS kernels serve (their bound: the rANS model's slot).
 int rans_striped_encode(const char *what, const scl_rans_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
                         u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
                         u32 *d_status, hipStream_t st) {
-    SCL_REQUIRE(m->fast && m->dev.K <= 256, "%s: this model is not served by the striped kernels (see scl_*_striped_ok)", what);
-    SCL_REQUIRE(!scl_force_generic(), "%s: the calling thread keeps the tuned kernels out; striped slots have no other", what);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0, "%s: d_out must be 16-byte aligned", what);
-    SCL_REQUIRE(out_stride >= scl_rans_slot_bytes(m, chunk_len) && out_stride < (1ull << 24),
-                "%s: out_stride %llu: striped slots need scl_*_slot_bytes(chunk_len) <= out_stride < 2^24", what,
-                (unsigned long long)out_stride);
-    if (n_chunks == 0) return SCL_OK;
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid
-    if (int rc_r = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc_r;
-    if (!scl_rows_aligned(d_sym, sym_stride)) {
-        scl_set_error("%s: out of device memory re-laying unaligned symbol rows (hipMallocAsync failed)", what);
-        return SCL_E_ALLOC;
-    }
-    rans_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits,
-                            d_status, st, true);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return scl_striped_encode(what, scl_rans_striped_ok(m), scl_rans_slot_bytes(m, chunk_len), d_sym, sym_stride,
+                              chunk_len, n_chunks, d_out, out_stride, st, [&](const u8 *sym, u64 stride) {
+                                  rans_fast_encode_launch(m, sym, stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                                                          d_bit_off, d_nbits, d_status, st, true);
+                              });
 }
 
 int rans_striped_decode(const char *what, const scl_rans_model *m, const u8 *d_in, u64 in_stride, const u64 *d_bit_off,
                         const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap, u32 *d_out_lens,
                         u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    SCL_REQUIRE(m->fast && m->dev.K <= 256, "%s: this model is not served by the striped kernels (see scl_*_striped_ok)", what);
-    SCL_REQUIRE(!scl_force_generic(), "%s: the calling thread keeps the tuned kernels out; striped slots have no other", what);
-    SCL_REQUIRE(((uintptr_t)d_in & 15) == 0 && in_stride % 16 == 0 && in_stride > 0 && in_stride < (1ull << 24),
-                "%s: d_in must be 16-byte aligned and in_stride a multiple of 16 below 2^24", what);
-    if (n_chunks == 0) return SCL_OK;
-    RowRelay relay;  // output rows the kernels cannot store to go through aligned scratch and are copied back
-    if (int rc_r = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc_r;
-    if (!scl_rows_aligned(d_out_sym, out_stride)) {
-        scl_set_error("%s: out of device memory re-laying unaligned output rows (hipMallocAsync failed)", what);
-        return SCL_E_ALLOC;
-    }
-    rans_fast_decode_launch(m, d_in, in_stride, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                            d_out_lens, d_consumed, d_status, st, true);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
+    return scl_striped_decode(what, scl_rans_striped_ok(m), d_in, in_stride, n_chunks, d_out_sym, out_stride, out_cap,
+                              d_out_lens, st, [&](u8 *out, u64 stride) {
+                                  rans_fast_decode_launch(m, d_in, in_stride, d_bit_off, d_in_nbits, n_chunks, out, stride,
+                                                          out_cap, d_out_lens, d_consumed, d_status, st, true);
+                              });
 }
 
 extern "C" int scl_rans_striped_ok(const scl_rans_model *m) { return (m && m->fast && m->dev.K <= 256) ? 1 : 0; }
@@ -434,11 +434,11 @@ extern "C" int scl_rans_encode_batch_striped(const scl_rans_model *m, const uint
                                              const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                              uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                              uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    int rc = check_batch_args("rans_encode_batch_striped", m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride);
-    if (rc) return rc;
-    if (int rc_dev = scl_check_device(m->device, "rans_encode_batch_striped")) return rc_dev;
-    return rans_striped_encode("rans_encode_batch_striped", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
-                               out_stride, d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    const char *what = "rans_encode_batch_striped";
+    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride))
+        return rc;
+    return rans_striped_encode(what, m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                               d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
 }
 
 extern "C" int scl_rans_decode_batch_striped(const scl_rans_model *m, const uint8_t *d_in, uint64_t in_stride,
@@ -446,112 +446,35 @@ extern "C" int scl_rans_decode_batch_striped(const scl_rans_model *m, const uint
                                              uint64_t n_chunks, uint8_t *d_out_sym, uint64_t out_stride,
                                              uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                              uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "rans_decode_batch_striped: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "rans_decode_batch_striped")) return rc_dev;
-    return rans_striped_decode("rans_decode_batch_striped", m, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks,
-                               d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
-}
-
-extern "C" int scl_rans_encode_batch_u16(const scl_rans_model *m, const uint16_t *d_sym, uint64_t sym_stride,
-                                         const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
-                                         uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
-                                         uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    int rc = check_batch_args("rans_encode_batch_u16", m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride);
-    if (rc) return rc;
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0 && ((uintptr_t)d_sym & 1) == 0,
-                "rans_encode_batch_u16: d_out must be 16-byte aligned, d_sym 2-byte aligned");
-    if (int rc_dev = scl_check_device(m->device, "rans_encode_batch_u16")) return rc_dev;
-    SCL_REQUIRE(out_stride * 8 < (1ull << 32), "rans_encode_batch_u16: slot larger than 512 MiB");
-    if (n_chunks == 0) return SCL_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    if (m->state32)
-        hipLaunchKernelGGL((rans_encode_generic<u32, u16>), dim3(blocks), dim3(threads), 0, st, m->dev, d_sym,
-                           sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits,
-                           d_status);
-    else
-        hipLaunchKernelGGL((rans_encode_generic<u64, u16>), dim3(blocks), dim3(threads), 0, st, m->dev, d_sym,
-                           sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits,
-                           d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
-}
-
-extern "C" int scl_rans_decode_batch_u16(const scl_rans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
-                                         const uint64_t *d_bit_offset, const uint32_t *d_in_nbits,
-                                         uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
-                                         uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
-                                         uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "rans_decode_batch_u16: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "rans_decode_batch_u16")) return rc_dev;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0 && ((uintptr_t)d_out_sym & 1) == 0,
-                "rans_decode_batch_u16: d_in must be 4-byte aligned, d_out_sym 2-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    if (m->state32)
-        hipLaunchKernelGGL((rans_decode_generic<u32, u16>), dim3(blocks), dim3(threads), 0, st, m->dev, d_in,
-                           in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
-    else
-        hipLaunchKernelGGL((rans_decode_generic<u64, u16>), dim3(blocks), dim3(threads), 0, st, m->dev, d_in,
-                           in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    const char *what = "rans_decode_batch_striped";
+    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, d_in, d_bit_offset, d_in_nbits, d_out_sym, d_out_lens,
+                                  d_consumed))
+        return rc;
+    return rans_striped_decode(what, m, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
+                               out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
 }
 
 // ---- single-chunk host drivers ------------------------------------------------------------------------
-static int rans_run_enc(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                        u32 *d_nbits, u32 *d_status, void *, u64) {
-    return scl_rans_encode_batch((const scl_rans_model *)model, d_sym, n, nullptr, n, 1, d_out, out_stride, d_bit_off,
-                                 d_nbits, d_status, nullptr);
-}
-static u64 rans_slot(const void *model, u64 n) { return scl_rans_slot_bytes((const scl_rans_model *)model, n); }
-static int rans_run_dec(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-                        u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *, u64) {
-    return scl_rans_decode_batch((const scl_rans_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1, d_out_sym,
-                                 scl_round_up((u64)out_cap + 1, 16), out_cap, d_out_len, d_consumed, d_status, nullptr);
-}
-
 extern "C" int scl_rans_encode_host(const scl_rans_model *m, const uint8_t *h_sym, uint64_t n, uint8_t *h_out,
                                     uint64_t out_cap_bytes, uint64_t *nbits) {
-    HostEncodeCall call = {rans_run_enc, rans_slot, nullptr};
-    return scl_host_encode_one(call, m, h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(scl_host_encode_call<scl_rans_encode_batch, scl_rans_slot_bytes>(), m, h_sym, n, h_out,
+                               out_cap_bytes, nbits);
 }
 
 extern "C" int scl_rans_decode_host(const scl_rans_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                     uint8_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
-    HostDecodeCall call = {rans_run_dec, nullptr};
-    return scl_host_decode_one(call, m, h_in, in_nbits, h_out_sym, out_cap, n_out, consumed);
-}
-
-static int rans_run_enc16(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                          u32 *d_nbits, u32 *d_status, void *, u64) {
-    return scl_rans_encode_batch_u16((const scl_rans_model *)model, (const u16 *)d_sym, n, nullptr, n, 1, d_out,
-                                     out_stride, d_bit_off, d_nbits, d_status, nullptr);
-}
-static int rans_run_dec16(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-                          u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *, u64) {
-    return scl_rans_decode_batch_u16((const scl_rans_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1,
-                                     (u16 *)d_out_sym, (u64)out_cap + 1, out_cap, d_out_len, d_consumed, d_status,
-                                     nullptr);
+    return scl_host_decode_one(scl_host_decode_call<scl_rans_decode_batch>(), m, h_in, in_nbits, h_out_sym, out_cap,
+                               n_out, consumed);
 }
 
 extern "C" int scl_rans_encode_host_u16(const scl_rans_model *m, const uint16_t *h_sym, uint64_t n, uint8_t *h_out,
                                         uint64_t out_cap_bytes, uint64_t *nbits) {
-    HostEncodeCall call = {rans_run_enc16, rans_slot, nullptr};
-    call.sym_bytes = 2;
-    return scl_host_encode_one(call, m, (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(scl_host_encode_call<scl_rans_encode_batch_u16, scl_rans_slot_bytes>(), m,
+                               (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
 }
 
 extern "C" int scl_rans_decode_host_u16(const scl_rans_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                         uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
-    HostDecodeCall call = {rans_run_dec16, nullptr};
-    call.sym_bytes = 2;
-    return scl_host_decode_one(call, m, h_in, in_nbits, (u8 *)h_out_sym, out_cap, n_out, consumed);
+    return scl_host_decode_one(scl_host_decode_call<scl_rans_decode_batch_u16>(), m, h_in, in_nbits, (u8 *)h_out_sym,
+                               out_cap, n_out, consumed);
 }

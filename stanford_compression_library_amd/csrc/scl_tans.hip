@@ -17,6 +17,7 @@
 
 #include <vector>
 
+#include "scl_entry.h"
 #include "scl_tans_internal.h"
 #include "scl_rans_internal.h"
 
@@ -397,17 +398,16 @@ extern "C" int scl_tans_kernel_names_striped(const scl_tans_model *m, uint64_t n
     return SCL_OK;
 }
 
+// (the rANS model serves exactly the tANS models scl_tans_striped_ok names: rans_striped_* refuse the others)
 extern "C" int scl_tans_encode_batch_striped(const scl_tans_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                              const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                              uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                              uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_sym && d_out && d_out_bit_offset && d_out_nbits, "tans_encode_batch_striped: null pointer argument");
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0, "tans_encode_batch_striped: bad out_stride %llu",
-                (unsigned long long)out_stride);
-    if (int rc_dev = scl_check_device(m->device, "tans_encode_batch_striped")) return rc_dev;
-    SCL_REQUIRE(scl_tans_striped_ok(m), "tans_encode_batch_striped: this model is not served by the striped kernels");
-    return rans_striped_encode("tans_encode_batch_striped", m->rans, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
-                               out_stride, d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    const char *what = "tans_encode_batch_striped";
+    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride))
+        return rc;
+    return rans_striped_encode(what, m->rans, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                               d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
 }
 
 extern "C" int scl_tans_decode_batch_striped(const scl_tans_model *m, const uint8_t *d_in, uint64_t in_stride,
@@ -415,135 +415,130 @@ extern "C" int scl_tans_decode_batch_striped(const scl_tans_model *m, const uint
                                              uint64_t n_chunks, uint8_t *d_out_sym, uint64_t out_stride,
                                              uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                              uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "tans_decode_batch_striped: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "tans_decode_batch_striped")) return rc_dev;
-    SCL_REQUIRE(scl_tans_striped_ok(m), "tans_decode_batch_striped: this model is not served by the striped kernels");
-    return rans_striped_decode("tans_decode_batch_striped", m->rans, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks,
-                               d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    const char *what = "tans_decode_batch_striped";
+    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, d_in, d_bit_offset, d_in_nbits, d_out_sym, d_out_lens,
+                                  d_consumed))
+        return rc;
+    return rans_striped_decode(what, m->rans, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
+                               out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+}
+
+// ---- batch entry points: one body for uint8 symbols (the tuned kernels first) and uint16 symbols (alphabets up to
+// 65536: lookup tables in device memory) -----------------------------------------------------------------------------
+template <class SYM>
+static int tans_encode(const char *what, const scl_tans_model *m, const SYM *d_sym, u64 sym_stride, const u32 *d_lens,
+                       u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
+                       u32 *d_status, hipStream_t st) {
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, d_sym, d_out, d_bit_off, d_nbits, out_stride)) return rc;
+    if (n_chunks == 0) return SCL_OK;
+    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
+    if constexpr (sizeof(SYM) == 1) {
+        const bool tuned = !scl_force_generic();
+        const bool table_first = m->fast && tans_table_kernels_forced();  // else the table-free kernels when the model has them
+        if ((tuned || !m->tables) && (m->fast || m->rans))
+            if (int rc = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc;
+        const bool rows_ok = scl_rows_aligned(d_sym, sym_stride);
+        const bool fast_ok = tuned && m->fast && rows_ok && out_stride >= scl_tans_slot_bytes(m, chunk_len);
+        // same stream from the table-free rANS kernels (32-bit slot offsets per workgroup)
+        const bool rans_ok = (tuned || !m->tables) && m->rans && rows_ok &&
+                             out_stride >= scl_rans_slot_bytes(m->rans, chunk_len) && out_stride < (1ull << 24);
+        if (rans_ok && !(table_first && fast_ok)) {
+            rans_fast_encode_launch(m->rans, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
+                                    d_nbits, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return SCL_OK;
+        }
+        if (fast_ok) {
+            tans_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
+                                    d_nbits, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return SCL_OK;
+        }
+        if (!m->tables && relay.failed) {  // the rows WERE the problem, and the scratch to re-lay them could not be had
+            scl_set_error("%s: out of device memory re-laying unaligned symbol rows (hipMallocAsync failed) and this "
+                          "model has no lookup tables for the any-parameter kernels", what);
+            return SCL_E_ALLOC;
+        }
+    }
+    SCL_REQUIRE(m->tables, "%s: this model has no lookup tables (RANGE_FACTOR*M > 2^26)%s", what,
+                sizeof(SYM) == 1 ? "; it needs 16-byte aligned symbol rows and slots of scl_tans_slot_bytes" : "");
+    if (int rc = tans_ensure_tables(m)) return rc;
+    const u32 lds = sizeof(SYM) == 1 ? (768 + (m->dev.lds_tables ? m->dev.L : 0)) * sizeof(u32) : 16;
+    hipLaunchKernelGGL(tans_encode_kernel<SYM>, dim3((u32)((n_chunks + 255) / 256)), dim3(256), lds, st, m->dev, d_sym,
+                       sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status);
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+template <class SYM>
+static int tans_decode(const char *what, const scl_tans_model *m, const u8 *d_in, u64 in_size_bytes,
+                       const u64 *d_bit_off, const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride,
+                       u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, d_in, d_bit_off, d_in_nbits, d_out_sym, d_out_lens,
+                                  d_consumed))
+        return rc;
+    if (n_chunks == 0) return SCL_OK;
+    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
+    if constexpr (sizeof(SYM) == 1) {
+        const bool tuned = !scl_force_generic();
+        const bool in_ok = ((uintptr_t)d_in & 15) == 0;
+        if ((tuned || !m->tables) && (m->fast || m->rans) && in_ok)
+            if (int rc = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc;
+        const bool table_first = m->fast && tans_table_kernels_forced();
+        const bool bufs_ok = in_ok && scl_rows_aligned(d_out_sym, out_stride);
+        const bool fast_ok = tuned && m->fast && bufs_ok;
+        const bool rans_ok = (tuned || !m->tables) && m->rans && bufs_ok;
+        if (rans_ok && !(table_first && fast_ok)) {
+            rans_fast_decode_launch(m->rans, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
+                                    out_cap, d_out_lens, d_consumed, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return relay.out_end(d_out_lens);
+        }
+        if (fast_ok) {
+            tans_fast_decode_launch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
+                                    out_cap, d_out_lens, d_consumed, d_status, st);
+            SCL_HIP_TRY(hipGetLastError());
+            return relay.out_end(d_out_lens);
+        }
+        if (!m->tables && relay.failed) {
+            scl_set_error("%s: out of device memory re-laying unaligned output rows (hipMallocAsync failed) and this "
+                          "model has no lookup tables for the any-parameter kernels", what);
+            return SCL_E_ALLOC;
+        }
+    }
+    SCL_REQUIRE(m->tables, "%s: this model has no lookup tables (RANGE_FACTOR*M > 2^26)%s", what,
+                sizeof(SYM) == 1 ? "; it needs 16-byte aligned buffers" : "");
+    if (int rc = tans_ensure_tables(m)) return rc;
+    const u32 lds = (m->dev.lds_tables ? 2 * m->dev.L : 4) * sizeof(u32);
+    hipLaunchKernelGGL(tans_decode_kernel<SYM>, dim3((u32)((n_chunks + 255) / 256)), dim3(256), lds, st, m->dev, d_in,
+                       in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
+                       d_consumed, d_status);
+    SCL_HIP_TRY(hipGetLastError());
+    return relay.out_end(d_out_lens);
 }
 
 extern "C" int scl_tans_encode_batch(const scl_tans_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                      const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                      uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                      uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_sym && d_out && d_out_bit_offset && d_out_nbits, "tans_encode_batch: null pointer argument");
-    SCL_REQUIRE(m->dev.K <= 256, "tans_encode_batch: alphabet of %u symbols: use scl_tans_encode_batch_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "tans_encode_batch")) return rc_dev;
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && out_stride * 8 < (1ull << 32),
-                "tans_encode_batch: bad out_stride %llu", (unsigned long long)out_stride);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0, "tans_encode_batch: d_out must be 16-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    const bool tuned = !scl_force_generic();
-    const bool table_first = m->fast && tans_table_kernels_forced();  // else the table-free kernels when the model has them
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
-    if ((tuned || !m->tables) && (m->fast || m->rans))
-        if (int rc_r = relay.in(d_sym, sym_stride, chunk_len, n_chunks, (hipStream_t)stream)) return rc_r;
-    const bool rows_ok = ((uintptr_t)d_sym & 15) == 0 && (sym_stride & 15) == 0;
-    const bool fast_ok = tuned && m->fast && rows_ok && out_stride >= scl_tans_slot_bytes(m, chunk_len);
-    // same stream from the table-free rANS kernels (32-bit slot offsets per workgroup)
-    const bool rans_ok = (tuned || !m->tables) && m->rans && rows_ok &&
-                         out_stride >= scl_rans_slot_bytes(m->rans, chunk_len) && out_stride < (1ull << 24);
-    if (rans_ok && !(table_first && fast_ok)) {
-        rans_fast_encode_launch(m->rans, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                                d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
-        SCL_HIP_TRY(hipGetLastError());
-        return SCL_OK;
-    }
-    if (fast_ok) {
-        tans_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                                d_out_nbits, d_status, (hipStream_t)stream);
-        SCL_HIP_TRY(hipGetLastError());
-        return SCL_OK;
-    }
-    if (!m->tables && relay.failed) {  // the rows WERE the problem, and the scratch to re-lay them could not be had
-        scl_set_error("tans_encode_batch: out of device memory re-laying unaligned symbol rows (hipMallocAsync failed) and "
-                      "this model has no lookup tables for the any-parameter kernels");
-        return SCL_E_ALLOC;
-    }
-    SCL_REQUIRE(m->tables, "tans_encode_batch: this model has no lookup tables (RANGE_FACTOR*M > 2^26); it needs "
-                           "16-byte aligned symbol rows and slots of scl_tans_slot_bytes");
-    if (int rc = tans_ensure_tables(m)) return rc;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    const u32 lds = (768 + (m->dev.lds_tables ? m->dev.L : 0)) * sizeof(u32);
-    hipLaunchKernelGGL(tans_encode_kernel<u8>, dim3(blocks), dim3(threads), lds, (hipStream_t)stream, m->dev, d_sym,
-                       sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits,
-                       d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return tans_encode("tans_encode_batch", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                       d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
 }
 
 extern "C" int scl_tans_decode_batch(const scl_tans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
                                      const uint64_t *d_bit_offset, const uint32_t *d_in_nbits, uint64_t n_chunks,
                                      uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
                                      uint32_t *d_consumed, uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "tans_decode_batch: null pointer argument");
-    SCL_REQUIRE(m->dev.K <= 256, "tans_decode_batch: alphabet of %u symbols: use scl_tans_decode_batch_u16", m->dev.K);
-    if (int rc_dev = scl_check_device(m->device, "tans_decode_batch")) return rc_dev;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0, "tans_decode_batch: d_in must be 4-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    const bool tuned = !scl_force_generic();
-    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
-    if ((tuned || !m->tables) && (m->fast || m->rans) && ((uintptr_t)d_in & 15) == 0)
-        if (int rc_r = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, (hipStream_t)stream)) return rc_r;
-    const bool table_first = m->fast && tans_table_kernels_forced();
-    const bool bufs_ok = ((uintptr_t)d_in & 15) == 0 && ((uintptr_t)d_out_sym & 15) == 0 && (out_stride & 15) == 0;
-    const bool fast_ok = tuned && m->fast && bufs_ok;
-    const bool rans_ok = (tuned || !m->tables) && m->rans && bufs_ok;
-    if (rans_ok && !(table_first && fast_ok)) {
-        rans_fast_decode_launch(m->rans, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
-        SCL_HIP_TRY(hipGetLastError());
-        return relay.out_end(d_out_lens);
-    }
-    if (fast_ok) {
-        tans_fast_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
-        SCL_HIP_TRY(hipGetLastError());
-        return relay.out_end(d_out_lens);
-    }
-    if (!m->tables && relay.failed) {
-        scl_set_error("tans_decode_batch: out of device memory re-laying unaligned output rows (hipMallocAsync failed) and "
-                      "this model has no lookup tables for the any-parameter kernels");
-        return SCL_E_ALLOC;
-    }
-    SCL_REQUIRE(m->tables, "tans_decode_batch: this model has no lookup tables (RANGE_FACTOR*M > 2^26); it needs "
-                           "16-byte aligned buffers");
-    if (int rc = tans_ensure_tables(m)) return rc;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    const u32 lds = (m->dev.lds_tables ? 2 * m->dev.L : 4) * sizeof(u32);
-    hipLaunchKernelGGL(tans_decode_kernel<u8>, dim3(blocks), dim3(threads), lds, (hipStream_t)stream, m->dev, d_in,
-                       in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
-                       d_consumed, d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
+    return tans_decode("tans_decode_batch", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                       out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
 }
 
-// ---- uint16 symbol indices: alphabets up to 65536 (lookup tables in device memory) --------------------------
 extern "C" int scl_tans_encode_batch_u16(const scl_tans_model *m, const uint16_t *d_sym, uint64_t sym_stride,
                                          const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                          uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                          uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_sym && d_out && d_out_bit_offset && d_out_nbits,
-                "tans_encode_batch_u16: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "tans_encode_batch_u16")) return rc_dev;
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && out_stride * 8 < (1ull << 32),
-                "tans_encode_batch_u16: bad out_stride %llu", (unsigned long long)out_stride);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0 && ((uintptr_t)d_sym & 1) == 0,
-                "tans_encode_batch_u16: d_out must be 16-byte aligned, d_sym 2-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    SCL_REQUIRE(m->tables, "tans_encode_batch_u16: this model has no lookup tables (RANGE_FACTOR*M > 2^26)");
-    if (int rc = tans_ensure_tables(m)) return rc;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    hipLaunchKernelGGL(tans_encode_kernel<u16>, dim3(blocks), dim3(threads), 16, (hipStream_t)stream, m->dev, d_sym,
-                       sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits,
-                       d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return tans_encode("tans_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
+                       d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
 }
 
 extern "C" int scl_tans_decode_batch_u16(const scl_tans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -551,73 +546,34 @@ extern "C" int scl_tans_decode_batch_u16(const scl_tans_model *m, const uint8_t 
                                          uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
                                          uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                          uint32_t *d_status, void *stream) {
-    SCL_REQUIRE(m && d_in && d_bit_offset && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
-                "tans_decode_batch_u16: null pointer argument");
-    if (int rc_dev = scl_check_device(m->device, "tans_decode_batch_u16")) return rc_dev;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0 && ((uintptr_t)d_out_sym & 1) == 0,
-                "tans_decode_batch_u16: d_in must be 4-byte aligned, d_out_sym 2-byte aligned");
-    if (n_chunks == 0) return SCL_OK;
-    SCL_REQUIRE(m->tables, "tans_decode_batch_u16: this model has no lookup tables (RANGE_FACTOR*M > 2^26)");
-    if (int rc = tans_ensure_tables(m)) return rc;
-    const u32 threads = 256;
-    const u32 blocks = (u32)((n_chunks + threads - 1) / threads);
-    const u32 lds = (m->dev.lds_tables ? 2 * m->dev.L : 4) * sizeof(u32);
-    hipLaunchKernelGGL(tans_decode_kernel<u16>, dim3(blocks), dim3(threads), lds, (hipStream_t)stream, m->dev, d_in,
-                       in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
-                       d_consumed, d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return tans_decode("tans_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                       out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
 }
 
 // ---- single-chunk host drivers --------------------------------------------------------------------------
-static int tans_run_enc(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                        u32 *d_nbits, u32 *d_status, void *, u64) {
-    const scl_tans_model *m = (const scl_tans_model *)model;
-    // one row: its stride is free, and a multiple of 16 lets a table-less model reach the kernels that serve it
-    return scl_tans_encode_batch(m, d_sym, (m->tables && !m->rans) ? n : scl_round_up(n, 16), nullptr, n, 1, d_out, out_stride,
-                                 d_bit_off, d_nbits, d_status, nullptr);
-}
-static u64 tans_slot(const void *model, u64 n) { return scl_tans_slot_bytes((const scl_tans_model *)model, n); }
-static int tans_run_dec(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-                        u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *, u64) {
-    return scl_tans_decode_batch((const scl_tans_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1, d_out_sym,
-                                 scl_round_up((u64)out_cap + 1, 16), out_cap, d_out_len, d_consumed, d_status, nullptr);
-}
+// one byte row: its stride is free, and a multiple of 16 lets a table-less model reach the kernels that serve it
+static u64 tans_row_stride(const scl_tans_model *m, u64 n) { return (m->tables && !m->rans) ? n : scl_round_up(n, 16); }
 
 extern "C" int scl_tans_encode_host(const scl_tans_model *m, const uint8_t *h_sym, uint64_t n, uint8_t *h_out,
                                     uint64_t out_cap_bytes, uint64_t *nbits) {
-    HostEncodeCall call = {tans_run_enc, tans_slot, nullptr};
-    return scl_host_encode_one(call, m, h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(scl_host_encode_call<scl_tans_encode_batch, scl_tans_slot_bytes, nullptr, tans_row_stride>(),
+                               m, h_sym, n, h_out, out_cap_bytes, nbits);
 }
 
 extern "C" int scl_tans_decode_host(const scl_tans_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                     uint8_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
-    HostDecodeCall call = {tans_run_dec, nullptr};
-    return scl_host_decode_one(call, m, h_in, in_nbits, h_out_sym, out_cap, n_out, consumed);
-}
-
-static int tans_run_enc16(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                          u32 *d_nbits, u32 *d_status, void *, u64) {
-    return scl_tans_encode_batch_u16((const scl_tans_model *)model, (const u16 *)d_sym, n, nullptr, n, 1, d_out,
-                                     out_stride, d_bit_off, d_nbits, d_status, nullptr);
-}
-static int tans_run_dec16(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-                          u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *, u64) {
-    return scl_tans_decode_batch_u16((const scl_tans_model *)model, d_in, in_bytes, d_bit_off, d_in_nbits, 1,
-                                     (u16 *)d_out_sym, (u64)out_cap + 1, out_cap, d_out_len, d_consumed, d_status,
-                                     nullptr);
+    return scl_host_decode_one(scl_host_decode_call<scl_tans_decode_batch>(), m, h_in, in_nbits, h_out_sym, out_cap,
+                               n_out, consumed);
 }
 
 extern "C" int scl_tans_encode_host_u16(const scl_tans_model *m, const uint16_t *h_sym, uint64_t n, uint8_t *h_out,
                                         uint64_t out_cap_bytes, uint64_t *nbits) {
-    HostEncodeCall call = {tans_run_enc16, tans_slot, nullptr};
-    call.sym_bytes = 2;
-    return scl_host_encode_one(call, m, (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
+    return scl_host_encode_one(scl_host_encode_call<scl_tans_encode_batch_u16, scl_tans_slot_bytes>(), m,
+                               (const u8 *)h_sym, n, h_out, out_cap_bytes, nbits);
 }
 
 extern "C" int scl_tans_decode_host_u16(const scl_tans_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                         uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed) {
-    HostDecodeCall call = {tans_run_dec16, nullptr};
-    call.sym_bytes = 2;
-    return scl_host_decode_one(call, m, h_in, in_nbits, (u8 *)h_out_sym, out_cap, n_out, consumed);
+    return scl_host_decode_one(scl_host_decode_call<scl_tans_decode_batch_u16>(), m, h_in, in_nbits, (u8 *)h_out_sym,
+                               out_cap, n_out, consumed);
 }

@@ -69,6 +69,25 @@ def test_parameter_validation_needs_no_gpu(built_lib):
     assert L.scl_rans_model_create(g, 3, 1 << 62, 8, 32, ctypes.byref(h)) == backend_lib.E_PARAM  # H >= 2^63
 
 
+
+BATCH_ENTRY_POINTS = [
+    f"scl_{coder}_{op}_batch{form}"
+    for coder, forms in (("rans", ("", "_u16", "_striped")), ("tans", ("", "_u16", "_striped")),
+                         ("range", ("", "_u16", "_striped")), ("aec", ("", "_u16", "_resume", "_resume_u16")))
+    for form in forms
+    for op in ("encode", "decode")
+]
+
+
+@pytest.mark.parametrize("name", BATCH_ENTRY_POINTS)
+def test_batch_entry_points_refuse_a_null_model(built_lib, name):
+    """every batch entry point checks its arguments before it touches a device: a null model is SCL_E_PARAM, and the
+    error names the entry point it came from"""
+    L = backend_lib.load()
+    fn = getattr(L, name)
+    assert fn(*[None if t is ctypes.c_void_p else 0 for t in fn.argtypes]) == backend_lib.E_PARAM
+    assert backend_lib.last_error().startswith(name[len("scl_"):] + ":"), backend_lib.last_error()
+
 def test_product_path_fails_loudly_without_gpu():
     """no CPU fallback: on a host without an MI355X the drop-in classes raise instead of computing"""
     if backend_lib.device_count() > 0:
