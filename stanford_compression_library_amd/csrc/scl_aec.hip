@@ -580,11 +580,6 @@ extern "C" uint64_t scl_aec_scratch_bytes(const scl_aec_model *m, uint64_t n_chu
     return scl_round_up(m->dev.cells * n_chunks * sizeof(u32), 256);
 }
 
-extern "C" int scl_aec_fast_path(const scl_aec_model *m, uint64_t max_symbols) {
-    return (m && (aec_fast_ok(m, max_symbols) || aec_static_ok(m) || aec_iid_ok(m, max_symbols) ||
-                  aec_wide_ok(m, max_symbols))) ? 1 : 0;
-}
-
 // per-lane context tables in LDS: at most 256 cells, counts (initial + one per symbol) must fit 16 bits
 static bool aec_use_lds(const scl_aec_model *m, u64 max_symbols) {
     if (m->dev.kind == SCL_MODEL_FIXED || m->dev.cells == 0 || m->dev.cells > AEC_LDS_CELLS) return false;
@@ -600,110 +595,171 @@ static bool aec_wide_dense_forced() {
     return e && e[0] == 'd';
 }
 
-// zero_bytes != 0: the kernels about to run use (and need zero-filled) only that much of it (scl_aec_wide.hip: u16 cells)
-static int aec_prepare_scratch(const scl_aec_model *m, u64 n_chunks, void *d_scratch, u64 scratch_bytes,
-                               hipStream_t st, u64 zero_bytes = 0) {
+// ---- the tuned kernel families of the byte entry points ---------------------------------------------------------------
+// In priority order: the FIRST family that serves the model and can take the call's rows runs it; the any-parameter
+// kernels follow the table.  The row relay, scl_aec_fast_path and both dispatches walk it.
+struct AecFamily {
+    const char *name;  // for comments and error text
+    bool (*served)(const scl_aec_model *m, u64 max_symbols);
+    // what the kernels need of the rows, beyond what holds for every tuned family (encode: slots of scl_aec_slot_bytes;
+    // decode: at least one whole 32-bit word of input).  in_ok: d_in is 16-byte aligned
+    bool (*enc_rows_ok)(const SclEncodeArgs<u8> &a, const scl_aec_model *m);
+    bool (*dec_rows_ok)(const SclDecodeArgs<u8> &a, const scl_aec_model *m, bool in_ok);
+    u64 (*zero_bytes)(const scl_aec_model *m, u64 n_chunks);  // scratch the kernels need zero-filled; null: they use none
+    void (*encode)(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
+    void (*decode)(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
+};
+
+// rows start on `align`-byte boundaries and hold `row` bytes rounded up to it
+static bool aec_rows(const void *p, u64 stride, u64 align, u64 row) {
+    return (((uintptr_t)p | stride) & (align - 1)) == 0 && stride >= scl_round_up(row, align);
+}
+static bool aec_enc_rows4(const SclEncodeArgs<u8> &a, const scl_aec_model *) {
+    return aec_rows(a.d_sym, a.sym_stride, 4, a.chunk_len);
+}
+static bool aec_dec_rows4(const SclDecodeArgs<u8> &a, const scl_aec_model *, bool) {
+    return aec_rows(a.d_out_sym, a.out_stride, 4, a.out_cap);
+}
+static bool aec_wide_sparse_ok(const scl_aec_model *m, u64 n) { return aec_wide_ok(m, n) && !aec_wide_dense_forced(); }
+static bool aec_wide_dense_ok(const scl_aec_model *m, u64 n) { return aec_wide_ok(m, n) && aec_wide_dense_forced(); }
+
+static const AecFamily aec_families[] = {
+    // small-alphabet adaptive models: cumulative context rows in LDS, closed-form renormalisation (scl_aec_fast.hip; the
+    // encoder with a chunk's work split over three waves, scl_aec_split.hip)
+    {"fast/split", aec_fast_ok,
+     [](const SclEncodeArgs<u8> &a, const scl_aec_model *) {
+         return aec_rows(a.d_sym, a.sym_stride, 16, a.chunk_len) && (a.out_stride & 63) == 0;
+     },
+     [](const SclDecodeArgs<u8> &a, const scl_aec_model *, bool in_ok) {
+         return in_ok && aec_rows(a.d_out_sym, a.out_stride, 16, a.out_cap);
+     },
+     nullptr, aec_fast_encode_launch, aec_fast_decode_launch},
+    // adaptive i.i.d. model on a large alphabet: two-level cumulative table per lane in LDS (scl_aec_iid.hip)
+    {"iid", aec_iid_ok, aec_enc_rows4, aec_dec_rows4, nullptr, aec_iid_encode_launch, aec_iid_decode_launch},
+    // static model: shared table in LDS, line-granular I/O, 32-bit byte offsets into the input (scl_aec_static.hip)
+    {"static", [](const scl_aec_model *m, u64) { return aec_static_ok(m); },
+     [](const SclEncodeArgs<u8> &a, const scl_aec_model *) {
+         return aec_rows(a.d_sym, a.sym_stride, 16, 0) && (a.out_stride & 15) == 0;
+     },
+     [](const SclDecodeArgs<u8> &a, const scl_aec_model *, bool in_ok) {
+         return in_ok && a.in_size_bytes < (1ull << 34) && aec_rows(a.d_out_sym, a.out_stride, 16, a.out_cap);
+     },
+     nullptr, aec_static_encode_launch, aec_static_decode_launch},
+    // order-k on a large alphabet: one table line per symbol while a context is young (scl_aec_sparse.hip) ...
+    {"sparse", aec_wide_sparse_ok, aec_enc_rows4, aec_dec_rows4, aec_sparse_zero_bytes, aec_sparse_encode_launch,
+     aec_sparse_decode_launch},
+    // ... or, under SCL_AEC_WIDE=dense, the two-level rows in device memory, tuned arithmetic, lookups issued ahead
+    // (scl_aec_wide.hip: u16 cells)
+    {"wide", aec_wide_dense_ok, aec_enc_rows4, aec_dec_rows4, aec_wide_scratch_bytes, aec_wide_encode_launch,
+     aec_wide_decode_launch},
+};
+
+static bool aec_tuned_serves(const scl_aec_model *m, u64 max_symbols) {
+    for (const AecFamily &f : aec_families)
+        if (f.served(m, max_symbols)) return true;
+    return false;
+}
+
+extern "C" int scl_aec_fast_path(const scl_aec_model *m, uint64_t max_symbols) {
+    return (m && aec_tuned_serves(m, max_symbols)) ? 1 : 0;
+}
+
+// d_scratch / scratch_bytes of a batch call
+struct AecScratch {
+    void *p;
+    u64 bytes;
+};
+
+// zero_bytes != 0: the kernels about to run use (and need zero-filled) only that much of it
+static int aec_prepare_scratch(const scl_aec_model *m, u64 n_chunks, AecScratch scratch, hipStream_t st,
+                               u64 zero_bytes = 0) {
     const u64 need = m->dev.cells * n_chunks * sizeof(u32);
-    SCL_REQUIRE(need == 0 || (d_scratch && scratch_bytes >= need), "aec: scratch of %llu bytes required, got %llu",
-                (unsigned long long)need, (unsigned long long)scratch_bytes);
-    if (m->dev.kind == SCL_MODEL_ORDERK) SCL_HIP_TRY(hipMemsetAsync(d_scratch, 0, zero_bytes ? zero_bytes : need, st));
+    SCL_REQUIRE(need == 0 || (scratch.p && scratch.bytes >= need), "aec: scratch of %llu bytes required, got %llu",
+                (unsigned long long)need, (unsigned long long)scratch.bytes);
+    if (m->dev.kind == SCL_MODEL_ORDERK) SCL_HIP_TRY(hipMemsetAsync(scratch.p, 0, zero_bytes ? zero_bytes : need, st));
     return SCL_OK;
 }
 
 // the any-parameter kernels: a lane's model in LDS (lds: byte symbols only, aec_use_lds) or in `cells` (scratch, or the
 // state a *_resume call carries on, with its contexts in ctx_state), 64-bit arithmetic for PRECISION above 32
 template <class SYM>
-static int aec_encode_any(const scl_aec_model *m, bool lds, const SYM *d_sym, u64 sym_stride, const u32 *d_lens,
-                          u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                          u32 *d_status, u32 *cells, u64 *ctx_state, hipStream_t st) {
+static int aec_encode_any(const scl_aec_model *m, bool lds, const SclEncodeArgs<SYM> &a, u32 *cells, u64 *ctx_state,
+                          hipStream_t st) {
     const bool wide = m->dev.P > 32;
     auto kernel = wide ? aec_encode_kernel<false, true, SYM> : aec_encode_kernel<false, false, SYM>;
     if constexpr (sizeof(SYM) == 1)
         if (lds) kernel = wide ? aec_encode_kernel<true, true> : aec_encode_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_sym, sym_stride, d_lens,
-                       chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status, cells, ctx_state);
+    scl_launch_encode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a, cells, ctx_state);
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
 template <class SYM>
-static int aec_decode_any(const scl_aec_model *m, bool lds, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_off,
-                          const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride, u32 out_cap,
-                          u32 *d_out_lens, u32 *d_consumed, u32 *d_status, u32 *cells, u64 *ctx_state, hipStream_t st) {
+static int aec_decode_any(const scl_aec_model *m, bool lds, const SclDecodeArgs<SYM> &a, u32 *cells, u64 *ctx_state,
+                          hipStream_t st) {
     const bool wide = m->dev.P > 32;
     auto kernel = wide ? aec_decode_kernel<false, true, SYM> : aec_decode_kernel<false, false, SYM>;
     if constexpr (sizeof(SYM) == 1)
         if (lds) kernel = wide ? aec_decode_kernel<true, true> : aec_decode_kernel<true, false>;
-    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_in, in_size_bytes,
-                       d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status,
-                       cells, ctx_state);
+    scl_launch_decode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a, cells, ctx_state);
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
+}
+
+// the byte batch calls, after their argument checks
+static int aec_encode_bytes(const scl_aec_model *m, const SclEncodeArgs<u8> &args, AecScratch scratch, hipStream_t st) {
+    if (args.n_chunks == 0) return SCL_OK;
+    SclEncodeArgs<u8> a = args;
+    // (the tuned kernels have no capacity check)
+    const bool tuned = !scl_force_generic() && a.out_stride >= scl_aec_slot_bytes(m, a.chunk_len);
+    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
+    if (tuned && aec_tuned_serves(m, a.chunk_len))
+        if (int rc = relay.in(a, st)) return rc;
+    const bool lds = aec_use_lds(m, a.chunk_len);
+    for (const AecFamily &f : aec_families) {
+        if (!tuned || !f.served(m, a.chunk_len) || !f.enc_rows_ok(a, m)) continue;
+        if (f.zero_bytes && !lds)
+            if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st, f.zero_bytes(m, a.n_chunks))) return rc;
+        f.encode(m, a, st, (u32 *)scratch.p);
+        SCL_HIP_TRY(hipGetLastError());
+        return SCL_OK;
+    }
+    if (!lds)
+        if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
+    return aec_encode_any(m, lds, a, (u32 *)scratch.p, nullptr, st);
+}
+
+static int aec_decode_bytes(const scl_aec_model *m, const SclDecodeArgs<u8> &args, AecScratch scratch, hipStream_t st) {
+    if (args.n_chunks == 0) return SCL_OK;
+    SclDecodeArgs<u8> a = args;
+    const bool tuned = !scl_force_generic() && a.in_size_bytes >= 4;  // the tuned readers load whole 32-bit words
+    const bool in_ok = ((uintptr_t)a.d_in & 15) == 0;
+    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
+    if (tuned && aec_tuned_serves(m, a.out_cap) && in_ok)
+        if (int rc = relay.out_begin(a, st)) return rc;
+    const bool lds = aec_use_lds(m, a.out_cap);
+    for (const AecFamily &f : aec_families) {
+        if (!tuned || !f.served(m, a.out_cap) || !f.dec_rows_ok(a, m, in_ok)) continue;
+        if (f.zero_bytes && !lds)
+            if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st, f.zero_bytes(m, a.n_chunks))) return rc;
+        f.decode(m, a, st, (u32 *)scratch.p);
+        SCL_HIP_TRY(hipGetLastError());
+        return relay.out_end(a);
+    }
+    if (!lds)
+        if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
+    if (int rc = aec_decode_any(m, lds, a, (u32 *)scratch.p, nullptr, st)) return rc;
+    return relay.out_end(a);
 }
 
 extern "C" int scl_aec_encode_batch(const scl_aec_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                     const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                     uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                     uint32_t *d_status, void *d_scratch, uint64_t scratch_bytes, void *stream) {
-    if (int rc = scl_check_encode("aec_encode_batch", SCL_ROWS_U8, m, d_sym, d_out, d_out_bit_offset, d_out_nbits,
-                                  out_stride))
-        return rc;
-    if (n_chunks == 0) return SCL_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const bool tuned = !scl_force_generic();
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
-    if (tuned && (aec_fast_ok(m, chunk_len) || aec_iid_ok(m, chunk_len) || aec_static_ok(m) || aec_wide_ok(m, chunk_len)) &&
-        out_stride >= scl_aec_slot_bytes(m, chunk_len))
-        if (int rc_r = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc_r;
-    // small-alphabet adaptive models: cumulative context rows in LDS, closed-form renormalisation (scl_aec_fast.hip)
-    if (tuned && aec_fast_ok(m, chunk_len) && ((uintptr_t)d_sym & 15) == 0 && (sym_stride & 15) == 0 &&
-        sym_stride >= scl_round_up(chunk_len, 16) && (out_stride & 63) == 0 &&
-        out_stride >= scl_aec_slot_bytes(m, chunk_len)) {
-        aec_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                               d_out_nbits, d_status, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return SCL_OK;
-    }
-    // adaptive i.i.d. model on a large alphabet: two-level cumulative table per lane in LDS (scl_aec_iid.hip)
-    if (tuned && aec_iid_ok(m, chunk_len) && ((uintptr_t)d_sym & 3) == 0 && (sym_stride & 3) == 0 &&
-        sym_stride >= scl_round_up(chunk_len, 4) && out_stride >= scl_aec_slot_bytes(m, chunk_len)) {
-        aec_iid_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                              d_out_nbits, d_status, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return SCL_OK;
-    }
-    // static model: shared table in LDS, line-granular I/O (scl_aec_static.hip)
-    if (tuned && aec_static_ok(m) && ((uintptr_t)d_sym & 15) == 0 && (sym_stride & 15) == 0 && (out_stride & 15) == 0 &&
-        out_stride >= scl_aec_slot_bytes(m, chunk_len)) {
-        aec_static_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                                 d_out_bit_offset, d_out_nbits, d_status, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return SCL_OK;
-    }
-    // order-k on a large alphabet: the same two-level rows in device memory, tuned arithmetic, lookups issued ahead (scl_aec_wide.hip)
-    const bool wide = tuned && aec_wide_ok(m, chunk_len) && ((uintptr_t)d_sym & 3) == 0 && (sym_stride & 3) == 0 &&
-                      sym_stride >= scl_round_up(chunk_len, 4) && out_stride >= scl_aec_slot_bytes(m, chunk_len);
-    if (!aec_use_lds(m, chunk_len)) {
-        int rc = aec_prepare_scratch(m, n_chunks, d_scratch, scratch_bytes, st,
-                                     wide ? (aec_wide_dense_forced() ? aec_wide_scratch_bytes(m, n_chunks)
-                                                                     : aec_sparse_zero_bytes(m, n_chunks))
-                                          : 0);
-        if (rc) return rc;
-    }
-    if (wide && !aec_wide_dense_forced()) {  // one table line per symbol while a context is young (scl_aec_sparse.hip)
-        aec_sparse_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                                 d_out_nbits, d_status, (u32 *)d_scratch, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return SCL_OK;
-    }
-    if (wide) {
-        aec_wide_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                               d_out_nbits, d_status, (u32 *)d_scratch, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return SCL_OK;
-    }
-    return aec_encode_any(m, aec_use_lds(m, chunk_len), d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
-                          out_stride, d_out_bit_offset, d_out_nbits, d_status, (u32 *)d_scratch, nullptr, st);
+    const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                 d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    if (int rc = scl_check_encode("aec_encode_batch", SCL_ROWS_U8, m, a)) return rc;
+    return aec_encode_bytes(m, a, {d_scratch, scratch_bytes}, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_decode_batch(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -711,63 +767,10 @@ extern "C" int scl_aec_decode_batch(const scl_aec_model *m, const uint8_t *d_in,
                                     uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
                                     uint32_t *d_consumed, uint32_t *d_status, void *d_scratch, uint64_t scratch_bytes,
                                     void *stream) {
-    if (int rc = scl_check_decode("aec_decode_batch", SCL_ROWS_U8, m, d_in, d_bit_offset, d_in_nbits, d_out_sym,
-                                  d_out_lens, d_consumed))
-        return rc;
-    if (n_chunks == 0) return SCL_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const bool tuned = !scl_force_generic() && in_size_bytes >= 4;  // the tuned readers load whole 32-bit words
-    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
-    if (tuned && (aec_fast_ok(m, out_cap) || aec_iid_ok(m, out_cap) || aec_static_ok(m) || aec_wide_ok(m, out_cap)) &&
-        ((uintptr_t)d_in & 15) == 0)
-        if (int rc_r = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc_r;
-    if (tuned && aec_fast_ok(m, out_cap) && ((uintptr_t)d_in & 15) == 0 && ((uintptr_t)d_out_sym & 15) == 0 &&
-        (out_stride & 15) == 0 && out_stride >= scl_round_up(out_cap, 16)) {
-        aec_fast_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                               out_cap, d_out_lens, d_consumed, d_status, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return relay.out_end(d_out_lens);
-    }
-    if (tuned && aec_iid_ok(m, out_cap) && ((uintptr_t)d_out_sym & 3) == 0 && (out_stride & 3) == 0 &&
-        out_stride >= scl_round_up(out_cap, 4)) {
-        aec_iid_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                              out_cap, d_out_lens, d_consumed, d_status, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return relay.out_end(d_out_lens);
-    }
-    if (tuned && aec_static_ok(m) && ((uintptr_t)d_in & 15) == 0 && in_size_bytes < (1ull << 34) &&
-        ((uintptr_t)d_out_sym & 15) == 0 && (out_stride & 15) == 0 && out_stride >= out_cap) {
-        aec_static_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                 out_cap, d_out_lens, d_consumed, d_status, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return relay.out_end(d_out_lens);
-    }
-    const bool wide = tuned && aec_wide_ok(m, out_cap) && ((uintptr_t)d_out_sym & 3) == 0 && (out_stride & 3) == 0 &&
-                      out_stride >= scl_round_up(out_cap, 4);
-    if (!aec_use_lds(m, out_cap)) {
-        int rc = aec_prepare_scratch(m, n_chunks, d_scratch, scratch_bytes, st,
-                                     wide ? (aec_wide_dense_forced() ? aec_wide_scratch_bytes(m, n_chunks)
-                                                                     : aec_sparse_zero_bytes(m, n_chunks))
-                                          : 0);
-        if (rc) return rc;
-    }
-    if (wide && !aec_wide_dense_forced()) {
-        aec_sparse_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                                 d_out_lens, d_consumed, d_status, (u32 *)d_scratch, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return relay.out_end(d_out_lens);
-    }
-    if (wide) {
-        aec_wide_decode_launch(m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                               d_out_lens, d_consumed, d_status, (u32 *)d_scratch, st);
-        SCL_HIP_TRY(hipGetLastError());
-        return relay.out_end(d_out_lens);
-    }
-    if (int rc = aec_decode_any(m, aec_use_lds(m, out_cap), d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
-                                d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, (u32 *)d_scratch,
-                                nullptr, st))
-        return rc;
-    return relay.out_end(d_out_lens);
+    const SclDecodeArgs<u8> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                 out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    if (int rc = scl_check_decode("aec_decode_batch", SCL_ROWS_U8, m, a)) return rc;
+    return aec_decode_bytes(m, a, {d_scratch, scratch_bytes}, (hipStream_t)stream);
 }
 
 // ---- coder state carried across blocks (quirk Q4) -----------------------------------------------------------
@@ -903,62 +906,54 @@ extern "C" int scl_aec_state_download(const scl_aec_model *m, const void *d_stat
 // of both widths: chunk c continues coder c of a state d_state reset with n_coders coders; the layout of d_state is a
 // function of n_coders (the context array follows the cells of ALL coders), so a batch may be shorter, never longer.
 // A FIXED model has nothing to carry: its *_resume calls are the plain batch calls.
-static int aec_resume_state(const char *what, const scl_aec_model *m, u64 n_chunks, void *d_state, u64 state_bytes,
-                            u64 n_coders, u32 *&cells, u64 *&ctx_state) {
-    SCL_REQUIRE(d_state, "%s: null pointer argument", what);
-    SCL_REQUIRE(((uintptr_t)d_state & 255) == 0, "%s: d_state must be 256-byte aligned", what);
-    SCL_REQUIRE(n_chunks <= n_coders, "%s: %llu chunks but the state holds %llu coders", what,
-                (unsigned long long)n_chunks, (unsigned long long)n_coders);
-    SCL_REQUIRE(state_bytes >= scl_aec_state_bytes(m, n_coders), "%s: state of %llu bytes required", what,
-                (unsigned long long)scl_aec_state_bytes(m, n_coders));
-    cells = (u32 *)d_state;
-    ctx_state = (u64 *)((u8 *)d_state + aec_state_cells_bytes(m, n_coders));
+struct AecResume {  // d_state, state_bytes, n_coders of a *_resume call
+    void *d_state;
+    u64 state_bytes, n_coders;
+};
+static int aec_resume_state(const char *what, const scl_aec_model *m, u64 n_chunks, const AecResume &r, u32 *&cells,
+                            u64 *&ctx_state) {
+    SCL_REQUIRE(r.d_state, "%s: null pointer argument", what);
+    SCL_REQUIRE(((uintptr_t)r.d_state & 255) == 0, "%s: d_state must be 256-byte aligned", what);
+    SCL_REQUIRE(n_chunks <= r.n_coders, "%s: %llu chunks but the state holds %llu coders", what,
+                (unsigned long long)n_chunks, (unsigned long long)r.n_coders);
+    SCL_REQUIRE(r.state_bytes >= scl_aec_state_bytes(m, r.n_coders), "%s: state of %llu bytes required", what,
+                (unsigned long long)scl_aec_state_bytes(m, r.n_coders));
+    cells = (u32 *)r.d_state;
+    ctx_state = (u64 *)((u8 *)r.d_state + aec_state_cells_bytes(m, r.n_coders));
     return SCL_OK;
 }
 
+// resume: null for the plain batch calls
 template <class SYM>
-static int aec_encode_cells(const char *what, const scl_aec_model *m, const SYM *d_sym, u64 sym_stride,
-                            const u32 *d_lens, u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-                            u32 *d_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes, bool resume,
-                            void *d_state, u64 state_bytes, u64 n_coders, hipStream_t st) {
-    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, d_sym, d_out, d_bit_off, d_nbits, out_stride)) return rc;
-    u32 *cells = (u32 *)d_scratch;
+static int aec_encode_cells(const char *what, const scl_aec_model *m, const SclEncodeArgs<SYM> &a, AecScratch scratch,
+                            const AecResume *resume, hipStream_t st) {
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, a)) return rc;
+    u32 *cells = (u32 *)scratch.p;
     u64 *ctx_state = nullptr;
     if (resume && m->dev.kind != SCL_MODEL_FIXED)
-        if (int rc = aec_resume_state(what, m, n_chunks, d_state, state_bytes, n_coders, cells, ctx_state)) return rc;
+        if (int rc = aec_resume_state(what, m, a.n_chunks, *resume, cells, ctx_state)) return rc;
     if constexpr (sizeof(SYM) == 1)
-        if (!ctx_state)
-            return scl_aec_encode_batch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
-                                        d_nbits, d_status, d_scratch, scratch_bytes, st);
-    if (n_chunks == 0) return SCL_OK;
+        if (!ctx_state) return aec_encode_bytes(m, a, scratch, st);
+    if (a.n_chunks == 0) return SCL_OK;
     if (!ctx_state)
-        if (int rc = aec_prepare_scratch(m, n_chunks, d_scratch, scratch_bytes, st)) return rc;
-    return aec_encode_any(m, false, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
-                          d_nbits, d_status, cells, ctx_state, st);
+        if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
+    return aec_encode_any(m, false, a, cells, ctx_state, st);
 }
 
 template <class SYM>
-static int aec_decode_cells(const char *what, const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes,
-                            const u64 *d_bit_off, const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride,
-                            u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, void *d_scratch,
-                            u64 scratch_bytes, bool resume, void *d_state, u64 state_bytes, u64 n_coders,
-                            hipStream_t st) {
-    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, d_in, d_bit_off, d_in_nbits, d_out_sym, d_out_lens,
-                                  d_consumed))
-        return rc;
-    u32 *cells = (u32 *)d_scratch;
+static int aec_decode_cells(const char *what, const scl_aec_model *m, const SclDecodeArgs<SYM> &a, AecScratch scratch,
+                            const AecResume *resume, hipStream_t st) {
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, a)) return rc;
+    u32 *cells = (u32 *)scratch.p;
     u64 *ctx_state = nullptr;
     if (resume && m->dev.kind != SCL_MODEL_FIXED)
-        if (int rc = aec_resume_state(what, m, n_chunks, d_state, state_bytes, n_coders, cells, ctx_state)) return rc;
+        if (int rc = aec_resume_state(what, m, a.n_chunks, *resume, cells, ctx_state)) return rc;
     if constexpr (sizeof(SYM) == 1)
-        if (!ctx_state)
-            return scl_aec_decode_batch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                        out_cap, d_out_lens, d_consumed, d_status, d_scratch, scratch_bytes, st);
-    if (n_chunks == 0) return SCL_OK;
+        if (!ctx_state) return aec_decode_bytes(m, a, scratch, st);
+    if (a.n_chunks == 0) return SCL_OK;
     if (!ctx_state)
-        if (int rc = aec_prepare_scratch(m, n_chunks, d_scratch, scratch_bytes, st)) return rc;
-    return aec_decode_any(m, false, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                          d_out_lens, d_consumed, d_status, cells, ctx_state, st);
+        if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
+    return aec_decode_any(m, false, a, cells, ctx_state, st);
 }
 
 extern "C" int scl_aec_encode_batch_resume(const scl_aec_model *m, const uint8_t *d_sym, uint64_t sym_stride,
@@ -966,9 +961,10 @@ extern "C" int scl_aec_encode_batch_resume(const scl_aec_model *m, const uint8_t
                                            uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                            uint32_t *d_out_nbits, uint32_t *d_status, void *d_state,
                                            uint64_t state_bytes, uint64_t n_coders, void *stream) {
-    return aec_encode_cells("aec_encode_batch_resume", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
-                            out_stride, d_out_bit_offset, d_out_nbits, d_status, nullptr, 0, true, d_state, state_bytes,
-                            n_coders, (hipStream_t)stream);
+    const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                 d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    const AecResume resume = {d_state, state_bytes, n_coders};
+    return aec_encode_cells("aec_encode_batch_resume", m, a, {nullptr, 0}, &resume, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_decode_batch_resume(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -976,18 +972,19 @@ extern "C" int scl_aec_decode_batch_resume(const scl_aec_model *m, const uint8_t
                                            uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap,
                                            uint32_t *d_out_lens, uint32_t *d_consumed, uint32_t *d_status,
                                            void *d_state, uint64_t state_bytes, uint64_t n_coders, void *stream) {
-    return aec_decode_cells("aec_decode_batch_resume", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
-                            d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, nullptr, 0, true, d_state,
-                            state_bytes, n_coders, (hipStream_t)stream);
+    const SclDecodeArgs<u8> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                 out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    const AecResume resume = {d_state, state_bytes, n_coders};
+    return aec_decode_cells("aec_decode_batch_resume", m, a, {nullptr, 0}, &resume, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_encode_batch_u16(const scl_aec_model *m, const uint16_t *d_sym, uint64_t sym_stride,
                                         const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                         uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                         uint32_t *d_status, void *d_scratch, uint64_t scratch_bytes, void *stream) {
-    return aec_encode_cells("aec_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                            d_out_bit_offset, d_out_nbits, d_status, d_scratch, scratch_bytes, false, nullptr, 0, 0,
-                            (hipStream_t)stream);
+    const SclEncodeArgs<u16> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                  d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    return aec_encode_cells("aec_encode_batch_u16", m, a, {d_scratch, scratch_bytes}, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_decode_batch_u16(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -995,9 +992,9 @@ extern "C" int scl_aec_decode_batch_u16(const scl_aec_model *m, const uint8_t *d
                                         uint16_t *d_out_sym, uint64_t out_stride, uint32_t out_cap,
                                         uint32_t *d_out_lens, uint32_t *d_consumed, uint32_t *d_status, void *d_scratch,
                                         uint64_t scratch_bytes, void *stream) {
-    return aec_decode_cells("aec_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
-                            d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, d_scratch, scratch_bytes,
-                            false, nullptr, 0, 0, (hipStream_t)stream);
+    const SclDecodeArgs<u16> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                  out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    return aec_decode_cells("aec_decode_batch_u16", m, a, {d_scratch, scratch_bytes}, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_encode_batch_resume_u16(const scl_aec_model *m, const uint16_t *d_sym, uint64_t sym_stride,
@@ -1005,9 +1002,10 @@ extern "C" int scl_aec_encode_batch_resume_u16(const scl_aec_model *m, const uin
                                                uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                                uint32_t *d_out_nbits, uint32_t *d_status, void *d_state,
                                                uint64_t state_bytes, uint64_t n_coders, void *stream) {
-    return aec_encode_cells("aec_encode_batch_resume_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
-                            out_stride, d_out_bit_offset, d_out_nbits, d_status, nullptr, 0, true, d_state, state_bytes,
-                            n_coders, (hipStream_t)stream);
+    const SclEncodeArgs<u16> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                  d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    const AecResume resume = {d_state, state_bytes, n_coders};
+    return aec_encode_cells("aec_encode_batch_resume_u16", m, a, {nullptr, 0}, &resume, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_decode_batch_resume_u16(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -1016,9 +1014,10 @@ extern "C" int scl_aec_decode_batch_resume_u16(const scl_aec_model *m, const uin
                                                uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                                uint32_t *d_status, void *d_state, uint64_t state_bytes,
                                                uint64_t n_coders, void *stream) {
-    return aec_decode_cells("aec_decode_batch_resume_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
-                            d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, nullptr, 0, true, d_state,
-                            state_bytes, n_coders, (hipStream_t)stream);
+    const SclDecodeArgs<u16> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                  out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    const AecResume resume = {d_state, state_bytes, n_coders};
+    return aec_decode_cells("aec_decode_batch_resume_u16", m, a, {nullptr, 0}, &resume, (hipStream_t)stream);
 }
 
 // ---- single-chunk host drivers --------------------------------------------------------------------------

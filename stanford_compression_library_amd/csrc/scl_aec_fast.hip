@@ -475,39 +475,26 @@ static AecFastDev aec_fast_dev(const scl_aec_model *m) {
     return f;
 }
 
-void aec_fast_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens, u32 chunk_len,
-                            u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset, u32 *d_out_nbits,
-                            u32 *d_status, hipStream_t st) {
+void aec_fast_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *) {
     // round 3: the two-role encoder (scl_aec_split.hip) serves every batch; SCL_AEC_ENC=lane keeps the one-lane-per-
     // chunk kernel below for A/B timing and as a second implementation the tests compare against
     const char *enc_env = getenv("SCL_AEC_ENC");  // read at every call, like the other switches
     const bool lane_kernel = enc_env && (enc_env[0] == 'l' || enc_env[0] == 'L');
     if (!lane_kernel) {
-        (void)aec_split_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                                      d_out_bit_offset, d_out_nbits, d_status, st);
+        aec_split_encode_launch(m, a, st);
         return;
     }
-    const u32 blocks = (u32)((n_chunks + AF_THREADS - 1) / AF_THREADS);
+    const SclGrid g = {(u32)((a.n_chunks + AF_THREADS - 1) / AF_THREADS), AF_THREADS};
     if (m->dev.k == 1)
-        hipLaunchKernelGGL(aec_fast_encode_kernel<true>, dim3(blocks), dim3(AF_THREADS), 0, st, aec_fast_dev(m),
-                           d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                           d_out_nbits, d_status);
+        scl_launch_encode(aec_fast_encode_kernel<true>, g, st, aec_fast_dev(m), a);
     else
-        hipLaunchKernelGGL(aec_fast_encode_kernel<false>, dim3(blocks), dim3(AF_THREADS), 0, st, aec_fast_dev(m),
-                           d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset,
-                           d_out_nbits, d_status);
+        scl_launch_encode(aec_fast_encode_kernel<false>, g, st, aec_fast_dev(m), a);
 }
 
-void aec_fast_decode_launch(const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_offset,
-                            const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                            u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    const u32 blocks = (u32)((n_chunks + AF_THREADS - 1) / AF_THREADS);
+void aec_fast_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *) {
+    const SclGrid g = {(u32)((a.n_chunks + AF_THREADS - 1) / AF_THREADS), AF_THREADS};
     if (m->dev.k == 1)
-        hipLaunchKernelGGL(aec_fast_decode_kernel<true>, dim3(blocks), dim3(AF_THREADS), 0, st, aec_fast_dev(m), d_in,
-                           in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
+        scl_launch_decode(aec_fast_decode_kernel<true>, g, st, aec_fast_dev(m), a);
     else
-        hipLaunchKernelGGL(aec_fast_decode_kernel<false>, dim3(blocks), dim3(AF_THREADS), 0, st, aec_fast_dev(m),
-                           d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
+        scl_launch_decode(aec_fast_decode_kernel<false>, g, st, aec_fast_dev(m), a);
 }

@@ -25,50 +25,30 @@ struct scl_aec_model {
     u32 *d_iid_init;  // IID, alphabet > 16: the two-level cumulative table of scl_aec_iid.hip (17 rows x 8 u32)
 };
 
+// The tuned kernel families.  Every launch takes (model, the batch call's arguments, stream, the call's scratch): the
+// scratch is used by the order-k families on large alphabets only (scl_aec.hip holds the table of families).
 // scl_aec_fast.hip
 bool aec_fast_ok(const scl_aec_model *m, u64 max_symbols);
-void aec_fast_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens, u32 chunk_len,
-                            u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset, u32 *d_out_nbits,
-                            u32 *d_status, hipStream_t st);
-void aec_fast_decode_launch(const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_offset,
-                            const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                            u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st);
+void aec_fast_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
+void aec_fast_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
 // scl_aec_split.hip: the encoder of the same models with the model side and the coder side of a chunk in two waves
-int aec_split_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens, u32 chunk_len,
-                            u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset, u32 *d_out_nbits,
-                            u32 *d_status, hipStream_t st);
+void aec_split_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st);
 // scl_aec_wide.hip: order-k models in the two-level row layout (large alphabets), tuned arithmetic over device-memory rows
 bool aec_wide_ok(const scl_aec_model *m, u64 max_symbols);
 u64 aec_wide_scratch_bytes(const scl_aec_model *m, u64 n_chunks);
-void aec_wide_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens, u32 chunk_len,
-                            u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset, u32 *d_out_nbits,
-                            u32 *d_status, u32 *d_scratch, hipStream_t st);
-void aec_wide_decode_launch(const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_offset,
-                            const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                            u32 *d_out_lens, u32 *d_consumed, u32 *d_status, u32 *d_scratch, hipStream_t st);
+void aec_wide_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
+void aec_wide_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
 // scl_aec_sparse.hip: the same models with one 64-byte line per context (the symbols seen in it) until it has been seen 28
 // times, then its dense row: one table piece read and written per symbol instead of two
 u64 aec_sparse_zero_bytes(const scl_aec_model *m, u64 n_chunks);
-void aec_sparse_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens, u32 chunk_len,
-                              u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset, u32 *d_out_nbits,
-                              u32 *d_status, u32 *d_scratch, hipStream_t st);
-void aec_sparse_decode_launch(const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_offset,
-                              const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                              u32 *d_out_lens, u32 *d_consumed, u32 *d_status, u32 *d_scratch, hipStream_t st);
+void aec_sparse_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
+void aec_sparse_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
 // scl_aec_static.hip
 bool aec_static_ok(const scl_aec_model *m);
-void aec_static_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
-                              u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset,
-                              u32 *d_out_nbits, u32 *d_status, hipStream_t st);
-void aec_static_decode_launch(const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_offset,
-                              const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                              u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st);
+void aec_static_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
+void aec_static_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
 // scl_aec_iid.hip
 bool aec_iid_ok(const scl_aec_model *m, u64 max_symbols);
 void aec_iid_build_init(const u32 *h_freq, u32 K, u32 *out136);
-void aec_iid_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens, u32 chunk_len,
-                           u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset, u32 *d_out_nbits,
-                           u32 *d_status, hipStream_t st);
-void aec_iid_decode_launch(const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_offset,
-                           const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                           u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st);
+void aec_iid_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
+void aec_iid_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);

@@ -498,20 +498,12 @@ static AecSparseDev aec_sparse_dev(const scl_aec_model *m, u64 n_chunks) {
 // alphabet these kernels serve)
 u64 aec_sparse_zero_bytes(const scl_aec_model *m, u64 n_chunks) { return 64ull * m->dev.ctx_mod * n_chunks; }
 
-void aec_sparse_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens, u32 chunk_len,
-                              u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset, u32 *d_out_nbits,
-                              u32 *d_status, u32 *d_scratch, hipStream_t st) {
-    const u32 blocks = (u32)((n_chunks + AP_THREADS - 1) / AP_THREADS);
-    hipLaunchKernelGGL(aec_sparse_encode_kernel, dim3(blocks), dim3(AP_THREADS), 0, st, aec_sparse_dev(m, n_chunks), d_sym,
-                       sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status,
-                       d_scratch);
+void aec_sparse_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch) {
+    const SclGrid g = {(u32)((a.n_chunks + AP_THREADS - 1) / AP_THREADS), AP_THREADS};
+    scl_launch_encode(aec_sparse_encode_kernel, g, st, aec_sparse_dev(m, a.n_chunks), a, d_scratch);
 }
 
-void aec_sparse_decode_launch(const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_offset,
-                              const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                              u32 *d_out_lens, u32 *d_consumed, u32 *d_status, u32 *d_scratch, hipStream_t st) {
-    const u32 blocks = (u32)((n_chunks + AP_THREADS - 1) / AP_THREADS);
-    hipLaunchKernelGGL(aec_sparse_decode_kernel, dim3(blocks), dim3(AP_THREADS), 0, st, aec_sparse_dev(m, n_chunks), d_in,
-                       in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
-                       d_consumed, d_status, d_scratch);
+void aec_sparse_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch) {
+    const SclGrid g = {(u32)((a.n_chunks + AP_THREADS - 1) / AP_THREADS), AP_THREADS};
+    scl_launch_decode(aec_sparse_decode_kernel, g, st, aec_sparse_dev(m, a.n_chunks), a, d_scratch);
 }

@@ -27,7 +27,8 @@
 // conflict free whatever the lanes' contexts and symbols.  `count[s] += 1` is X[j] += 1 for j > s: eight ds_add_u32
 // with an addend row from a 512-byte LUT (no read-modify-write through registers, so all LDS traffic of a tile is
 // issued back to back and waited for once); c = X[s], d = X[s + 1] come out of ONE two-word read (ds_read2st64) and
-// one v_alignbit.  Row totals are u16 [ctx][lane], counted by a ds_add_u32 on the pair's word.
+// one v_alignbit.  A row's total rides in the u16 of X[0] (as a count always 0; see AS_TABLE_BYTES below): the addend
+// rows count it up with every symbol, the lookup masks it out for s = 0.
 // Coder side.  hm' = low + ((rng * d) // T - 1) is evaluated as trunc(fma(fma(rng, d, .5), 1/T, -1)): no special case
 // for d == T (where the quotient may be 2^32), so FIFO 1 carries just c | d << 16 and 1/T as binary64 = 12 B.  The
 // closed-form step counts k, m and the corner test are those of scl_aec_math.h, the test rewritten on the shifted
@@ -377,17 +378,10 @@ static AecSplitDev aec_split_dev(const scl_aec_model *m) {
     return f;
 }
 
-int aec_split_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens, u32 chunk_len,
-                            u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset, u32 *d_out_nbits,
-                            u32 *d_status, hipStream_t st) {
-    const u32 blocks = (u32)((n_chunks + AS_LANES - 1) / AS_LANES);
+void aec_split_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st) {
+    const SclGrid g = {(u32)((a.n_chunks + AS_LANES - 1) / AS_LANES), AS_THREADS};
     if (m->dev.k == 1)
-        hipLaunchKernelGGL(aec_split_encode_kernel<true>, dim3(blocks), dim3(AS_THREADS), 0, st, aec_split_dev(m), d_sym,
-                           sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits,
-                           d_status);
+        scl_launch_encode(aec_split_encode_kernel<true>, g, st, aec_split_dev(m), a);
     else
-        hipLaunchKernelGGL(aec_split_encode_kernel<false>, dim3(blocks), dim3(AS_THREADS), 0, st, aec_split_dev(m), d_sym,
-                           sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits,
-                           d_status);
-    return SCL_OK;
+        scl_launch_encode(aec_split_encode_kernel<false>, g, st, aec_split_dev(m), a);
 }

@@ -356,29 +356,20 @@ static AecStaticDev aec_static_dev(const scl_aec_model *m) {
     return f;
 }
 
-void aec_static_encode_launch(const scl_aec_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
-                              u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_out_bit_offset,
-                              u32 *d_out_nbits, u32 *d_status, hipStream_t st) {
-    const u32 blocks = (u32)((n_chunks + AS_THREADS - 1) / AS_THREADS);
+void aec_static_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *) {
+    const SclGrid g = {(u32)((a.n_chunks + AS_THREADS - 1) / AS_THREADS), AS_THREADS};
     const AecStaticDev dev = aec_static_dev(m);
     if (dev.t != 0xFFFFFFFFu)
-        hipLaunchKernelGGL(aec_static_encode_kernel<true>, dim3(blocks), dim3(AS_THREADS), 0, st, dev, d_sym, sym_stride,
-                           d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status);
+        scl_launch_encode(aec_static_encode_kernel<true>, g, st, dev, a);
     else
-        hipLaunchKernelGGL(aec_static_encode_kernel<false>, dim3(blocks), dim3(AS_THREADS), 0, st, dev, d_sym, sym_stride,
-                           d_lens, chunk_len, n_chunks, d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status);
+        scl_launch_encode(aec_static_encode_kernel<false>, g, st, dev, a);
 }
 
-void aec_static_decode_launch(const scl_aec_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_offset,
-                              const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                              u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    const u32 blocks = (u32)((n_chunks + AS_THREADS - 1) / AS_THREADS);
+void aec_static_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *) {
+    const SclGrid g = {(u32)((a.n_chunks + AS_THREADS - 1) / AS_THREADS), AS_THREADS};
     const AecStaticDev dev = aec_static_dev(m);
     const bool pow2 = dev.t != 0xFFFFFFFFu;
-#define AS_LAUNCH_DEC(LUT, POW2)                                                                                         \
-    hipLaunchKernelGGL((aec_static_decode_kernel<LUT, POW2>), dim3(blocks), dim3(AS_THREADS), 0, st, dev, d_in,          \
-                       in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,   \
-                       d_consumed, d_status)
+#define AS_LAUNCH_DEC(LUT, POW2) scl_launch_decode(aec_static_decode_kernel<LUT, POW2>, g, st, dev, a)
     if (m->dev.total0 <= 4096) {
         if (pow2)
             AS_LAUNCH_DEC(true, true);

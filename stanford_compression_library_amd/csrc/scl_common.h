@@ -63,18 +63,72 @@ int scl_check_device(int model_device, const char *what);
 // SCL_ANY_PARAMETER_KERNELS=1 in the environment keeps the tuned kernels out altogether (tests, stress tools: it is
 // how the two implementations of every coder are compared word for word).
 bool scl_force_generic(void);
+
+// ---- the arguments of a batch call ------------------------------------------------------------------------------------
+// What every *_encode_batch* / *_decode_batch* entry point takes between the model and the stream, under the names of
+// include/scl_hip.h.  An entry point fills one on its first line; everything below takes it whole.  SYM: u8 or u16.
+// The field order is written twice: here, and in scl_launch_encode / scl_launch_decode below.
+template <class SYM>
+struct SclEncodeArgs {
+    const SYM *d_sym;
+    u64 sym_stride;
+    const u32 *d_lens;
+    u32 chunk_len;
+    u64 n_chunks;
+    u8 *d_out;
+    u64 out_stride;
+    u64 *d_bit_off;
+    u32 *d_nbits;
+    u32 *d_status;
+};
+template <class SYM>
+struct SclDecodeArgs {
+    const u8 *d_in;
+    u64 in_size_bytes;  // the slot stride on wave-striped slots
+    const u64 *d_bit_off;
+    const u32 *d_in_nbits;
+    u64 n_chunks;
+    SYM *d_out_sym;
+    u64 out_stride;
+    u32 out_cap;
+    u32 *d_out_lens;
+    u32 *d_consumed;
+    u32 *d_status;
+};
+
+// Starts a batch kernel: its parameters are (dev, the struct's fields in ABI order, extra...).
+struct SclGrid {
+    u32 blocks, threads, lds = 0;
+};
+template <class KERNEL, class DEV, class SYM, class... EXTRA>
+void scl_launch_encode(KERNEL kernel, SclGrid g, hipStream_t st, const DEV &dev, const SclEncodeArgs<SYM> &a,
+                       EXTRA... extra) {
+    hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds, st, dev, a.d_sym, a.sym_stride, a.d_lens,
+                       a.chunk_len, a.n_chunks, a.d_out, a.out_stride, a.d_bit_off, a.d_nbits, a.d_status, extra...);
+}
+template <class KERNEL, class DEV, class SYM, class... EXTRA>
+void scl_launch_decode(KERNEL kernel, SclGrid g, hipStream_t st, const DEV &dev, const SclDecodeArgs<SYM> &a,
+                       EXTRA... extra) {
+    hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds, st, dev, a.d_in, a.in_size_bytes, a.d_bit_off,
+                       a.d_in_nbits, a.n_chunks, a.d_out_sym, a.out_stride, a.out_cap, a.d_out_lens, a.d_consumed,
+                       a.d_status, extra...);
+}
+
 struct RowRelay {
     u8 *scratch = nullptr;
     hipStream_t st = nullptr;
     u8 *user_out = nullptr;  // decode side: where the rows go back to
     u64 user_stride = 0, stride = 0, n_rows = 0;
-    u32 row_bytes = 0, sym_bytes = 1;
+    u32 row_bytes = 0;
     bool failed = false;  // the scratch could not be allocated: rows stay as they are (scl_last_error has the reason)
-    // encode side: d_sym / sym_stride are replaced by an aligned copy when they are not aligned
-    int in(const u8 *&d_sym, u64 &sym_stride, u32 chunk_len, u64 n_chunks, hipStream_t stream);
-    // decode side: d_out / out_stride are replaced by aligned scratch; out_end() copies the rows back
-    int out_begin(u8 *&d_out, u64 &out_stride, u32 out_cap, u64 n_chunks, hipStream_t stream);
-    int out_end(const u32 *d_out_lens);
+    // encode side: a.d_sym / a.sym_stride are replaced by an aligned copy when they are not aligned (a: the caller's
+    // own copy of its arguments)
+    int in(SclEncodeArgs<u8> &a, hipStream_t stream);
+    // decode side: a.d_out_sym / a.out_stride are replaced by aligned scratch; out_end() copies the rows back
+    int out_begin(SclDecodeArgs<u8> &a, hipStream_t stream);
+    template <class SYM>  // (uint16 rows are never re-laid: nothing to copy back)
+    int out_end(const SclDecodeArgs<SYM> &a) { return copy_back(a.d_out_lens); }
+    int copy_back(const u32 *d_out_lens);
     ~RowRelay();
 };
 static inline bool scl_rows_aligned(const void *p, u64 stride) { return (((uintptr_t)p | stride) & 15) == 0; }
@@ -98,9 +152,8 @@ struct ScratchDev {
 
 // generic single-chunk host driver shared by the four coders (scl_core.hip)
 struct HostEncodeCall {
-    // launches the batch encoder for n_chunks = 1 on device buffers
-    int (*run)(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off,
-               u32 *d_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes);
+    // launches the batch encoder for n_chunks = 1 on device buffers (a.d_sym: sym_bytes wide; a.sym_stride = a.chunk_len)
+    int (*run)(const void *model, const SclEncodeArgs<u8> &a, void *d_scratch, u64 scratch_bytes);
     u64 (*slot_bytes)(const void *model, u64 n);
     u64 (*scratch_bytes)(const void *model);
     // optional hooks around the launch (coder state carried across blocks): pre() fills d_scratch before the
@@ -111,9 +164,8 @@ struct HostEncodeCall {
     u32 sym_bytes = 1;  // 2: h_sym / d_sym hold uint16 indices (run() forwards to the *_u16 batch entry point)
 };
 struct HostDecodeCall {
-    int (*run)(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-               u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *d_scratch,
-               u64 scratch_bytes);
+    // a.d_out_sym: sym_bytes wide, room for out_cap + 16 symbols; run() chooses the row's stride
+    int (*run)(const void *model, const SclDecodeArgs<u8> &a, void *d_scratch, u64 scratch_bytes);
     u64 (*scratch_bytes)(const void *model);
     int (*pre)(const void *model, void *d_scratch, void *user) = nullptr;
     int (*post)(const void *model, const void *d_scratch, void *user) = nullptr;

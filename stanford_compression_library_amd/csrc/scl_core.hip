@@ -92,28 +92,32 @@ __global__ void __launch_bounds__(256) relay_rows_kernel(u8 *__restrict__ dst, u
     }
 }
 
-static int relay_launch(u8 *dst, u64 dst_stride, const u8 *src, u64 src_stride, u32 row_bytes, u64 n_rows, hipStream_t st,
-                        const u32 *row_lens = nullptr, u32 sym_bytes = 1) {
+struct RelayRows {
+    const u8 *p;
+    u64 stride;
+};
+static int relay_launch(RelayRows dst, RelayRows src, u32 row_bytes, u64 n_rows, hipStream_t st,
+                        const u32 *row_lens = nullptr) {
     if (!n_rows || !row_bytes) return SCL_OK;
     const u64 total = n_rows * ((row_bytes + 3) / 4);
     u64 blocks = (total + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(relay_rows_kernel, dim3((u32)blocks), dim3(256), 0, st, dst, dst_stride, src, src_stride, row_bytes,
-                       n_rows, row_lens, sym_bytes);
+    hipLaunchKernelGGL(relay_rows_kernel, dim3((u32)blocks), dim3(256), 0, st, (u8 *)dst.p, dst.stride, src.p, src.stride,
+                       row_bytes, n_rows, row_lens, 1u);
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
-int RowRelay::in(const u8 *&d_sym, u64 &sym_stride, u32 chunk_len, u64 n_chunks, hipStream_t stream) {
-    if (scl_rows_aligned(d_sym, sym_stride) || n_chunks == 0) return SCL_OK;
-    if (n_chunks == 1 && ((uintptr_t)d_sym & 15) == 0) {  // one row: its stride is free
-        sym_stride = scl_round_up((u64)chunk_len + 1, 16);
+int RowRelay::in(SclEncodeArgs<u8> &a, hipStream_t stream) {
+    if (scl_rows_aligned(a.d_sym, a.sym_stride) || a.n_chunks == 0) return SCL_OK;
+    if (a.n_chunks == 1 && ((uintptr_t)a.d_sym & 15) == 0) {  // one row: its stride is free
+        a.sym_stride = scl_round_up((u64)a.chunk_len + 1, 16);
         return SCL_OK;
     }
     st = stream;
-    stride = scl_round_up((u64)chunk_len, 16);
+    stride = scl_round_up((u64)a.chunk_len, 16);
     if (stride == 0) stride = 16;
-    hipError_t e = hipMallocAsync((void **)&scratch, n_chunks * stride + 16, st);
+    hipError_t e = hipMallocAsync((void **)&scratch, a.n_chunks * stride + 16, st);
     if (e != hipSuccess) {
         // no scratch, no re-laying: the caller's rows stay as they are, which sends the call to the any-parameter kernels
         // (they take any alignment and need no scratch) instead of failing it.  The failure is RECORDED -- `failed`, and the
@@ -123,42 +127,42 @@ int RowRelay::in(const u8 *&d_sym, u64 &sym_stride, u32 chunk_len, u64 n_chunks,
         failed = true;
         (void)hipGetLastError();
         scl_set_error("row relay: hipMallocAsync(%llu bytes) failed (%s): rows not re-laid, the any-parameter kernels serve "
-                      "this call", (unsigned long long)(n_chunks * stride + 16), hipGetErrorString(e));
+                      "this call", (unsigned long long)(a.n_chunks * stride + 16), hipGetErrorString(e));
         return SCL_OK;
     }
-    if (int rc = relay_launch(scratch, stride, d_sym, sym_stride, chunk_len, n_chunks, st)) return rc;
-    d_sym = scratch;
-    sym_stride = stride;
+    if (int rc = relay_launch({scratch, stride}, {a.d_sym, a.sym_stride}, a.chunk_len, a.n_chunks, st)) return rc;
+    a.d_sym = scratch;
+    a.sym_stride = stride;
     return SCL_OK;
 }
 
-int RowRelay::out_begin(u8 *&d_out, u64 &out_stride, u32 out_cap, u64 n_chunks, hipStream_t stream) {
-    if (scl_rows_aligned(d_out, out_stride) || n_chunks == 0) return SCL_OK;
+int RowRelay::out_begin(SclDecodeArgs<u8> &a, hipStream_t stream) {
+    if (scl_rows_aligned(a.d_out_sym, a.out_stride) || a.n_chunks == 0) return SCL_OK;
     st = stream;
-    stride = scl_round_up((u64)out_cap + 1, 16);
-    hipError_t e = hipMallocAsync((void **)&scratch, n_chunks * stride + 16, st);
+    stride = scl_round_up((u64)a.out_cap + 1, 16);
+    hipError_t e = hipMallocAsync((void **)&scratch, a.n_chunks * stride + 16, st);
     if (e != hipSuccess) {  // as above: the any-parameter kernels store to the caller's rows directly
         scratch = nullptr;
         failed = true;
         (void)hipGetLastError();
         scl_set_error("row relay: hipMallocAsync(%llu bytes) failed (%s): output rows not re-laid, the any-parameter kernels "
-                      "serve this call", (unsigned long long)(n_chunks * stride + 16), hipGetErrorString(e));
+                      "serve this call", (unsigned long long)(a.n_chunks * stride + 16), hipGetErrorString(e));
         return SCL_OK;
     }
-    user_out = d_out;
-    user_stride = out_stride;
-    n_rows = n_chunks;
-    row_bytes = out_cap;
-    d_out = scratch;
-    out_stride = stride;
+    user_out = a.d_out_sym;
+    user_stride = a.out_stride;
+    n_rows = a.n_chunks;
+    row_bytes = a.out_cap;
+    a.d_out_sym = scratch;
+    a.out_stride = stride;
     return SCL_OK;
 }
 
-// d_out_lens: the decoder's per-row symbol counts (device).  Only those bytes go back: whatever else the scratch holds --
-// stale pool memory behind a row's symbols, the whole row of a chunk that failed -- never reaches the caller's buffer.
-int RowRelay::out_end(const u32 *d_out_lens) {
+// d_out_lens: the decoder's per-row symbol counts (device).  Only those bytes go back: whatever else the scratch holds
+// -- stale pool memory behind a row's symbols, the whole row of a chunk that failed -- never reaches the caller's buffer.
+int RowRelay::copy_back(const u32 *d_out_lens) {
     if (!user_out) return SCL_OK;
-    return relay_launch(user_out, user_stride, scratch, stride, row_bytes * sym_bytes, n_rows, st, d_out_lens, sym_bytes);
+    return relay_launch({user_out, user_stride}, {scratch, stride}, row_bytes, n_rows, st, d_out_lens);
 }
 
 RowRelay::~RowRelay() {
@@ -771,8 +775,9 @@ int scl_host_encode_one(const HostEncodeCall &call, const void *model, const u8 
     if (n) SCL_HIP_TRY(hipMemcpy(d_sym.p, h_sym, n * call.sym_bytes, hipMemcpyHostToDevice));
     SCL_HIP_TRY(hipMemset(d_meta.p, 0, 64));
     if (call.pre && (rc = call.pre(model, d_scr.p, call.user))) return rc;
-    rc = call.run(model, (const u8 *)d_sym.p, (u32)n, (u8 *)d_slot.p, slot, d_bit_off, d_nbits, d_status, d_scr.p,
-                  scratch_bytes);
+    const SclEncodeArgs<u8> a = {(const u8 *)d_sym.p, n, nullptr, (u32)n, 1, (u8 *)d_slot.p, slot, d_bit_off, d_nbits,
+                                 d_status};
+    rc = call.run(model, a, d_scr.p, scratch_bytes);
     if (rc) return rc;
     rc = scl_streams_compact((const u8 *)d_slot.p, d_bit_off, d_nbits, 1, SCL_COMPACT_DENSE, (u8 *)d_dense.p, slot + 16,
                              d_rec_off, d_cscr.p, nullptr);
@@ -815,8 +820,9 @@ int scl_host_decode_one(const HostDecodeCall &call, const void *model, const u8 
     SCL_HIP_TRY(hipMemcpy(d_bit_off, &h_bit_off, 8, hipMemcpyHostToDevice));
     SCL_HIP_TRY(hipMemcpy(d_nb, &h_nb, 4, hipMemcpyHostToDevice));
     if (call.pre && (rc = call.pre(model, d_scr.p, call.user))) return rc;
-    rc = call.run(model, (const u8 *)d_in.p, in_bytes + 32, d_bit_off, d_nb, (u8 *)d_out.p, (u32)out_cap, d_len, d_used,
-                  d_status, d_scr.p, scratch_bytes);
+    const SclDecodeArgs<u8> a = {(const u8 *)d_in.p, in_bytes + 32, d_bit_off, d_nb, 1, (u8 *)d_out.p, 0, (u32)out_cap,
+                                 d_len, d_used, d_status};
+    rc = call.run(model, a, d_scr.p, scratch_bytes);
     if (rc) return rc;
     SCL_HIP_TRY(hipDeviceSynchronize());
     u32 meta[3];

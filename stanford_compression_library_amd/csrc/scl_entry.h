@@ -17,31 +17,30 @@ enum SclRows { SCL_ROWS_U8, SCL_ROWS_U16, SCL_ROWS_STRIPED };
 template <class SYM>
 constexpr SclRows scl_rows_of() { return sizeof(SYM) == 1 ? SCL_ROWS_U8 : SCL_ROWS_U16; }
 
-template <class MODEL>
-int scl_check_encode(const char *what, SclRows rows, const MODEL *m, const void *d_sym, const void *d_out,
-                     const void *d_bit_off, const void *d_nbits, u64 out_stride) {
-    SCL_REQUIRE(m && d_sym && d_out && d_bit_off && d_nbits, "%s: null pointer argument", what);
+template <class MODEL, class SYM>
+int scl_check_encode(const char *what, SclRows rows, const MODEL *m, const SclEncodeArgs<SYM> &a) {
+    SCL_REQUIRE(m && a.d_sym && a.d_out && a.d_bit_off && a.d_nbits, "%s: null pointer argument", what);
     SCL_REQUIRE(rows != SCL_ROWS_U8 || m->dev.K <= 256, "%s: alphabet of %u symbols: use scl_%s_u16", what, m->dev.K,
                 what);
     if (int rc = scl_check_device(m->device, what)) return rc;
-    SCL_REQUIRE(out_stride % 16 == 0 && out_stride > 0 && (rows == SCL_ROWS_STRIPED || out_stride * 8 < (1ull << 32)),
-                "%s: bad out_stride %llu", what, (unsigned long long)out_stride);
+    SCL_REQUIRE(a.out_stride % 16 == 0 && a.out_stride > 0 &&
+                    (rows == SCL_ROWS_STRIPED || a.out_stride * 8 < (1ull << 32)),
+                "%s: bad out_stride %llu", what, (unsigned long long)a.out_stride);
     if (rows == SCL_ROWS_STRIPED) return SCL_OK;
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0 && (rows == SCL_ROWS_U8 || ((uintptr_t)d_sym & 1) == 0),
+    SCL_REQUIRE(((uintptr_t)a.d_out & 15) == 0 && (rows == SCL_ROWS_U8 || ((uintptr_t)a.d_sym & 1) == 0),
                 "%s: d_out must be 16-byte aligned%s", what, rows == SCL_ROWS_U8 ? "" : ", d_sym 2-byte aligned");
     return SCL_OK;
 }
 
-template <class MODEL>
-int scl_check_decode(const char *what, SclRows rows, const MODEL *m, const void *d_in, const void *d_bit_off,
-                     const void *d_in_nbits, const void *d_out_sym, const void *d_out_lens, const void *d_consumed) {
-    SCL_REQUIRE(m && d_in && d_bit_off && d_in_nbits && d_out_sym && d_out_lens && d_consumed,
+template <class MODEL, class SYM>
+int scl_check_decode(const char *what, SclRows rows, const MODEL *m, const SclDecodeArgs<SYM> &a) {
+    SCL_REQUIRE(m && a.d_in && a.d_bit_off && a.d_in_nbits && a.d_out_sym && a.d_out_lens && a.d_consumed,
                 "%s: null pointer argument", what);
     SCL_REQUIRE(rows != SCL_ROWS_U8 || m->dev.K <= 256, "%s: alphabet of %u symbols: use scl_%s_u16", what, m->dev.K,
                 what);
     if (int rc = scl_check_device(m->device, what)) return rc;
     if (rows == SCL_ROWS_STRIPED) return SCL_OK;
-    SCL_REQUIRE(((uintptr_t)d_in & 3) == 0 && (rows == SCL_ROWS_U8 || ((uintptr_t)d_out_sym & 1) == 0),
+    SCL_REQUIRE(((uintptr_t)a.d_in & 3) == 0 && (rows == SCL_ROWS_U8 || ((uintptr_t)a.d_out_sym & 1) == 0),
                 "%s: d_in must be 4-byte aligned%s", what, rows == SCL_ROWS_U8 ? "" : ", d_out_sym 2-byte aligned");
     return SCL_OK;
 }
@@ -51,45 +50,45 @@ int scl_check_decode(const char *what, SclRows rows, const MODEL *m, const void 
 // is a call made while the calling thread keeps them out (scl_set_any_parameter_kernels).  Slots start on 16-byte
 // boundaries and stay below 2^24 bytes (32-bit offsets per workgroup); an encoder's are at least min_slot bytes (0: no
 // bound -- the range coder reports a short slot as SCL_ST_CAPACITY).  Rows that do not start on 16-byte boundaries go
-// through the row relay; launch(rows, stride) then starts the coder's striped kernel on the rows it is given.
+// through the row relay; launch(a) then starts the coder's striped kernel on the arguments it is given (the caller's,
+// with the rows re-laid where they had to be; a decoder's in_size_bytes is the slot stride).
 template <class LAUNCH>
-int scl_striped_encode(const char *what, bool served, u64 min_slot, const u8 *d_sym, u64 sym_stride, u32 chunk_len,
-                       u64 n_chunks, const u8 *d_out, u64 out_stride, hipStream_t st, LAUNCH launch) {
+int scl_striped_encode(const char *what, bool served, u64 min_slot, SclEncodeArgs<u8> a, hipStream_t st, LAUNCH launch) {
     SCL_REQUIRE(served, "%s: this model is not served by the striped kernels (see scl_*_striped_ok)", what);
     SCL_REQUIRE(!scl_force_generic(), "%s: the calling thread keeps the tuned kernels out; striped slots have no other", what);
-    SCL_REQUIRE(((uintptr_t)d_out & 15) == 0, "%s: d_out must be 16-byte aligned", what);
-    SCL_REQUIRE(out_stride >= min_slot && out_stride < (1ull << 24),
+    SCL_REQUIRE(((uintptr_t)a.d_out & 15) == 0, "%s: d_out must be 16-byte aligned", what);
+    SCL_REQUIRE(a.out_stride >= min_slot && a.out_stride < (1ull << 24),
                 "%s: out_stride %llu: striped slots need scl_*_slot_bytes(chunk_len) <= out_stride < 2^24", what,
-                (unsigned long long)out_stride);
-    if (n_chunks == 0) return SCL_OK;
+                (unsigned long long)a.out_stride);
+    if (a.n_chunks == 0) return SCL_OK;
     RowRelay relay;
-    if (int rc = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc;
-    if (!scl_rows_aligned(d_sym, sym_stride)) {
+    if (int rc = relay.in(a, st)) return rc;
+    if (!scl_rows_aligned(a.d_sym, a.sym_stride)) {
         scl_set_error("%s: out of device memory re-laying unaligned symbol rows (hipMallocAsync failed)", what);
         return SCL_E_ALLOC;
     }
-    launch(d_sym, sym_stride);
+    launch(a);
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
 template <class LAUNCH>
-int scl_striped_decode(const char *what, bool served, const u8 *d_in, u64 in_stride, u64 n_chunks, u8 *d_out_sym,
-                       u64 out_stride, u32 out_cap, const u32 *d_out_lens, hipStream_t st, LAUNCH launch) {
+int scl_striped_decode(const char *what, bool served, SclDecodeArgs<u8> a, hipStream_t st, LAUNCH launch) {
     SCL_REQUIRE(served, "%s: this model is not served by the striped kernels (see scl_*_striped_ok)", what);
     SCL_REQUIRE(!scl_force_generic(), "%s: the calling thread keeps the tuned kernels out; striped slots have no other", what);
-    SCL_REQUIRE(((uintptr_t)d_in & 15) == 0 && in_stride % 16 == 0 && in_stride > 0 && in_stride < (1ull << 24),
+    SCL_REQUIRE(((uintptr_t)a.d_in & 15) == 0 && a.in_size_bytes % 16 == 0 && a.in_size_bytes > 0 &&
+                    a.in_size_bytes < (1ull << 24),
                 "%s: d_in must be 16-byte aligned and in_stride a multiple of 16 below 2^24", what);
-    if (n_chunks == 0) return SCL_OK;
+    if (a.n_chunks == 0) return SCL_OK;
     RowRelay relay;  // output rows the kernels cannot store to go through aligned scratch and are copied back
-    if (int rc = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc;
-    if (!scl_rows_aligned(d_out_sym, out_stride)) {
+    if (int rc = relay.out_begin(a, st)) return rc;
+    if (!scl_rows_aligned(a.d_out_sym, a.out_stride)) {
         scl_set_error("%s: out of device memory re-laying unaligned output rows (hipMallocAsync failed)", what);
         return SCL_E_ALLOC;
     }
-    launch(d_out_sym, out_stride);
+    launch(a);
     SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
+    return relay.out_end(a);
 }
 
 // ---- single-chunk host drivers over a batch entry point ----------------------------------------------------------------
@@ -122,26 +121,24 @@ int scl_batch_one(void *d_scratch, u64 scratch_bytes, A... args) {
 
 // ROW_STRIDE(model, n): the symbol row's stride when it is not n (a row's stride is free)
 template <auto BATCH, auto ROW_STRIDE>
-int scl_host_run_enc(const void *model, const u8 *d_sym, u32 n, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                     u32 *d_status, void *d_scratch, u64 scratch_bytes) {
+int scl_host_run_enc(const void *model, const SclEncodeArgs<u8> &a, void *d_scratch, u64 scratch_bytes) {
     using B = SclBatch<decltype(BATCH)>;
     const auto *m = (const typename B::Model *)model;
-    u64 sym_stride = n;
-    if constexpr (!std::is_null_pointer_v<decltype(ROW_STRIDE)>) sym_stride = ROW_STRIDE(m, n);
-    return scl_batch_one<BATCH>(d_scratch, scratch_bytes, m, (const typename B::Sym *)d_sym, sym_stride,
-                                (const u32 *)nullptr, n, (u64)1, d_out, out_stride, d_bit_off, d_nbits, d_status);
+    u64 sym_stride = a.sym_stride;
+    if constexpr (!std::is_null_pointer_v<decltype(ROW_STRIDE)>) sym_stride = ROW_STRIDE(m, a.chunk_len);
+    return scl_batch_one<BATCH>(d_scratch, scratch_bytes, m, (const typename B::Sym *)a.d_sym, sym_stride, a.d_lens,
+                                a.chunk_len, a.n_chunks, a.d_out, a.out_stride, a.d_bit_off, a.d_nbits, a.d_status);
 }
 
 // decoded rows: byte rows padded to a multiple of 16 (what the tuned decoders store), uint16 rows as they are
 template <auto BATCH>
-int scl_host_run_dec(const void *model, const u8 *d_in, u64 in_bytes, const u64 *d_bit_off, const u32 *d_in_nbits,
-                     u8 *d_out_sym, u32 out_cap, u32 *d_out_len, u32 *d_consumed, u32 *d_status, void *d_scratch,
-                     u64 scratch_bytes) {
+int scl_host_run_dec(const void *model, const SclDecodeArgs<u8> &a, void *d_scratch, u64 scratch_bytes) {
     using B = SclBatch<decltype(BATCH)>;
     using S = typename B::Sym;
-    const u64 out_stride = sizeof(S) == 1 ? scl_round_up((u64)out_cap + 1, 16) : (u64)out_cap + 1;
-    return scl_batch_one<BATCH>(d_scratch, scratch_bytes, (const typename B::Model *)model, d_in, in_bytes, d_bit_off,
-                                d_in_nbits, (u64)1, (S *)d_out_sym, out_stride, out_cap, d_out_len, d_consumed, d_status);
+    const u64 out_stride = sizeof(S) == 1 ? scl_round_up((u64)a.out_cap + 1, 16) : (u64)a.out_cap + 1;
+    return scl_batch_one<BATCH>(d_scratch, scratch_bytes, (const typename B::Model *)model, a.d_in, a.in_size_bytes,
+                                a.d_bit_off, a.d_in_nbits, a.n_chunks, (S *)a.d_out_sym, out_stride, a.out_cap,
+                                a.d_out_lens, a.d_consumed, a.d_status);
 }
 
 // SLOT / SCRATCH: the coder's scl_*_slot_bytes(model, n) / scratch size (model, 1 chunk), nullptr if it needs none

@@ -242,83 +242,78 @@ extern "C" uint64_t scl_range_slot_bytes(const scl_range_model *m, uint64_t n_sy
 // ---- batch entry points: one body for uint8 symbols (the tuned kernels first) and uint16 symbols (alphabets up to
 // 65536: the any-parameter kernels) --------------------------------------------------------------------------------------
 template <class SYM>
-static int range_encode(const char *what, const scl_range_model *m, const SYM *d_sym, u64 sym_stride, const u32 *d_lens,
-                        u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                        u32 *d_status, hipStream_t st) {
-    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, d_sym, d_out, d_bit_off, d_nbits, out_stride)) return rc;
-    if (n_chunks == 0) return SCL_OK;
+static int range_encode(const char *what, const scl_range_model *m, const SclEncodeArgs<SYM> &args, hipStream_t st) {
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, args)) return rc;
+    if (args.n_chunks == 0) return SCL_OK;
+    SclEncodeArgs<SYM> a = args;
     RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
     if constexpr (sizeof(SYM) == 1) {
         const bool tuned = !scl_force_generic();
         if (tuned && m->fast)
-            if (int rc = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc;
-        if (tuned && m->fast && scl_rows_aligned(d_sym, sym_stride)) {
-            range_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
-                                     d_nbits, d_status, st);
+            if (int rc = relay.in(a, st)) return rc;
+        if (tuned && m->fast && scl_rows_aligned(a.d_sym, a.sym_stride)) {
+            range_fast_encode_launch(m, a, st);
             SCL_HIP_TRY(hipGetLastError());
             return SCL_OK;
         }
     }
     auto kernel = m->dev.P <= 32 ? range_encode_kernel<u32, SYM> : range_encode_kernel<u64, SYM>;
-    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_sym, sym_stride, d_lens,
-                       chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status);
+    scl_launch_encode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
 template <class SYM>
-static int range_decode(const char *what, const scl_range_model *m, const u8 *d_in, u64 in_size_bytes,
-                        const u64 *d_bit_off, const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride,
-                        u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, d_in, d_bit_off, d_in_nbits, d_out_sym, d_out_lens,
-                                  d_consumed))
-        return rc;
-    if (n_chunks == 0) return SCL_OK;
+static int range_decode(const char *what, const scl_range_model *m, const SclDecodeArgs<SYM> &args, hipStream_t st) {
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, args)) return rc;
+    if (args.n_chunks == 0) return SCL_OK;
+    SclDecodeArgs<SYM> a = args;
     RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
     RangeDev dev = m->dev;
     if constexpr (sizeof(SYM) == 1) {
         const bool tuned = !scl_force_generic();
-        const bool in_ok = ((uintptr_t)d_in & 15) == 0;
+        const bool in_ok = ((uintptr_t)a.d_in & 15) == 0;
         if (tuned && m->fast && in_ok)
-            if (int rc = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc;
-        if (tuned && m->fast && in_ok && scl_rows_aligned(d_out_sym, out_stride)) {
-            range_fast_decode_launch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                     out_cap, d_out_lens, d_consumed, d_status, st);
+            if (int rc = relay.out_begin(a, st)) return rc;
+        if (tuned && m->fast && in_ok && scl_rows_aligned(a.d_out_sym, a.out_stride)) {
+            range_fast_decode_launch(m, a, st);
             SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(d_out_lens);
+            return relay.out_end(a);
         }
     } else {
         dev.d_slot2sym = nullptr;  // a table of BYTES: the u16 kernels search the cumulative counts
     }
     auto kernel = m->dev.P <= 32 ? range_decode_kernel<u32, SYM> : range_decode_kernel<u64, SYM>;
-    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, dev, d_in, in_size_bytes,
-                       d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status);
+    scl_launch_decode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, dev, a);
     SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
+    return relay.out_end(a);
 }
 
 extern "C" int scl_range_encode_batch(const scl_range_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                       const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                       uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                       uint32_t *d_status, void *stream) {
-    return range_encode("range_encode_batch", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                        d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                 d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    return range_encode("range_encode_batch", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_range_decode_batch(const scl_range_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
                                       const uint64_t *d_bit_offset, const uint32_t *d_in_nbits, uint64_t n_chunks,
                                       uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
                                       uint32_t *d_consumed, uint32_t *d_status, void *stream) {
-    return range_decode("range_decode_batch", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
-                        out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    const SclDecodeArgs<u8> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                 out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    return range_decode("range_decode_batch", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_range_encode_batch_u16(const scl_range_model *m, const uint16_t *d_sym, uint64_t sym_stride,
                                           const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                           uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                           uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    return range_encode("range_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                        d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    const SclEncodeArgs<u16> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                  d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    return range_encode("range_encode_batch_u16", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_range_decode_batch_u16(const scl_range_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -326,8 +321,9 @@ extern "C" int scl_range_decode_batch_u16(const scl_range_model *m, const uint8_
                                           uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
                                           uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                           uint32_t *d_status, void *stream) {
-    return range_decode("range_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks,
-                        d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    const SclDecodeArgs<u16> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                  out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    return range_decode("range_decode_batch_u16", m, a, (hipStream_t)stream);
 }
 
 // ---- wave-striped slots (ABI version 8; scl_range_fast.hip: RgOutT, scl_ans_fast_io.h: AnsBitReaderT) ------------------------
@@ -340,15 +336,13 @@ extern "C" int scl_range_encode_batch_striped(const scl_range_model *m, const ui
                                               const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                               uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                               uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
+    const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                 d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
     const char *what = "range_encode_batch_striped";
-    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride))
-        return rc;
+    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, a)) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    return scl_striped_encode(what, scl_range_striped_ok(m), 0, d_sym, sym_stride, chunk_len, n_chunks, d_out,
-                              out_stride, st, [&](const u8 *sym, u64 stride) {
-                                  range_fast_encode_launch(m, sym, stride, d_lens, chunk_len, n_chunks, d_out,
-                                                           out_stride, d_out_bit_offset, d_out_nbits, d_status, st, true);
-                              });
+    return scl_striped_encode(what, scl_range_striped_ok(m), 0, a, st,
+                              [&](const SclEncodeArgs<u8> &rows) { range_fast_encode_launch(m, rows, st, true); });
 }
 
 extern "C" int scl_range_decode_batch_striped(const scl_range_model *m, const uint8_t *d_in, uint64_t in_stride,
@@ -356,16 +350,13 @@ extern "C" int scl_range_decode_batch_striped(const scl_range_model *m, const ui
                                               uint64_t n_chunks, uint8_t *d_out_sym, uint64_t out_stride,
                                               uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                               uint32_t *d_status, void *stream) {
+    const SclDecodeArgs<u8> a = {d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                 out_stride, out_cap, d_out_lens, d_consumed, d_status};
     const char *what = "range_decode_batch_striped";
-    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, d_in, d_bit_offset, d_in_nbits, d_out_sym, d_out_lens,
-                                  d_consumed))
-        return rc;
+    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, a)) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    return scl_striped_decode(what, scl_range_striped_ok(m), d_in, in_stride, n_chunks, d_out_sym, out_stride, out_cap,
-                              d_out_lens, st, [&](u8 *out, u64 stride) {
-                                  range_fast_decode_launch(m, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, out,
-                                                           stride, out_cap, d_out_lens, d_consumed, d_status, st, true);
-                              });
+    return scl_striped_decode(what, scl_range_striped_ok(m), a, st,
+                              [&](const SclDecodeArgs<u8> &rows) { range_fast_decode_launch(m, rows, st, true); });
 }
 
 // ---- single-chunk host drivers --------------------------------------------------------------------------

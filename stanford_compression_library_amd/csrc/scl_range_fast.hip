@@ -976,23 +976,17 @@ bool range_fast_striped_ok(const scl_range_model *m) {
     return m->fdev.uni_t == 0xFFFFFFFFu && m->fdev.M >= 256 && m->fdev.M <= 4096;
 }
 
-void range_fast_encode_launch(const scl_range_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
-                              u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                              u32 *d_status, hipStream_t st, bool striped) {
-    const u32 blocks = (u32)((n_chunks + RGE_THREADS - 1) / RGE_THREADS);
+void range_fast_encode_launch(const scl_range_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, bool striped) {
+    const SclGrid g = {(u32)((a.n_chunks + RGE_THREADS - 1) / RGE_THREADS), RGE_THREADS};
     if (striped) {  // (range_fast_striped_ok holds: the caller checked)
-#define RG_LAUNCH_ENC_T(MODE)                                                                                         \
-    hipLaunchKernelGGL((range_encode_fast_kernel<MODE, RgOutT>), dim3(blocks), dim3(RGE_THREADS), 0, st, m->fdev, d_sym, \
-                       sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status)
+#define RG_LAUNCH_ENC_T(MODE) scl_launch_encode(range_encode_fast_kernel<MODE, RgOutT>, g, st, m->fdev, a)
         if (m->fdev.uni_t == 0) RG_LAUNCH_ENC_T(3);
         else if (m->fdev.m_log2 != 0xFFFFFFFFu) RG_LAUNCH_ENC_T(4);
         else RG_LAUNCH_ENC_T(5);
 #undef RG_LAUNCH_ENC_T
         return;
     }
-#define RG_LAUNCH_ENC(MODE)                                                                                      \
-    hipLaunchKernelGGL(range_encode_fast_kernel<MODE>, dim3(blocks), dim3(RGE_THREADS), 0, st, m->fdev, d_sym,       \
-                       sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status)
+#define RG_LAUNCH_ENC(MODE) scl_launch_encode(range_encode_fast_kernel<MODE>, g, st, m->fdev, a)
     if (m->fdev.uni_t == 0) RG_LAUNCH_ENC(3);
     else if (m->fdev.uni_t != 0xFFFFFFFFu) RG_LAUNCH_ENC(2);
     else if (m->fdev.m_log2 != 0xFFFFFFFFu) {
@@ -1003,26 +997,17 @@ void range_fast_encode_launch(const scl_range_model *m, const u8 *d_sym, u64 sym
 #undef RG_LAUNCH_ENC
 }
 
-void range_fast_decode_launch(const scl_range_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_off,
-                              const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                              u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st, bool striped) {
-    const u32 blocks = (u32)((n_chunks + RGD_THREADS - 1) / RGD_THREADS);
+void range_fast_decode_launch(const scl_range_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, bool striped) {
+    const SclGrid g = {(u32)((a.n_chunks + RGD_THREADS - 1) / RGD_THREADS), RGD_THREADS};
     if (striped) {  // totals 256..4096: slot table + binary32 quotient (range_fast_striped_ok)
-#define RG_LAUNCH_DEC_T(MODE)                                                                                          \
-    hipLaunchKernelGGL((range_decode_fast_kernel<MODE, true, true, true>), dim3(blocks), dim3(RGD_THREADS), 0, st, m->fdev, \
-                       d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,   \
-                       d_consumed, d_status)
+#define RG_LAUNCH_DEC_T(MODE) scl_launch_decode(range_decode_fast_kernel<MODE, true, true, true>, g, st, m->fdev, a)
         if (m->fdev.uni_t == 0) RG_LAUNCH_DEC_T(3);
         else if (m->fdev.m_log2 != 0xFFFFFFFFu) RG_LAUNCH_DEC_T(0);
         else RG_LAUNCH_DEC_T(1);
 #undef RG_LAUNCH_DEC_T
         return;
     }
-#define RG_LAUNCH_DEC2(MODE, LUT, DIV32)                                                                          \
-    hipLaunchKernelGGL((range_decode_fast_kernel<MODE, LUT, DIV32>), dim3(blocks), dim3(RGD_THREADS), 0, st, m->fdev, \
-                       d_in,                                                                                      \
-                       in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,   \
-                       d_consumed, d_status)
+#define RG_LAUNCH_DEC2(MODE, LUT, DIV32) scl_launch_decode(range_decode_fast_kernel<MODE, LUT, DIV32>, g, st, m->fdev, a)
     // totals of 256 and more divide in binary32 (rg_div32)
 #define RG_LAUNCH_DEC(MODE, LUT)                                       \
     do {                                                               \

@@ -296,95 +296,88 @@ extern "C" uint64_t scl_rans_slot_bytes(const scl_rans_model *m, uint64_t n_symb
 // ---- batch entry points: one body for uint8 symbols (the tuned kernels first) and uint16 symbols (alphabets up to
 // 65536: the any-parameter kernels) --------------------------------------------------------------------------------------
 template <class SYM>
-static int rans_encode(const char *what, const scl_rans_model *m, const SYM *d_sym, u64 sym_stride, const u32 *d_lens,
-                       u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                       u32 *d_status, hipStream_t st) {
-    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, d_sym, d_out, d_bit_off, d_nbits, out_stride)) return rc;
-    if (n_chunks == 0) return SCL_OK;
+static int rans_encode(const char *what, const scl_rans_model *m, const SclEncodeArgs<SYM> &args, hipStream_t st) {
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, args)) return rc;
+    if (args.n_chunks == 0) return SCL_OK;
+    SclEncodeArgs<SYM> a = args;
     RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
     if constexpr (sizeof(SYM) == 1) {
         const bool tuned = !scl_force_generic();
-        const bool fits = out_stride >= scl_rans_slot_bytes(m, chunk_len);  // the tuned kernels have no capacity check
+        const bool fits = a.out_stride >= scl_rans_slot_bytes(m, a.chunk_len);  // the tuned kernels have no capacity check
         if (tuned && (m->fast || m->fastb) && fits)
-            if (int rc = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc;
-        const bool rows_ok = scl_rows_aligned(d_sym, sym_stride);
-        if (tuned && m->fast && rows_ok && fits && out_stride < (1ull << 24)) {  // 256 slots within 32-bit offsets
-            rans_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
-                                    d_nbits, d_status, st);
+            if (int rc = relay.in(a, st)) return rc;
+        const bool rows_ok = scl_rows_aligned(a.d_sym, a.sym_stride);
+        if (tuned && m->fast && rows_ok && fits && a.out_stride < (1ull << 24)) {  // 256 slots within 32-bit offsets
+            rans_fast_encode_launch(m, a, st);
             SCL_HIP_TRY(hipGetLastError());
             return SCL_OK;
         }
         if (tuned && m->fastb && rows_ok && fits) {
-            rans_fastb_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
-                                     d_nbits, d_status, st);
+            rans_fastb_encode_launch(m, a, st);
             SCL_HIP_TRY(hipGetLastError());
             return SCL_OK;
         }
     }
     auto kernel = m->state32 ? rans_encode_generic<u32, SYM> : rans_encode_generic<u64, SYM>;
-    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_sym, sym_stride, d_lens,
-                       chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status);
+    scl_launch_encode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
 template <class SYM>
-static int rans_decode(const char *what, const scl_rans_model *m, const u8 *d_in, u64 in_size_bytes,
-                       const u64 *d_bit_off, const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride,
-                       u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, d_in, d_bit_off, d_in_nbits, d_out_sym, d_out_lens,
-                                  d_consumed))
-        return rc;
-    if (n_chunks == 0) return SCL_OK;
+static int rans_decode(const char *what, const scl_rans_model *m, const SclDecodeArgs<SYM> &args, hipStream_t st) {
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, args)) return rc;
+    if (args.n_chunks == 0) return SCL_OK;
+    SclDecodeArgs<SYM> a = args;
     RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
     if constexpr (sizeof(SYM) == 1) {
         const bool tuned = !scl_force_generic();
-        const bool in_ok = ((uintptr_t)d_in & 15) == 0;
+        const bool in_ok = ((uintptr_t)a.d_in & 15) == 0;
         if (tuned && (m->fast || m->fastb) && in_ok)
-            if (int rc = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc;
-        const bool rows_ok = in_ok && scl_rows_aligned(d_out_sym, out_stride);
+            if (int rc = relay.out_begin(a, st)) return rc;
+        const bool rows_ok = in_ok && scl_rows_aligned(a.d_out_sym, a.out_stride);
         if (tuned && m->fast && rows_ok) {
-            rans_fast_decode_launch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                    out_cap, d_out_lens, d_consumed, d_status, st);
+            rans_fast_decode_launch(m, a, st);
             SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(d_out_lens);
+            return relay.out_end(a);
         }
         if (tuned && m->fastb && rows_ok) {
-            rans_fastb_decode_launch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                     out_cap, d_out_lens, d_consumed, d_status, st);
+            rans_fastb_decode_launch(m, a, st);
             SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(d_out_lens);
+            return relay.out_end(a);
         }
     }
     auto kernel = m->state32 ? rans_decode_generic<u32, SYM> : rans_decode_generic<u64, SYM>;
-    hipLaunchKernelGGL(kernel, dim3((u32)((n_chunks + 255) / 256)), dim3(256), 0, st, m->dev, d_in, in_size_bytes,
-                       d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status);
+    scl_launch_decode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
     SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
+    return relay.out_end(a);
 }
 
 extern "C" int scl_rans_encode_batch(const scl_rans_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                      const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                      uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                      uint32_t *d_status, void *stream) {
-    return rans_encode("rans_encode_batch", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                       d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                 d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    return rans_encode("rans_encode_batch", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_rans_decode_batch(const scl_rans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
                                      const uint64_t *d_bit_offset, const uint32_t *d_in_nbits, uint64_t n_chunks,
                                      uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
                                      uint32_t *d_consumed, uint32_t *d_status, void *stream) {
-    return rans_decode("rans_decode_batch", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
-                       out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    const SclDecodeArgs<u8> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                 out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    return rans_decode("rans_decode_batch", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_rans_encode_batch_u16(const scl_rans_model *m, const uint16_t *d_sym, uint64_t sym_stride,
                                          const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                          uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                          uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    return rans_encode("rans_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                       d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    const SclEncodeArgs<u16> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                  d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    return rans_encode("rans_encode_batch_u16", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_rans_decode_batch_u16(const scl_rans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -392,32 +385,23 @@ extern "C" int scl_rans_decode_batch_u16(const scl_rans_model *m, const uint8_t 
                                          uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
                                          uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                          uint32_t *d_status, void *stream) {
-    return rans_decode("rans_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
-                       out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    const SclDecodeArgs<u16> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                  out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    return rans_decode("rans_decode_batch_u16", m, a, (hipStream_t)stream);
 }
 
 // ---- wave-striped slots (ABI version 8; scl_ans_fast_io.h: AnsBackWriterT / AnsBitReaderT) -----------------------------
 // The same streams at the same LOGICAL bit positions, the 64 slots of a wave interleaved in 16-byte pieces in memory.
 // Only the tuned kernels have a striped form (scl_entry.h: scl_striped_encode / scl_striped_decode).  These two bodies
 // serve the rANS entry points and the tANS models the table-free rANS kernels serve (their bound: the rANS model's slot).
-int rans_striped_encode(const char *what, const scl_rans_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
-                        u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                        u32 *d_status, hipStream_t st) {
-    return scl_striped_encode(what, scl_rans_striped_ok(m), scl_rans_slot_bytes(m, chunk_len), d_sym, sym_stride,
-                              chunk_len, n_chunks, d_out, out_stride, st, [&](const u8 *sym, u64 stride) {
-                                  rans_fast_encode_launch(m, sym, stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                                                          d_bit_off, d_nbits, d_status, st, true);
-                              });
+int rans_striped_encode(const char *what, const scl_rans_model *m, const SclEncodeArgs<u8> &args, hipStream_t st) {
+    return scl_striped_encode(what, scl_rans_striped_ok(m), scl_rans_slot_bytes(m, args.chunk_len), args, st,
+                              [&](const SclEncodeArgs<u8> &a) { rans_fast_encode_launch(m, a, st, true); });
 }
 
-int rans_striped_decode(const char *what, const scl_rans_model *m, const u8 *d_in, u64 in_stride, const u64 *d_bit_off,
-                        const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap, u32 *d_out_lens,
-                        u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    return scl_striped_decode(what, scl_rans_striped_ok(m), d_in, in_stride, n_chunks, d_out_sym, out_stride, out_cap,
-                              d_out_lens, st, [&](u8 *out, u64 stride) {
-                                  rans_fast_decode_launch(m, d_in, in_stride, d_bit_off, d_in_nbits, n_chunks, out, stride,
-                                                          out_cap, d_out_lens, d_consumed, d_status, st, true);
-                              });
+int rans_striped_decode(const char *what, const scl_rans_model *m, const SclDecodeArgs<u8> &args, hipStream_t st) {
+    return scl_striped_decode(what, scl_rans_striped_ok(m), args, st,
+                              [&](const SclDecodeArgs<u8> &a) { rans_fast_decode_launch(m, a, st, true); });
 }
 
 extern "C" int scl_rans_striped_ok(const scl_rans_model *m) { return (m && m->fast && m->dev.K <= 256) ? 1 : 0; }
@@ -434,11 +418,11 @@ extern "C" int scl_rans_encode_batch_striped(const scl_rans_model *m, const uint
                                              const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                              uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                              uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
+    const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                 d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
     const char *what = "rans_encode_batch_striped";
-    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride))
-        return rc;
-    return rans_striped_encode(what, m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                               d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, a)) return rc;
+    return rans_striped_encode(what, m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_rans_decode_batch_striped(const scl_rans_model *m, const uint8_t *d_in, uint64_t in_stride,
@@ -446,12 +430,11 @@ extern "C" int scl_rans_decode_batch_striped(const scl_rans_model *m, const uint
                                              uint64_t n_chunks, uint8_t *d_out_sym, uint64_t out_stride,
                                              uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                              uint32_t *d_status, void *stream) {
+    const SclDecodeArgs<u8> a = {d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                 out_stride, out_cap, d_out_lens, d_consumed, d_status};
     const char *what = "rans_decode_batch_striped";
-    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, d_in, d_bit_offset, d_in_nbits, d_out_sym, d_out_lens,
-                                  d_consumed))
-        return rc;
-    return rans_striped_decode(what, m, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                               out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, a)) return rc;
+    return rans_striped_decode(what, m, a, (hipStream_t)stream);
 }
 
 // ---- single-chunk host drivers ------------------------------------------------------------------------

@@ -743,14 +743,11 @@ static RfEncChoice rf_encode_choice(const scl_rans_model *m, u64 n_chunks, bool 
     return c;
 }
 
-void rans_fast_encode_launch(const scl_rans_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
-                             u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                             u32 *d_status, hipStream_t st, bool striped) {
-    const u32 blocks = (u32)((n_chunks + RF_THREADS - 1) / RF_THREADS);
-    const RfEncChoice ch = rf_encode_choice(m, n_chunks, striped);
-#define RF_LAUNCH_ENC_K(OUT, CHECK, MSH, R, NB)                                                                       \
-    hipLaunchKernelGGL((rans_encode_fast_kernel<OUT, CHECK, MSH, R, NB>), dim3(blocks), dim3(RF_THREADS), 0, st, m->fdev, \
-                       d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status)
+void rans_fast_encode_launch(const scl_rans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, bool striped) {
+    const u32 blocks = (u32)((a.n_chunks + RF_THREADS - 1) / RF_THREADS);
+    const RfEncChoice ch = rf_encode_choice(m, a.n_chunks, striped);
+#define RF_LAUNCH_ENC_K(OUT, CHECK, MSH, R, NB) \
+    scl_launch_encode(rans_encode_fast_kernel<OUT, CHECK, MSH, R, NB>, {blocks, RF_THREADS}, st, m->fdev, a)
 #define RF_LAUNCH_ENC_W(CHECK, MSH, R, NB)                  \
     do {                                                    \
         if (ch.striped)                                     \
@@ -815,14 +812,11 @@ void rans_fast_kernel_names(const scl_rans_model *m, u64 n_chunks, char *enc, ch
                  striped ? "true" : "false");
 }
 
-void rans_fast_decode_launch(const scl_rans_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_off,
-                             const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                             u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st, bool striped) {
-    const RfDecChoice ch = rf_decode_choice(m, n_chunks);
-#define RF_LAUNCH_DEC_K(ML, CB, TH, NB, ST)                                                                           \
-    hipLaunchKernelGGL((rans_decode_fast_kernel<ML, CB, TH, NB, ST>), dim3((u32)((n_chunks + TH - 1) / TH)), dim3(TH), 0, \
-                       st, m->fdev, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, \
-                       d_out_lens, d_consumed, d_status)
+void rans_fast_decode_launch(const scl_rans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, bool striped) {
+    const RfDecChoice ch = rf_decode_choice(m, a.n_chunks);
+#define RF_LAUNCH_DEC_K(ML, CB, TH, NB, ST)                                                                          \
+    scl_launch_decode(rans_decode_fast_kernel<ML, CB, TH, NB, ST>, {(u32)((a.n_chunks + TH - 1) / TH), TH}, st, m->fdev, \
+                      a)
 #define RF_LAUNCH_DEC_T(ML, CB, TH, NB)                     \
     do {                                                    \
         if (striped)                                        \

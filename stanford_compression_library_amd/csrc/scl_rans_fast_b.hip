@@ -291,28 +291,20 @@ int rans_fastb_build_tables(scl_rans_model *m, const u32 *h_freq, const u32 *h_c
     return SCL_OK;
 }
 
-void rans_fastb_encode_launch(const scl_rans_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
-                              u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                              u32 *d_status, hipStream_t st) {
-    const u32 blocks = (u32)((n_chunks + RB_THREADS - 1) / RB_THREADS);
+void rans_fastb_encode_launch(const scl_rans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st) {
+    const SclGrid g = {(u32)((a.n_chunks + RB_THREADS - 1) / RB_THREADS), RB_THREADS};
     if (m->fbdev.K < 256)
-        hipLaunchKernelGGL((rans_encode_fastb_kernel<true>), dim3(blocks), dim3(RB_THREADS), 0, st, m->fbdev, d_sym,
-                           sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status);
+        scl_launch_encode(rans_encode_fastb_kernel<true>, g, st, m->fbdev, a);
     else
-        hipLaunchKernelGGL((rans_encode_fastb_kernel<false>), dim3(blocks), dim3(RB_THREADS), 0, st, m->fbdev, d_sym,
-                           sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status);
+        scl_launch_encode(rans_encode_fastb_kernel<false>, g, st, m->fbdev, a);
 }
 
-void rans_fastb_decode_launch(const scl_rans_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_off,
-                              const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                              u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    if (n_chunks > 2ull * 256 * RBD_THREADS_SMALL)  // more than two 256-lane workgroups per CU: the 1024-lane form
-        hipLaunchKernelGGL((rans_decode_fastb_kernel<RBD_THREADS>), dim3((u32)((n_chunks + RBD_THREADS - 1) / RBD_THREADS)),
-                           dim3(RBD_THREADS), 0, st, m->fbdev, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks,
-                           d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status);
+void rans_fastb_decode_launch(const scl_rans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st) {
+    if (a.n_chunks > 2ull * 256 * RBD_THREADS_SMALL)  // more than two 256-lane workgroups per CU: the 1024-lane form
+        scl_launch_decode(rans_decode_fastb_kernel<RBD_THREADS>,
+                          {(u32)((a.n_chunks + RBD_THREADS - 1) / RBD_THREADS), RBD_THREADS}, st, m->fbdev, a);
     else
-        hipLaunchKernelGGL((rans_decode_fastb_kernel<RBD_THREADS_SMALL>),
-                           dim3((u32)((n_chunks + RBD_THREADS_SMALL - 1) / RBD_THREADS_SMALL)), dim3(RBD_THREADS_SMALL), 0,
-                           st, m->fbdev, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                           out_cap, d_out_lens, d_consumed, d_status);
+        scl_launch_decode(rans_decode_fastb_kernel<RBD_THREADS_SMALL>,
+                          {(u32)((a.n_chunks + RBD_THREADS_SMALL - 1) / RBD_THREADS_SMALL), RBD_THREADS_SMALL}, st,
+                          m->fbdev, a);
 }

@@ -403,11 +403,11 @@ extern "C" int scl_tans_encode_batch_striped(const scl_tans_model *m, const uint
                                              const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                              uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                              uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
+    const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                 d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
     const char *what = "tans_encode_batch_striped";
-    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, d_sym, d_out, d_out_bit_offset, d_out_nbits, out_stride))
-        return rc;
-    return rans_striped_encode(what, m->rans, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                               d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    if (int rc = scl_check_encode(what, SCL_ROWS_STRIPED, m, a)) return rc;
+    return rans_striped_encode(what, m->rans, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_tans_decode_batch_striped(const scl_tans_model *m, const uint8_t *d_in, uint64_t in_stride,
@@ -415,42 +415,38 @@ extern "C" int scl_tans_decode_batch_striped(const scl_tans_model *m, const uint
                                              uint64_t n_chunks, uint8_t *d_out_sym, uint64_t out_stride,
                                              uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                              uint32_t *d_status, void *stream) {
+    const SclDecodeArgs<u8> a = {d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                 out_stride, out_cap, d_out_lens, d_consumed, d_status};
     const char *what = "tans_decode_batch_striped";
-    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, d_in, d_bit_offset, d_in_nbits, d_out_sym, d_out_lens,
-                                  d_consumed))
-        return rc;
-    return rans_striped_decode(what, m->rans, d_in, in_stride, d_bit_offset, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                               out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    if (int rc = scl_check_decode(what, SCL_ROWS_STRIPED, m, a)) return rc;
+    return rans_striped_decode(what, m->rans, a, (hipStream_t)stream);
 }
 
 // ---- batch entry points: one body for uint8 symbols (the tuned kernels first) and uint16 symbols (alphabets up to
 // 65536: lookup tables in device memory) -----------------------------------------------------------------------------
 template <class SYM>
-static int tans_encode(const char *what, const scl_tans_model *m, const SYM *d_sym, u64 sym_stride, const u32 *d_lens,
-                       u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                       u32 *d_status, hipStream_t st) {
-    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, d_sym, d_out, d_bit_off, d_nbits, out_stride)) return rc;
-    if (n_chunks == 0) return SCL_OK;
+static int tans_encode(const char *what, const scl_tans_model *m, const SclEncodeArgs<SYM> &args, hipStream_t st) {
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, args)) return rc;
+    if (args.n_chunks == 0) return SCL_OK;
+    SclEncodeArgs<SYM> a = args;
     RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
     if constexpr (sizeof(SYM) == 1) {
         const bool tuned = !scl_force_generic();
         const bool table_first = m->fast && tans_table_kernels_forced();  // else the table-free kernels when the model has them
         if ((tuned || !m->tables) && (m->fast || m->rans))
-            if (int rc = relay.in(d_sym, sym_stride, chunk_len, n_chunks, st)) return rc;
-        const bool rows_ok = scl_rows_aligned(d_sym, sym_stride);
-        const bool fast_ok = tuned && m->fast && rows_ok && out_stride >= scl_tans_slot_bytes(m, chunk_len);
+            if (int rc = relay.in(a, st)) return rc;
+        const bool rows_ok = scl_rows_aligned(a.d_sym, a.sym_stride);
+        const bool fast_ok = tuned && m->fast && rows_ok && a.out_stride >= scl_tans_slot_bytes(m, a.chunk_len);
         // same stream from the table-free rANS kernels (32-bit slot offsets per workgroup)
         const bool rans_ok = (tuned || !m->tables) && m->rans && rows_ok &&
-                             out_stride >= scl_rans_slot_bytes(m->rans, chunk_len) && out_stride < (1ull << 24);
+                             a.out_stride >= scl_rans_slot_bytes(m->rans, a.chunk_len) && a.out_stride < (1ull << 24);
         if (rans_ok && !(table_first && fast_ok)) {
-            rans_fast_encode_launch(m->rans, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
-                                    d_nbits, d_status, st);
+            rans_fast_encode_launch(m->rans, a, st);
             SCL_HIP_TRY(hipGetLastError());
             return SCL_OK;
         }
         if (fast_ok) {
-            tans_fast_encode_launch(m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
-                                    d_nbits, d_status, st);
+            tans_fast_encode_launch(m, a, st);
             SCL_HIP_TRY(hipGetLastError());
             return SCL_OK;
         }
@@ -464,41 +460,35 @@ static int tans_encode(const char *what, const scl_tans_model *m, const SYM *d_s
                 sizeof(SYM) == 1 ? "; it needs 16-byte aligned symbol rows and slots of scl_tans_slot_bytes" : "");
     if (int rc = tans_ensure_tables(m)) return rc;
     const u32 lds = sizeof(SYM) == 1 ? (768 + (m->dev.lds_tables ? m->dev.L : 0)) * sizeof(u32) : 16;
-    hipLaunchKernelGGL(tans_encode_kernel<SYM>, dim3((u32)((n_chunks + 255) / 256)), dim3(256), lds, st, m->dev, d_sym,
-                       sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off, d_nbits, d_status);
+    scl_launch_encode(tans_encode_kernel<SYM>, {(u32)((a.n_chunks + 255) / 256), 256, lds}, st, m->dev, a);
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
 template <class SYM>
-static int tans_decode(const char *what, const scl_tans_model *m, const u8 *d_in, u64 in_size_bytes,
-                       const u64 *d_bit_off, const u32 *d_in_nbits, u64 n_chunks, SYM *d_out_sym, u64 out_stride,
-                       u32 out_cap, u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, d_in, d_bit_off, d_in_nbits, d_out_sym, d_out_lens,
-                                  d_consumed))
-        return rc;
-    if (n_chunks == 0) return SCL_OK;
+static int tans_decode(const char *what, const scl_tans_model *m, const SclDecodeArgs<SYM> &args, hipStream_t st) {
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, args)) return rc;
+    if (args.n_chunks == 0) return SCL_OK;
+    SclDecodeArgs<SYM> a = args;
     RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
     if constexpr (sizeof(SYM) == 1) {
         const bool tuned = !scl_force_generic();
-        const bool in_ok = ((uintptr_t)d_in & 15) == 0;
+        const bool in_ok = ((uintptr_t)a.d_in & 15) == 0;
         if ((tuned || !m->tables) && (m->fast || m->rans) && in_ok)
-            if (int rc = relay.out_begin(d_out_sym, out_stride, out_cap, n_chunks, st)) return rc;
+            if (int rc = relay.out_begin(a, st)) return rc;
         const bool table_first = m->fast && tans_table_kernels_forced();
-        const bool bufs_ok = in_ok && scl_rows_aligned(d_out_sym, out_stride);
+        const bool bufs_ok = in_ok && scl_rows_aligned(a.d_out_sym, a.out_stride);
         const bool fast_ok = tuned && m->fast && bufs_ok;
         const bool rans_ok = (tuned || !m->tables) && m->rans && bufs_ok;
         if (rans_ok && !(table_first && fast_ok)) {
-            rans_fast_decode_launch(m->rans, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                    out_cap, d_out_lens, d_consumed, d_status, st);
+            rans_fast_decode_launch(m->rans, a, st);
             SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(d_out_lens);
+            return relay.out_end(a);
         }
         if (fast_ok) {
-            tans_fast_decode_launch(m, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride,
-                                    out_cap, d_out_lens, d_consumed, d_status, st);
+            tans_fast_decode_launch(m, a, st);
             SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(d_out_lens);
+            return relay.out_end(a);
         }
         if (!m->tables && relay.failed) {
             scl_set_error("%s: out of device memory re-laying unaligned output rows (hipMallocAsync failed) and this "
@@ -510,35 +500,36 @@ static int tans_decode(const char *what, const scl_tans_model *m, const u8 *d_in
                 sizeof(SYM) == 1 ? "; it needs 16-byte aligned buffers" : "");
     if (int rc = tans_ensure_tables(m)) return rc;
     const u32 lds = (m->dev.lds_tables ? 2 * m->dev.L : 4) * sizeof(u32);
-    hipLaunchKernelGGL(tans_decode_kernel<SYM>, dim3((u32)((n_chunks + 255) / 256)), dim3(256), lds, st, m->dev, d_in,
-                       in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap, d_out_lens,
-                       d_consumed, d_status);
+    scl_launch_decode(tans_decode_kernel<SYM>, {(u32)((a.n_chunks + 255) / 256), 256, lds}, st, m->dev, a);
     SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(d_out_lens);
+    return relay.out_end(a);
 }
 
 extern "C" int scl_tans_encode_batch(const scl_tans_model *m, const uint8_t *d_sym, uint64_t sym_stride,
                                      const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out,
                                      uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits,
                                      uint32_t *d_status, void *stream) {
-    return tans_encode("tans_encode_batch", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                       d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                 d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    return tans_encode("tans_encode_batch", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_tans_decode_batch(const scl_tans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
                                      const uint64_t *d_bit_offset, const uint32_t *d_in_nbits, uint64_t n_chunks,
                                      uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens,
                                      uint32_t *d_consumed, uint32_t *d_status, void *stream) {
-    return tans_decode("tans_decode_batch", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
-                       out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    const SclDecodeArgs<u8> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                 out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    return tans_decode("tans_decode_batch", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_tans_encode_batch_u16(const scl_tans_model *m, const uint16_t *d_sym, uint64_t sym_stride,
                                          const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
                                          uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
                                          uint32_t *d_out_nbits, uint32_t *d_status, void *stream) {
-    return tans_encode("tans_encode_batch_u16", m, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride,
-                       d_out_bit_offset, d_out_nbits, d_status, (hipStream_t)stream);
+    const SclEncodeArgs<u16> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
+                                  d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
+    return tans_encode("tans_encode_batch_u16", m, a, (hipStream_t)stream);
 }
 
 extern "C" int scl_tans_decode_batch_u16(const scl_tans_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -546,8 +537,9 @@ extern "C" int scl_tans_decode_batch_u16(const scl_tans_model *m, const uint8_t 
                                          uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
                                          uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                          uint32_t *d_status, void *stream) {
-    return tans_decode("tans_decode_batch_u16", m, d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
-                       out_stride, out_cap, d_out_lens, d_consumed, d_status, (hipStream_t)stream);
+    const SclDecodeArgs<u16> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
+                                  out_stride, out_cap, d_out_lens, d_consumed, d_status};
+    return tans_decode("tans_decode_batch_u16", m, a, (hipStream_t)stream);
 }
 
 // ---- single-chunk host drivers --------------------------------------------------------------------------

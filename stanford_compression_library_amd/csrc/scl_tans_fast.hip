@@ -294,30 +294,20 @@ int tans_fast_build_tables(scl_tans_model *m, const u32 *h_freq, const u32 *h_cu
     return SCL_OK;
 }
 
-void tans_fast_encode_launch(const scl_tans_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
-                             u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                             u32 *d_status, hipStream_t st) {
-    if (n_chunks > 2ull * 256 * TF_THREADS_SMALL)
-        hipLaunchKernelGGL((tans_encode_fast_kernel<TF_THREADS>), dim3((u32)((n_chunks + TF_THREADS - 1) / TF_THREADS)),
-                           dim3(TF_THREADS), 0, st, m->fdev, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out,
-                           out_stride, d_bit_off, d_nbits, d_status);
+void tans_fast_encode_launch(const scl_tans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st) {
+    if (a.n_chunks > 2ull * 256 * TF_THREADS_SMALL)
+        scl_launch_encode(tans_encode_fast_kernel<TF_THREADS>,
+                          {(u32)((a.n_chunks + TF_THREADS - 1) / TF_THREADS), TF_THREADS}, st, m->fdev, a);
     else
-        hipLaunchKernelGGL((tans_encode_fast_kernel<TF_THREADS_SMALL>),
-                           dim3((u32)((n_chunks + TF_THREADS_SMALL - 1) / TF_THREADS_SMALL)), dim3(TF_THREADS_SMALL), 0, st,
-                           m->fdev, d_sym, sym_stride, d_lens, chunk_len, n_chunks, d_out, out_stride, d_bit_off,
-                           d_nbits, d_status);
+        scl_launch_encode(tans_encode_fast_kernel<TF_THREADS_SMALL>,
+                          {(u32)((a.n_chunks + TF_THREADS_SMALL - 1) / TF_THREADS_SMALL), TF_THREADS_SMALL}, st, m->fdev, a);
 }
 
-void tans_fast_decode_launch(const scl_tans_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_off,
-                             const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                             u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st) {
-    if (n_chunks > 2ull * 256 * TF_THREADS_SMALL)
-        hipLaunchKernelGGL((tans_decode_fast_kernel<TF_THREADS>), dim3((u32)((n_chunks + TF_THREADS - 1) / TF_THREADS)),
-                           dim3(TF_THREADS), 0, st, m->fdev, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks,
-                           d_out_sym, out_stride, out_cap, d_out_lens, d_consumed, d_status);
+void tans_fast_decode_launch(const scl_tans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st) {
+    if (a.n_chunks > 2ull * 256 * TF_THREADS_SMALL)
+        scl_launch_decode(tans_decode_fast_kernel<TF_THREADS>,
+                          {(u32)((a.n_chunks + TF_THREADS - 1) / TF_THREADS), TF_THREADS}, st, m->fdev, a);
     else
-        hipLaunchKernelGGL((tans_decode_fast_kernel<TF_THREADS_SMALL>),
-                           dim3((u32)((n_chunks + TF_THREADS_SMALL - 1) / TF_THREADS_SMALL)), dim3(TF_THREADS_SMALL), 0, st,
-                           m->fdev, d_in, in_size_bytes, d_bit_off, d_in_nbits, n_chunks, d_out_sym, out_stride, out_cap,
-                           d_out_lens, d_consumed, d_status);
+        scl_launch_decode(tans_decode_fast_kernel<TF_THREADS_SMALL>,
+                          {(u32)((a.n_chunks + TF_THREADS_SMALL - 1) / TF_THREADS_SMALL), TF_THREADS_SMALL}, st, m->fdev, a);
 }

@@ -51,9 +51,5 @@ struct scl_tans_model {
 };
 
 int tans_fast_build_tables(scl_tans_model *m, const u32 *h_freq, const u32 *h_cum);
-void tans_fast_encode_launch(const scl_tans_model *m, const u8 *d_sym, u64 sym_stride, const u32 *d_lens,
-                             u32 chunk_len, u64 n_chunks, u8 *d_out, u64 out_stride, u64 *d_bit_off, u32 *d_nbits,
-                             u32 *d_status, hipStream_t st);
-void tans_fast_decode_launch(const scl_tans_model *m, const u8 *d_in, u64 in_size_bytes, const u64 *d_bit_off,
-                             const u32 *d_in_nbits, u64 n_chunks, u8 *d_out_sym, u64 out_stride, u32 out_cap,
-                             u32 *d_out_lens, u32 *d_consumed, u32 *d_status, hipStream_t st);
+void tans_fast_encode_launch(const scl_tans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st);
+void tans_fast_decode_launch(const scl_tans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st);
