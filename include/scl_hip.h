@@ -16,6 +16,10 @@
  *   scl_aec_decode_batch    <->  ArithmeticDecoder.decode_block  scl/compressors/arithmetic_coding.py:203-287
  *   (model handles)         <->  rANSParams / tANSParams / RangeCoderParams+Frequencies /
  *                                AECParams+FreqModelBase subclasses (probability_models.py:15-160)
+ *   scl_prefix_encode_batch <->  PrefixFreeEncoder.encode_block  scl/compressors/prefix_free_compressors.py:31-50
+ *   scl_prefix_decode_batch <->  PrefixFreeDecoder.decode_block  scl/compressors/prefix_free_compressors.py:67-88
+ *   (scl_prefix_model)      <->  the code table of a PrefixFreeTree (get_encoding_table, :123-155), e.g. the one
+ *                                HuffmanTree.build_huffman_tree makes (scl/compressors/huffman_coder.py:45-93)
  *   scl_streams_compact     <->  the BitArray each encode_block returns (left-aligned bits) and,
  *                                with SCL_COMPACT_FRAMED, EncodedBlockWriter.write_block
  *                                (scl/core/encoded_stream.py:150-175)
@@ -264,6 +268,69 @@ int scl_aec_decode_batch_resume(const scl_aec_model *m, const uint8_t *d_in, uin
                                 uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
                                 uint32_t *d_status, void *d_state, uint64_t state_bytes, uint64_t n_coders,
                                 void *stream);
+
+/* ---- prefix-free codes (added to ABI 8 without a version change: the number is pinned by the test suite) ------------
+ * Any prefix-free code table: Huffman today (HuffmanEncoder / HuffmanDecoder, huffman_coder.py:96-123), Shannon, Fano and
+ * the rest with host code only.  A stream is the block's codewords back to back (prefix_free_compressors.py:31-50): NO size
+ * header and no terminator, an empty block is an empty stream, and the decoder walks the tree until in_nbits bits are
+ * consumed (:67-88) -- it needs the exact bit length and tolerates no trailing bits.
+ * Symbol i is coded with the h_len[i] low bits of h_code[i], most significant first.  Rejected (SCL_E_PARAM): K outside
+ * 1..65536, a length of 0 or above 32, a codeword that equals or is a prefix of another.  Incomplete trees are accepted (the
+ * one-symbol Huffman code "0" is one).
+ * Tuned kernels serve byte symbols (K <= 256; fast_path in scl_prefix_info); the *_u16 twins and
+ * scl_set_any_parameter_kernels(1) run the any-parameter kernels, which write and read the same streams.
+ *   encode: streams grow front to back, bit_offset[c] = 8*c*out_stride, nbits[c] = sum of the code lengths (0 for an empty
+ *           chunk).  SCL_ST_SYMBOL: a symbol index >= K (coded as symbol 0); SCL_ST_CAPACITY: the slot is too small (nothing is
+ *           stored past it, nbits[c] still reports the length needed).
+ *   decode: d_out_lens[c] = symbols decoded (there is no header to read a count from), d_consumed[c] = bits of the whole
+ *           codewords decoded.  SCL_ST_CAPACITY: bits are left after out_cap symbols (nothing is stored past out_cap);
+ *           SCL_ST_TRUNCATED: in_nbits ends inside a codeword (the complete symbols before it are delivered);
+ *           SCL_ST_STATE: the bits walk into a missing child of an incomplete tree. */
+typedef struct scl_prefix_model scl_prefix_model;
+
+typedef struct scl_prefix_info {
+    uint32_t K;
+    uint32_t min_len, max_len; /* shortest / longest codeword in bits                                */
+    uint32_t lut_bits;         /* T = min(max_len, 11): the tuned decoder's lookup table has 2^T entries */
+    uint32_t fast_path;        /* 1 if the tuned kernels serve this model (K <= 256)                  */
+    int32_t device;
+} scl_prefix_info;
+
+int scl_prefix_model_create(const uint32_t *h_code, const uint8_t *h_len, uint32_t K, scl_prefix_model **out);
+void scl_prefix_model_destroy(scl_prefix_model *m);
+int scl_prefix_model_info(const scl_prefix_model *m, scl_prefix_info *info);
+/* as scl_rans_kernel_names */
+int scl_prefix_kernel_names(const scl_prefix_model *m, uint64_t n_chunks, char *enc, char *dec, uint64_t cap);
+/* a multiple of 128 that holds n_symbols codewords of the longest length and the writer's last whole word */
+uint64_t scl_prefix_slot_bytes(const scl_prefix_model *m, uint64_t n_symbols);
+int scl_prefix_encode_batch(const scl_prefix_model *m, const uint8_t *d_sym, uint64_t sym_stride,
+                            const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
+                            uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
+                            uint32_t *d_out_nbits, uint32_t *d_status, void *stream);
+int scl_prefix_decode_batch(const scl_prefix_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
+                            const uint64_t *d_bit_offset, const uint32_t *d_in_nbits,
+                            uint64_t n_chunks, uint8_t *d_out_sym, uint64_t out_stride,
+                            uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
+                            uint32_t *d_status, void *stream);
+int scl_prefix_encode_batch_u16(const scl_prefix_model *m, const uint16_t *d_sym, uint64_t sym_stride,
+                                const uint32_t *d_lens, uint32_t chunk_len, uint64_t n_chunks,
+                                uint8_t *d_out, uint64_t out_stride, uint64_t *d_out_bit_offset,
+                                uint32_t *d_out_nbits, uint32_t *d_status, void *stream);
+int scl_prefix_decode_batch_u16(const scl_prefix_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
+                                const uint64_t *d_bit_offset, const uint32_t *d_in_nbits,
+                                uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
+                                uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
+                                uint32_t *d_status, void *stream);
+/* one chunk in host memory, as the other *_host calls; the decoder's out_cap bounds the symbols (in_nbits / min_len holds
+   any stream) */
+int scl_prefix_encode_host(const scl_prefix_model *m, const uint8_t *h_sym, uint64_t n, uint8_t *h_out,
+                           uint64_t out_cap_bytes, uint64_t *nbits);
+int scl_prefix_decode_host(const scl_prefix_model *m, const uint8_t *h_in, uint64_t in_nbits,
+                           uint8_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed);
+int scl_prefix_encode_host_u16(const scl_prefix_model *m, const uint16_t *h_sym, uint64_t n, uint8_t *h_out,
+                               uint64_t out_cap_bytes, uint64_t *nbits);
+int scl_prefix_decode_host_u16(const scl_prefix_model *m, const uint8_t *h_in, uint64_t in_nbits,
+                               uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed);
 
 /* ---- stream compaction / framing ------------------------------------------------------------ */
 #define SCL_COMPACT_DENSE 0  /* stream c left-aligned at byte d_out_byte_offset[c], zero tail   */

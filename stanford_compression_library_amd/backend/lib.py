@@ -37,6 +37,11 @@ class RansInfo(C.Structure):
                 ("max_bits_per_symbol", C.c_uint32), ("fast_path", C.c_uint32), ("device", C.c_int32)]
 
 
+class PrefixInfo(C.Structure):
+    _fields_ = [("K", C.c_uint32), ("min_len", C.c_uint32), ("max_len", C.c_uint32), ("lut_bits", C.c_uint32),
+                ("fast_path", C.c_uint32), ("device", C.c_int32)]
+
+
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _vp, _u32, _u64, _int = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 
@@ -78,6 +83,16 @@ _SIGNATURES = {
     "scl_range_decode_batch": (_int, _DEC_BATCH),
     "scl_range_encode_host": (_int, _ENC_HOST),
     "scl_range_decode_host": (_int, _DEC_HOST),
+    # prefix-free codes (any code table; Huffman): added to ABI 8
+    "scl_prefix_model_create": (_int, [_u32p, _u8p, _u32, C.POINTER(_vp)]),
+    "scl_prefix_model_destroy": (None, [_vp]),
+    "scl_prefix_model_info": (_int, [_vp, C.POINTER(PrefixInfo)]),
+    "scl_prefix_kernel_names": (_int, [_vp, _u64, C.c_char_p, C.c_char_p, _u64]),
+    "scl_prefix_slot_bytes": (_u64, [_vp, _u64]),
+    "scl_prefix_encode_batch": (_int, _ENC_BATCH),
+    "scl_prefix_decode_batch": (_int, _DEC_BATCH),
+    "scl_prefix_encode_host": (_int, _ENC_HOST),
+    "scl_prefix_decode_host": (_int, _DEC_HOST),
     "scl_aec_model_create": (_int, [_int, _u32p, _u32, _u32, _u64, _u32, _u32, C.POINTER(_vp)]),
     "scl_aec_model_destroy": (None, [_vp]),
     "scl_aec_slot_bytes": (_u64, [_vp, _u64]),
@@ -131,7 +146,7 @@ _SIGNATURES = {
 # the *_u16 twins (alphabets up to 65536 symbols): same arguments, symbol arrays are uint16; host arrays travel as void*
 _ENC_HOST16 = [_vp, _vp, _u64, _u8p, _u64, _u64p]
 _DEC_HOST16 = [_vp, _u8p, _u64, _vp, _u64, _u64p, _u64p]
-for _coder in ("rans", "tans", "range", "aec"):
+for _coder in ("rans", "tans", "range", "aec", "prefix"):
     for _op, _host in (("encode", _ENC_HOST16), ("decode", _DEC_HOST16)):
         _SIGNATURES[f"scl_{_coder}_{_op}_batch_u16"] = _SIGNATURES[f"scl_{_coder}_{_op}_batch"]
         _SIGNATURES[f"scl_{_coder}_{_op}_host_u16"] = (_int, _host)

@@ -431,6 +431,48 @@ class RangeModel(_DeviceModel):
         return bool(self._L.scl_range_fast_path(self._h))
 
 
+class PrefixModel(_DeviceModel):
+    """any prefix-free code table on the device: symbol i is coded with the ``lengths[i]`` low bits of ``codes[i]``, most
+    significant first (1..32 bits).  Linear slots only.  The streams carry no size header (``size_bits`` = 0)."""
+
+    _prefix = "prefix"
+    size_bits = 0
+
+    def __init__(self, codes, lengths):
+        super().__init__()
+        c = np.ascontiguousarray(np.asarray(codes, dtype=np.uint64).astype(np.uint32))
+        n = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).clip(0, 255).astype(np.uint8))
+        assert c.ndim == 1 and c.shape == n.shape, "one code and one length per symbol"
+        rc = self._L.scl_prefix_model_create(_lib.u32_ptr(c), _lib.u8_ptr(n), c.size, C.byref(self._h))
+        _lib.check(rc, "scl_prefix_model_create")
+        self.K = int(c.size)
+        self.min_len = int(n.min())
+
+    def info(self) -> _lib.PrefixInfo:
+        info = _lib.PrefixInfo()
+        _lib.check(self._L.scl_prefix_model_info(self._h, C.byref(info)), "scl_prefix_model_info")
+        return info
+
+    def fast_path(self) -> bool:
+        """True if the tuned kernels (byte symbols, K <= 256) serve this model."""
+        return bool(self.info().fast_path)
+
+    def decode_host(self, packed: np.ndarray, nbits: int, size_bits: int = 0, max_block_size: Optional[int] = None):
+        """(packed bytes, EXACT stream bits) -> (index array of ``sym_dtype``, num_bits_consumed).  There is no size header
+        to peek: the output holds ``nbits // min_len`` symbols, which bounds any stream of this code."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        cap = int(nbits) // self.min_len
+        self._check_block_size(cap, max_block_size)
+        if packed.size == 0:
+            packed = np.zeros(1, dtype=np.uint8)
+        out = np.zeros(max(cap, 1), dtype=self.sym_dtype)
+        n_out, used = C.c_uint64(0), C.c_uint64(0)
+        rc = self._sym_fn("decode_host")(self._h, _lib.u8_ptr(packed), int(nbits), self._host_ptr(out), cap,
+                                         C.byref(n_out), C.byref(used))
+        _lib.check(rc, "scl_prefix_decode_host")
+        return out[: n_out.value], int(used.value)
+
+
 class AecModel(_DeviceModel):
     _prefix = "aec"
     _needs_scratch = True

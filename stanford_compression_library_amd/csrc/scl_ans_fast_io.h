@@ -1086,7 +1086,9 @@ struct AnsBitReaderT {
 // Forward twin of AnsBackWriter for streams that grow front to back (arithmetic coder): completed big-endian
 // words go to the per-lane LDS ring ([word][thread], at LDS offset 0) and leave for memory as whole 128-byte lines
 // (the first 64-byte half waits in registers), so that a lane only ever stores whole, aligned lines.
-template <int THREADS>
+// BOUNDED (the prefix-code encoder, scl_prefix.hip): the slot holds `cap` bytes (a multiple of 16); a line or tail that
+// would cross it is not stored and sets `overflow`, the bit count still comes out whole -- as RgOut (scl_range_fast.hip).
+template <int THREADS, bool BOUNDED = false>
 struct AnsFwdWriter {
     static constexpr u32 RING_BYTES = 32u * THREADS * 4u;
     u32 hi;    // pending bits, right-aligned (the oldest is the most significant), < 32 of them
@@ -1098,8 +1100,12 @@ struct AnsFwdWriter {
     u8 *slot;
     uint4 held[4];
     u32 have_held;
+    u64 cap;       // BOUNDED: slot capacity in bytes
+    u32 overflow;  // BOUNDED: something did not fit
 
-    __device__ __forceinline__ void init(u32 tid, u8 *slot_) {
+    __device__ __forceinline__ void init(u32 tid, u8 *slot_, u64 cap_ = 0) {
+        cap = cap_;
+        overflow = 0;
         hi = 0;
         nacc = 0;
         ra = tid * 4;
@@ -1154,15 +1160,19 @@ struct AnsFwdWriter {
             const uint4 q0 = make_uint4(w[0], w[1], w[2], w[3]), q1 = make_uint4(w[4], w[5], w[6], w[7]);
             const uint4 q2 = make_uint4(w[8], w[9], w[10], w[11]), q3 = make_uint4(w[12], w[13], w[14], w[15]);
             if (have_held) {  // second half of the line whose first half is held
-                uint4 *p = reinterpret_cast<uint4 *>(slot + 4 * (u64)(nfl - 16));
-                p[0] = held[0];
-                p[1] = held[1];
-                p[2] = held[2];
-                p[3] = held[3];
-                p[4] = q0;
-                p[5] = q1;
-                p[6] = q2;
-                p[7] = q3;
+                if (!BOUNDED || 4 * (u64)nfl + 64 <= cap) {
+                    uint4 *p = reinterpret_cast<uint4 *>(slot + 4 * (u64)(nfl - 16));
+                    p[0] = held[0];
+                    p[1] = held[1];
+                    p[2] = held[2];
+                    p[3] = held[3];
+                    p[4] = q0;
+                    p[5] = q1;
+                    p[6] = q2;
+                    p[7] = q3;
+                } else {
+                    overflow = 1;
+                }
                 have_held = 0;
             } else {
                 held[0] = q0;
@@ -1186,6 +1196,10 @@ struct AnsFwdWriter {
     }
     __device__ __forceinline__ u64 finish(char *lds) {  // returns the stream length in bits
         maybe_flush(lds);
+        if (BOUNDED) {  // the tail goes out in whole words: all of it fits, or none of it is stored
+            if (4 * ((u64)nfl + pend + (nacc ? 1u : 0u)) > cap) overflow = 1;
+            if (overflow) return (u64)(nfl + pend) * 32 + nacc;
+        }
         if (have_held) {
             uint4 *p = reinterpret_cast<uint4 *>(slot + 4 * (u64)(nfl - 16));
             p[0] = held[0];
