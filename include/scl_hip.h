@@ -332,6 +332,68 @@ int scl_prefix_encode_host_u16(const scl_prefix_model *m, const uint16_t *h_sym,
 int scl_prefix_decode_host_u16(const scl_prefix_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed);
 
+/* ---- prefix-free codes, ONE large block coded by the whole grid (scl_prefix_block.hip; added to ABI 8 as above) ----------
+ * The batch calls give a chunk to one lane; these give one block to every CU and write / read the very same stream
+ * (codewords back to back, no side information), from the same scl_prefix_model.  Positions and counts are 64-bit.
+ *   encode: per-tile sums of the code lengths, an exclusive scan of the tile sums, then every workgroup assembles its
+ *           tile in LDS and stores whole 32-bit words; the words two tiles share are merged with atomic ORs, so the
+ *           call zeroes d_out first (up to out_cap_bytes).  d_out 4-byte aligned.  *d_nbits = sum of the code lengths,
+ *           also when it does not fit.  *d_status: SCL_ST_SYMBOL (an index >= K, coded as symbol 0), SCL_ST_CAPACITY
+ *           ((nbits + 7) / 8 > out_cap_bytes: the stream is not written; nothing is ever stored at or past
+ *           d_out + out_cap_bytes).  Asynchronous on `stream`.
+ *   decode: self-synchronising speculative decoding (Weissenberger & Schmidt 2018): the stream is cut into subsequences
+ *           of sub_bits bits, one per thread, 256 per workgroup; every thread decodes from a guessed start, takes its
+ *           left neighbour's exit as its start and decodes again until nothing changes -- inside a workgroup under
+ *           __syncthreads, between workgroups by relaunching a pass until a device flag says that no workgroup's exit
+ *           changed.  THE CALL READS THAT FLAG BETWEEN PASSES: it synchronises `stream` once per pass (a stream inside
+ *           one workgroup needs no pass and no synchronisation).  No kernel waits on another workgroup.  The result is the sequential decode for every table and
+ *           every stream; a code that never falls into step costs one pass per workgroup.
+ *           d_in 4-byte aligned; the stream is the in_nbits bits from absolute bit in_bit_offset of d_in, and reads stay
+ *           inside [d_in, d_in + in_size_bytes).  d_result receives what the one-lane decoder reports for the same
+ *           stream: n_out symbols stored (never more than out_cap), consumed = bits of the whole codewords decoded,
+ *           status 0 / SCL_ST_TRUNCATED / SCL_ST_STATE / SCL_ST_CAPACITY, and sync_passes = passes after the first in
+ *           which a workgroup had to move its start (0: the speculation was right at every workgroup boundary).
+ * SCL_E_PARAM (message = the entry point's name + ':'), before any device call: null model or buffers, a model of
+ * another device, the uint8 form with K > 256, misaligned d_out / d_in / d_scratch (8 bytes), scratch_bytes below
+ * scl_prefix_block_scratch_bytes, n >= 2^32 symbols, in_nbits >= 2^46. */
+typedef struct scl_prefix_block_info {
+    uint32_t sub_bits;     /* S: bits per decoder thread; a decoder workgroup owns 256 * S bits */
+    uint32_t tile_symbols; /* symbols per encoder workgroup                                      */
+    uint32_t code_len_gcd; /* gcd of the code lengths: a start guess is a multiple of it         */
+} scl_prefix_block_info;
+
+typedef struct scl_prefix_block_result {
+    uint64_t n_out, consumed;
+    uint32_t status, sync_passes;
+} scl_prefix_block_result;
+
+int scl_prefix_block_info_get(const scl_prefix_model *m, scl_prefix_block_info *info);
+/* device scratch that serves an encode of n_symbols and a decode of in_nbits (0 for a null model) */
+uint64_t scl_prefix_block_scratch_bytes(const scl_prefix_model *m, uint64_t n_symbols, uint64_t in_nbits);
+int scl_prefix_encode_block(const scl_prefix_model *m, const uint8_t *d_sym, uint64_t n, uint8_t *d_out,
+                            uint64_t out_cap_bytes, uint64_t *d_nbits, uint32_t *d_status, void *d_scratch,
+                            uint64_t scratch_bytes, void *stream);
+int scl_prefix_encode_block_u16(const scl_prefix_model *m, const uint16_t *d_sym, uint64_t n, uint8_t *d_out,
+                                uint64_t out_cap_bytes, uint64_t *d_nbits, uint32_t *d_status, void *d_scratch,
+                                uint64_t scratch_bytes, void *stream);
+int scl_prefix_decode_block(const scl_prefix_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
+                            uint64_t in_bit_offset, uint64_t in_nbits, uint8_t *d_out_sym, uint64_t out_cap,
+                            scl_prefix_block_result *d_result, void *d_scratch, uint64_t scratch_bytes, void *stream);
+int scl_prefix_decode_block_u16(const scl_prefix_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
+                                uint64_t in_bit_offset, uint64_t in_nbits, uint16_t *d_out_sym, uint64_t out_cap,
+                                scl_prefix_block_result *d_result, void *d_scratch, uint64_t scratch_bytes,
+                                void *stream);
+/* one block in host memory: allocate, copy, run, synchronise -- as scl_prefix_encode_host / _decode_host and with their
+   error codes for a non-zero status, without their limit of 2^32 bits per stream */
+int scl_prefix_encode_block_host(const scl_prefix_model *m, const uint8_t *h_sym, uint64_t n, uint8_t *h_out,
+                                 uint64_t out_cap_bytes, uint64_t *nbits);
+int scl_prefix_decode_block_host(const scl_prefix_model *m, const uint8_t *h_in, uint64_t in_nbits,
+                                 uint8_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed);
+int scl_prefix_encode_block_host_u16(const scl_prefix_model *m, const uint16_t *h_sym, uint64_t n, uint8_t *h_out,
+                                     uint64_t out_cap_bytes, uint64_t *nbits);
+int scl_prefix_decode_block_host_u16(const scl_prefix_model *m, const uint8_t *h_in, uint64_t in_nbits,
+                                     uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed);
+
 /* ---- stream compaction / framing ------------------------------------------------------------ */
 #define SCL_COMPACT_DENSE 0  /* stream c left-aligned at byte d_out_byte_offset[c], zero tail   */
 #define SCL_COMPACT_FRAMED 1 /* EncodedBlockWriter framing per stream:

@@ -42,6 +42,14 @@ class PrefixInfo(C.Structure):
                 ("fast_path", C.c_uint32), ("device", C.c_int32)]
 
 
+class PrefixBlockInfo(C.Structure):
+    _fields_ = [("sub_bits", C.c_uint32), ("tile_symbols", C.c_uint32), ("code_len_gcd", C.c_uint32)]
+
+
+class PrefixBlockResult(C.Structure):
+    _fields_ = [("n_out", C.c_uint64), ("consumed", C.c_uint64), ("status", C.c_uint32), ("sync_passes", C.c_uint32)]
+
+
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _vp, _u32, _u64, _int = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 
@@ -93,6 +101,13 @@ _SIGNATURES = {
     "scl_prefix_decode_batch": (_int, _DEC_BATCH),
     "scl_prefix_encode_host": (_int, _ENC_HOST),
     "scl_prefix_decode_host": (_int, _DEC_HOST),
+    # one large block coded by the whole grid (scl_prefix_block.hip)
+    "scl_prefix_block_info_get": (_int, [_vp, C.POINTER(PrefixBlockInfo)]),
+    "scl_prefix_block_scratch_bytes": (_u64, [_vp, _u64, _u64]),
+    "scl_prefix_encode_block": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "scl_prefix_decode_block": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "scl_prefix_encode_block_host": (_int, _ENC_HOST),
+    "scl_prefix_decode_block_host": (_int, _DEC_HOST),
     "scl_aec_model_create": (_int, [_int, _u32p, _u32, _u32, _u64, _u32, _u32, C.POINTER(_vp)]),
     "scl_aec_model_destroy": (None, [_vp]),
     "scl_aec_slot_bytes": (_u64, [_vp, _u64]),
@@ -153,6 +168,11 @@ for _coder in ("rans", "tans", "range", "aec", "prefix"):
 for _op, _host in (("encode", _ENC_HOST16), ("decode", _DEC_HOST16)):
     _SIGNATURES[f"scl_aec_{_op}_batch_resume_u16"] = _SIGNATURES[f"scl_aec_{_op}_batch_resume"]
     _SIGNATURES[f"scl_aec_{_op}_host_resume_u16"] = (_int, _host + [_u32p, _u32p])
+
+for _op, _host in (("encode", _ENC_HOST16), ("decode", _DEC_HOST16)):
+    _SIGNATURES[f"scl_prefix_{_op}_block_u16"] = _SIGNATURES[f"scl_prefix_{_op}_block"]
+    _SIGNATURES[f"scl_prefix_{_op}_block_host_u16"] = (_int, _host)
+
 
 def any_parameter_forced() -> bool:
     """are the tuned kernels kept out of the calling thread's batch calls right now?  (``scl_set_any_parameter_kernels``

@@ -457,9 +457,31 @@ class PrefixModel(_DeviceModel):
         """True if the tuned kernels (byte symbols, K <= 256) serve this model."""
         return bool(self.info().fast_path)
 
+    # A block of at least this many symbols (a stream of at least this many times ``min_len`` bits) is coded by the whole
+    # grid (csrc/scl_prefix_block.hip) instead of by one lane: same stream, same symbols, same errors.  A class attribute
+    # that an instance may override.  Measured end to end through encode_host / decode_host from 4 Ki to 1 Mi symbols
+    # (profiles/prefix_block_bench.txt, DESIGN.md 3.5.1): the block path was the faster one at every size, 4.7x on encode
+    # and 49x on decode at 4 Ki symbols already, so the threshold is the smallest size of the sweep; below it is unmeasured.
+    BLOCK_PARALLEL_MIN = 1 << 12
+
+    def encode_host(self, sym: np.ndarray):
+        """index array (``sym_dtype``) -> (packed MSB-first bytes, nbits); blocks of ``BLOCK_PARALLEL_MIN`` symbols and
+        more through ``scl_prefix_encode_block_host``"""
+        sym = np.ascontiguousarray(sym, dtype=self.sym_dtype)
+        if sym.size < self.BLOCK_PARALLEL_MIN:
+            return super().encode_host(sym)
+        cap = self.slot_bytes(sym.size) + 16
+        out = np.zeros(cap, dtype=np.uint8)
+        nbits = C.c_uint64(0)
+        rc = self._sym_fn("encode_block_host")(self._h, self._host_ptr(sym), sym.size, _lib.u8_ptr(out), cap,
+                                               C.byref(nbits))
+        _lib.check(rc, "scl_prefix_encode_block_host")
+        return out[: (nbits.value + 7) // 8], int(nbits.value)
+
     def decode_host(self, packed: np.ndarray, nbits: int, size_bits: int = 0, max_block_size: Optional[int] = None):
         """(packed bytes, EXACT stream bits) -> (index array of ``sym_dtype``, num_bits_consumed).  There is no size header
-        to peek: the output holds ``nbits // min_len`` symbols, which bounds any stream of this code."""
+        to peek: the output holds ``nbits // min_len`` symbols, which bounds any stream of this code.  Streams of
+        ``BLOCK_PARALLEL_MIN * min_len`` bits and more go through ``scl_prefix_decode_block_host``."""
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
         cap = int(nbits) // self.min_len
         self._check_block_size(cap, max_block_size)
@@ -467,10 +489,84 @@ class PrefixModel(_DeviceModel):
             packed = np.zeros(1, dtype=np.uint8)
         out = np.zeros(max(cap, 1), dtype=self.sym_dtype)
         n_out, used = C.c_uint64(0), C.c_uint64(0)
-        rc = self._sym_fn("decode_host")(self._h, _lib.u8_ptr(packed), int(nbits), self._host_ptr(out), cap,
-                                         C.byref(n_out), C.byref(used))
-        _lib.check(rc, "scl_prefix_decode_host")
+        name = "decode_block_host" if int(nbits) >= self.BLOCK_PARALLEL_MIN * self.min_len else "decode_host"
+        rc = self._sym_fn(name)(self._h, _lib.u8_ptr(packed), int(nbits), self._host_ptr(out), cap,
+                                C.byref(n_out), C.byref(used))
+        _lib.check(rc, f"scl_prefix_{name}")
         return out[: n_out.value], int(used.value)
+
+    # -- one large block, device memory (torch tensors): the whole grid codes it ---------------------------------------
+    def block_info(self) -> _lib.PrefixBlockInfo:
+        """the geometry of the block kernels: bits per decoder thread, symbols per encoder tile, gcd of the code lengths"""
+        info = _lib.PrefixBlockInfo()
+        _lib.check(self._L.scl_prefix_block_info_get(self._h, C.byref(info)), "scl_prefix_block_info_get")
+        return info
+
+    def _block_scratch(self, n_symbols: int, nbits: int, device, st):
+        import torch
+
+        nbytes = int(self._L.scl_prefix_block_scratch_bytes(self._h, int(n_symbols), int(nbits)))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self._keep_scratch(st, scratch)
+        return scratch, nbytes
+
+    def encode_block_into(self, sym, out, out_cap_bytes: Optional[int] = None, stream=None):
+        """1-D symbol tensor -> its stream at the front of the uint8 tensor ``out`` (zeroed by the call), asynchronously.
+        -> int64 tensor ``[nbits, status]`` on the device; status ``ST_CAPACITY``: ``out_cap_bytes`` (default: all of
+        ``out``) is too small and nothing was written."""
+        import torch
+
+        assert sym.is_cuda and sym.dtype in self._torch_sym_dtypes() and sym.dim() == 1 and sym.is_contiguous()
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+        cap = out.numel() if out_cap_bytes is None else int(out_cap_bytes)
+        assert cap <= out.numel()
+        dev = sym.device
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        meta = torch.zeros(2, dtype=torch.int64, device=dev)
+        scratch, nbytes = self._block_scratch(sym.numel(), 0, dev, st)
+        with torch.cuda.device(dev):
+            rc = self._sym_fn("encode_block")(self._h, sym.data_ptr(), sym.numel(), out.data_ptr(), cap, meta.data_ptr(),
+                                              meta.data_ptr() + 8, scratch.data_ptr(), nbytes, st)
+        _lib.check(rc, "scl_prefix_encode_block")
+        return meta
+
+    def encode_block_device(self, sym):
+        """1-D symbol tensor on the device -> (uint8 tensor holding the stream, nbits).  Waits for the result (``nbits`` is
+        a host integer); a symbol index outside the alphabet raises."""
+        import torch
+
+        out = torch.empty(self.slot_bytes(sym.numel()), dtype=torch.uint8, device=sym.device)
+        nbits, status = (int(v) for v in self.encode_block_into(sym, out).cpu())
+        if status & 0xFFFFFFFF:
+            raise _lib.SclHipError(_lib.E_CHUNK, "scl_prefix_encode_block", f"block status 0x{status & 0xFFFFFFFF:x}")
+        return out[: (nbits + 7) // 8], nbits
+
+    def decode_block_device(self, data, nbits: int, bit_offset: int = 0, out_cap: Optional[int] = None, out=None,
+                            stream=None):
+        """the ``nbits`` bits from bit ``bit_offset`` of the uint8 device tensor ``data`` -> (symbols, n_out, consumed,
+        status, sync_passes), what the one-lane decoder reports for the same stream (``sync_passes``: inter-workgroup
+        correction passes that moved a start).  ``out_cap`` defaults to ``nbits // min_len``, which holds any stream;
+        ``out`` is an optional symbol tensor of at least ``out_cap`` elements.  The call synchronises the stream: the
+        library reads a device flag between its passes."""
+        import torch
+
+        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
+        dev = data.device
+        cap = int(nbits) // self.min_len if out_cap is None else int(out_cap)
+        if out is None:
+            out = torch.empty(max(cap, 1), dtype=self._torch_sym_dtypes()[0], device=dev)
+        assert out.is_cuda and out.dtype in self._torch_sym_dtypes() and out.is_contiguous() and out.numel() >= cap
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        result = torch.zeros(3, dtype=torch.int64, device=dev)
+        scratch, nbytes = self._block_scratch(0, nbits, dev, st)
+        with torch.cuda.device(dev):
+            rc = self._sym_fn("decode_block")(self._h, data.data_ptr(), data.numel(), int(bit_offset), int(nbits),
+                                              out.data_ptr(), cap, result.data_ptr(), scratch.data_ptr(), nbytes, st)
+        _lib.check(rc, "scl_prefix_decode_block")
+        if stream is not None:
+            torch.cuda.ExternalStream(int(st), device=dev).synchronize()
+        n_out, consumed, tail = (int(v) for v in result.cpu())
+        return out[:n_out], n_out, consumed, tail & 0xFFFFFFFF, (tail >> 32) & 0xFFFFFFFF
 
 
 class AecModel(_DeviceModel):

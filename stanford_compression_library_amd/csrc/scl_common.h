@@ -172,6 +172,8 @@ struct HostDecodeCall {
     void *user = nullptr;
     u32 sym_bytes = 1;
 };
+// a chunk's non-zero status as the error of a *_host call: SCL_E_CHUNK, the flags by name in scl_last_error
+int scl_status_to_error(u32 st, const char *what);
 int scl_host_encode_one(const HostEncodeCall &call, const void *model, const u8 *h_sym, u64 n, u8 *h_out,
                         u64 out_cap_bytes, u64 *nbits);
 int scl_host_decode_one(const HostDecodeCall &call, const void *model, const u8 *h_in, u64 in_nbits,

@@ -747,7 +747,7 @@ extern "C" int scl_stream_block_size_host(const uint8_t *h_in, uint64_t in_nbits
     return SCL_OK;
 }
 
-static int status_to_error(u32 st, const char *what) {
+int scl_status_to_error(u32 st, const char *what) {
     if (st == 0) return SCL_OK;
     scl_set_error("%s: chunk status 0x%x%s%s%s%s%s%s", what, st, (st & SCL_ST_CAPACITY) ? " CAPACITY" : "",
                   (st & SCL_ST_SYMBOL) ? " SYMBOL" : "", (st & SCL_ST_TRUNCATED) ? " TRUNCATED" : "",
@@ -785,7 +785,7 @@ int scl_host_encode_one(const HostEncodeCall &call, const void *model, const u8 
     SCL_HIP_TRY(hipDeviceSynchronize());
     u32 meta[2];
     SCL_HIP_TRY(hipMemcpy(meta, d_nbits, 8, hipMemcpyDeviceToHost));
-    if ((rc = status_to_error(meta[1], "encode_host"))) return rc;
+    if ((rc = scl_status_to_error(meta[1], "encode_host"))) return rc;
     const u64 bytes = ((u64)meta[0] + 7) / 8;
     if (bytes > out_cap_bytes) {
         scl_set_error("encode_host: output needs %llu bytes, capacity %llu", (unsigned long long)bytes,
@@ -829,7 +829,7 @@ int scl_host_decode_one(const HostDecodeCall &call, const void *model, const u8 
     SCL_HIP_TRY(hipMemcpy(meta, d_len, 12, hipMemcpyDeviceToHost));
     *n_out = meta[0];
     *consumed = meta[1];
-    if ((rc = status_to_error(meta[2], "decode_host"))) return rc;
+    if ((rc = scl_status_to_error(meta[2], "decode_host"))) return rc;
     if (meta[0]) SCL_HIP_TRY(hipMemcpy(h_out_sym, d_out.p, (u64)meta[0] * call.sym_bytes, hipMemcpyDeviceToHost));
     if (call.post && (rc = call.post(model, d_scr.p, call.user))) return rc;
     return SCL_OK;

@@ -28,43 +28,10 @@
 
 #include "scl_ans_fast_io.h"
 #include "scl_entry.h"
+#include "scl_prefix_internal.h"
 
-#define PF_MAX_LEN 32u
-#define PF_LUT_BITS 11u  // 2^11 16-bit entries = 4 KiB: with the 32 KiB ring and the deep nodes four workgroups per CU
-#define PF_DEEP_NODES 512u
 #define PF_THREADS 256
 #define PF_RING_BYTES (32 * PF_THREADS * 4)
-
-// a child in the any-parameter tree (uint2 {child on 0, child on 1} per node, node 0 = root)
-#define PF_NONE 0xFFFFFFFFu
-#define PF_LEAF 0x80000000u  // | symbol
-// a child in the tuned decoder's deep-node table (two u16 per node: low half = child on 0)
-#define PF16_NONE 0xFFFFu
-#define PF16_LEAF 0x8000u  // | symbol
-// a lookup-table entry: len in bits 0..3, kind in bits 4..5, symbol / deep node in bits 6..15
-#define PF_KIND_SYM 0u
-#define PF_KIND_NODE 1u  // len = T: the walk continues at deep node `payload`
-#define PF_KIND_NONE 2u  // len = number of bits read when the walk meets a missing child
-
-struct PrefixDev {
-    u32 K;
-    u32 min_len, max_len;
-    u32 lut_bits;  // T
-    u32 n_deep;
-    const uint2 *d_enc;    // [max(K, 256)] {code, len}
-    const uint2 *d_nodes;  // any-parameter decoder
-    const u16 *d_lut;      // tuned decoder: [2^T]
-    const u32 *d_deep;     // tuned decoder: [n_deep]
-};
-
-struct scl_prefix_model {
-    int device;
-    PrefixDev dev;
-    u32 fast;
-    uint2 *d_enc, *d_nodes;
-    u16 *d_lut;
-    u32 *d_deep;
-};
 
 // ---- any-parameter kernels ---------------------------------------------------------------------------------------------
 template <typename SYM>
@@ -318,7 +285,7 @@ extern "C" int scl_prefix_model_create(const uint32_t *h_code, const uint8_t *h_
     // exists already, equals or is a prefix of another one (or the other way round)
     std::vector<uint2> nodes(1, make_uint2(PF_NONE, PF_NONE));
     std::vector<u32> depth(1, 0);
-    u32 min_len = PF_MAX_LEN, max_len = 0;
+    u32 min_len = PF_MAX_LEN, max_len = 0, len_gcd = 0;
     for (u32 s = 0; s < K; ++s) {
         const u32 len = h_len[s];
         SCL_REQUIRE(len >= 1 && len <= PF_MAX_LEN, "prefix_model_create: symbol %u has a code of %u bits (1..32 are coded)", s,
@@ -326,6 +293,15 @@ extern "C" int scl_prefix_model_create(const uint32_t *h_code, const uint8_t *h_
         const u32 code = len == 32 ? h_code[s] : (h_code[s] & ((1u << len) - 1u));  // the len low bits are the codeword
         min_len = len < min_len ? len : min_len;
         max_len = len > max_len ? len : max_len;
+        for (u32 a = len, b = len_gcd; ; ) {  // gcd(len, len_gcd); gcd(len, 0) = len
+            if (b == 0) {
+                len_gcd = a;
+                break;
+            }
+            const u32 t = a % b;
+            a = b;
+            b = t;
+        }
         u32 node = 0;
         for (u32 d = 0; d < len; ++d) {
             const u32 bit = (code >> (len - 1 - d)) & 1u;
@@ -393,6 +369,7 @@ extern "C" int scl_prefix_model_create(const uint32_t *h_code, const uint8_t *h_
     m->dev.min_len = min_len;
     m->dev.max_len = max_len;
     m->dev.lut_bits = T;
+    m->dev.len_gcd = len_gcd;
     m->dev.n_deep = fast ? n_deep : 0;
     m->fast = fast ? 1 : 0;
     hipError_t e = hipMalloc((void **)&m->d_enc, enc.size() * sizeof(uint2));
