@@ -31,10 +31,14 @@ def make_dist(case):
     return dist
 
 
+def bits_of_table(code, length):
+    """[K] list of uint8 bit arrays: the codeword of every symbol, most significant bit first"""
+    return [np.array([(int(c) >> (int(n) - 1 - j)) & 1 for j in range(int(n))], np.uint8) for c, n in zip(code, length)]
+
+
 def code_bits(case):
-    """[K] list of uint8 bit arrays: the codeword of every symbol"""
-    return [np.array([(int(c) >> (int(n) - 1 - j)) & 1 for j in range(int(n))], np.uint8)
-            for c, n in zip(case.arr("code"), case.arr("len"))]
+    """bits_of_table of a golden table case"""
+    return bits_of_table(case.arr("code"), case.arr("len"))
 
 
 def encode_numpy(bits_of, sym):
@@ -49,3 +53,138 @@ def stream_bits(data, bit_offset, nbits):
     first, last = bit_offset >> 3, (bit_offset + nbits + 7) >> 3
     bits = np.unpackbits(data[first:last])[bit_offset - 8 * first:][:nbits]
     return np.packbits(bits)
+
+
+# ---- the same stream with array operations, for blocks of millions of symbols ---------------------------------------------
+def encode_vectorised(code, length, sym):
+    """-> (packed MSB-first bytes, nbits): encode_numpy's stream from the {code, length} arrays.  Codeword i starts at the
+    sum of the lengths before it; bit j of every codeword that has one is scattered to start + j in one masked store."""
+    sym = np.asarray(sym, np.int64)
+    codes, lens = np.asarray(code).astype(np.uint64)[sym], np.asarray(length, np.int64)[sym]
+    ends = np.cumsum(lens)
+    nbits = int(ends[-1]) if sym.size else 0
+    starts = ends - lens
+    bits = np.zeros(nbits, np.uint8)
+    for j in range(int(lens.max(initial=0))):
+        has = lens > j
+        bits[starts[has] + j] = (codes[has] >> (lens[has] - 1 - j).astype(np.uint64)) & np.uint64(1)
+    return np.packbits(bits), nbits
+
+
+# ---- the decoder's rule, restated (PrefixFreeDecoder.decode_block, prefix_free_compressors.py:67-88 of the reference, and
+# the header of csrc/scl_prefix.hip) ---------------------------------------------------------------------------------------
+ST_CAPACITY, ST_TRUNCATED, ST_STATE = 0x1, 0x4, 0x8
+_MISSING = -1  # a child that no codeword leads to; a leaf for symbol s is -2 - s; anything >= 0 is an inner node
+
+
+@functools.lru_cache(maxsize=None)
+def _tree(code_bytes, len_bytes):
+    """the code tree as two lists, child on 0 and child on 1 of every inner node (node 0 = root)"""
+    code, length = np.frombuffer(code_bytes, np.int64), np.frombuffer(len_bytes, np.int64)
+    kids = ([_MISSING], [_MISSING])
+    for s, (c, n) in enumerate(zip(code.tolist(), length.tolist())):
+        node = 0
+        for d in range(n):
+            side = kids[(c >> (n - 1 - d)) & 1]
+            if d + 1 == n:
+                assert side[node] == _MISSING, f"symbol {s}: not prefix-free"
+                side[node] = -2 - s
+            else:
+                if side[node] == _MISSING:
+                    side[node] = len(kids[0])
+                    kids[0].append(_MISSING)
+                    kids[1].append(_MISSING)
+                assert side[node] >= 0, f"symbol {s}: not prefix-free"
+                node = side[node]
+    return kids
+
+
+def decode_reference(code, length, data, bit_offset, nbits, out_cap):
+    """-> (symbols, consumed, status) of the `nbits` bits from bit `bit_offset` of the byte array `data`.
+    Symbols are delivered one whole codeword at a time, decode_block's loop; the loop ends with status 0 when no bit is
+    left, ST_CAPACITY when bits are left after out_cap symbols, ST_TRUNCATED when the stream ends inside a codeword,
+    ST_STATE when a bit leads to a missing child of an incomplete tree.  `consumed` counts whole codewords only.
+    A Python loop over every bit, O(nbits): for short streams, or for the tail of a long one (bit_offset and nbits select
+    it; only those bytes are unpacked)."""
+    kids = _tree(np.asarray(code, np.int64).tobytes(), np.asarray(length, np.int64).tobytes())
+    bits = np.unpackbits(stream_bits(np.asarray(data, np.uint8), bit_offset, nbits))[:nbits].tolist()
+    out, consumed, status = [], 0, 0
+    while consumed < nbits:
+        if len(out) == out_cap:
+            status = ST_CAPACITY
+            break
+        node, pos = 0, consumed
+        while node >= 0:
+            if pos == nbits:
+                status = ST_TRUNCATED
+                break
+            node = kids[bits[pos]][node]
+            pos += 1
+        if status:
+            break
+        if node == _MISSING:
+            status = ST_STATE
+            break
+        out.append(-2 - node)
+        consumed = pos
+    return np.array(out, np.int64), consumed, status
+
+
+# ---- tables at the limits of the tuned decoder's geometry (an 11-bit lookup table, 512 nodes below it) --------------------
+LUT_BITS, DEEP_NODES = 11, 512
+
+
+def count_deep_nodes(code, length):
+    """inner nodes of the code tree at depth >= min(max_len, 11): the distinct proper prefixes that long"""
+    code, length = np.asarray(code, np.int64).tolist(), np.asarray(length, np.int64).tolist()
+    t = min(max(length), LUT_BITS)
+    return len({(d, c >> (n - d)) for c, n in zip(code, length) for d in range(t, n)})
+
+
+def comb(L, seed=0):
+    """-> (code, length) of the complete code with lengths 1, 2, ..., L - 1, L, L: i ones and a zero for i < L, and L ones.
+    Which symbol index gets which codeword is a seeded permutation.  Kraft sum 1, max_len L; the only inner nodes at
+    depth d are the runs of d ones, so count_deep_nodes is max(L - 11, 0)."""
+    code = [((1 << i) - 1) << 1 for i in range(L)] + [(1 << L) - 1]
+    length = list(range(1, L + 1)) + [L]
+    perm = np.random.default_rng(seed).permutation(L + 1)
+    out_code, out_len = np.zeros(L + 1, np.int64), np.zeros(L + 1, np.int64)
+    out_code[perm], out_len[perm] = code, length
+    assert count_deep_nodes(out_code, out_len) == max(L - LUT_BITS, 0)
+    return out_code, out_len
+
+
+DEEP_SHORT = ((0b00, 2), (0b010, 3), (0b0110, 4), (0b01110, 5))  # 11-bit prefixes 0 .. 959; "01111" leads nowhere
+DEEP_LONG_FIRST = 1024  # long symbol i has the 11-bit prefix 1024 + i to itself: all long codes start with a 1 bit
+
+
+def deep_chains(n_deep, seed=0):
+    """-> (code, length) of an incomplete code over all 256 byte symbols with exactly n_deep inner nodes at depth >= 11
+    (512 <= n_deep <= 533).  Long symbols: 24 of 32 bits and one of 19 bits (24 * 21 + 8 = 512 nodes: a symbol of L bits
+    behind its own 11-bit prefix adds L - 11), and for n_deep > 512 one more of 11 + (n_deep - 512) bits; the bits behind
+    the prefix are random.  Four short symbols (DEEP_SHORT); every other symbol has an 11-bit code, which adds no node.
+    Symbol 255 is one of the 32-bit ones; the other indices are a seeded permutation.
+    Kraft sum = 15/32 + sum over the long symbols of 2^-L + (number of 11-bit symbols) * 2^-11 < 1."""
+    rng = np.random.default_rng(seed)
+    long_lens = [32] * 24 + [19]
+    assert 0 <= n_deep - DEEP_NODES <= 32 - LUT_BITS
+    if n_deep > DEEP_NODES:
+        long_lens.append(LUT_BITS + n_deep - DEEP_NODES)
+    code, length = [], []
+    for i, n in enumerate(long_lens):
+        tail = int(rng.integers(0, 1 << (n - LUT_BITS)))
+        code.append(((DEEP_LONG_FIRST + i) << (n - LUT_BITS)) | tail)
+        length.append(n)
+    for c, n in DEEP_SHORT:
+        code.append(c)
+        length.append(n)
+    n_rest = 256 - len(code)
+    code += [DEEP_LONG_FIRST + len(long_lens) + i for i in range(n_rest)]
+    length += [LUT_BITS] * n_rest
+    perm = rng.permutation(256)
+    at = int(np.nonzero(perm == 255)[0][0])
+    perm[[0, at]] = perm[[at, 0]]  # symbol 255 takes the first 32-bit codeword
+    out_code, out_len = np.zeros(256, np.int64), np.zeros(256, np.int64)
+    out_code[perm], out_len[perm] = code, length
+    assert out_len[255] == 32 and count_deep_nodes(out_code, out_len) == n_deep
+    return out_code, out_len
