@@ -46,15 +46,6 @@
 #define AF_LUT_BYTES 512
 #define AF_LDS_BYTES (AF_LUT_BASE + AF_LUT_BYTES)
 
-struct AecFastDev {
-    u32 K;          // alphabet size 2..16
-    u32 nctx;       // K^k <= 16
-    u32 ctx_magic;  // ceil(2^16 / nctx): (v * magic) >> 16 == v / nctx for v < 272
-    u32 total0;     // initial total of a row
-    u32 size_bits;  // DATA_BLOCK_SIZE_BITS (1..32)
-    u32 initX[8];   // 16 packed u16: EXCLUSIVE cumulative initial counts X[j] = sum_{i<j}, padded with the total
-};
-
 struct AfRow {
     uint4 a, b;
 };
@@ -77,13 +68,6 @@ __device__ __forceinline__ void af_setup_tables(char *lds, const AecFastDev &P, 
     __syncthreads();
 }
 
-template <bool ORDER1>
-__device__ __forceinline__ u32 af_next_ctx(const AecFastDev &P, u32 ctx, u32 s) {  // past_k[1:] + [s], :146-151
-    if (ORDER1) return s;
-    // (24-bit multiplies: v < 272, magic <= 2^15, nctx <= 16 -- the 32-bit v_mul_lo_u32 is a quarter-rate instruction)
-    const u32 v = __umul24(ctx, P.K) + s;
-    return v - __umul24(__umul24(v, P.ctx_magic) >> 16, P.nctx);
-}
 __device__ __forceinline__ AfRow af_row_load(const char *lds, u32 rowbase) {
     AfRow R;
     R.a = *reinterpret_cast<const uint4_lds *>(lds + rowbase);
@@ -126,8 +110,8 @@ __global__ void __launch_bounds__(AF_THREADS)
     const u32 *src = reinterpret_cast<const u32 *>(sym + chunk * sym_stride);
     AfWriter wr;
     wr.init(out + chunk * out_stride);
-    wr.put(P.size_bits < 32 ? (n & ((1u << P.size_bits) - 1u)) : n, P.size_bits);  // header, :92-99
-    u32 st = (P.size_bits < 32 && (n >> P.size_bits)) ? SCL_ST_SIZE : 0u;
+    wr.put(af_header_value(n, P.size_bits), P.size_bits);  // :92-99
+    u32 st = af_header_status(n, P.size_bits);
     u32 low = 0, hm = 0xFFFFFFFFu;
     u32 pending = 0;  // E3 steps not yet resolved (<= 32 * n < 2^20)
     u32 ctx = 0;
@@ -160,34 +144,18 @@ __global__ void __launch_bounds__(AF_THREADS)
         d_nx = (m_s == 15) ? T_nx : m_draw;
         x_nx = af_recip((double)T_nx);
     };
+    // one step of the literal loops, and the termination: `bit`, then `pending` copies of its inverse
+    auto emit = [&](u32 bit) {
+        wr.put(bit, 1);
+        wr.put_run(bit ^ 1u, pending);
+    };
     // arithmetic stage: shrink_range (:58-78) and the renormalisation loops (:126-150) of one symbol
     auto code = [&](u32 cc, u32 dd, u32 TT, double xx) {
         af_shrink(low, hm, cc, dd, TT, xx);
         u32 k, m;
         const bool edge = af_renorm_counts(low, hm, k, m);
         if (__builtin_expect(edge || (k + pending > 32), 0)) {
-            u64 lo = low, hi = (u64)hm + 1;
-            while (hi < AF_HALF || lo > AF_HALF) {
-                if (hi < AF_HALF) {
-                    wr.put(0, 1);
-                    wr.put_run(1, pending);
-                    lo <<= 1;
-                    hi <<= 1;
-                } else {
-                    wr.put(1, 1);
-                    wr.put_run(0, pending);
-                    lo = (lo - AF_HALF) << 1;
-                    hi = (hi - AF_HALF) << 1;
-                }
-                pending = 0;
-            }
-            while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-                pending += 1;
-                lo = (lo - AF_QTR) << 1;
-                hi = (hi - AF_QTR) << 1;
-            }
-            low = (u32)lo;
-            hm = (u32)(hi - 1);
+            af_renorm_literal_enc(low, hm, pending, emit);
         } else {
             if (k > 0) {
                 // b0, then `pending` copies of !b0, then the other k-1 common bits
@@ -232,14 +200,7 @@ __global__ void __launch_bounds__(AF_THREADS)
         }
     }
     code(c_nx, d_nx, T_nx, x_nx);
-    pending += 1;  // termination, :153-159
-    if (low <= AF_QTR) {
-        wr.put(0, 1);
-        wr.put_run(1, pending);
-    } else {
-        wr.put(1, 1);
-        wr.put_run(0, pending);
-    }
+    af_terminate(low, pending, emit);  // :153-159
     const u64 total = wr.finish();
     out_bit_off[chunk] = chunk * out_stride * 8;
     out_nbits[chunk] = (u32)total;
@@ -289,24 +250,11 @@ __global__ void __launch_bounds__(AF_THREADS)
     const u64 chunk = (u64)blockIdx.x * AF_THREADS + tid;
     if (chunk >= n_chunks) return;
     const u32 nbits = in_nbits[chunk];
-    u32 st = 0;
     AfReader rd;
     rd.init(in, in_size_bytes, bit_off[chunk], nbits);
-    u32 n = rd.get(P.size_bits);
-    if (nbits < P.size_bits) {
-        st |= SCL_ST_TRUNCATED;
-        n = 0;
-    }
-    out_lens[chunk] = n;
-    if (n > out_cap) {
-        st |= SCL_ST_CAPACITY;
-        n = 0;
-    }
-    if (n == 0) {  // quirk Q5, as in scl_aec.hip
-        consumed[chunk] = (st == 0) ? P.size_bits + 2 : 0;
-        if (status) status[chunk] = st;
-        return;
-    }
+    u32 st;
+    const u32 n = af_decode_length(rd.get(P.size_bits), st, nbits, P.size_bits, out_cap, chunk, out_lens, consumed, status);
+    if (n == 0) return;
     AfSymOut so;
     so.init(lds + AD_OUT_BASE, tid, out_sym + chunk * out_stride);
     u32 state = rd.get(32);
@@ -365,28 +313,7 @@ __global__ void __launch_bounds__(AF_THREADS)
         u32 k, m, nlow, nhm;
         const bool edge = af_renorm2_dec(low, hm, k, m, nlow, nhm);
         if (__builtin_expect(edge, 0)) {
-            u64 lo = low, hi = (u64)hm + 1, stt = state;
-            while (hi < AF_HALF || lo > AF_HALF) {
-                if (hi < AF_HALF) {
-                    lo <<= 1;
-                    hi <<= 1;
-                    stt <<= 1;
-                } else {
-                    lo = (lo - AF_HALF) << 1;
-                    hi = (hi - AF_HALF) << 1;
-                    stt = (stt - AF_HALF) << 1;
-                }
-                stt += rd.get<UC>(1);
-            }
-            while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-                lo = (lo - AF_QTR) << 1;
-                hi = (hi - AF_QTR) << 1;
-                stt = (stt - AF_QTR) << 1;
-                stt += rd.get<UC>(1);
-            }
-            low = (u32)lo;
-            hm = (u32)(hi - 1);
-            state = (u32)stt;
+            af_renorm_literal_dec(low, hm, state, [&] { return rd.get<UC>(1); });
         } else {
             const u32 kt = k + m;  // <= 31
             state = af_state_shift_in<UC>(rd, state, k, kt);
@@ -437,15 +364,7 @@ __global__ void __launch_bounds__(AF_THREADS)
     }
     step(n - 1);
     so.finish(n);
-    // how many of the last PRECISION bits belonged to the encoder (:277-282)
-    const u64 lo = low, hi = (u64)hm + 1;
-    u32 e = 0;
-    for (; e < 32; ++e) {
-        const u64 slo = ((u64)state >> e) << e, shi = slo + (1ull << e);
-        if (slo < lo || shi > hi) break;
-    }
-    if (e == 32) e = 31;
-    consumed[chunk] = (u32)((i64)rd.position() - ((i64)e - 1));
+    consumed[chunk] = af_consumed_bits(low, hm, state, rd.position());  // :277-282
     if (status) status[chunk] = st;
 }
 
@@ -457,22 +376,6 @@ bool aec_fast_ok(const scl_aec_model *m, u64 max_symbols) {
     const u64 total_max = (u64)d.total0 + max_symbols;  // IID: total; ORDERK: bound on a row total and on any count
     if (total_max >= 32768 || total_max >= d.max_total) return false;
     return true;
-}
-
-static AecFastDev aec_fast_dev(const scl_aec_model *m) {
-    AecFastDev f;
-    f.K = m->dev.K;
-    f.nctx = (u32)m->dev.ctx_mod;
-    f.ctx_magic = (65536u + f.nctx - 1) / f.nctx;
-    u32 X[16], acc = 0;
-    for (u32 j = 0; j < 16; ++j) {
-        X[j] = acc;  // exclusive; entries past the alphabet hold the total
-        if (j < f.K) acc += m->h_freq[j];
-    }
-    f.total0 = acc;
-    f.size_bits = m->dev.size_bits;
-    for (u32 r = 0; r < 8; ++r) f.initX[r] = X[2 * r] | (X[2 * r + 1] << 16);
-    return f;
 }
 
 void aec_fast_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *) {

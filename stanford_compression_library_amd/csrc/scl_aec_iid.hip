@@ -75,8 +75,8 @@ __global__ void __launch_bounds__(AI_THREADS)
     const u32 *src = reinterpret_cast<const u32 *>(sym + chunk * sym_stride);
     AfWriterT<true> wr;
     wr.init(out + chunk * out_stride, lds + AI_OUT_BASE, tid);
-    wr.put(P.size_bits < 32 ? (n & ((1u << P.size_bits) - 1u)) : n, P.size_bits);  // header, :92-99
-    u32 st = (P.size_bits < 32 && (n >> P.size_bits)) ? SCL_ST_SIZE : 0u;
+    wr.put(af_header_value(n, P.size_bits), P.size_bits);  // :92-99
+    u32 st = af_header_status(n, P.size_bits);
     u32 low = 0, hm = 0xFFFFFFFFu, pending = 0;
     u32 T = P.total0;  // the total of an i.i.d. model is its initial total plus the symbols seen
     u32 nextw = 0;
@@ -119,34 +119,18 @@ __global__ void __launch_bounds__(AI_THREADS)
         *reinterpret_cast<uint4_lds *>(lds + tid * 32 + 16) = XB.b;
         T += 1;
     };
+    // one step of the literal loops, and the termination: `bit`, then `pending` copies of its inverse
+    auto emit = [&](u32 bit) {
+        wr.put(bit, 1);
+        wr.put_run(bit ^ 1u, pending);
+    };
     auto code = [&](u32 cc, u32 dd, u32 TT, double xx) {
         af_shrink2(low, hm, cc, dd, xx);
         u32 k, m, nlow, nhm;
         const bool edge = af_renorm2_dec(low, hm, k, m, nlow, nhm);  // the conservative corner test: two compares fewer
         const bool rare = edge | (k + pending > 32);  // one condition, one branch
         if (__builtin_expect(rare, 0)) {
-            u64 lo = low, hi = (u64)hm + 1;
-            while (hi < AF_HALF || lo > AF_HALF) {
-                if (hi < AF_HALF) {
-                    wr.put(0, 1);
-                    wr.put_run(1, pending);
-                    lo <<= 1;
-                    hi <<= 1;
-                } else {
-                    wr.put(1, 1);
-                    wr.put_run(0, pending);
-                    lo = (lo - AF_HALF) << 1;
-                    hi = (hi - AF_HALF) << 1;
-                }
-                pending = 0;
-            }
-            while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-                pending += 1;
-                lo = (lo - AF_QTR) << 1;
-                hi = (hi - AF_QTR) << 1;
-            }
-            low = (u32)lo;
-            hm = (u32)(hi - 1);
+            af_renorm_literal_enc(low, hm, pending, emit);
         } else {
             // b0, then `pending` copies of !b0, then the other k - 1 common bits -- without a branch on k: for k = 0 the
             // field is empty (v = 0, nb = 0) and the pending count just grows
@@ -187,14 +171,7 @@ __global__ void __launch_bounds__(AI_THREADS)
         }
     }
     code(c_nx, d_nx, T_nx, x_nx);
-    pending += 1;  // termination, :153-159
-    if (low <= AF_QTR) {
-        wr.put(0, 1);
-        wr.put_run(1, pending);
-    } else {
-        wr.put(1, 1);
-        wr.put_run(0, pending);
-    }
+    af_terminate(low, pending, emit);  // :153-159
     const u64 total = wr.finish();
     out_bit_off[chunk] = chunk * out_stride * 8;
     out_nbits[chunk] = (u32)total;
@@ -212,24 +189,11 @@ __global__ void __launch_bounds__(AI_THREADS)
     const u64 chunk = (u64)blockIdx.x * AI_THREADS + tid;
     if (chunk >= n_chunks) return;
     const u32 nbits = in_nbits[chunk];
-    u32 st = 0;
     AfReader rd;
     rd.init(in, in_size_bytes, bit_off[chunk], nbits);
-    u32 n = rd.get(P.size_bits);
-    if (nbits < P.size_bits) {
-        st |= SCL_ST_TRUNCATED;
-        n = 0;
-    }
-    out_lens[chunk] = n;
-    if (n > out_cap) {
-        st |= SCL_ST_CAPACITY;
-        n = 0;
-    }
-    if (n == 0) {  // quirk Q5, as in scl_aec.hip
-        consumed[chunk] = (st == 0) ? P.size_bits + 2 : 0;
-        if (status) status[chunk] = st;
-        return;
-    }
+    u32 st;
+    const u32 n = af_decode_length(rd.get(P.size_bits), st, nbits, P.size_bits, out_cap, chunk, out_lens, consumed, status);
+    if (n == 0) return;
     AfSymOut so;
     so.init(lds + AI_OUT_BASE, tid, out_sym + chunk * out_stride);
     u32 state = rd.get(32);
@@ -295,35 +259,13 @@ __global__ void __launch_bounds__(AI_THREADS)
         u32 k, m, nlow, nhm;
         const bool edge = af_renorm2_dec(low, hm, k, m, nlow, nhm);
         if (__builtin_expect(edge, 0)) {
-            u64 lo = low, hi = (u64)hm + 1, stt = state;
-            while (hi < AF_HALF || lo > AF_HALF) {
-                if (hi < AF_HALF) {
-                    lo <<= 1;
-                    hi <<= 1;
-                    stt <<= 1;
-                } else {
-                    lo = (lo - AF_HALF) << 1;
-                    hi = (hi - AF_HALF) << 1;
-                    stt = (stt - AF_HALF) << 1;
-                }
-                stt += rd.get<UC>(1);
-            }
-            while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-                lo = (lo - AF_QTR) << 1;
-                hi = (hi - AF_QTR) << 1;
-                stt = (stt - AF_QTR) << 1;
-                stt += rd.get<UC>(1);
-            }
-            low = (u32)lo;
-            hm = (u32)(hi - 1);
-            state = (u32)stt;
+            af_renorm_literal_dec(low, hm, state, [&] { return rd.get<UC>(1); });
         } else {
             const u32 kt = k + m;  // <= 31
             state = af_state_shift_in<UC>(rd, state, k, kt);
             low = nlow;
             hm = nhm;
         }
-    
     };
     // Stretches of symbols with the unchecked refill and a scalar trip count, then the checked loop for the chunks' last
     // symbols: as in scl_aec_fast.hip (the symbol index i is the same for every lane still at work).
@@ -365,15 +307,7 @@ __global__ void __launch_bounds__(AI_THREADS)
     }
     step(n - 1);
     so.finish(n);
-    // how many of the last PRECISION bits belonged to the encoder (:277-282)
-    const u64 lo = low, hi = (u64)hm + 1;
-    u32 e = 0;
-    for (; e < 32; ++e) {
-        const u64 slo = ((u64)state >> e) << e, shi = slo + (1ull << e);
-        if (slo < lo || shi > hi) break;
-    }
-    if (e == 32) e = 31;
-    consumed[chunk] = (u32)((i64)rd.position() - ((i64)e - 1));
+    consumed[chunk] = af_consumed_bits(low, hm, state, rd.position());  // :277-282
     if (status) status[chunk] = st;
 }
 

@@ -1,5 +1,6 @@
-// scl_aec_internal.h -- model handle of the arithmetic coder, shared by scl_aec.hip (any parameters) and
-// scl_aec_fast.hip (small-alphabet adaptive models with per-lane context tables in LDS).  Internal to csrc/.
+// scl_aec_internal.h -- model handle of the arithmetic coder and the launch entry points of its tuned kernel families,
+// shared by scl_aec.hip (any parameters, the table of families) and scl_aec_{fast,split,iid,static,wide,sparse}.hip;
+// the kernel parameters of the small-alphabet adaptive models, which two of those files code.  Internal to csrc/.
 #pragma once
 #include "scl_common.h"
 
@@ -52,3 +53,37 @@ bool aec_iid_ok(const scl_aec_model *m, u64 max_symbols);
 void aec_iid_build_init(const u32 *h_freq, u32 K, u32 *out136);
 void aec_iid_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
 void aec_iid_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
+
+// ---- small-alphabet adaptive models (aec_fast_ok): what scl_aec_fast.hip's and scl_aec_split.hip's kernels take ----------
+struct AecFastDev {
+    u32 K;          // alphabet size 2..16
+    u32 nctx;       // K^k <= 16
+    u32 ctx_magic;  // ceil(2^16 / nctx): (v * magic) >> 16 == v / nctx for v < 272
+    u32 total0;     // initial total of a row
+    u32 size_bits;  // DATA_BLOCK_SIZE_BITS (1..32)
+    u32 initX[8];   // 16 packed u16: EXCLUSIVE cumulative initial counts X[j] = sum_{i<j}, padded with the total
+};
+
+template <bool ORDER1>
+__device__ __forceinline__ u32 af_next_ctx(const AecFastDev &P, u32 ctx, u32 s) {  // past_k[1:] + [s], :146-151
+    if (ORDER1) return s;
+    // (24-bit multiplies: v < 272, magic <= 2^15, nctx <= 16 -- the 32-bit v_mul_lo_u32 is a quarter-rate instruction)
+    const u32 v = __umul24(ctx, P.K) + s;
+    return v - __umul24(__umul24(v, P.ctx_magic) >> 16, P.nctx);
+}
+
+static inline AecFastDev aec_fast_dev(const scl_aec_model *m) {
+    AecFastDev f;
+    f.K = m->dev.K;
+    f.nctx = (u32)m->dev.ctx_mod;
+    f.ctx_magic = (65536u + f.nctx - 1) / f.nctx;
+    u32 X[16], acc = 0;
+    for (u32 j = 0; j < 16; ++j) {
+        X[j] = acc;  // exclusive; entries past the alphabet hold the total
+        if (j < f.K) acc += m->h_freq[j];
+    }
+    f.total0 = acc;
+    f.size_bits = m->dev.size_bits;
+    for (u32 r = 0; r < 8; ++r) f.initX[r] = X[2 * r] | (X[2 * r + 1] << 16);
+    return f;
+}

@@ -1,5 +1,7 @@
-// scl_aec_math.h -- exact interval arithmetic shared by the arithmetic-coder fast kernels (scl_aec_fast.hip:
-// adaptive models with per-lane tables, scl_aec_static.hip: static model).  Internal to csrc/.
+// scl_aec_math.h -- exact interval arithmetic for PRECISION = 32, shared by every tuned arithmetic-coder kernel
+// (scl_aec_{fast,split,iid,static,wide,sparse}.hip): shrink_range, the closed-form renormalisation and its corner tests,
+// and -- one copy each -- the code few symbols run: the reference's literal renormalisation loops and a chunk's two ends.
+// Internal to csrc/.
 // Reference: ArithmeticEncoder.shrink_range scl/compressors/arithmetic_coding.py:58-78 and the renormalisation
 // loops :126-150 / :245-275.  See the header of scl_aec_fast.hip for the exactness arguments.
 #pragma once
@@ -122,4 +124,116 @@ __device__ __forceinline__ bool af_renorm2_dec(u32 low, u32 hm, u32 &k, u32 &m, 
     nlow = (low << kt) & 0x7FFFFFFFu;
     nhm = ~(~hm << kt) | AF_HALF;  // (hm << kt) | ones(kt) | HALF
     return nlow == 0 || nhm == 0xFFFFFFFFu;
+}
+
+// ---- the rare paths and a chunk's two ends: one copy for every tuned kernel --------------------------------------------
+// What differs between the kernels -- which writer or reader, where a flush or a bit counter sits -- comes in as a callable
+// and stays at the call site.
+
+// The encoder's renormalisation loops as the reference writes them (:126-150; the strict comparisons are quirk Q1): for the
+// symbols the closed form is not exact for (the corner tests above) and for those whose field would not fit one put
+// (k + pending > 32).  `emit(bit)` writes `bit` and then `pending` copies of its inverse; it reads the caller's count.
+template <class Emit>
+__device__ __forceinline__ void af_renorm_literal_enc(u32 &low, u32 &hm, u32 &pending, Emit emit) {
+    u64 lo = low, hi = (u64)hm + 1;
+    while (hi < AF_HALF || lo > AF_HALF) {
+        if (hi < AF_HALF) {
+            emit(0u);
+            lo <<= 1;
+            hi <<= 1;
+        } else {
+            emit(1u);
+            lo = (lo - AF_HALF) << 1;
+            hi = (hi - AF_HALF) << 1;
+        }
+        pending = 0;
+    }
+    while (lo > AF_QTR && hi < 3ull * AF_QTR) {
+        pending += 1;
+        lo = (lo - AF_QTR) << 1;
+        hi = (hi - AF_QTR) << 1;
+    }
+    low = (u32)lo;
+    hm = (u32)(hi - 1);
+}
+
+// The decoder's (:245-275): the same steps with the state shifted along, one stream bit from `next_bit()` per step.
+template <class NextBit>
+__device__ __forceinline__ void af_renorm_literal_dec(u32 &low, u32 &hm, u32 &state, NextBit next_bit) {
+    u64 lo = low, hi = (u64)hm + 1, stt = state;
+    while (hi < AF_HALF || lo > AF_HALF) {
+        if (hi < AF_HALF) {
+            lo <<= 1;
+            hi <<= 1;
+            stt <<= 1;
+        } else {
+            lo = (lo - AF_HALF) << 1;
+            hi = (hi - AF_HALF) << 1;
+            stt = (stt - AF_HALF) << 1;
+        }
+        stt += next_bit();
+    }
+    while (lo > AF_QTR && hi < 3ull * AF_QTR) {
+        lo = (lo - AF_QTR) << 1;
+        hi = (hi - AF_QTR) << 1;
+        stt = (stt - AF_QTR) << 1;
+        stt += next_bit();
+    }
+    low = (u32)lo;
+    hm = (u32)(hi - 1);
+    state = (u32)stt;
+}
+
+// Stream header (:92-99): the chunk's length in size_bits bits; a length that does not fit is reported, its low bits coded.
+__device__ __forceinline__ u32 af_header_value(u32 n, u32 size_bits) {
+    return size_bits < 32 ? (n & ((1u << size_bits) - 1u)) : n;
+}
+__device__ __forceinline__ u32 af_header_status(u32 n, u32 size_bits) {
+    return (size_bits < 32 && (n >> size_bits)) ? SCL_ST_SIZE : 0u;
+}
+
+// Termination (:153-159): one more pending bit, then the quarter low lies in decides; `emit` as in af_renorm_literal_enc.
+template <class Emit>
+__device__ __forceinline__ void af_terminate(u32 low, u32 &pending, Emit emit) {
+    pending += 1;
+    if (low <= AF_QTR)
+        emit(0u);
+    else
+        emit(1u);
+}
+
+// The decoders' start (:203-240) once the length header `n` is read: a stream shorter than a header (whatever was read is
+// void then), out_lens, the capacity refusal, and quirk Q5 (an empty chunk ends after size_bits + 2 bits, as in
+// scl_aec.hip).  Returns the number of symbols to decode; 0: the chunk is done, its results are written.
+__device__ __forceinline__ u32 af_decode_length(u32 n, u32 &st, u32 nbits, u32 size_bits, u32 out_cap, u64 chunk,
+                                                u32 *out_lens, u32 *consumed, u32 *status) {
+    st = 0;
+    if (nbits < size_bits) {
+        st |= SCL_ST_TRUNCATED;
+        n = 0;
+    }
+    out_lens[chunk] = n;
+    if (n > out_cap) {
+        st |= SCL_ST_CAPACITY;
+        n = 0;
+    }
+    if (n == 0) {
+        consumed[chunk] = (st == 0) ? size_bits + 2 : 0;
+        if (status) status[chunk] = st;
+    }
+    return n;
+}
+
+// The decoders' end (:277-282): how many of the last PRECISION bits belonged to the encoder -- the largest e for which
+// every completion of the state's top 32 - e bits lies inside [low, high) -- taken off `bits_read`, everything the decoder
+// took from the stream, header included.
+__device__ __forceinline__ u32 af_consumed_bits(u32 low, u32 hm, u32 state, u64 bits_read) {
+    const u64 lo = low, hi = (u64)hm + 1;
+    u32 e = 0;
+    for (; e < 32; ++e) {
+        const u64 slo = ((u64)state >> e) << e, shi = slo + (1ull << e);
+        if (slo < lo || shi > hi) break;
+    }
+    if (e == 32) e = 31;
+    return (u32)((i64)bits_read - ((i64)e - 1));
 }

@@ -65,26 +65,9 @@
 #define AS_LDS_BYTES (AS_RED_BASE + 16)
 static_assert(AS_LDS_BYTES <= 160 * 1024, "LDS of one CU");
 
-struct AecSplitDev {
-    u32 K;          // alphabet size 2..16
-    u32 nctx;       // K^k <= 16
-    u32 ctx_magic;  // ceil(2^16 / nctx): (v * magic) >> 16 == v / nctx for v < 272
-    u32 total0;     // initial total of a row
-    u32 size_bits;  // DATA_BLOCK_SIZE_BITS (1..32)
-    u32 initX[8];   // 16 packed u16: EXCLUSIVE cumulative initial counts, padded with the total
-};
-
-template <bool ORDER1>
-__device__ __forceinline__ u32 as_next_ctx(const AecSplitDev &P, u32 ctx, u32 s) {  // past_k[1:] + [s], :146-151
-    if (ORDER1) return s;
-    // (24-bit multiplies: v < 272, magic <= 2^15, nctx <= 16 -- the 32-bit v_mul_lo_u32 is a quarter-rate instruction)
-    const u32 v = __umul24(ctx, P.K) + s;
-    return v - __umul24(__umul24(v, P.ctx_magic) >> 16, P.nctx);
-}
-
 template <bool ORDER1>
 __global__ void __launch_bounds__(AS_THREADS)
-    aec_split_encode_kernel(AecSplitDev P, const u8 *__restrict__ sym, u64 sym_stride, const u32 *__restrict__ lens,
+    aec_split_encode_kernel(AecFastDev P, const u8 *__restrict__ sym, u64 sym_stride, const u32 *__restrict__ lens,
                             u32 chunk_len, u64 n_chunks, u8 *__restrict__ out, u64 out_stride,
                             u64 *__restrict__ out_bit_off, u32 *__restrict__ out_nbits, u32 *__restrict__ status) {
     __shared__ __attribute__((aligned(16))) char lds[AS_LDS_BYTES];
@@ -168,7 +151,7 @@ __global__ void __launch_bounds__(AS_THREADS)
                             __hip_atomic_fetch_add(row + p * (AS_PLANE / 4), add[p], __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
-                    ctx = as_next_ctx<ORDER1>(P, ctx, s[q]);
+                    ctx = af_next_ctx<ORDER1>(P, ctx, s[q]);
                 }
 #pragma unroll
                 for (u32 j = 0; j < AS_TILE; ++j) {
@@ -234,27 +217,12 @@ __global__ void __launch_bounds__(AS_THREADS)
                     const bool edge = nlow == 0 || nhm == 0xFFFFFFFFu;
                     u32 top;
                     if (__builtin_expect(edge, 0)) {
-                        u64 lo = low, hi = (u64)hm + 1;
+                        // the literal loops only count here: k steps that emit a bit, then m steps that add a pending one
+                        const u32 low0 = low;
                         k = 0;
                         m = 0;
-                        while (hi < AF_HALF || lo > AF_HALF) {
-                            if (hi < AF_HALF) {
-                                lo <<= 1;
-                                hi <<= 1;
-                            } else {
-                                lo = (lo - AF_HALF) << 1;
-                                hi = (hi - AF_HALF) << 1;
-                            }
-                            k += 1;
-                        }
-                        while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-                            m += 1;
-                            lo = (lo - AF_QTR) << 1;
-                            hi = (hi - AF_QTR) << 1;
-                        }
-                        top = k ? low >> (32 - k) : 0u;  // every step emitted the leading bit of lo
-                        low = (u32)lo;
-                        hm = (u32)(hi - 1);
+                        af_renorm_literal_enc(low, hm, m, [&](u32) { k += 1; });
+                        top = k ? low0 >> (32 - k) : 0u;  // every step emitted the leading bit of lo
                     } else {
                         top = low >> ((32 - k) & 31);  // k = 0: never looked at
                         low = nlow;
@@ -300,9 +268,9 @@ __global__ void __launch_bounds__(AS_THREADS)
         }
         if (count) push(bit ? ((1u << count) - 1u) : 0u, count);
     };
-    u32 st = (P.size_bits < 32 && (n >> P.size_bits)) ? SCL_ST_SIZE : 0u;
+    u32 st = af_header_status(n, P.size_bits);
     if (live) {  // header, :92-99
-        const u32 hv = P.size_bits < 32 ? (n & ((1u << P.size_bits) - 1u)) : n;
+        const u32 hv = af_header_value(n, P.size_bits);
         if (P.size_bits == 32) {
             push(hv >> 16, 16);
             push(hv & 0xFFFFu, 16);
@@ -346,14 +314,11 @@ __global__ void __launch_bounds__(AS_THREADS)
     st |= *reinterpret_cast<const u32_lds *>(lds + AS_F1C_BASE + lane * 4);
     const uint2 fin = *reinterpret_cast<const uint2 *>(lds + AS_F2_BASE + lane * 8);
     if (!live) return;
-    const u32 pending = fin.y + 1;  // termination, :153-159
-    if (fin.x <= AF_QTR) {
-        push(0, 1);
-        push_run(1, pending);
-    } else {
-        push(1, 1);
-        push_run(0, pending);
-    }
+    u32 pending = fin.y;
+    af_terminate(fin.x, pending, [&](u32 bit) {  // :153-159
+        push(bit, 1);
+        push_run(bit ^ 1u, pending);
+    });
     const u64 total = (u64)nwords * 32 + cnt;
     if (cnt) dst[nwords] = __builtin_bswap32(wlo << (32 - cnt));
     out_bit_off[chunk] = chunk * out_stride * 8;
@@ -362,26 +327,10 @@ __global__ void __launch_bounds__(AS_THREADS)
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------
-static AecSplitDev aec_split_dev(const scl_aec_model *m) {
-    AecSplitDev f;
-    f.K = m->dev.K;
-    f.nctx = (u32)m->dev.ctx_mod;
-    f.ctx_magic = (65536u + f.nctx - 1) / f.nctx;
-    u32 X[16], acc = 0;
-    for (u32 j = 0; j < 16; ++j) {
-        X[j] = acc;  // exclusive; entries past the alphabet hold the total
-        if (j < f.K) acc += m->h_freq[j];
-    }
-    f.total0 = acc;
-    f.size_bits = m->dev.size_bits;
-    for (u32 r = 0; r < 8; ++r) f.initX[r] = X[2 * r] | (X[2 * r + 1] << 16);
-    return f;
-}
-
 void aec_split_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st) {
     const SclGrid g = {(u32)((a.n_chunks + AS_LANES - 1) / AS_LANES), AS_THREADS};
     if (m->dev.k == 1)
-        scl_launch_encode(aec_split_encode_kernel<true>, g, st, aec_split_dev(m), a);
+        scl_launch_encode(aec_split_encode_kernel<true>, g, st, aec_fast_dev(m), a);
     else
-        scl_launch_encode(aec_split_encode_kernel<false>, g, st, aec_split_dev(m), a);
+        scl_launch_encode(aec_split_encode_kernel<false>, g, st, aec_fast_dev(m), a);
 }

@@ -55,6 +55,12 @@ __device__ __forceinline__ void as_setup_table16(char *lds, const AecStaticDev &
 typedef AnsFwdWriter<AS_THREADS> AsOut;
 typedef AnsBitReader<AS_THREADS, true> AsIn;
 
+// one step of the literal loops, and the termination: `bit`, then `pending` copies of its inverse
+__device__ __forceinline__ void as_emit(AsOut &wr, char *lds, u32 bit, u32 pending) {
+    wr.put(lds, bit, 1);
+    wr.put_run(lds, bit ^ 1u, pending);
+}
+
 // one symbol of the encoder: shrink_range, then the renormalisation loops (:126-150)
 template <bool POW2>
 __device__ __forceinline__ void as_encode_symbol(u32 &low, u32 &hm, u32 &pending, u64 c, u64 d, u32 t, double xT,
@@ -67,29 +73,10 @@ __device__ __forceinline__ void as_encode_symbol(u32 &low, u32 &hm, u32 &pending
     const bool edge = af_renorm2_dec(low, hm, k, m, nlow, nhm);  // the conservative corner test: two compares fewer
     const bool rare = edge | (k + pending > 32);                 // one condition, one branch
     if (__builtin_expect(rare, 0)) {
-        u64 lo = low, hi = (u64)hm + 1;
-        while (hi < AF_HALF || lo > AF_HALF) {
-            if (hi < AF_HALF) {
-                wr.put(lds, 0, 1);
-                wr.put_run(lds, 1, pending);
-                lo <<= 1;
-                hi <<= 1;
-            } else {
-                wr.put(lds, 1, 1);
-                wr.put_run(lds, 0, pending);
-                lo = (lo - AF_HALF) << 1;
-                hi = (hi - AF_HALF) << 1;
-            }
+        af_renorm_literal_enc(low, hm, pending, [&](u32 bit) {
+            as_emit(wr, lds, bit, pending);
             wr.maybe_flush(lds);
-            pending = 0;
-        }
-        while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-            pending += 1;
-            lo = (lo - AF_QTR) << 1;
-            hi = (hi - AF_QTR) << 1;
-        }
-        low = (u32)lo;
-        hm = (u32)(hi - 1);
+        });
     } else {
         // b0, then `pending` copies of !b0, then the other k - 1 common bits -- without a branch on k: for k = 0 the field is
         // empty (v = 0, nb = 0) and the pending count just grows (as in scl_aec_iid.hip)
@@ -126,7 +113,7 @@ __global__ void __launch_bounds__(AS_THREADS, 4)
     const double xT = af_recip((double)P.T);
     AsOut wr;
     wr.init(tid, out + chunk * out_stride);
-    wr.put(lds, P.size_bits < 32 ? (n & ((1u << P.size_bits) - 1u)) : n, P.size_bits);  // header, :92-99
+    wr.put(lds, af_header_value(n, P.size_bits), P.size_bits);  // :92-99
     u32 low = 0, hm = 0xFFFFFFFFu, pending = 0, bad = 0;
 
     auto code_word = [&](u32 w, u32 cnt) {  // up to four symbols, first symbol in the low byte
@@ -171,19 +158,12 @@ __global__ void __launch_bounds__(AS_THREADS, 4)
         for (u32 j = 0; i + j < n; ++j) w |= (u32)src[i + j] << (8 * j);
         code_word(w, n - i);
     }
-    pending += 1;  // termination, :153-159
-    if (low <= AF_QTR) {
-        wr.put(lds, 0, 1);
-        wr.put_run(lds, 1, pending);
-    } else {
-        wr.put(lds, 1, 1);
-        wr.put_run(lds, 0, pending);
-    }
+    af_terminate(low, pending, [&](u32 bit) { as_emit(wr, lds, bit, pending); });  // :153-159
     const u64 total = wr.finish(lds);
     out_bit_off[chunk] = chunk * out_stride * 8;
     out_nbits[chunk] = (u32)total;
     if (status)
-        status[chunk] = ((bad >= P.K) ? SCL_ST_SYMBOL : 0u) | ((P.size_bits < 32 && (n >> P.size_bits)) ? SCL_ST_SIZE : 0u);
+        status[chunk] = ((bad >= P.K) ? SCL_ST_SYMBOL : 0u) | af_header_status(n, P.size_bits);
 }
 
 // LUT = true: total <= 4096, the decoder's search is one byte read by target slot; else a binary search on c
@@ -199,8 +179,8 @@ __global__ void __launch_bounds__(AS_THREADS, 4)
     const u64 chunk = (u64)blockIdx.x * AS_THREADS + tid;
     if (chunk >= n_chunks) return;
     const u32 nbits = in_nbits[chunk];
-    u32 st = 0;
-    if (nbits < P.size_bits) {
+    u32 st;
+    if (nbits < P.size_bits) {  // refused without opening the stream (af_decode_length's first test, ahead of rd.init)
         out_lens[chunk] = 0;
         consumed[chunk] = 0;
         if (status) status[chunk] = SCL_ST_TRUNCATED;
@@ -208,17 +188,9 @@ __global__ void __launch_bounds__(AS_THREADS, 4)
     }
     AsIn rd;
     rd.init(in, in_size_bytes, bit_off[chunk], lds, tid, nbits);
-    u32 n = rd.get(lds, P.size_bits);
-    out_lens[chunk] = n;
-    if (n > out_cap) {
-        st |= SCL_ST_CAPACITY;
-        n = 0;
-    }
-    if (n == 0) {  // quirk Q5, as in scl_aec.hip
-        consumed[chunk] = (st == 0) ? P.size_bits + 2 : 0;
-        if (status) status[chunk] = st;
-        return;
-    }
+    const u32 n = af_decode_length(rd.get(lds, P.size_bits), st, nbits, P.size_bits, out_cap, chunk, out_lens, consumed,
+                                   status);
+    if (n == 0) return;
     rd.maybe_refill(lds);
     const double xT = af_recip((double)P.T), Td = (double)P.T;
     u8 *dst = out_sym + chunk * out_stride;
@@ -254,31 +226,11 @@ __global__ void __launch_bounds__(AS_THREADS, 4)
         u32 k, m, nlow, nhm;
         const bool edge = af_renorm2_dec(low, hm, k, m, nlow, nhm);
         if (__builtin_expect(edge, 0)) {
-            u64 lo = low, hi = (u64)hm + 1, stt = state;
-            while (hi < AF_HALF || lo > AF_HALF) {
-                if (hi < AF_HALF) {
-                    lo <<= 1;
-                    hi <<= 1;
-                    stt <<= 1;
-                } else {
-                    lo = (lo - AF_HALF) << 1;
-                    hi = (hi - AF_HALF) << 1;
-                    stt = (stt - AF_HALF) << 1;
-                }
-                stt += rd.get(lds, 1);
+            af_renorm_literal_dec(low, hm, state, [&] {
                 used++;
-            }
-            while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-                lo = (lo - AF_QTR) << 1;
-                hi = (hi - AF_QTR) << 1;
-                stt = (stt - AF_QTR) << 1;
-                stt += rd.get(lds, 1);
-                used++;
-            }
+                return rd.get(lds, 1);
+            });
             rd.maybe_refill(lds);
-            low = (u32)lo;
-            hm = (u32)(hi - 1);
-            state = (u32)stt;
         } else {
             const u32 kt = k + m;  // <= 31
             // kt bits come in from the stream: {state, look} << kt in one 64-bit shift (kt may be 0)
@@ -326,15 +278,7 @@ __global__ void __launch_bounds__(AS_THREADS, 4)
         dst[i] = (u8)decode_symbol(i + 1 == n);
         if ((i & 3u) == 3u) rd.maybe_refill(lds);
     }
-    // how many of the last PRECISION bits belonged to the encoder (:277-282)
-    const u64 lo = low, hi = (u64)hm + 1;
-    u32 e = 0;
-    for (; e < 32; ++e) {
-        const u64 slo = ((u64)state >> e) << e, shi = slo + (1ull << e);
-        if (slo < lo || shi > hi) break;
-    }
-    if (e == 32) e = 31;
-    consumed[chunk] = (u32)((i64)((u64)used + P.size_bits) - ((i64)e - 1));
+    consumed[chunk] = af_consumed_bits(low, hm, state, (u64)used + P.size_bits);  // :277-282
     if (status) status[chunk] = st;
 }
 

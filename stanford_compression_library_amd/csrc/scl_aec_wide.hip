@@ -72,39 +72,23 @@ __global__ void __launch_bounds__(AW_THREADS)
     aw_cell *cnt = reinterpret_cast<aw_cell *>(scratch) + chunk * P.cells;
     AfWriter wr;
     wr.init(out + chunk * out_stride);
-    wr.put(P.size_bits < 32 ? (n & ((1u << P.size_bits) - 1u)) : n, P.size_bits);  // header, :92-99
-    u32 st = (P.size_bits < 32 && (n >> P.size_bits)) ? SCL_ST_SIZE : 0u;
+    wr.put(af_header_value(n, P.size_bits), P.size_bits);  // :92-99
+    u32 st = af_header_status(n, P.size_bits);
     u32 low = 0, hm = 0xFFFFFFFFu;
     u32 pending = 0;  // E3 steps not yet resolved
 
+    // one step of the literal loops, and the termination: `bit`, then `pending` copies of its inverse
+    auto emit = [&](u32 bit) {
+        wr.put(bit, 1);
+        wr.put_run(bit ^ 1u, pending);
+    };
     // arithmetic stage: shrink_range (:58-78) and the renormalisation loops (:126-150) of one symbol
     auto code = [&](u32 cc, u32 dd, u32 TT, double xx) {
         af_shrink2(low, hm, cc, dd, xx);
         u32 k, m, nlow, nhm;
         const bool edge = af_renorm2(low, hm, k, m, nlow, nhm);
         if (__builtin_expect(edge || (k + pending > 32), 0)) {
-            u64 lo = low, hi = (u64)hm + 1;
-            while (hi < AF_HALF || lo > AF_HALF) {
-                if (hi < AF_HALF) {
-                    wr.put(0, 1);
-                    wr.put_run(1, pending);
-                    lo <<= 1;
-                    hi <<= 1;
-                } else {
-                    wr.put(1, 1);
-                    wr.put_run(0, pending);
-                    lo = (lo - AF_HALF) << 1;
-                    hi = (hi - AF_HALF) << 1;
-                }
-                pending = 0;
-            }
-            while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-                pending += 1;
-                lo = (lo - AF_QTR) << 1;
-                hi = (hi - AF_QTR) << 1;
-            }
-            low = (u32)lo;
-            hm = (u32)(hi - 1);
+            af_renorm_literal_enc(low, hm, pending, emit);
         } else {
             if (k > 0) {
                 const u32 top = low >> (32 - k);
@@ -182,14 +166,7 @@ __global__ void __launch_bounds__(AW_THREADS)
         cb = cb_nx;
     }
     code(c_pv, d_pv, T_pv, x_pv);
-    pending += 1;  // termination, :153-159
-    if (low <= AF_QTR) {
-        wr.put(0, 1);
-        wr.put_run(1, pending);
-    } else {
-        wr.put(1, 1);
-        wr.put_run(0, pending);
-    }
+    af_terminate(low, pending, emit);  // :153-159
     const u64 total = wr.finish();
     out_bit_off[chunk] = chunk * out_stride * 8;
     out_nbits[chunk] = (u32)total;
@@ -204,24 +181,11 @@ __global__ void __launch_bounds__(AW_THREADS)
     const u64 chunk = (u64)blockIdx.x * AW_THREADS + threadIdx.x;
     if (chunk >= n_chunks) return;
     const u32 nbits = in_nbits[chunk];
-    u32 st = 0;
     AfReader rd;
     rd.init(in, in_size_bytes, bit_off[chunk], nbits);
-    u32 n = rd.get(P.size_bits);
-    if (nbits < P.size_bits) {
-        st |= SCL_ST_TRUNCATED;
-        n = 0;
-    }
-    out_lens[chunk] = n;
-    if (n > out_cap) {
-        st |= SCL_ST_CAPACITY;
-        n = 0;
-    }
-    if (n == 0) {  // quirk Q5, as in scl_aec.hip
-        consumed[chunk] = (st == 0) ? P.size_bits + 2 : 0;
-        if (status) status[chunk] = st;
-        return;
-    }
+    u32 st;
+    const u32 n = af_decode_length(rd.get(P.size_bits), st, nbits, P.size_bits, out_cap, chunk, out_lens, consumed, status);
+    if (n == 0) return;
     aw_cell *cnt = reinterpret_cast<aw_cell *>(scratch) + chunk * P.cells;
     u32 *dst = reinterpret_cast<u32 *>(out_sym + chunk * out_stride);
     u64 used = 32;
@@ -286,30 +250,10 @@ __global__ void __launch_bounds__(AW_THREADS)
         u32 k, m, nlow, nhm;
         const bool edge = af_renorm2(low, hm, k, m, nlow, nhm);
         if (__builtin_expect(edge, 0)) {
-            u64 lo = low, hi = (u64)hm + 1, stt = state;
-            while (hi < AF_HALF || lo > AF_HALF) {
-                if (hi < AF_HALF) {
-                    lo <<= 1;
-                    hi <<= 1;
-                    stt <<= 1;
-                } else {
-                    lo = (lo - AF_HALF) << 1;
-                    hi = (hi - AF_HALF) << 1;
-                    stt = (stt - AF_HALF) << 1;
-                }
-                stt += rd.get(1);
+            af_renorm_literal_dec(low, hm, state, [&] {
                 used++;
-            }
-            while (lo > AF_QTR && hi < 3ull * AF_QTR) {
-                lo = (lo - AF_QTR) << 1;
-                hi = (hi - AF_QTR) << 1;
-                stt = (stt - AF_QTR) << 1;
-                stt += rd.get(1);
-                used++;
-            }
-            low = (u32)lo;
-            hm = (u32)(hi - 1);
-            state = (u32)stt;
+                return rd.get(1);
+            });
         } else {
             const u32 kt = k + m;  // <= 31
             state = af_state_shift_in(rd, state, k, kt);
@@ -319,15 +263,7 @@ __global__ void __launch_bounds__(AW_THREADS)
         }
     }
     if ((n & 3) != 0) dst[(n - 1) >> 2] = oword;  // last, partial word (zero-padded inside the row)
-    // how many of the last PRECISION bits belonged to the encoder (:277-282)
-    const u64 lo = low, hi = (u64)hm + 1;
-    u32 e = 0;
-    for (; e < 32; ++e) {
-        const u64 slo = ((u64)state >> e) << e, shi = slo + (1ull << e);
-        if (slo < lo || shi > hi) break;
-    }
-    if (e == 32) e = 31;
-    consumed[chunk] = (u32)((i64)(used + P.size_bits) - ((i64)e - 1));
+    consumed[chunk] = af_consumed_bits(low, hm, state, used + P.size_bits);  // :277-282
     if (status) status[chunk] = st;
 }
 
