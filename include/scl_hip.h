@@ -394,6 +394,82 @@ int scl_prefix_encode_block_host_u16(const scl_prefix_model *m, const uint16_t *
 int scl_prefix_decode_block_host_u16(const scl_prefix_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                      uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed);
 
+/* ---- LZ77: match index, greedy parse and sequence replay (scl_lz77.hip; added to ABI 8 as above) -----------------------
+ * The LZ layer of the reference's LZ77 coder, for a batch of independent streams, one wavefront per stream:
+ *   scl_lz77_parse_batch   <->  LZ77Encoder.lz77_parse_and_generate_sequences   scl/compressors/lz77.py:525-603
+ *   scl_lz77_replay_batch  <->  LZ77Decoder.execute_lz77_sequences              scl/compressors/lz77.py:640-665
+ * (the entropy stage above it is host code over the prefix-code entry points).  A stream's WINDOW is everything its coder
+ * has seen, the current block included; the windows of a batch lie one after another in d_win, window s = bytes
+ * [d_win_off[s], d_win_off[s + 1]) (any offsets: windows need no alignment), and positions inside a window are 32-bit.
+ *   parse : the block of stream s is its window from d_start[s] on.  With L = min_match_length (1..8: an L-gram is one
+ *           64-bit key) and M = max_matches (0 = no limit) the call writes what the reference's parse returns: sequences
+ *           (literal_count, match_length, match_offset) into row s (seq_cap entries) of the three arrays, d_n_seq[s] of
+ *           them, and the literals -- d_n_lit[s] bytes at d_literals + d_win_off[s] + d_start[s]: d_literals is laid out
+ *           like d_win, every block has room for itself.  It runs an index phase over all total_bytes positions of the
+ *           batch (total_bytes < 2^32; a stable radix sort by stream and gram, and one candidate bit per position) and the
+ *           parse phase proper; `phases` = 0 runs both, SCL_LZ77_INDEX / SCL_LZ77_PARSE one of them on the same scratch
+ *           (for measurements).  d_status[s]: SCL_ST_CAPACITY = more than seq_cap sequences (block_len / L always
+ *           suffices; the row holds the first seq_cap), SCL_ST_SIZE = window s does not lie inside [0, total_bytes) or
+ *           d_start[s] past its end (nothing is read or written for it).
+ *   replay: appends to window s, whose slot is [d_win_off[s], d_win_off[s + 1]) and holds d_have[s] bytes already (the
+ *           history: it stays on the device across blocks): per sequence literal_count literals, then match_length bytes
+ *           from match_offset back (overlapping matches repeat, as in the reference); then the literals left over.  Stream
+ *           s reads d_n_lit[s] literals at d_literals + d_lit_off[s] (inside lit_bytes) and d_n_seq[s] <= seq_cap
+ *           sequences; d_out_len[s] = bytes appended.  Nothing outside the slot is read or written on any input;
+ *           d_status[s]: SCL_ST_STATE = match_offset 0 or larger than the bytes so far, SCL_ST_TRUNCATED = the sequences
+ *           ask for more literals than there are, SCL_ST_CAPACITY = the slot is full, SCL_ST_SIZE = a slot or literal
+ *           range outside its buffer.  The stream stops at its first fault; d_out_len[s] counts what came before.
+ * Both are asynchronous on `stream`.  SCL_E_PARAM before any device call: a null pointer, L outside 1..8, total_bytes or
+ * n_streams >= 2^32, scratch misaligned (256 bytes) or smaller than scl_lz77_scratch_bytes. */
+#define SCL_LZ77_INDEX 1u
+#define SCL_LZ77_PARSE 2u
+
+typedef struct scl_lz77_parse_args {
+    const uint8_t *d_win;
+    const uint64_t *d_win_off; /* [n_streams + 1] */
+    const uint32_t *d_start;   /* [n_streams]     */
+    uint64_t n_streams;
+    uint64_t total_bytes;      /* bytes of d_win and of d_literals */
+    uint32_t min_match_length, max_matches;
+    uint32_t seq_cap, phases;
+    uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_streams * seq_cap] each */
+    uint8_t *d_literals;
+    uint32_t *d_n_seq, *d_n_lit, *d_status; /* [n_streams] each */
+    void *d_scratch;
+    uint64_t scratch_bytes;
+} scl_lz77_parse_args;
+
+typedef struct scl_lz77_replay_args {
+    uint8_t *d_win;
+    const uint64_t *d_win_off; /* [n_streams + 1]: the slots */
+    const uint32_t *d_have;    /* [n_streams]: bytes already in each slot */
+    uint64_t n_streams;
+    uint64_t total_bytes;      /* bytes of d_win */
+    uint32_t seq_cap, reserved;
+    const uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_streams * seq_cap] each */
+    const uint32_t *d_n_seq;
+    const uint8_t *d_literals;
+    uint64_t lit_bytes;
+    const uint64_t *d_lit_off; /* [n_streams] */
+    const uint32_t *d_n_lit;
+    uint32_t *d_out_len, *d_status;
+} scl_lz77_replay_args;
+
+uint64_t scl_lz77_scratch_bytes(uint64_t total_bytes, uint64_t n_streams);
+int scl_lz77_parse_batch(const scl_lz77_parse_args *args, void *stream);
+int scl_lz77_replay_batch(const scl_lz77_replay_args *args, void *stream);
+/* the kernels that carry the index (its scatter pass), the parse and the replay, as scl_rans_kernel_names; any may be NULL */
+int scl_lz77_kernel_names(char *index, char *parse, char *replay, uint64_t cap);
+/* one stream in host memory: allocate, copy, run, synchronise.  parse: the window is h_window[0..n), the block starts at
+   `start`; h_literals holds at least n - start bytes.  replay: h_window has room for `cap` bytes and holds `have`; the new
+   bytes are written behind them.  A non-zero stream status is SCL_E_CHUNK, as in the other *_host calls. */
+int scl_lz77_parse_host(const uint8_t *h_window, uint64_t n, uint64_t start, uint32_t min_match_length,
+                        uint32_t max_matches, uint32_t *h_lit_count, uint32_t *h_match_len, uint32_t *h_match_off,
+                        uint64_t seq_cap, uint64_t *n_seq, uint8_t *h_literals, uint64_t lit_cap, uint64_t *n_lit);
+int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, const uint32_t *h_lit_count,
+                         const uint32_t *h_match_len, const uint32_t *h_match_off, uint64_t n_seq,
+                         const uint8_t *h_literals, uint64_t n_lit, uint64_t *out_len);
+
 /* ---- stream compaction / framing ------------------------------------------------------------ */
 #define SCL_COMPACT_DENSE 0  /* stream c left-aligned at byte d_out_byte_offset[c], zero tail   */
 #define SCL_COMPACT_FRAMED 1 /* EncodedBlockWriter framing per stream:

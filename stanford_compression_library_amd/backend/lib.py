@@ -50,6 +50,26 @@ class PrefixBlockResult(C.Structure):
     _fields_ = [("n_out", C.c_uint64), ("consumed", C.c_uint64), ("status", C.c_uint32), ("sync_passes", C.c_uint32)]
 
 
+class Lz77ParseArgs(C.Structure):
+    """scl_lz77_parse_args: device pointers travel as integers"""
+    _fields_ = [("d_win", C.c_void_p), ("d_win_off", C.c_void_p), ("d_start", C.c_void_p), ("n_streams", C.c_uint64),
+                ("total_bytes", C.c_uint64), ("min_match_length", C.c_uint32), ("max_matches", C.c_uint32),
+                ("seq_cap", C.c_uint32), ("phases", C.c_uint32), ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p),
+                ("d_match_off", C.c_void_p), ("d_literals", C.c_void_p), ("d_n_seq", C.c_void_p), ("d_n_lit", C.c_void_p),
+                ("d_status", C.c_void_p), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
+
+
+class Lz77ReplayArgs(C.Structure):
+    """scl_lz77_replay_args"""
+    _fields_ = [("d_win", C.c_void_p), ("d_win_off", C.c_void_p), ("d_have", C.c_void_p), ("n_streams", C.c_uint64),
+                ("total_bytes", C.c_uint64), ("seq_cap", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p),
+                ("d_n_seq", C.c_void_p), ("d_literals", C.c_void_p), ("lit_bytes", C.c_uint64), ("d_lit_off", C.c_void_p),
+                ("d_n_lit", C.c_void_p), ("d_out_len", C.c_void_p), ("d_status", C.c_void_p)]
+
+
+LZ77_INDEX, LZ77_PARSE = 1, 2
+
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _vp, _u32, _u64, _int = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 
@@ -108,6 +128,13 @@ _SIGNATURES = {
     "scl_prefix_decode_block": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
     "scl_prefix_encode_block_host": (_int, _ENC_HOST),
     "scl_prefix_decode_block_host": (_int, _DEC_HOST),
+    # LZ77: match index, greedy parse, sequence replay (scl_lz77.hip)
+    "scl_lz77_scratch_bytes": (_u64, [_u64, _u64]),
+    "scl_lz77_parse_batch": (_int, [C.POINTER(Lz77ParseArgs), _vp]),
+    "scl_lz77_replay_batch": (_int, [C.POINTER(Lz77ReplayArgs), _vp]),
+    "scl_lz77_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
+    "scl_lz77_parse_host": (_int, [_u8p, _u64, _u64, _u32, _u32, _u32p, _u32p, _u32p, _u64, _u64p, _u8p, _u64, _u64p]),
+    "scl_lz77_replay_host": (_int, [_u8p, _u64, _u64, _u32p, _u32p, _u32p, _u64, _u8p, _u64, _u64p]),
     "scl_aec_model_create": (_int, [_int, _u32p, _u32, _u32, _u64, _u32, _u32, C.POINTER(_vp)]),
     "scl_aec_model_destroy": (None, [_vp]),
     "scl_aec_slot_bytes": (_u64, [_vp, _u64]),

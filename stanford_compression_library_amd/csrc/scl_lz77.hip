@@ -1,0 +1,648 @@
+// scl_lz77.hip -- the LZ layer of LZ77 for gfx950: match index, greedy parse, sequence replay.
+//
+//   scl_lz77_parse_batch   <->  LZ77Encoder.lz77_parse_and_generate_sequences   scl/compressors/lz77.py:525-603
+//   scl_lz77_replay_batch  <->  LZ77Decoder.execute_lz77_sequences              scl/compressors/lz77.py:640-665
+//
+// A batch is n_streams windows back to back in one buffer of N bytes.  The parse call runs
+//   index : a stable LSD radix sort of all N positions by (stream, L-gram) -> order[] and its inverse rank[]: the
+//           occurrences of one gram of one stream sit together, oldest first (the reference's substring_dict lists);
+//   bitmap: one bit per position: it has a candidate (an equal gram at q <= p - L) -- parallel over positions;
+//   parse : ONE WAVEFRONT PER STREAM walks the stream: skip to the next set bit (4096 positions per step), score the
+//           candidates 64 at a time (lane j = the j-th most recent), longest wins, lowest lane on ties.
+// No workgroup waits on another (every dependency between workgroups is a kernel boundary), every loop is bounded by the
+// data, and reads and writes are checked against the buffers' sizes on any input.
+#include "scl_lz77_internal.h"
+
+namespace {
+
+__device__ __forceinline__ u32 lz_lane() { return threadIdx.x & (SCL_WAVE - 1); }
+
+// the stream that owns global position v: the last s with win_off[s] <= v if v < win_off[s + 1], else n_streams
+__device__ __forceinline__ u32 lz_stream_of(const u64 *win_off, u32 n_streams, u64 v) {
+    u32 lo = 0, hi = n_streams;  // invariant: the answer, if any, is in [lo, hi)
+    while (hi - lo > 1) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if (win_off[mid] <= v)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    if (n_streams == 0 || win_off[lo] > v || v >= win_off[lo + 1]) return n_streams;
+    return lo;
+}
+
+// the L-gram at global position g as a little-endian integer; the caller guarantees g + L <= N
+__device__ __forceinline__ u64 lz_gram(const u8 *win, u64 g, u32 L) {
+    u64 k = 0;
+    for (u32 j = 0; j < L; ++j) k |= (u64)win[g + j] << (8 * j);
+    return k;
+}
+
+// digit of position v in pass `pass`: passes 0..L-1 read gram byte `pass`, later ones a byte of the stream number
+__device__ __forceinline__ u32 lz_digit(const u8 *win, u64 N, const u64 *win_off, u32 n_streams, u32 L, u32 pass, u32 v) {
+    if (pass < L) {
+        const u64 g = (u64)v + pass;
+        return g < N ? win[g] : 0u;
+    }
+    return (lz_stream_of(win_off, n_streams, v) >> (8 * (pass - L))) & 255u;
+}
+
+// ---- index sort ------------------------------------------------------------------------------------------------------
+// in == nullptr: the identity permutation (the first pass)
+__global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_histogram(const u8 *win, u64 N, const u64 *win_off,
+                                                                       u32 n_streams, u32 L, u32 pass, const u32 *in,
+                                                                       u32 *hist, u64 n_tiles) {
+    __shared__ u32 cnt[256];
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const u64 first = (u64)blockIdx.x * LZ_SORT_TILE + (u64)(threadIdx.x / SCL_WAVE) * (SCL_WAVE * LZ_SORT_ROUNDS) + lz_lane();
+    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
+        const u64 i = first + (u64)r * SCL_WAVE;
+        if (i < N) atomicAdd(&cnt[lz_digit(win, N, win_off, n_streams, L, pass, in ? in[i] : (u32)i)], 1u);
+    }
+    __syncthreads();
+    hist[(u64)threadIdx.x * n_tiles + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// exclusive scan of 256 values, one per thread; *total = their sum.  tmp: 256 words of LDS.
+__device__ __forceinline__ u32 lz_block_scan(u32 v, u32 *tmp, u32 *total) {
+    const u32 t = threadIdx.x;
+    tmp[t] = v;
+    __syncthreads();
+    for (u32 d = 1; d < LZ_SCAN_THREADS; d <<= 1) {
+        const u32 add = t >= d ? tmp[t - d] : 0u;
+        __syncthreads();
+        tmp[t] += add;
+        __syncthreads();
+    }
+    const u32 incl = tmp[t];
+    *total = tmp[LZ_SCAN_THREADS - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+// the scan of the tile histograms in three kernels: every block scans its 2048 entries, one workgroup scans the block
+// sums, every block adds its offset
+__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_blocks(u32 *hist, u64 n, u32 *block_sums) {
+    __shared__ u32 tmp[LZ_SCAN_THREADS];
+    const u64 at = ((u64)blockIdx.x * LZ_SCAN_THREADS + threadIdx.x) * LZ_SCAN_PER_THREAD;
+    u32 v[LZ_SCAN_PER_THREAD], sum = 0;
+#pragma unroll
+    for (u32 j = 0; j < LZ_SCAN_PER_THREAD; ++j) {
+        v[j] = at + j < n ? hist[at + j] : 0u;
+        sum += v[j];
+    }
+    u32 total;
+    u32 run = lz_block_scan(sum, tmp, &total);
+#pragma unroll
+    for (u32 j = 0; j < LZ_SCAN_PER_THREAD; ++j) {
+        if (at + j < n) hist[at + j] = run;
+        run += v[j];
+    }
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_block_sums(u32 *block_sums, u64 n) {
+    __shared__ u32 tmp[LZ_SCAN_THREADS];
+    u32 carry = 0;
+    for (u64 at = 0; at < n; at += LZ_SCAN_THREADS) {
+        const u64 i = at + threadIdx.x;
+        const u32 v = i < n ? block_sums[i] : 0u;
+        u32 total;
+        const u32 ex = lz_block_scan(v, tmp, &total);
+        if (i < n) block_sums[i] = carry + ex;
+        carry += total;
+    }
+}
+
+__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_add(u32 *hist, u64 n, const u32 *block_sums) {
+    const u64 at = ((u64)blockIdx.x * LZ_SCAN_THREADS + threadIdx.x) * LZ_SCAN_PER_THREAD;
+    const u32 add = block_sums[blockIdx.x];
+#pragma unroll
+    for (u32 j = 0; j < LZ_SCAN_PER_THREAD; ++j)
+        if (at + j < n) hist[at + j] += add;
+}
+
+// ranked scatter: hist[digit * n_tiles + tile] = where this tile's first entry with that digit goes.  Inside the tile the
+// waves take their digits' places in wave order, and a wave ranks its 64 entries of a round by ballots: entry -> place
+// + (entries with the same digit in lower lanes).  rank_out != nullptr on the last pass: the inverse permutation.
+__global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_scatter(const u8 *win, u64 N, const u64 *win_off,
+                                                                     u32 n_streams, u32 L, u32 pass, const u32 *in,
+                                                                     u32 *out, u32 *rank_out, const u32 *hist,
+                                                                     u64 n_tiles) {
+    __shared__ u32 place[LZ_SORT_WAVES][256];
+    const u32 wave = threadIdx.x / SCL_WAVE, lane = lz_lane();
+    for (u32 w = 0; w < LZ_SORT_WAVES; ++w) place[w][threadIdx.x] = 0;
+    __syncthreads();
+    const u64 first = (u64)blockIdx.x * LZ_SORT_TILE + (u64)wave * (SCL_WAVE * LZ_SORT_ROUNDS) + lane;
+    u32 val[LZ_SORT_ROUNDS];
+    u32 dig[LZ_SORT_ROUNDS / 4] = {};  // four digits to a word
+#pragma unroll
+    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
+        const u64 i = first + (u64)r * SCL_WAVE;
+        val[r] = 0;
+        if (i < N) {
+            val[r] = in ? in[i] : (u32)i;
+            const u32 d = lz_digit(win, N, win_off, n_streams, L, pass, val[r]);
+            dig[r / 4] |= d << (8 * (r % 4));
+            atomicAdd(&place[wave][d], 1u);
+        }
+    }
+    __syncthreads();
+    {
+        u32 at = hist[(u64)threadIdx.x * n_tiles + blockIdx.x];
+        for (u32 w = 0; w < LZ_SORT_WAVES; ++w) {
+            const u32 c = place[w][threadIdx.x];
+            place[w][threadIdx.x] = at;
+            at += c;
+        }
+    }
+    __syncthreads();
+    volatile u32 *mine = place[wave];
+    const u64 below = (1ull << lane) - 1;
+#pragma unroll
+    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
+        const u64 i = first + (u64)r * SCL_WAVE;
+        const bool live = i < N;
+        const u32 d = (dig[r / 4] >> (8 * (r % 4))) & 255u;
+        u64 same = __ballot(live);
+#pragma unroll
+        for (u32 b = 0; b < 8; ++b) {
+            const u64 set = __ballot(live && ((d >> b) & 1u));
+            same &= ((d >> b) & 1u) ? set : ~set;
+        }
+        if (live) {
+            const u32 at = mine[d];
+            const u32 dest = at + (u32)__popcll(same & below);
+            if ((same >> lane) == 1ull) mine[d] = at + (u32)__popcll(same);  // the highest lane of the group moves the place
+            out[dest] = val[r];
+            if (rank_out) rank_out[val[r]] = dest;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// ---- candidate bitmap ------------------------------------------------------------------------------------------------
+// bit g: position g of its stream has a candidate.  Predecessors of g in order[] with g's (stream, gram) are earlier
+// occurrences, newest first; at most L - 1 of them overlap g (q > p - L), so L looks decide.
+__global__ __launch_bounds__(256) void lz77_candidate_bitmap(const u8 *win, u64 N, const u64 *win_off, u32 n_streams,
+                                                             u32 L, const u32 *order, const u32 *rank, u64 *bitmap) {
+    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bit = false;
+    if (g < N) {
+        const u32 s = lz_stream_of(win_off, n_streams, g);
+        if (s < n_streams) {
+            const u64 base = win_off[s];
+            u64 end = win_off[s + 1];
+            if (end > N) end = N;
+            if (g + L <= end) {
+                const u32 i = rank[g];
+                const u64 key = lz_gram(win, g, L);
+                for (u32 k = 1; k <= L && k <= i; ++k) {
+                    const u64 c = order[i - k];
+                    if (c < base || c >= g || lz_gram(win, c, L) != key) break;
+                    if (c + L <= g) {
+                        bit = true;
+                        break;
+                    }
+                }
+            }
+        }
+    }
+    const u64 word = __ballot(bit);
+    if (lz_lane() == 0 && (g >> 6) < (N + 63) / 64) bitmap[g >> 6] = word;
+}
+
+// ---- parse -----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u64 lz_readlane64(u64 v, u32 lane) {
+    const u32 lo = __builtin_amdgcn_readlane((int)(u32)v, (int)lane);
+    const u32 hi = __builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)lane);
+    return ((u64)hi << 32) | lo;
+}
+
+// first set bit in [from, to) of the bitmap, or `to`: 64 words per step, one per lane (wave-uniform result)
+__device__ __forceinline__ u64 lz_next_bit(const u64 *bitmap, u64 from, u64 to) {
+    if (from >= to) return to;
+    const u64 w_first = from >> 6, w_last = (to - 1) >> 6;
+    for (u64 wb = w_first; wb <= w_last; wb += SCL_WAVE) {
+        const u64 wi = wb + lz_lane();
+        u64 word = wi <= w_last ? bitmap[wi] : 0ull;
+        if (wi == w_first) word &= ~0ull << (from & 63);
+        if (wi == w_last && (to & 63)) word &= (1ull << (to & 63)) - 1;
+        const u64 hit = __ballot(word != 0);
+        if (hit) {
+            const u32 l = (u32)__builtin_ctzll(hit);
+            return (wb + l) * 64 + (u32)__builtin_ctzll(lz_readlane64(word, l));
+        }
+    }
+    return to;
+}
+
+__device__ __forceinline__ u64 lz_load8(const u8 *p) {
+    u64 v;
+    __builtin_memcpy(&v, p, 8);
+    return v;
+}
+
+// largest l <= limit with a[0..l) == b[0..l), given that the first `known` bytes are equal; reads stay below a + limit
+// and b + limit
+__device__ __forceinline__ u32 lz_extend(const u8 *a, const u8 *b, u32 known, u32 limit) {
+    u32 len = known;
+    while (len + 8 <= limit) {
+        const u64 x = lz_load8(a + len) ^ lz_load8(b + len);
+        if (x) return len + ((u32)__builtin_ctzll(x) >> 3);
+        len += 8;
+    }
+    while (len < limit && a[len] == b[len]) ++len;
+    return len;
+}
+
+__global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_parse(const u8 *win, u64 N, const u64 *win_off,
+                                                                const u32 *start, u32 n_streams, u32 L, u32 M,
+                                                                const u32 *order, const u32 *rank, const u64 *bitmap,
+                                                                u32 seq_cap, u32 *lit_count, u32 *match_len,
+                                                                u32 *match_off, u8 *literals, u32 *n_seq_out,
+                                                                u32 *n_lit_out, u32 *status_out) {
+    const u32 s = blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE;
+    if (s >= n_streams) return;
+    const u32 lane = lz_lane();
+    const u64 base = win_off[s], end = win_off[s + 1];
+    const u32 st = start[s];
+    u32 n_seq = 0, n_lit = 0, status = 0;
+    if (base > end || end > N || end - base >= (1ull << 32) || st > end - base) {
+        status = SCL_ST_SIZE;
+    } else {
+        const u32 n = (u32)(end - base);
+        const u8 *w = win + base;
+        u8 *lit = literals + base + st;  // the block's own place in a buffer laid out like the windows: n - st bytes
+        u32 *out_lc = lit_count + (u64)s * seq_cap, *out_ml = match_len + (u64)s * seq_cap,
+            *out_mo = match_off + (u64)s * seq_cap;
+        const u64 g_stop = n >= L ? base + (n - L) + 1 : base;  // positions at or past it have no whole gram
+        u32 pos = st;
+        while (true) {
+            const u64 gp = lz_next_bit(bitmap, base + pos, g_stop);
+            if (gp >= g_stop) break;
+            const u32 p = (u32)(gp - base);
+            const u32 i = rank[gp];
+            const u64 key = lz_gram(win, gp, L);
+            // the newest occurrences may overlap p (q > p - L): at most L - 1, and they come first
+            bool near = false;
+            if (lane + 1 < L && lane < i) {
+                const u64 c = order[i - 1 - lane];
+                near = c >= base && c < gp && c + L > gp && lz_gram(win, c, L) == key;
+            }
+            const u32 skip = (u32)__popcll(__ballot(near));
+            u32 best_len = 0, best_q = 0;
+            for (u32 group = 0;; group += SCL_WAVE) {
+                const u32 nth = group + lane;  // this lane scores the nth most recent candidate
+                const u64 back = (u64)skip + nth;
+                bool ok = back < i && (M == 0 || nth < M);
+                u32 c = 0;
+                if (ok) {
+                    c = order[i - 1 - back];
+                    ok = c >= base && (u64)c + L <= gp && lz_gram(win, c, L) == key;
+                }
+                const u64 valid = __ballot(ok);
+                if (!(valid & 1ull)) break;
+                u64 score = 0;  // (length, 63 - lane): the maximum is the longest match, the lowest lane on ties
+                if (ok) score = ((u64)lz_extend(win + c, win + gp, L, n - p) << 6) | (63u - lane);
+                for (u32 d = 32; d; d >>= 1) {
+                    const u32 lo = __shfl_xor((u32)score, d), hi = __shfl_xor((u32)(score >> 32), d);
+                    const u64 other = ((u64)hi << 32) | lo;
+                    score = other > score ? other : score;
+                }
+                const u32 len = (u32)(score >> 6);
+                if (len > best_len) {  // an older group replaces only on strictly longer
+                    best_len = len;
+                    best_q = (u32)__builtin_amdgcn_readlane((int)c, (int)(63u - (u32)(score & 63)));
+                }
+                if (valid != ~0ull || (M != 0 && group + SCL_WAVE >= M)) break;
+            }
+            if (best_len == 0) {  // the bitmap promised a candidate: unreachable, and never a reason to spin
+                status |= SCL_ST_STATE;
+                break;
+            }
+            if (n_seq >= seq_cap) {
+                status |= SCL_ST_CAPACITY;
+                break;
+            }
+            const u32 run = p - pos;
+            for (u32 k = lane; k < run; k += SCL_WAVE) lit[n_lit + k] = w[pos + k];
+            if (lane == 0) {
+                out_lc[n_seq] = run;
+                out_ml[n_seq] = best_len;
+                out_mo[n_seq] = (u32)(gp - best_q);
+            }
+            n_lit += run;
+            n_seq += 1;
+            pos = p + best_len;
+        }
+        if (status == 0) {
+            const u32 run = n - pos;
+            for (u32 k = lane; k < run; k += SCL_WAVE) lit[n_lit + k] = w[pos + k];
+            n_lit += run;
+        }
+    }
+    if (lane == 0) {
+        n_seq_out[s] = n_seq;
+        n_lit_out[s] = n_lit;
+        status_out[s] = status;
+    }
+}
+
+// ---- replay ----------------------------------------------------------------------------------------------------------
+// One wavefront per stream appends to the stream's window.  A match reads bytes this same wave stored while it executed
+// the sequences before: the release fence and the drain in front of every match copy order them (workgroup scope: the
+// wave's loads and stores go through the one L1 of its CU; no other wave touches the stream).  `win` is deliberately
+// neither const nor __restrict__: the reads must take the vector path, not the scalar cache.
+__global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_replay(u8 *win, u64 N, const u64 *win_off, const u32 *have_in,
+                                                                 u32 n_streams, u32 seq_cap, const u32 *lit_count,
+                                                                 const u32 *match_len, const u32 *match_off,
+                                                                 const u32 *n_seq_in, const u8 *literals, u64 lit_bytes,
+                                                                 const u64 *lit_off, const u32 *n_lit_in, u32 *out_len,
+                                                                 u32 *status_out) {
+    const u32 s = blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE;
+    if (s >= n_streams) return;
+    const u32 lane = lz_lane();
+    const u64 base = win_off[s], end = win_off[s + 1];
+    const u32 have = have_in[s], n_seq = n_seq_in[s], n_lit = n_lit_in[s];
+    const u64 l_at = lit_off[s];
+    u32 status = 0, d = have;
+    if (base > end || end > N || end - base >= (1ull << 32) || have > end - base || n_seq > seq_cap ||
+        l_at > lit_bytes || n_lit > lit_bytes - l_at) {
+        status = SCL_ST_SIZE;
+    } else {
+        const u32 cap = (u32)(end - base);
+        u8 *out = win + base;
+        const u8 *lit = literals + l_at;
+        const u32 *lc = lit_count + (u64)s * seq_cap, *ml = match_len + (u64)s * seq_cap,
+                  *mo = match_off + (u64)s * seq_cap;
+        u32 lp = 0;
+        for (u32 k = 0; k < n_seq; ++k) {
+            const u32 run = lc[k], len = ml[k], off = mo[k];
+            if (run > n_lit - lp) {
+                status = SCL_ST_TRUNCATED;
+                break;
+            }
+            if (run > cap - d) {
+                status = SCL_ST_CAPACITY;
+                break;
+            }
+            for (u32 j = lane; j < run; j += SCL_WAVE) out[d + j] = lit[lp + j];
+            d += run;
+            lp += run;
+            if (off == 0 || off > d) {
+                status = SCL_ST_STATE;
+                break;
+            }
+            if (len > cap - d) {
+                status = SCL_ST_CAPACITY;
+                break;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            // out[d + j] = out[d - off + (j mod off)]: every source byte was there before this sequence began
+            const u8 *src = out + (d - off);
+            u32 from = lane % off;
+            const u32 step = SCL_WAVE % off;
+            for (u32 j = lane; j < len; j += SCL_WAVE) {
+                out[d + j] = src[from];
+                from += step;
+                if (from >= off) from -= off;
+            }
+            d += len;
+        }
+        if (status == 0) {
+            const u32 rest = n_lit - lp;
+            if (rest > cap - d) {
+                status = SCL_ST_CAPACITY;
+            } else {
+                for (u32 j = lane; j < rest; j += SCL_WAVE) out[d + j] = lit[lp + j];
+                d += rest;
+            }
+        }
+    }
+    if (lane == 0) {
+        out_len[s] = d - have;
+        status_out[s] = status;
+    }
+}
+
+u32 lz_stream_passes(u64 n_streams) {  // bytes of a stream number; n_streams itself marks bytes that belong to no stream
+    u32 passes = 0;
+    while (n_streams >> (8 * passes)) ++passes;
+    return n_streams > 1 ? passes : 0;
+}
+
+}  // namespace
+
+extern "C" uint64_t scl_lz77_scratch_bytes(uint64_t total_bytes, uint64_t n_streams) {
+    (void)n_streams;
+    return lz77_scratch_layout(total_bytes).total;
+}
+
+extern "C" int scl_lz77_kernel_names(char *index, char *parse, char *replay, uint64_t cap) {
+    SCL_REQUIRE(cap >= 96, "lz77_kernel_names: cap must be at least 96");
+    if (index) snprintf(index, cap, "lz77_sort_scatter");
+    if (parse) snprintf(parse, cap, "lz77_parse");
+    if (replay) snprintf(replay, cap, "lz77_replay");
+    return SCL_OK;
+}
+
+extern "C" int scl_lz77_parse_batch(const scl_lz77_parse_args *a, void *stream) {
+    const char *what = "lz77_parse_batch";
+    SCL_REQUIRE(a, "%s: null pointer argument", what);
+    SCL_REQUIRE(a->d_win_off && a->d_start && a->d_n_seq && a->d_n_lit && a->d_status && a->d_scratch &&
+                    (a->total_bytes == 0 || (a->d_win && a->d_literals)) &&
+                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
+                "%s: null pointer argument", what);
+    SCL_REQUIRE(a->min_match_length >= 1 && a->min_match_length <= 8,
+                "%s: min_match_length %u: an L-gram is one 64-bit key, 1 <= L <= 8", what, a->min_match_length);
+    SCL_REQUIRE(a->total_bytes < (1ull << 32) && a->n_streams < (1ull << 32),
+                "%s: a batch holds less than 2^32 bytes and 2^32 streams", what);
+    SCL_REQUIRE(a->phases <= 3, "%s: phases is a mask of SCL_LZ77_INDEX | SCL_LZ77_PARSE", what);
+    const Lz77Scratch lay = lz77_scratch_layout(a->total_bytes);
+    SCL_REQUIRE(((uintptr_t)a->d_scratch & 255) == 0 && a->scratch_bytes >= lay.total,
+                "%s: d_scratch must be 256-byte aligned and hold scl_lz77_scratch_bytes = %llu bytes", what,
+                (unsigned long long)lay.total);
+    if (a->n_streams == 0) return SCL_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const u64 N = a->total_bytes;
+    const u32 L = a->min_match_length, n_streams = (u32)a->n_streams;
+    u8 *scr = (u8 *)a->d_scratch;
+    u32 *order_a = (u32 *)(scr + lay.order_a), *order_b = (u32 *)(scr + lay.order_b), *rank = (u32 *)(scr + lay.rank);
+    u64 *bitmap = (u64 *)(scr + lay.bitmap);
+    u32 *hist = (u32 *)(scr + lay.hist), *sums = (u32 *)(scr + lay.block_sums);
+    const u32 phases = a->phases ? a->phases : 3u;
+    const u32 passes = L + lz_stream_passes(a->n_streams);
+    // the passes ping-pong between the two buffers and end in order_a
+    u32 *out = (passes & 1) ? order_a : order_b;
+    if ((phases & SCL_LZ77_INDEX) && N) {
+        const u32 *in = nullptr;
+        for (u32 pass = 0; pass < passes; ++pass) {
+            hipLaunchKernelGGL(lz77_sort_histogram, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, a->d_win, N,
+                               a->d_win_off, n_streams, L, pass, in, hist, lay.n_tiles);
+            hipLaunchKernelGGL(lz77_scan_blocks, dim3((u32)lay.n_scan_blocks), dim3(LZ_SCAN_THREADS), 0, st, hist,
+                               lay.n_hist, sums);
+            hipLaunchKernelGGL(lz77_scan_block_sums, dim3(1), dim3(LZ_SCAN_THREADS), 0, st, sums, lay.n_scan_blocks);
+            hipLaunchKernelGGL(lz77_scan_add, dim3((u32)lay.n_scan_blocks), dim3(LZ_SCAN_THREADS), 0, st, hist,
+                               lay.n_hist, sums);
+            hipLaunchKernelGGL(lz77_sort_scatter, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, a->d_win, N,
+                               a->d_win_off, n_streams, L, pass, in, out, pass + 1 == passes ? rank : nullptr, hist,
+                               lay.n_tiles);
+            in = out;
+            out = out == order_a ? order_b : order_a;
+        }
+        hipLaunchKernelGGL(lz77_candidate_bitmap, dim3((u32)((N + 255) / 256)), dim3(256), 0, st, a->d_win, N,
+                           a->d_win_off, n_streams, L, order_a, rank, bitmap);
+    }
+    if (phases & SCL_LZ77_PARSE) {
+        const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
+        hipLaunchKernelGGL(lz77_parse, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, st, a->d_win, N, a->d_win_off,
+                           a->d_start, n_streams, L, a->max_matches, order_a, rank, bitmap, a->seq_cap, a->d_lit_count,
+                           a->d_match_len, a->d_match_off, a->d_literals, a->d_n_seq, a->d_n_lit, a->d_status);
+    }
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+extern "C" int scl_lz77_replay_batch(const scl_lz77_replay_args *a, void *stream) {
+    const char *what = "lz77_replay_batch";
+    SCL_REQUIRE(a, "%s: null pointer argument", what);
+    SCL_REQUIRE(a->d_win_off && a->d_have && a->d_n_seq && a->d_lit_off && a->d_n_lit && a->d_out_len && a->d_status &&
+                    (a->total_bytes == 0 || a->d_win) && (a->lit_bytes == 0 || a->d_literals) &&
+                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
+                "%s: null pointer argument", what);
+    SCL_REQUIRE(a->n_streams < (1ull << 32), "%s: a batch holds less than 2^32 streams", what);
+    if (a->n_streams == 0) return SCL_OK;
+    const u32 n_streams = (u32)a->n_streams;
+    const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
+    hipLaunchKernelGGL(lz77_replay, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, (hipStream_t)stream, a->d_win,
+                       a->total_bytes, a->d_win_off, a->d_have, n_streams, a->seq_cap, a->d_lit_count, a->d_match_len,
+                       a->d_match_off, a->d_n_seq, a->d_literals, a->lit_bytes, a->d_lit_off, a->d_n_lit, a->d_out_len,
+                       a->d_status);
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+// ---- one stream in host memory -----------------------------------------------------------------------------------------
+namespace {
+struct LzMeta {  // the small per-stream words of a batch of one, in one allocation
+    u64 win_off[2];
+    u64 lit_off;
+    u32 start, n_seq, n_lit, status, have, out_len;
+};
+}  // namespace
+
+extern "C" int scl_lz77_parse_host(const uint8_t *h_window, uint64_t n, uint64_t start, uint32_t min_match_length,
+                                   uint32_t max_matches, uint32_t *h_lit_count, uint32_t *h_match_len,
+                                   uint32_t *h_match_off, uint64_t seq_cap, uint64_t *n_seq, uint8_t *h_literals,
+                                   uint64_t lit_cap, uint64_t *n_lit) {
+    const char *what = "lz77_parse_host";
+    SCL_REQUIRE(n_seq && n_lit && (h_window || n == 0) && (seq_cap == 0 || (h_lit_count && h_match_len && h_match_off)) &&
+                    (h_literals || lit_cap == 0),
+                "%s: null pointer argument", what);
+    SCL_REQUIRE(min_match_length >= 1 && min_match_length <= 8,
+                "%s: min_match_length %u: an L-gram is one 64-bit key, 1 <= L <= 8", what, min_match_length);
+    SCL_REQUIRE(n < (1ull << 32) && start <= n && seq_cap < (1ull << 32), "%s: start <= n < 2^32 and seq_cap < 2^32", what);
+    SCL_REQUIRE(lit_cap >= n - start, "%s: h_literals must hold the block (%llu bytes)", what,
+                (unsigned long long)(n - start));
+    const u64 scratch_bytes = scl_lz77_scratch_bytes(n, 1);
+    ScratchDev d_win, d_lit, d_seq, d_meta, d_scr;
+    int rc;
+    if ((rc = d_win.alloc(n)) || (rc = d_lit.alloc(n)) || (rc = d_seq.alloc(3 * seq_cap * 4)) ||
+        (rc = d_meta.alloc(sizeof(LzMeta))) || (rc = d_scr.alloc(scratch_bytes)))
+        return rc;
+    LzMeta meta = {};
+    meta.win_off[1] = n;
+    meta.start = (u32)start;
+    if (n) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, n, hipMemcpyHostToDevice));
+    SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
+    LzMeta *dm = (LzMeta *)d_meta.p;
+    scl_lz77_parse_args a = {};
+    a.d_win = (const u8 *)d_win.p;
+    a.d_win_off = dm->win_off;
+    a.d_start = &dm->start;
+    a.n_streams = 1;
+    a.total_bytes = n;
+    a.min_match_length = min_match_length;
+    a.max_matches = max_matches;
+    a.seq_cap = (u32)seq_cap;
+    a.d_lit_count = (u32 *)d_seq.p;
+    a.d_match_len = a.d_lit_count + seq_cap;
+    a.d_match_off = a.d_match_len + seq_cap;
+    a.d_literals = (u8 *)d_lit.p;
+    a.d_n_seq = &dm->n_seq;
+    a.d_n_lit = &dm->n_lit;
+    a.d_status = &dm->status;
+    a.d_scratch = d_scr.p;
+    a.scratch_bytes = scratch_bytes;
+    if ((rc = scl_lz77_parse_batch(&a, nullptr))) return rc;
+    SCL_HIP_TRY(hipDeviceSynchronize());
+    SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+    *n_seq = meta.n_seq;
+    *n_lit = meta.n_lit;
+    if (meta.status) return scl_status_to_error(meta.status, what);
+    if (meta.n_seq) {
+        SCL_HIP_TRY(hipMemcpy(h_lit_count, a.d_lit_count, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+        SCL_HIP_TRY(hipMemcpy(h_match_len, a.d_match_len, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+        SCL_HIP_TRY(hipMemcpy(h_match_off, a.d_match_off, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+    }
+    if (meta.n_lit) SCL_HIP_TRY(hipMemcpy(h_literals, a.d_literals + start, meta.n_lit, hipMemcpyDeviceToHost));
+    return SCL_OK;
+}
+
+extern "C" int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, const uint32_t *h_lit_count,
+                                    const uint32_t *h_match_len, const uint32_t *h_match_off, uint64_t n_seq,
+                                    const uint8_t *h_literals, uint64_t n_lit, uint64_t *out_len) {
+    const char *what = "lz77_replay_host";
+    SCL_REQUIRE(out_len && (h_window || cap == 0) && (n_seq == 0 || (h_lit_count && h_match_len && h_match_off)) &&
+                    (h_literals || n_lit == 0),
+                "%s: null pointer argument", what);
+    SCL_REQUIRE(cap < (1ull << 32) && have <= cap && n_seq < (1ull << 32) && n_lit < (1ull << 32),
+                "%s: have <= cap < 2^32, n_seq and n_lit < 2^32", what);
+    ScratchDev d_win, d_lit, d_seq, d_meta;
+    int rc;
+    if ((rc = d_win.alloc(cap)) || (rc = d_lit.alloc(n_lit)) || (rc = d_seq.alloc(3 * n_seq * 4)) ||
+        (rc = d_meta.alloc(sizeof(LzMeta))))
+        return rc;
+    LzMeta meta = {};
+    meta.win_off[1] = cap;
+    meta.have = (u32)have;
+    meta.n_seq = (u32)n_seq;
+    meta.n_lit = (u32)n_lit;
+    u32 *d_lc = (u32 *)d_seq.p, *d_ml = d_lc + n_seq, *d_mo = d_ml + n_seq;
+    if (have) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, have, hipMemcpyHostToDevice));
+    if (n_lit) SCL_HIP_TRY(hipMemcpy(d_lit.p, h_literals, n_lit, hipMemcpyHostToDevice));
+    if (n_seq) {
+        SCL_HIP_TRY(hipMemcpy(d_lc, h_lit_count, n_seq * 4, hipMemcpyHostToDevice));
+        SCL_HIP_TRY(hipMemcpy(d_ml, h_match_len, n_seq * 4, hipMemcpyHostToDevice));
+        SCL_HIP_TRY(hipMemcpy(d_mo, h_match_off, n_seq * 4, hipMemcpyHostToDevice));
+    }
+    SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
+    LzMeta *dm = (LzMeta *)d_meta.p;
+    scl_lz77_replay_args a = {};
+    a.d_win = (u8 *)d_win.p;
+    a.d_win_off = dm->win_off;
+    a.d_have = &dm->have;
+    a.n_streams = 1;
+    a.total_bytes = cap;
+    a.seq_cap = (u32)n_seq;
+    a.d_lit_count = d_lc;
+    a.d_match_len = d_ml;
+    a.d_match_off = d_mo;
+    a.d_n_seq = &dm->n_seq;
+    a.d_literals = (const u8 *)d_lit.p;
+    a.lit_bytes = n_lit;
+    a.d_lit_off = &dm->lit_off;
+    a.d_n_lit = &dm->n_lit;
+    a.d_out_len = &dm->out_len;
+    a.d_status = &dm->status;
+    if ((rc = scl_lz77_replay_batch(&a, nullptr))) return rc;
+    SCL_HIP_TRY(hipDeviceSynchronize());
+    SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+    *out_len = meta.out_len;
+    if (meta.out_len) SCL_HIP_TRY(hipMemcpy(h_window + have, (u8 *)d_win.p + have, meta.out_len, hipMemcpyDeviceToHost));
+    return scl_status_to_error(meta.status, what);
+}

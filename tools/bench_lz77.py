@@ -1,0 +1,111 @@
+"""Times the LZ77 device layer -- index, parse, replay -- on a batch of streams and on one large stream as a batch of one.
+Recorded, not gated: profiles/lz77_bench.txt.
+
+    python tools/bench_lz77.py [--streams 4096] [--stream-kib 64] [--single-mib 16] [--steps 20] [--warmup 5]
+                               [--single-steps N] [--single-warmup N] [--out FILE]
+
+Data: the first-order Markov source of bench_data.py over 16 symbols, one chain per stream (generated on the device).  The
+single stream is the first --single-mib MiB of the very same bytes, read as ONE window: its parse is one wavefront.
+Kernel time only: HIP events around each call on the current stream, buffers and scratch allocated once.  Every shape is
+verified: the replay of the parse's output must restore the input.
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stanford_compression_library_amd import bench_data  # noqa: E402
+from stanford_compression_library_amd.backend import lib  # noqa: E402
+from stanford_compression_library_amd.backend import lz77  # noqa: E402
+
+L, M = 6, 64
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return ms
+
+
+def run_shape(name, win, n_streams, stream_len, steps, warmup, dev):
+    total = n_streams * stream_len
+    win_off = torch.arange(n_streams + 1, dtype=torch.int64, device=dev) * stream_len
+    start = torch.zeros(n_streams, dtype=torch.int32, device=dev)
+    seq_cap = lz77.default_seq_cap(stream_len, L)
+    scratch = torch.empty(lz77.scratch_bytes(total, n_streams), dtype=torch.uint8, device=dev)
+    res = lz77.parse_batch(win, win_off, start, L, M, seq_cap, scratch=scratch)
+    out = torch.empty_like(win)
+    have = torch.zeros(n_streams, dtype=torch.int32, device=dev)
+
+    def replay():
+        return lz77.replay_batch(out, win_off, have, res.literal_count, res.match_length, res.match_offset, res.n_seq,
+                                 res.literals, res.lit_off, res.n_lit)
+
+    phases = (("index", lambda: lz77.parse_batch(win, win_off, start, L, M, seq_cap, scratch=scratch, out=res,
+                                                  phases=lib.LZ77_INDEX)),
+              ("parse", lambda: lz77.parse_batch(win, win_off, start, L, M, seq_cap, scratch=scratch, out=res,
+                                                  phases=lib.LZ77_PARSE)),
+              ("replay", replay))
+    lines = []
+    for what, fn in phases:
+        ms = timed(fn, steps, warmup)
+        med = statistics.median(ms)
+        lines.append(f"{name:22s} {what:6s}: median {med:10.3f} ms  min {min(ms):10.3f}  max {max(ms):10.3f}  "
+                     f"{total / med / 1e6:8.3f} GB/s of input")
+    out.fill_(0)
+    out_len, status = replay()
+    torch.cuda.synchronize()
+    ok = bool((res.status == 0).all() and (status == 0).all() and (out_len == stream_len).all() and torch.equal(out, win))
+    n_seq, n_lit = int(res.n_seq.to(torch.int64).sum()), int(res.n_lit.to(torch.int64).sum())
+    lines.append(f"{name:22s} {n_seq} sequences, {n_lit} literals ({total / max(n_seq, 1):.1f} input bytes per sequence), "
+                 f"{steps} timed steps after {warmup}, round trip {'ok' if ok else 'FAILED'}")
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=4096)
+    ap.add_argument("--stream-kib", type=int, default=64)
+    ap.add_argument("--single-mib", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--single-steps", type=int, default=None)
+    ap.add_argument("--single-warmup", type=int, default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lib.require_device()
+    dev = torch.device("cuda:0")
+    stream_len = args.stream_kib << 10
+    single_len = args.single_mib << 20
+    assert single_len <= args.streams * stream_len
+    win = bench_data.markov1_chunks_device(16, args.streams, stream_len, 77, dev).reshape(-1)
+    lines = [f"lz77 bench: min_match_length {L}, max_num_matches_considered {M}, first-order Markov source over 16 symbols, "
+             f"HIP events, {torch.cuda.get_device_name(0)}", f"kernels: {', '.join(lz77.kernel_names())}"]
+    print("\n".join(lines), flush=True)
+    lines += run_shape(f"{args.streams} x {args.stream_kib} KiB", win, args.streams, stream_len, args.steps, args.warmup, dev)
+    print("\n".join(lines[2:]), flush=True)
+    n_batch = len(lines)
+    lines += run_shape(f"1 x {args.single_mib} MiB", win[:single_len].contiguous(), 1, single_len,
+                       args.steps if args.single_steps is None else args.single_steps,
+                       args.warmup if args.single_warmup is None else args.single_warmup, dev)
+    print("\n".join(lines[n_batch:]), flush=True)
+    text = "\n".join(lines)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
