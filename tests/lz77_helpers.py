@@ -10,6 +10,7 @@ p + l <= n; the longest wins, the newest on ties.  From pos = s: the first p >= 
 """
 import bisect
 import functools
+import types
 
 import numpy as np
 
@@ -175,12 +176,15 @@ def ragged_batch(n_streams=130, seed=5):
     return pack_windows(windows, start)
 
 
-def pack_windows(windows, start):
+def pack_windows(windows, start, lead=None, tail=None):
     """the windows back to back behind ONE filler byte, so that the first offset is odd and, with ragged lengths, so are
-    many of the others: window s = buf[win_off[s]:win_off[s + 1]]"""
+    many of the others: window s = buf[win_off[s]:win_off[s + 1]].  `lead` replaces the filler byte by bytes of the
+    caller's, `tail` adds bytes behind the last window: both belong to no stream."""
+    lead = np.full(1, 0xA5, np.uint8) if lead is None else np.asarray(lead, np.uint8)
+    tail = np.zeros(0, np.uint8) if tail is None else np.asarray(tail, np.uint8)
     lens = np.array([len(w) for w in windows], np.int64)
-    win_off = 1 + np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    buf = np.concatenate([np.full(1, 0xA5, np.uint8)] + [np.asarray(w, np.uint8) for w in windows])
+    win_off = len(lead) + np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    buf = np.concatenate([lead] + [np.asarray(w, np.uint8) for w in windows] + [tail])
     return dict(buf=buf, win_off=win_off, start=np.array(start, np.int32), windows=[np.asarray(w, np.uint8) for w in windows])
 
 
@@ -189,3 +193,174 @@ def ragged_reference(L, M):
     """parse_restated of every stream of ragged_batch(): [(sequences, literals)]"""
     b = ragged_batch()
     return [parse_restated(w, int(s), L, M) for w, s in zip(b["windows"], b["start"])]
+
+
+# ---- the batch past every limit of the index ---------------------------------------------------------------------------------
+TILED_STREAMS, TILED_TEMPLATES = 70000, 61
+
+
+@functools.lru_cache(maxsize=None)
+def tiled_batch(n_streams=TILED_STREAMS, seed=11):
+    """n_streams short streams drawn from K = 61 templates of 97..160 bytes over alphabets of 2, 4 and 256 symbols; every
+    fifth template is a period of 3..6 bytes repeated (all candidates tie at "runs to the end": the newest wins only if
+    the sort is stable).  Stream s is template ids[s]; every block starts at 0.  ids = s % K, except that every third
+    group of four streams is one template four times: different AND identical neighbours.  With 70 000 streams the batch
+    has more than 65 536 streams (three stream-number passes of the sort) and more than 8 388 608 bytes (more than 256 scan
+    blocks).  The restatement is needed for the K templates only: tiled_reference().
+    -> pack_windows' dict + templates = [uint8 arrays], ids [n_streams]"""
+    rng = np.random.default_rng(seed)
+    K = TILED_TEMPLATES
+    templates = []
+    for t in range(K):
+        n, k = int(rng.integers(97, 161)), (2, 4, 256)[t % 3]
+        w = rng.integers(0, k, n).astype(np.uint8)
+        if t % 5 == 4:
+            w = np.resize(w[: int(rng.integers(3, 7))], n)
+        templates.append(w)
+    s = np.arange(n_streams)
+    ids = np.where((s // 4) % 3 == 0, (s // 4) % K, s % K)
+    batch = pack_windows([templates[t] for t in ids.tolist()], np.zeros(n_streams, np.int32))
+    return dict(batch, templates=templates, ids=ids)
+
+
+@functools.lru_cache(maxsize=None)
+def tiled_reference(L, M):
+    """parse_restated of the K templates of tiled_batch(): [(sequences, literals)]; stream s has entry ids[s]"""
+    return [parse_restated(w, 0, L, M) for w in tiled_batch()["templates"]]
+
+
+# ---- the index, restated ---------------------------------------------------------------------------------------------------------
+def _round_up(x, to):
+    return (x + to - 1) // to * to
+
+
+def index_shape(N):
+    """The scratch of one parse call over N bytes, restated from csrc/scl_lz77_internal.h: a sort tile is 4096 positions, the
+    tile histograms are 256 x tiles counts, a scan block is 2048 of them, the bitmap has a 64-bit word per 64 positions;
+    the parts order_a, order_b, rank (4 N bytes each), bitmap, hist, block_sums follow each other, each rounded up to 256
+    bytes, an empty one taking 256.
+    -> namespace(n_tiles, n_hist, n_scan_blocks, n_words, order_a, order_b, rank, bitmap, hist, block_sums, total)"""
+    sh = types.SimpleNamespace(n_tiles=(N + 4095) // 4096)
+    sh.n_hist = 256 * sh.n_tiles
+    sh.n_scan_blocks = (sh.n_hist + 2047) // 2048
+    sh.n_words = (N + 63) // 64
+    at = 0
+    for name, size in (("order_a", 4 * N), ("order_b", 4 * N), ("rank", 4 * N), ("bitmap", 8 * sh.n_words),
+                       ("hist", 4 * sh.n_hist), ("block_sums", 4 * sh.n_scan_blocks)):
+        setattr(sh, name, at)
+        at += _round_up(max(size, 1), 256)
+    sh.total = at
+    return sh
+
+
+def index_restated(buf, win_off, L):
+    """The definition of the match index of a batch -> (order [N] int64, rank [N] int64, bitmap: uint64
+    words).  order is the STABLE sort of all N positions by (stream of v, L-gram at v): the gram is the L bytes from v on
+    as a little-endian number, read as they lie -- into the next stream, and as 0 past the buffer; the stream of a position
+    outside every stream is n_streams.  A batch of one stream is sorted by the gram alone (there is no stream-number pass
+    for it).  rank is the inverse of order.  Bit g of the bitmap: g + L <= end of g's stream (the end clamped to N), and
+    the oldest equal gram of that stream lies at q <= g - L."""
+    buf, win_off = np.asarray(buf, np.uint8), np.asarray(win_off, np.int64)
+    N, n_streams = len(buf), len(win_off) - 1
+    v = np.arange(N, dtype=np.int64)
+    stream = np.searchsorted(win_off, v, side="right") - 1  # the last s with win_off[s] <= v, of all n_streams + 1 entries
+    stream[(stream < 0) | (stream >= n_streams)] = n_streams
+    padded = np.concatenate([buf, np.zeros(L, np.uint8)]).astype(np.uint64)
+    gram = np.zeros(N, np.uint64)
+    for j in range(L):
+        gram |= padded[j: j + N] << np.uint64(8 * j)
+    order = np.lexsort((gram, stream)) if n_streams > 1 else np.argsort(gram, kind="stable")
+    order = order.astype(np.int64)
+    rank = np.empty(N, np.int64)
+    rank[order] = v
+    # the groups of equal (stream, gram) along order[]: the first entry of a group is its oldest position
+    ss, gg = stream[order], gram[order]
+    first = np.ones(N, bool)
+    first[1:] = (ss[1:] != ss[:-1]) | (gg[1:] != gg[:-1])
+    oldest = order[np.maximum.accumulate(np.where(first, v, 0))] if N else order
+    end = np.minimum(np.append(win_off[1:], 0)[ss], N)
+    bit = np.zeros(_round_up(N, 64), bool)
+    bit[order] = (ss < n_streams) & (order + L <= end) & (oldest + L <= order)
+    return order, rank, np.packbits(bit, bitorder="little").view(np.uint64)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_batch(n_streams, seed=23):
+    """n_streams streams of 40..90 bytes over 2 to 4 symbols between bytes that belong to no stream but look like stream
+    content: a lead of 40 bytes that copies the start of stream 0 and a tail of 40 bytes that copies the start of the last
+    stream that has bytes.  Every third stream is an identical copy of the one in front of it; from 8 streams on, three
+    streams in the middle and the last three are empty.  Histories of 0 and 7 bytes.
+    -> pack_windows' dict; the buffer is 40 bytes longer than win_off[-1]"""
+    rng = np.random.default_rng(seed + n_streams)
+    empty = set()
+    if n_streams >= 8:
+        mid = n_streams // 2
+        empty = {mid, mid + 1, mid + 2, n_streams - 3, n_streams - 2, n_streams - 1}
+    windows = []
+    for s in range(n_streams):
+        if s in empty:
+            windows.append(np.zeros(0, np.uint8))
+        elif s % 3 == 2 and len(windows[-1]):
+            windows.append(windows[-1].copy())
+        else:
+            windows.append(rng.integers(0, 2 + s % 3, int(rng.integers(40, 91))).astype(np.uint8))
+    start = [min((0, 7)[s % 2], len(w)) for s, w in enumerate(windows)]
+    last = [w for w in windows if len(w)][-1]
+    return pack_windows(windows, start, lead=windows[0][:40], tail=last[:40])
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(n_streams, L, M):
+    b = edge_batch(n_streams)
+    return [parse_restated(w, int(s), L, M) for w, s in zip(b["windows"], b["start"])]
+
+
+def parse_with_order(buf, win_off, start, s, L, M, order):
+    """What the device parse makes of stream s given ANY permutation `order` of the positions as its index (rank = the
+    inverse, the bitmap by the kernel's own looks at the L entries in front of rank[g]).  It takes the entries in front of
+    rank[p] newest first, re-checks stream and gram of each, scores them in groups of 64 and keeps the longest, the first
+    on ties: with the true index that is the rule; with a wrong one it is still a valid parse -- of other matches.
+    -> (sequences [k, 3], literals), as parse_restated"""
+    w, order = bytes(np.asarray(buf, np.uint8)), np.asarray(order).tolist()
+    rank = {v: i for i, v in enumerate(order)}
+    base, end = int(win_off[s]), int(win_off[s + 1])
+
+    def ok(c, g):
+        return base <= c and c + L <= g and w[c:c + L] == w[g:g + L]
+
+    def has_candidate(g):
+        for k in range(1, min(L, rank[g]) + 1):
+            c = order[rank[g] - k]
+            if c < base or c >= g or w[c:c + L] != w[g:g + L]:
+                return False
+            if c + L <= g:
+                return True
+        return False
+
+    seqs, lits, pos = [], bytearray(), base + int(start[s])
+    while True:
+        p = next((g for g in range(pos, end - L + 1) if has_candidate(g)), None)
+        if p is None:
+            break
+        i = rank[p]
+        skip = sum(1 for j in range(min(L - 1, i)) if base <= order[i - 1 - j] < p < order[i - 1 - j] + L
+                   and w[order[i - 1 - j]:order[i - 1 - j] + L] == w[p:p + L])
+        best_len, best_q, group = 0, -1, 0
+        while True:
+            lanes = [order[i - 1 - skip - nth] for nth in range(group, group + 64) if skip + nth < i and (M == 0 or nth < M)]
+            valid = [ok(c, p) for c in lanes]
+            if not valid or not valid[0]:
+                break
+            for c in (c for c, v in zip(lanes, valid) if v):
+                length = _common_prefix(w, c, p, end - p)
+                if length > best_len:
+                    best_len, best_q = length, c
+            if len(lanes) < 64 or not all(valid) or (M and group + 64 >= M):
+                break
+            group += 64
+        assert best_len, "the bitmap promised a candidate"
+        seqs.append((p - pos, best_len, p - best_q))
+        lits += w[pos:p]
+        pos = p + best_len
+    lits += w[pos:end]
+    return np.array(seqs, np.int64).reshape(-1, 3), np.frombuffer(bytes(lits), np.uint8)

@@ -144,10 +144,11 @@ def no_repeat_bytes(n):
     return np.stack([np.full(c.size, 255), c % 250, c // 250], axis=1).astype(np.uint8).reshape(-1)[:n]
 
 
-@pytest.mark.parametrize("gap", [4095, 4096, 4097])
+@pytest.mark.parametrize("gap", [4095, 4096, 4097, 3 * 4096 + 17])
 def test_bitmap_skip_lands_on_the_first_repeat(gap, dev):
     """`gap` positions without a candidate, then the first L-gram of the stream again: the first sequence's literal_count is
-    exactly `gap`.  4096 positions are one step of the skip; the stream starts at an odd offset of the batch."""
+    exactly `gap`.  4096 positions are one step of the skip; the stream starts at an odd offset of the batch, so the skip
+    starts in the middle of a bitmap word, and the longest gap takes four steps of lz_next_bit."""
     L, rng = 6, np.random.default_rng(gap)
     body = no_repeat_bytes(gap)
     tail = rng.integers(0, 250, 40).astype(np.uint8)

@@ -1,13 +1,17 @@
 """LZ77, host side (no GPU): the parse rule and replay as restated in lz77_helpers reproduce the reference's sequences and
 literals (goldens); the integer coders and the streams coder reproduce its bits, with the prefix-code device calls replaced
-by their definition; the C ABI refuses bad arguments before it touches a device."""
+by their definition; the C ABI refuses bad arguments before it touches a device.  The fixtures of the GPU limits tests
+(tests/test_gpu_lz77_limits.py) are checked here: the restated scratch layout against the library's, the restated index
+against values written out by hand, the large batch against the conditions it exists for."""
 import ctypes
+import itertools
 
 import numpy as np
 import pytest
 
 from conftest import golden_ids
-from lz77_helpers import (ST_CAPACITY, ST_STATE, ST_TRUNCATED, golden_blocks, goldens, parse_restated, replay_restated,
+from lz77_helpers import (ST_CAPACITY, ST_STATE, ST_TRUNCATED, edge_batch, golden_blocks, goldens, index_restated, index_shape,
+                          parse_restated, parse_with_order, replay_restated, tiled_batch, tiled_reference,
                           use_host_prefix_coder, with_garbage)
 from stanford_compression_library_amd.backend import lib as backend_lib
 from stanford_compression_library_amd.backend import lz77 as dev_lz77
@@ -192,3 +196,98 @@ def test_parameter_validation_needs_no_gpu():
     assert L.scl_lz77_replay_host(buf8, 4, 16, None, buf32, buf32, 1, buf8, 1, ctypes.byref(n_out)) == E
     assert L.scl_lz77_replay_host(buf8, 4, 16, buf32, buf32, buf32, 1, buf8, 1, None) == E
     assert backend_lib.last_error().startswith("lz77_replay_host:")
+
+
+# ---- the fixtures of the GPU limits tests ----------------------------------------------------------------------------------------
+def test_restated_scratch_layout_equals_the_library():
+    """pins index_shape to scl_lz77_internal.h: the white-box GPU test reads the scratch at these offsets"""
+    L = backend_lib.load()
+    for n in (0, 1, 63, 64, 65, 4095, 4096, 4097, 8388608, 8388609, len(tiled_batch()["buf"])):
+        assert index_shape(n).total == L.scl_lz77_scratch_bytes(n, 1), n
+    sh = index_shape(4097)
+    assert (sh.n_tiles, sh.n_hist, sh.n_scan_blocks, sh.n_words) == (2, 512, 1, 65)
+    assert (sh.order_a, sh.order_b, sh.rank, sh.bitmap) == (0, 16640, 33280, 49920)
+    assert (sh.hist, sh.block_sums, sh.total) == (49920 + 768, 49920 + 768 + 2048, 49920 + 768 + 2048 + 256)
+    assert index_shape(0).total == 6 * 256
+    assert index_shape(8388608).n_scan_blocks == 256 and index_shape(8388609).n_scan_blocks == 257
+
+
+def test_the_tiled_batch_reaches_what_it_is_for():
+    b = tiled_batch()
+    ids, win_off, buf = b["ids"], b["win_off"], b["buf"]
+    n_streams = len(b["windows"])
+    assert n_streams > 65536 and index_shape(len(buf)).n_scan_blocks > 256 and win_off[-1] == len(buf)
+    assert len(b["templates"]) == 61 and all(97 <= len(t) <= 160 for t in b["templates"])
+    assert sorted(set(ids.tolist())) == list(range(61))
+    same = ids[1:] == ids[:-1]
+    assert same.sum() > 10000 and (~same).sum() > 10000  # identical and different neighbours
+    periodic = [t for i, t in enumerate(b["templates"]) if i % 5 == 4]
+    assert all(any(np.array_equal(t, np.resize(t[:p], len(t))) for p in (3, 4, 5, 6)) for t in periodic)
+    # the broadcast reference is the restatement of what actually lies in the buffer
+    for L, M in ((3, 0), (6, 64)):
+        ref = tiled_reference(L, M)
+        assert any(len(seq) for seq, _ in ref)
+        for s in np.random.default_rng(L).integers(0, n_streams, 150).tolist() + [0, n_streams - 1]:
+            seq, lit = parse_restated(buf[win_off[s]: win_off[s + 1]], 0, L, M)
+            assert seq.tolist() == ref[ids[s]][0].tolist() and lit.tolist() == ref[ids[s]][1].tolist(), s
+
+
+def test_the_edge_batches_have_their_edges():
+    for n in (1, 2, 255, 256, 257):
+        b = edge_batch(n)
+        lens = np.diff(b["win_off"])
+        assert len(lens) == n and b["win_off"][0] == 40 and len(b["buf"]) == b["win_off"][-1] + 40
+        assert b["buf"][:40].tolist() == b["windows"][0][:40].tolist()
+        if n >= 8:
+            assert (lens[-3:] == 0).all() and (lens[n // 2: n // 2 + 3] == 0).all() and lens[n // 2 - 1] and lens[n // 2 + 3]
+            assert sum(np.array_equal(a, c) and len(a) > 0 for a, c in zip(b["windows"], b["windows"][1:])) >= n // 4
+
+
+def test_index_restatement_on_a_batch_written_out_by_hand():
+    """L = 2.  A lead (1 2) that copies the start of stream 0, stream 0 = 1 2 1 2 1, stream 1 = 5 5 5 5, a tail 5 5.
+    Grams as numbers (first byte + 256 * second): 1 2 -> 513, 2 1 -> 258, 1 5 -> 1281 (the last position of stream 0 reads
+    into stream 1), 5 5 -> 1285 (so does the last one of stream 1, into the tail), 5 0 -> 5 (past the buffer)."""
+    buf = np.array([1, 2, 1, 2, 1, 2, 1, 5, 5, 5, 5, 5, 5], np.uint8)
+    order, rank, bitmap = index_restated(buf, [2, 7, 11], 2)
+    #                      stream 0: 258 258 513 513 1281 | stream 1: 1285 x 4 | no stream: 5, 258, 513, 1285
+    assert order.tolist() == [3, 5, 2, 4, 6, 7, 8, 9, 10, 12, 1, 0, 11]
+    assert rank.tolist() == [11, 10, 2, 0, 3, 1, 4, 5, 6, 7, 8, 12, 9]
+    # 4 and 5 repeat 2 and 3; 6 has no whole gram in its stream; 8 overlaps 7 (q = p - 1), 9 has 7 at q = p - L, 10 has
+    # no whole gram; the lead's 1 2 is no candidate for position 2, nor is anything a candidate for the tail
+    assert bitmap.tolist() == [(1 << 4) | (1 << 5) | (1 << 9)]
+    # one stream: sorted by the gram alone, the lead among the stream's own positions; still no bit from the lead
+    order, rank, bitmap = index_restated(buf[:7], [2, 7], 2)
+    assert order.tolist() == [6, 1, 3, 5, 0, 2, 4] and rank[order].tolist() == list(range(7))
+    assert bitmap.tolist() == [(1 << 4) | (1 << 5)]
+    order, rank, bitmap = index_restated(buf[:0], [0, 0], 2)
+    assert order.size == 0 and rank.size == 0 and bitmap.size == 0
+
+
+def test_a_round_trip_cannot_see_a_wrong_index_and_the_comparison_can():
+    """Why the GPU tests compare with the rule.  parse_with_order is the device parse on any permutation: with the index of
+    the definition it gives the rule's sequences; with a planted fault -- equal grams in reverse order, an unstable sort --
+    it gives other sequences, which replay into the same bytes."""
+    rng = np.random.default_rng(2)
+    windows = [np.resize(np.array([3, 1, 2], np.uint8), 120), rng.integers(0, 2, 150).astype(np.uint8),
+               np.resize(np.array([3, 1, 2], np.uint8), 120), rng.integers(0, 4, 90).astype(np.uint8)]
+    start = np.array([0, 10, 0, 0], np.int32)
+    buf = np.concatenate([windows[0][:40]] + windows + [windows[3][:40]])  # a lead and a tail that look like stream content
+    win_off = 40 + np.concatenate([[0], np.cumsum([len(w) for w in windows])])
+    for L, M in ((3, 0), (3, 2), (1, 64), (6, 1)):
+        order, _, _ = index_restated(buf, win_off, L)
+        for s, w in enumerate(windows):
+            seq, lit = parse_with_order(buf, win_off, start, s, L, M, order)
+            want = parse_restated(w, int(start[s]), L, M)
+            assert seq.tolist() == want[0].tolist() and lit.tolist() == want[1].tolist(), (L, M, s)
+    # the fault: every group of equal (stream, gram) reversed
+    L, M = 3, 0
+    order, _, _ = index_restated(buf, win_off, L)
+    padded = np.concatenate([buf, np.zeros(L, np.uint8)])
+    same = lambda v: (int(np.searchsorted(win_off, v, side="right")), bytes(padded[v:v + L]))  # noqa: E731
+    wrong = np.array([v for _, group in itertools.groupby(order.tolist(), key=same) for v in list(group)[::-1]])
+    assert sorted(wrong.tolist()) == list(range(len(buf))) and wrong.tolist() != order.tolist()
+    seq, lit = parse_with_order(buf, win_off, start, 0, L, M, wrong)
+    want_seq, want_lit = parse_restated(windows[0], 0, L, M)
+    assert seq.tolist() != want_seq.tolist(), "the comparison with the rule sees the fault"
+    back, status = replay_restated(windows[0][:0], seq, lit)
+    assert status == 0 and back.tolist() == windows[0].tolist(), "and the round trip does not"

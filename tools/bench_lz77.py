@@ -7,7 +7,9 @@ Recorded, not gated: profiles/lz77_bench.txt.
 Data: the first-order Markov source of bench_data.py over 16 symbols, one chain per stream (generated on the device).  The
 single stream is the first --single-mib MiB of the very same bytes, read as ONE window: its parse is one wavefront.
 Kernel time only: HIP events around each call on the current stream, buffers and scratch allocated once.  Every shape is
-verified: the replay of the parse's output must restore the input.
+verified: the replay of the parse's output must restore the input.  That round trip checks parse and replay, NOT the index:
+the parse re-checks every entry it reads from order[], so a misplaced entry still gives a valid parse, only with other
+matches.  The index is compared with its definition, and the parse with the restated rule, in tests/test_gpu_lz77_limits.py.
 """
 import argparse
 import os
