@@ -398,7 +398,8 @@ int scl_prefix_decode_block_host_u16(const scl_prefix_model *m, const uint8_t *h
  * The LZ layer of the reference's LZ77 coder, for a batch of independent streams, one wavefront per stream:
  *   scl_lz77_parse_batch   <->  LZ77Encoder.lz77_parse_and_generate_sequences   scl/compressors/lz77.py:525-603
  *   scl_lz77_replay_batch  <->  LZ77Decoder.execute_lz77_sequences              scl/compressors/lz77.py:640-665
- * (the entropy stage above it is host code over the prefix-code entry points).  A stream's WINDOW is everything its coder
+ * (the entropy stage above it: host code over the prefix-code entry points in the classes, the scl_lz77_entropy_* calls
+ * below for batches).  A stream's WINDOW is everything its coder
  * has seen, the current block included; the windows of a batch lie one after another in d_win, window s = bytes
  * [d_win_off[s], d_win_off[s + 1]) (any offsets: windows need no alignment), and positions inside a window are 32-bit.
  *   parse : the block of stream s is its window from d_start[s] on.  With L = min_match_length (1..8: an L-gram is one
@@ -469,6 +470,87 @@ int scl_lz77_parse_host(const uint8_t *h_window, uint64_t n, uint64_t start, uin
 int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, const uint32_t *h_lit_count,
                          const uint32_t *h_match_len, const uint32_t *h_match_off, uint64_t n_seq,
                          const uint8_t *h_literals, uint64_t n_lit, uint64_t *out_len);
+
+/* ---- LZ77: the entropy stage, sequences and literals <-> block bits (scl_lz77_entropy.hip; added to ABI 8 as above) -------
+ *   scl_lz77_entropy_encode_batch  <->  LZ77StreamsEncoder.encode_block   scl/compressors/lz77.py:301-361
+ *   scl_lz77_entropy_decode_batch  <->  LZ77StreamsDecoder.decode_block   scl/compressors/lz77.py:364-428
+ * One wavefront per stream.  A stream's bits are four fields in this order: literal counts, match lengths, match offsets,
+ * literals.  A sequence field is log-scale binned with o = binned_offset (0..32; the reference's default is 16): v < o is its
+ * own bin, otherwise the bin is o + floor(log2(v - o + 1)) and the bits of v - o + 1 below its leading one follow as a
+ * residual; the alphabet is 32 + o bins.  Each field is
+ *     [32-bit counts_size][Elias-delta code of every count of the alphabet][32-bit values_size][Huffman codewords]
+ * followed by its residual bits; the literals have the same shape over 256 symbols and no residuals.  A field without values
+ * is one zero header, an empty stream 128 zero bits.  The Huffman code is the reference's tree over the field's own counts
+ * (probabilities double(count) / double(total), Python's heapq step for step: scl_lz77_huffman_from_counts_host runs the
+ * very function the kernels run).  Sequence rows, d_n_seq, d_literals / d_lit_off / d_n_lit are those of
+ * scl_lz77_parse_args / scl_lz77_replay_args.
+ *   encode: stream s goes to slot s of out_stride bytes (a positive multiple of 16, d_out 16-byte aligned), front to back:
+ *           d_bit_off[s] = 8*s*out_stride, d_nbits[s] = its length, and every bit of the slot up to the next 32-bit word
+ *           boundary behind the stream is defined.  All sizes are known before a bit is stored, so a stream with a non-zero
+ *           status stores NOTHING: SCL_ST_CAPACITY = the slot is too small (d_nbits[s] still reports the length needed) or
+ *           the stream has 2^32 bits or more (d_nbits[s] = 2^32 - 1); SCL_ST_SIZE = a codeword longer than 32 bits (a field
+ *           of at least 14 930 351 values with Fibonacci counts), d_n_seq[s] > seq_cap or a literal range outside
+ *           lit_bytes; SCL_ST_SYMBOL = a value without a bin (binned_offset 0 and the value 2^32 - 1: the reference raises
+ *           "too large").  d_nbits[s] = 0 for the last two.
+ *   decode: stream s is the d_in_nbits[s] bits from absolute bit d_bit_off[s] of d_in, at any alignment; bits behind the
+ *           block are not an error.  The values go to row s (seq_cap entries) of the three arrays and to the literal range
+ *           [d_lit_off[s], d_lit_off[s] + d_lit_cap[s]) of d_literals; d_n_seq[s] = the count of the shortest sequence
+ *           field, d_n_lit[s] = the literals, d_consumed[s] = LZ77StreamsDecoder.decode_block's num_bits_consumed.  The
+ *           stream stops at its first fault, and what its rows (up to seq_cap entries) and its literal range then hold is
+ *           undefined -- a field may be left half turned from bins into values; d_n_seq[s] counts whole sequences of
+ *           the fields decoded before the fault, 0 unless all three were.  SCL_ST_TRUNCATED = a header or a section reaches past d_in_nbits[s];
+ *           SCL_ST_STATE = the counts section is not used up exactly, holds fewer counts than the alphabet (more are
+ *           ignored), only zeros, or a count of 2^32 or more; a codeword cut by the end of its section or a bit into the
+ *           missing child of the one-symbol code; a value that no 32-bit field holds; field counts that differ;
+ *           SCL_ST_CAPACITY = more values than a row or a literal range holds (nothing is stored past it); SCL_ST_SIZE = a
+ *           code above 32 bits, or an input or literal range outside its buffer.
+ * Nothing outside a stream's own slot / input bits / rows / literal range is read or written on any input; no kernel uses
+ * device scratch.  Both calls are asynchronous on `stream`.  SCL_E_PARAM before any device call: a null pointer,
+ * binned_offset above 32, n_streams >= 2^32, a bad out_stride or a misaligned d_out. */
+typedef struct scl_lz77_entropy_encode_args {
+    uint64_t n_streams;
+    uint32_t seq_cap, binned_offset;
+    const uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_streams * seq_cap] each */
+    const uint32_t *d_n_seq;
+    const uint8_t *d_literals;
+    uint64_t lit_bytes;
+    const uint64_t *d_lit_off; /* [n_streams] */
+    const uint32_t *d_n_lit;
+    uint8_t *d_out;            /* [n_streams * out_stride] */
+    uint64_t out_stride;
+    uint64_t *d_bit_off;       /* [n_streams] each */
+    uint32_t *d_nbits, *d_status;
+} scl_lz77_entropy_encode_args;
+
+typedef struct scl_lz77_entropy_decode_args {
+    const uint8_t *d_in;
+    uint64_t in_size_bytes;
+    const uint64_t *d_bit_off; /* [n_streams] */
+    const uint32_t *d_in_nbits;
+    uint64_t n_streams;
+    uint32_t seq_cap, binned_offset;
+    uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_streams * seq_cap] each */
+    uint32_t *d_n_seq;
+    uint8_t *d_literals;
+    uint64_t lit_bytes;
+    const uint64_t *d_lit_off; /* [n_streams] */
+    const uint32_t *d_lit_cap;
+    uint32_t *d_n_lit, *d_consumed, *d_status;
+} scl_lz77_entropy_decode_args;
+
+int scl_lz77_entropy_encode_batch(const scl_lz77_entropy_encode_args *args, void *stream);
+int scl_lz77_entropy_decode_batch(const scl_lz77_entropy_decode_args *args, void *stream);
+/* a multiple of 128 that holds any stream of at most max_n_seq sequences and max_n_lit literals: the headers, the counts
+   at 43 bits each, 31 residual bits per sequence value, and for the codewords of a field of n values n * (ceil(log2 K) + 1)
+   bits IN TOTAL.  That is a bound on the field, not on a codeword (one codeword may have 32 bits): a Huffman code of the
+   values' own counts spends less than n * (H + 1) bits on them, H their empirical entropy, and H <= log2 K. */
+uint64_t scl_lz77_entropy_slot_bytes(uint64_t max_n_seq, uint64_t max_n_lit, uint32_t binned_offset);
+/* as scl_lz77_kernel_names */
+int scl_lz77_entropy_kernel_names(char *enc, char *dec, uint64_t cap);
+/* The tree builder of the two kernels, on the host (no device): code[i] / len[i] = the codeword of symbol i, most
+   significant bit first in the low len[i] bits, 0 / 0 for a symbol without a count.  SCL_E_PARAM: K outside 1..256, a count
+   of 2^32 or more, no count at all, a codeword longer than 32 bits. */
+int scl_lz77_huffman_from_counts_host(const uint64_t *counts, uint32_t K, uint32_t *code, uint8_t *len);
 
 /* ---- stream compaction / framing ------------------------------------------------------------ */
 #define SCL_COMPACT_DENSE 0  /* stream c left-aligned at byte d_out_byte_offset[c], zero tail   */

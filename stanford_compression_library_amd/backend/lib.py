@@ -68,6 +68,24 @@ class Lz77ReplayArgs(C.Structure):
                 ("d_n_lit", C.c_void_p), ("d_out_len", C.c_void_p), ("d_status", C.c_void_p)]
 
 
+class Lz77EntropyEncodeArgs(C.Structure):
+    """scl_lz77_entropy_encode_args"""
+    _fields_ = [("n_streams", C.c_uint64), ("seq_cap", C.c_uint32), ("binned_offset", C.c_uint32),
+                ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p),
+                ("d_n_seq", C.c_void_p), ("d_literals", C.c_void_p), ("lit_bytes", C.c_uint64), ("d_lit_off", C.c_void_p),
+                ("d_n_lit", C.c_void_p), ("d_out", C.c_void_p), ("out_stride", C.c_uint64), ("d_bit_off", C.c_void_p),
+                ("d_nbits", C.c_void_p), ("d_status", C.c_void_p)]
+
+
+class Lz77EntropyDecodeArgs(C.Structure):
+    """scl_lz77_entropy_decode_args"""
+    _fields_ = [("d_in", C.c_void_p), ("in_size_bytes", C.c_uint64), ("d_bit_off", C.c_void_p), ("d_in_nbits", C.c_void_p),
+                ("n_streams", C.c_uint64), ("seq_cap", C.c_uint32), ("binned_offset", C.c_uint32),
+                ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p),
+                ("d_n_seq", C.c_void_p), ("d_literals", C.c_void_p), ("lit_bytes", C.c_uint64), ("d_lit_off", C.c_void_p),
+                ("d_lit_cap", C.c_void_p), ("d_n_lit", C.c_void_p), ("d_consumed", C.c_void_p), ("d_status", C.c_void_p)]
+
+
 LZ77_INDEX, LZ77_PARSE = 1, 2
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -135,6 +153,12 @@ _SIGNATURES = {
     "scl_lz77_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
     "scl_lz77_parse_host": (_int, [_u8p, _u64, _u64, _u32, _u32, _u32p, _u32p, _u32p, _u64, _u64p, _u8p, _u64, _u64p]),
     "scl_lz77_replay_host": (_int, [_u8p, _u64, _u64, _u32p, _u32p, _u32p, _u64, _u8p, _u64, _u64p]),
+    # LZ77: the entropy stage (scl_lz77_entropy.hip)
+    "scl_lz77_entropy_encode_batch": (_int, [C.POINTER(Lz77EntropyEncodeArgs), _vp]),
+    "scl_lz77_entropy_decode_batch": (_int, [C.POINTER(Lz77EntropyDecodeArgs), _vp]),
+    "scl_lz77_entropy_slot_bytes": (_u64, [_u64, _u64, _u32]),
+    "scl_lz77_entropy_kernel_names": (_int, [C.c_char_p, C.c_char_p, _u64]),
+    "scl_lz77_huffman_from_counts_host": (_int, [_u64p, _u32, _u32p, _u8p]),
     "scl_aec_model_create": (_int, [_int, _u32p, _u32, _u32, _u64, _u32, _u32, C.POINTER(_vp)]),
     "scl_aec_model_destroy": (None, [_vp]),
     "scl_aec_slot_bytes": (_u64, [_vp, _u64]),

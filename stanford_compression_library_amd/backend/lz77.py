@@ -1,9 +1,12 @@
-"""The LZ layer of LZ77 on the device (csrc/scl_lz77.hip): match index + greedy parse, and sequence replay.
+"""LZ77 on the device: the LZ layer (csrc/scl_lz77.hip: match index + greedy parse, and sequence replay) and the entropy
+stage above it (csrc/scl_lz77_entropy.hip: sequences and literals <-> the reference's block bits).
 
 Two call shapes, as in :mod:`.models`:
 
 * ``parse_host`` / ``replay_host`` -- one stream in host memory (what ``LZ77Encoder`` / ``LZ77Decoder`` use);
-* ``parse_batch`` / ``replay_batch`` -- many independent streams resident in HBM, given as torch tensors.
+* ``parse_batch`` / ``replay_batch`` -- many independent streams resident in HBM, given as torch tensors;
+  ``encode_batch`` / ``decode_batch`` turn their sequences and literals into block bits and back, ``compress_batch`` /
+  ``decompress_batch`` do both steps.  No call loops over streams on the host.
 
 A batch is ``n_streams`` windows laid out one after another in one uint8 tensor; ``win_off`` (int64, ``n_streams + 1``
 entries) says where each starts.  uint32 / uint64 arrays of the C ABI travel as int32 / int64 tensors (the bit patterns).
@@ -153,6 +156,181 @@ def replay_batch(win, win_off, have, literal_count, match_length, match_offset, 
         rc = L.scl_lz77_replay_batch(C.byref(a), _stream_handle(stream, dev))
     _lib.check(rc, "scl_lz77_replay_batch")
     return out_len, status
+
+
+# ---- the entropy stage: sequences and literals <-> block bits (csrc/scl_lz77_entropy.hip) ------------------------------------
+DEFAULT_BINNED_OFFSET = 16  # LZ77StreamsEncoder's log_scale_binned_coder_offset
+
+
+@dataclass
+class EncodedBatch:
+    """Device-resident result of :func:`encode_batch`: stream ``s`` is the ``nbits[s]`` bits from absolute bit
+    ``bit_offset[s]`` (= ``8 * s * out_stride``) of ``bits`` -- the bits ``LZ77StreamsEncoder.encode_block`` returns.
+    ``models.compact`` / ``compact_into`` (``scl_streams_compact``) take it as they take any batch of slots.
+
+    LOOK AT ``status`` BEFORE COMPACTING.  A stream with a non-zero status has stored nothing, but ``nbits[s]`` of a
+    ``lib.ST_CAPACITY`` stream is the length it needs, which is more than its slot: the compaction knows no slot size and
+    would read that many bits from the slot on.  Encode such a batch again with a larger ``out_stride``."""
+
+    bits: "torch.Tensor"        # uint8 [n_streams * out_stride + 16]
+    bit_offset: "torch.Tensor"  # uint64 as int64 [n_streams]
+    nbits: "torch.Tensor"       # uint32 as int32 [n_streams]
+    status: "torch.Tensor"      # int32 [n_streams]
+    out_stride: int
+
+    # the names models.EncodedBatch gives the same things
+    layout = "linear"
+    data = property(lambda self: self.bits)
+    stride = property(lambda self: self.out_stride)
+    n_chunks = property(lambda self: int(self.nbits.numel()))
+
+
+@dataclass
+class DecodedBatch(ParsedBatch):
+    """:class:`ParsedBatch` as :func:`decode_batch` fills it, plus ``consumed[s]`` = the bits of stream s the block took
+    (``LZ77StreamsDecoder.decode_block``'s ``num_bits_consumed``)"""
+
+    consumed: "torch.Tensor" = None
+
+
+def entropy_slot_bytes(max_n_seq: int, max_n_lit: int, binned_offset: int = DEFAULT_BINNED_OFFSET) -> int:
+    return int(_lib.load().scl_lz77_entropy_slot_bytes(int(max_n_seq), int(max_n_lit), int(binned_offset)))
+
+
+def encode_batch(parsed: ParsedBatch, binned_offset: int = DEFAULT_BINNED_OFFSET, out_stride: Optional[int] = None,
+                 stream=None, out: Optional[EncodedBatch] = None) -> EncodedBatch:
+    """The reference's block bits of every stream of ``parsed``, each in a slot of ``out_stride`` bytes (a multiple of 16;
+    default: ``entropy_slot_bytes`` of the largest counts, which reads ``n_seq`` / ``n_lit`` back once).  ``status[s]``:
+    ``lib.ST_CAPACITY`` = the slot is too small (``nbits[s]`` says what it takes), see include/scl_hip.h for the rest.
+    ``out``: an :class:`EncodedBatch` whose buffers are written instead of new ones (``bits`` 16-byte aligned, at least
+    ``n_streams * out.out_stride`` bytes)."""
+    import torch
+
+    L = _lib.load()
+    lc, ml, mo = parsed.literal_count, parsed.match_length, parsed.match_offset
+    assert lc.is_cuda and lc.dim() == 2 and lc.shape == ml.shape == mo.shape
+    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in (lc, ml, mo, parsed.n_seq, parsed.n_lit))
+    assert parsed.literals.dtype == torch.uint8 and parsed.lit_off.dtype == torch.int64
+    dev, n_streams = lc.device, int(parsed.n_seq.numel())
+    assert lc.shape[0] == n_streams and parsed.n_lit.numel() == n_streams and parsed.lit_off.numel() == n_streams
+    lit_off = parsed.lit_off.contiguous()
+    if out is not None:
+        out_stride = out.out_stride
+    if out_stride is None:
+        top_seq = int(parsed.n_seq.max().item()) if n_streams else 0
+        top_lit = int(parsed.n_lit.to(torch.int64).bitwise_and(0xFFFFFFFF).max().item()) if n_streams else 0
+        out_stride = entropy_slot_bytes(min(top_seq & 0xFFFFFFFF, int(lc.shape[1])), top_lit, binned_offset)
+    out_stride = int(out_stride)
+    if out is None:
+        out = EncodedBatch(torch.zeros(n_streams * out_stride + 16, dtype=torch.uint8, device=dev),
+                           torch.zeros(n_streams, dtype=torch.int64, device=dev),
+                           torch.zeros(n_streams, dtype=torch.int32, device=dev),
+                           torch.zeros(n_streams, dtype=torch.int32, device=dev), out_stride)
+    bits, bit_offset, nbits, status = out.bits, out.bit_offset, out.nbits, out.status
+    assert bits.dtype == torch.uint8 and bits.is_contiguous() and bits.numel() >= n_streams * out_stride
+    assert bit_offset.numel() == n_streams and nbits.numel() == n_streams and status.numel() == n_streams
+    a = _lib.Lz77EntropyEncodeArgs(n_streams, int(lc.shape[1]), int(binned_offset), lc.data_ptr(), ml.data_ptr(),
+                                   mo.data_ptr(), parsed.n_seq.data_ptr(), parsed.literals.data_ptr(),
+                                   int(parsed.literals.numel()), lit_off.data_ptr(), parsed.n_lit.data_ptr(),
+                                   bits.data_ptr(), out_stride, bit_offset.data_ptr(), nbits.data_ptr(), status.data_ptr())
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_entropy_encode_batch(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_entropy_encode_batch")
+    out._inputs = (parsed, lit_off)  # read asynchronously: they live as long as the result
+    return out
+
+
+def decode_batch(bits, bit_offset, nbits, seq_cap: int, lit_off, lit_cap, binned_offset: int = DEFAULT_BINNED_OFFSET,
+                 stream=None, out: Optional[DecodedBatch] = None) -> DecodedBatch:
+    """bits: uint8 CUDA tensor; stream s = the ``nbits[s]`` (int32) bits from absolute bit ``bit_offset[s]`` (int64) on, at
+    any alignment.  Its sequences go to row s (``seq_cap`` entries) of the result, its literals to
+    ``literals[lit_off[s] : lit_off[s] + lit_cap[s]]`` (int64 / int32 per stream); ``literals`` has ``max(lit_off +
+    lit_cap)`` bytes unless ``out`` brings buffers of its own.  -> :class:`DecodedBatch` (``status``, ``consumed``: int32)."""
+    import torch
+
+    L = _lib.load()
+    assert bits.is_cuda and bits.dtype == torch.uint8 and bits.is_contiguous()
+    assert bit_offset.dtype == torch.int64 and lit_off.dtype == torch.int64
+    assert nbits.dtype == torch.int32 and lit_cap.dtype == torch.int32
+    dev, n_streams = bits.device, int(nbits.numel())
+    assert bit_offset.numel() == n_streams and lit_off.numel() == n_streams and lit_cap.numel() == n_streams
+    bit_offset, nbits, lit_off, lit_cap = (t.contiguous() for t in (bit_offset, nbits, lit_off, lit_cap))
+    if out is None:
+        lit_bytes = int((lit_off + lit_cap.to(torch.int64).bitwise_and(0xFFFFFFFF)).max().item()) if n_streams else 0
+        rows = lambda: torch.zeros((n_streams, seq_cap), dtype=torch.int32, device=dev)  # noqa: E731
+        words = lambda: torch.zeros(n_streams, dtype=torch.int32, device=dev)  # noqa: E731
+        out = DecodedBatch(rows(), rows(), rows(), torch.zeros(max(lit_bytes, 1), dtype=torch.uint8, device=dev), words(),
+                           words(), words(), lit_off, int(seq_cap), words())
+    assert out.seq_cap == int(seq_cap) and out.literal_count.shape == (n_streams, int(seq_cap))
+    a = _lib.Lz77EntropyDecodeArgs(bits.data_ptr(), int(bits.numel()), bit_offset.data_ptr(), nbits.data_ptr(), n_streams,
+                                   int(seq_cap), int(binned_offset), out.literal_count.data_ptr(),
+                                   out.match_length.data_ptr(), out.match_offset.data_ptr(), out.n_seq.data_ptr(),
+                                   out.literals.data_ptr(), int(out.literals.numel()), lit_off.data_ptr(),
+                                   lit_cap.data_ptr(), out.n_lit.data_ptr(), out.consumed.data_ptr(), out.status.data_ptr())
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_entropy_decode_batch(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_entropy_decode_batch")
+    out._inputs = (bits, bit_offset, nbits, lit_off, lit_cap)
+    return out
+
+
+def compress_batch(win, win_off, start, min_match_length: int, max_matches: int, seq_cap: Optional[int] = None,
+                   binned_offset: int = DEFAULT_BINNED_OFFSET, out_stride: Optional[int] = None, scratch=None, stream=None):
+    """parse + encode: the blocks of a batch of windows (see :func:`parse_batch`) -> (:class:`EncodedBatch`,
+    :class:`ParsedBatch`).  A stream's status is ``parsed.status[s] | encoded.status[s]``: nothing here reads it back, so
+    check it before the bits are used (see :class:`EncodedBatch`).  ``seq_cap`` defaults to ``default_seq_cap`` of the
+    longest block and ``out_stride`` to ``entropy_slot_bytes(seq_cap, longest block)`` -- a block has at most as many
+    literals as bytes -- so the defaults cost ONE read-back, of the block lengths, before anything is launched; parse and
+    encode then follow each other on ``stream`` without the host in between.  That stride is the worst case (about 3.5
+    bytes per input byte at ``min_match_length`` 6); pass a smaller one where the data allows it."""
+    import torch
+
+    if seq_cap is None or out_stride is None:
+        lens = win_off[1:] - win_off[:-1] - start.to(torch.int64).bitwise_and(0xFFFFFFFF)
+        longest = max(int(lens.max().item()), 0) if start.numel() else 0
+        if seq_cap is None:
+            seq_cap = default_seq_cap(longest, min_match_length)
+        if out_stride is None:
+            out_stride = entropy_slot_bytes(seq_cap, longest, binned_offset)
+    parsed = parse_batch(win, win_off, start, min_match_length, max_matches, seq_cap, scratch=scratch, stream=stream)
+    return encode_batch(parsed, binned_offset, out_stride, stream=stream), parsed
+
+
+def decompress_batch(bits, bit_offset, nbits, win, win_off, have, seq_cap: int,
+                     binned_offset: int = DEFAULT_BINNED_OFFSET, stream=None):
+    """decode + replay: appends the block of every stream to its window slot ``win[win_off[s] : win_off[s + 1]]``, which
+    holds ``have[s]`` bytes already (see :func:`replay_batch`).  A block has at most as many literals as bytes, so the
+    room left in the slot bounds them.  -> (out_len, status, consumed): int32 [n_streams] each; status = the decoder's
+    | the replay's (a stream the decoder faulted on replays what was decoded before the fault)."""
+    import torch
+
+    # (uint32 values travel as int32 bit patterns: masked on the way in, wrapped on the way out)
+    room = (win_off[1:] - win_off[:-1] - have.to(torch.int64).bitwise_and(0xFFFFFFFF)).clamp(min=0, max=0xFFFFFFFF)
+    lit_off = torch.cumsum(room, 0) - room
+    lit_cap = torch.where(room >= 1 << 31, room - (1 << 32), room).to(torch.int32)
+    decoded = decode_batch(bits, bit_offset, nbits, seq_cap, lit_off, lit_cap, binned_offset, stream=stream)
+    out_len, status = replay_batch(win, win_off, have, decoded.literal_count, decoded.match_length, decoded.match_offset,
+                                   decoded.n_seq, decoded.literals, lit_off, decoded.n_lit, stream=stream)
+    return out_len, status | decoded.status, decoded.consumed
+
+
+def entropy_kernel_names():
+    """-> (encode, decode) kernel names of the entropy stage as a kernel trace prints them"""
+    bufs = [C.create_string_buffer(128) for _ in range(2)]
+    _lib.check(_lib.load().scl_lz77_entropy_kernel_names(*bufs, 128), "scl_lz77_entropy_kernel_names")
+    return tuple(b.value.decode() for b in bufs)
+
+
+def huffman_from_counts(counts):
+    """The tree builder of the entropy kernels, run on the host: counts [K <= 256] -> (codes uint32, lengths uint8), the
+    codeword of symbol i = the ``lengths[i]`` low bits of ``codes[i]``; (0, 0) for a symbol without a count.  Raises
+    ``SclHipError`` (SCL_E_PARAM) for a code above 32 bits.  Needs no device."""
+    counts = np.ascontiguousarray(counts, np.uint64)
+    code, length = np.zeros(counts.size, np.uint32), np.zeros(counts.size, np.uint8)
+    rc = _lib.load().scl_lz77_huffman_from_counts_host(counts.ctypes.data_as(_lib._u64p), int(counts.size),
+                                                      _lib.u32_ptr(code), _lib.u8_ptr(length))
+    _lib.check(rc, "scl_lz77_huffman_from_counts_host")
+    return code, length
 
 
 def kernel_names():

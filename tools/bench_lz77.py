@@ -1,8 +1,10 @@
-"""Times the LZ77 device layer -- index, parse, replay -- on a batch of streams and on one large stream as a batch of one.
-Recorded, not gated: profiles/lz77_bench.txt.
+"""Times the LZ77 device layer -- index, parse, replay -- on a batch of streams and on one large stream as a batch of one,
+and on the batch the entropy stage (encode_batch / decode_batch) beside its yardstick: the host stage of the classes,
+LZ77StreamsEncoder.encode_block / LZ77StreamsDecoder.decode_block, timed on --host-streams of the same parsed streams and
+scaled to the batch.  Recorded, not gated: profiles/lz77_bench.txt.
 
     python tools/bench_lz77.py [--streams 4096] [--stream-kib 64] [--single-mib 16] [--steps 20] [--warmup 5]
-                               [--single-steps N] [--single-warmup N] [--out FILE]
+                               [--single-steps N] [--single-warmup N] [--host-streams 64] [--out FILE]
 
 Data: the first-order Markov source of bench_data.py over 16 symbols, one chain per stream (generated on the device).  The
 single stream is the first --single-mib MiB of the very same bytes, read as ONE window: its parse is one wavefront.
@@ -10,11 +12,14 @@ Kernel time only: HIP events around each call on the current stream, buffers and
 verified: the replay of the parse's output must restore the input.  That round trip checks parse and replay, NOT the index:
 the parse re-checks every entry it reads from order[], so a misplaced entry still gives a valid parse, only with other
 matches.  The index is compared with its definition, and the parse with the restated rule, in tests/test_gpu_lz77_limits.py.
+The entropy rows are verified the same way: the decoder's output, replayed, must restore the input; that the bits are the
+reference's is the business of tests/test_gpu_lz77_entropy.py.
 """
 import argparse
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -41,7 +46,60 @@ def timed(fn, steps, warmup):
     return ms
 
 
-def run_shape(name, win, n_streams, stream_len, steps, warmup, dev):
+def entropy_rows(name, win, win_off, res, n_streams, stream_len, steps, warmup, host_streams, dev):
+    """the entropy stage on the parsed batch `res`, and the host classes on its first `host_streams` streams"""
+    from stanford_compression_library_amd.compressors.lz77 import LZ77Sequence, LZ77StreamsDecoder, LZ77StreamsEncoder
+
+    total = n_streams * stream_len
+    enc = lz77.encode_batch(res)
+    lit_cap = torch.full((n_streams,), stream_len, dtype=torch.int32, device=dev)
+    dec = lz77.decode_batch(enc.bits, enc.bit_offset, enc.nbits, res.seq_cap, res.lit_off, lit_cap)
+    rows = (("encode", lambda: lz77.encode_batch(res, out=enc)),
+            ("decode", lambda: lz77.decode_batch(enc.bits, enc.bit_offset, enc.nbits, res.seq_cap, res.lit_off, lit_cap, out=dec)))
+    lines = []
+    for what, fn in rows:
+        ms = timed(fn, steps, warmup)
+        med = statistics.median(ms)
+        lines.append(f"{name:22s} entropy {what}: median {med:10.3f} ms  min {min(ms):10.3f}  max {max(ms):10.3f}  "
+                     f"{total / med / 1e6:8.3f} GB/s of input")
+    out = torch.zeros_like(win)
+    have = torch.zeros(n_streams, dtype=torch.int32, device=dev)
+    out_len, status = lz77.replay_batch(out, win_off, have, dec.literal_count, dec.match_length, dec.match_offset, dec.n_seq,
+                                        dec.literals, dec.lit_off, dec.n_lit)
+    torch.cuda.synchronize()
+    ok = bool((enc.status == 0).all() and (dec.status == 0).all() and torch.equal(dec.consumed, enc.nbits) and
+              (status == 0).all() and torch.equal(out, win))
+    coded = int(enc.nbits.to(torch.int64).sum()) // 8
+    lines.append(f"{name:22s} entropy stage: {coded} coded bytes ({total / max(coded, 1):.2f} : 1), slots of {enc.out_stride} "
+                 f"bytes, kernels {', '.join(lz77.entropy_kernel_names())}, {steps} timed steps after {warmup}, "
+                 f"encode -> decode -> replay {'ok' if ok else 'FAILED'}")
+    # the yardstick: the host stage of the classes, stream by stream
+    k = min(host_streams, n_streams)
+    n_seq, n_lit = res.n_seq[:k].cpu().tolist(), res.n_lit[:k].cpu().tolist()
+    fields = [t[:k].cpu().numpy().view("uint32") for t in (res.literal_count, res.match_length, res.match_offset)]
+    lits, lit_off = res.literals.cpu().numpy(), res.lit_off[:k].cpu().tolist()
+    t_enc = t_dec = 0.0
+    same = True
+    nbits = enc.nbits[:k].cpu().tolist()
+    for s in range(k):
+        seqs = [LZ77Sequence(*t) for t in zip(*(f[s, : n_seq[s]].tolist() for f in fields))]
+        literals = lits[lit_off[s]: lit_off[s] + n_lit[s]].tolist()
+        t0 = time.perf_counter()
+        bits = LZ77StreamsEncoder().encode_block(seqs, literals)
+        t1 = time.perf_counter()
+        (got_seqs, got_lits), used = LZ77StreamsDecoder().decode_block(bits)
+        t2 = time.perf_counter()
+        t_enc += t1 - t0
+        t_dec += t2 - t1
+        same = same and len(bits) == nbits[s] and used == nbits[s] and got_seqs == seqs and got_lits == literals
+    scale = n_streams / max(k, 1)
+    lines.append(f"{name:22s} host stage of the classes on {k} streams: encode {t_enc:.3f} s, decode {t_dec:.3f} s; scaled to "
+                 f"{n_streams} streams: encode {t_enc * scale * 1e3:.0f} ms, decode {t_dec * scale * 1e3:.0f} ms; "
+                 f"same bit counts and values as the device stage: {'yes' if same else 'NO'}")
+    return lines
+
+
+def run_shape(name, win, n_streams, stream_len, steps, warmup, dev, host_streams=0):
     total = n_streams * stream_len
     win_off = torch.arange(n_streams + 1, dtype=torch.int64, device=dev) * stream_len
     start = torch.zeros(n_streams, dtype=torch.int32, device=dev)
@@ -73,6 +131,8 @@ def run_shape(name, win, n_streams, stream_len, steps, warmup, dev):
     n_seq, n_lit = int(res.n_seq.to(torch.int64).sum()), int(res.n_lit.to(torch.int64).sum())
     lines.append(f"{name:22s} {n_seq} sequences, {n_lit} literals ({total / max(n_seq, 1):.1f} input bytes per sequence), "
                  f"{steps} timed steps after {warmup}, round trip {'ok' if ok else 'FAILED'}")
+    if host_streams:
+        lines += entropy_rows(name, win, win_off, res, n_streams, stream_len, steps, warmup, host_streams, dev)
     return lines
 
 
@@ -85,6 +145,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--single-steps", type=int, default=None)
     ap.add_argument("--single-warmup", type=int, default=None)
+    ap.add_argument("--host-streams", type=int, default=64)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     lib.require_device()
@@ -96,7 +157,8 @@ def main():
     lines = [f"lz77 bench: min_match_length {L}, max_num_matches_considered {M}, first-order Markov source over 16 symbols, "
              f"HIP events, {torch.cuda.get_device_name(0)}", f"kernels: {', '.join(lz77.kernel_names())}"]
     print("\n".join(lines), flush=True)
-    lines += run_shape(f"{args.streams} x {args.stream_kib} KiB", win, args.streams, stream_len, args.steps, args.warmup, dev)
+    lines += run_shape(f"{args.streams} x {args.stream_kib} KiB", win, args.streams, stream_len, args.steps, args.warmup, dev,
+                       host_streams=args.host_streams)
     print("\n".join(lines[2:]), flush=True)
     n_batch = len(lines)
     lines += run_shape(f"1 x {args.single_mib} MiB", win[:single_len].contiguous(), 1, single_len,
