@@ -856,7 +856,10 @@ __global__ void __launch_bounds__(RGD_THREADS) range_decode_fast_kernel(RangeFas
     }
     // the rANS decoder's windowless reader (scl_ans_fast_io.h): the 32 bits at the position come straight out of the ring,
     // once per PAIR of symbols; nothing is advanced under a branch
-    typename std::conditional<STRIPED, AnsBitReaderT<RGD_THREADS>, AnsBitReaderW<RGD_THREADS>>::type r;
+    // (ONE_WAIT = false: the one-wait refill of AnsBitReaderT that the rANS / tANS decoders take measured 0.2 % SLOWER here --
+    // this kernel refills every eight symbols and is bound by its instruction stream -- and costs the any-total form a 91st
+    // register: the range decoders keep the refill as it was, profiles/ans_refill_timing.txt)
+    typename std::conditional<STRIPED, AnsBitReaderT<RGD_THREADS, false>, AnsBitReaderW<RGD_THREADS>>::type r;
     if constexpr (STRIPED)
         r.init(in, in_size_bytes, c, bit_off[c], lds, threadIdx.x);
     else
