@@ -471,6 +471,66 @@ int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, const u
                          const uint32_t *h_match_len, const uint32_t *h_match_off, uint64_t n_seq,
                          const uint8_t *h_literals, uint64_t n_lit, uint64_t *out_len);
 
+/* ---- LZ77: one large stream across the whole GPU (scl_lz77_wide.hip; added to ABI 8 as above) ---------------------------
+ * scl_lz77_parse_batch / scl_lz77_replay_batch give every stream one wavefront: right for thousands of streams, serial
+ * for one.  These two calls take ONE stream and use the whole chip; what they store is what the batch calls store for a
+ * batch of that one stream, bit for bit: sequences, literals, d_n_seq, d_n_lit, d_out_len, d_status.
+ *   parse : the window is d_win[0..n), the block starts at `start` (host values: they size the launches).  The batch
+ *           call's index phase is followed by: every position scored in parallel (extensions capped at `cap` bytes; a
+ *           position whose match reaches the cap is LONG), per tile of `tile` positions where the chain entering at p
+ *           leaves the tile, ONE wavefront walking tile to tile (it scores the LONG positions it meets in full), and one
+ *           wavefront per entered tile writing rows and literals after scans over the tiles.  tile <= cap:
+ *           scl_lz77_wide_shape.  d_literals is laid out like d_win: d_n_lit bytes at d_literals + start.  1 <= M <= 64
+ *           only (the batch call keeps M = 0 and M > 64).  d_status: SCL_ST_CAPACITY as in the batch call.
+ *   replay: appends to the slot d_win[0..cap), which holds `have` bytes: 64-bit prefix sums place every sequence, all are
+ *           validated in parallel in the batch kernel's order of checks and the first fault decides d_status and
+ *           d_out_len; a match byte follows root = root[root] to the history or literal byte it equals, in at most
+ *           ceil(log2(n_seq + 1)) + 1 launched rounds.  Nothing outside the slot is read or written on any input.
+ * Both are asynchronous on `stream` and read their scratch until they finish.  SCL_E_PARAM before any device call: a null
+ * pointer, L outside 1..8, M outside 1..64, n or cap >= 2^32, start > n, have > cap, scratch misaligned (256 bytes) or
+ * smaller than scl_lz77_wide_scratch_bytes(n) / scl_lz77_wide_replay_scratch_bytes(n_seq, cap - have). */
+#define SCL_LZ77_WIDE_INDEX 1u
+#define SCL_LZ77_WIDE_SCORE 2u /* the scores and the tile exits */
+#define SCL_LZ77_WIDE_WALK 4u
+#define SCL_LZ77_WIDE_EMIT 8u
+
+typedef struct scl_lz77_wide_parse_args {
+    const uint8_t *d_win;
+    uint64_t n, start;
+    uint32_t min_match_length, max_matches;
+    uint32_t seq_cap, phases; /* phases: 0 = all, else a mask of SCL_LZ77_WIDE_* run on the same scratch, in this order
+                                 (for measurements; every phase can be repeated) */
+    uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [seq_cap] each */
+    uint8_t *d_literals;                               /* n bytes */
+    uint32_t *d_n_seq, *d_n_lit, *d_status;            /* one word each */
+    void *d_scratch;
+    uint64_t scratch_bytes;
+} scl_lz77_wide_parse_args;
+
+typedef struct scl_lz77_wide_replay_args {
+    uint8_t *d_win;
+    uint64_t have, cap;
+    const uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_seq] each */
+    uint64_t n_seq;
+    const uint8_t *d_literals;
+    uint64_t n_lit;
+    uint32_t *d_out_len, *d_status; /* one word each */
+    void *d_scratch;
+    uint64_t scratch_bytes;
+} scl_lz77_wide_replay_args;
+
+uint64_t scl_lz77_wide_scratch_bytes(uint64_t n);
+uint64_t scl_lz77_wide_replay_scratch_bytes(uint64_t n_seq, uint64_t grow_bytes);
+int scl_lz77_parse_wide(const scl_lz77_wide_parse_args *args, void *stream);
+int scl_lz77_replay_wide(const scl_lz77_wide_replay_args *args, void *stream);
+/* the compile-time shape: positions per tile and the cap of a scored extension; either may be NULL */
+void scl_lz77_wide_shape(uint32_t *tile, uint32_t *cap);
+/* scl_lz77_parse_host takes the wide path for a block of at least this many bytes (and 1 <= M <= 64),
+   scl_lz77_replay_host for cap - have of at least this many; below it the one-wave path.  Same results either way. */
+uint64_t scl_lz77_wide_threshold(void);
+/* the kernels that carry the scoring, the walk and the replay's pointer doubling, as scl_lz77_kernel_names */
+int scl_lz77_wide_kernel_names(char *score, char *walk, char *resolve, uint64_t cap);
+
 /* ---- LZ77: the entropy stage, sequences and literals <-> block bits (scl_lz77_entropy.hip; added to ABI 8 as above) -------
  *   scl_lz77_entropy_encode_batch  <->  LZ77StreamsEncoder.encode_block   scl/compressors/lz77.py:301-361
  *   scl_lz77_entropy_decode_batch  <->  LZ77StreamsDecoder.decode_block   scl/compressors/lz77.py:364-428

@@ -68,6 +68,23 @@ class Lz77ReplayArgs(C.Structure):
                 ("d_n_lit", C.c_void_p), ("d_out_len", C.c_void_p), ("d_status", C.c_void_p)]
 
 
+class Lz77WideParseArgs(C.Structure):
+    """scl_lz77_wide_parse_args"""
+    _fields_ = [("d_win", C.c_void_p), ("n", C.c_uint64), ("start", C.c_uint64), ("min_match_length", C.c_uint32),
+                ("max_matches", C.c_uint32), ("seq_cap", C.c_uint32), ("phases", C.c_uint32),
+                ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p),
+                ("d_literals", C.c_void_p), ("d_n_seq", C.c_void_p), ("d_n_lit", C.c_void_p), ("d_status", C.c_void_p),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
+
+
+class Lz77WideReplayArgs(C.Structure):
+    """scl_lz77_wide_replay_args"""
+    _fields_ = [("d_win", C.c_void_p), ("have", C.c_uint64), ("cap", C.c_uint64), ("d_lit_count", C.c_void_p),
+                ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p), ("n_seq", C.c_uint64),
+                ("d_literals", C.c_void_p), ("n_lit", C.c_uint64), ("d_out_len", C.c_void_p), ("d_status", C.c_void_p),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
+
+
 class Lz77EntropyEncodeArgs(C.Structure):
     """scl_lz77_entropy_encode_args"""
     _fields_ = [("n_streams", C.c_uint64), ("seq_cap", C.c_uint32), ("binned_offset", C.c_uint32),
@@ -87,6 +104,7 @@ class Lz77EntropyDecodeArgs(C.Structure):
 
 
 LZ77_INDEX, LZ77_PARSE = 1, 2
+LZ77_WIDE_INDEX, LZ77_WIDE_SCORE, LZ77_WIDE_WALK, LZ77_WIDE_EMIT = 1, 2, 4, 8
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _vp, _u32, _u64, _int = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
@@ -153,6 +171,14 @@ _SIGNATURES = {
     "scl_lz77_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
     "scl_lz77_parse_host": (_int, [_u8p, _u64, _u64, _u32, _u32, _u32p, _u32p, _u32p, _u64, _u64p, _u8p, _u64, _u64p]),
     "scl_lz77_replay_host": (_int, [_u8p, _u64, _u64, _u32p, _u32p, _u32p, _u64, _u8p, _u64, _u64p]),
+    # LZ77: one large stream across the whole GPU (scl_lz77_wide.hip)
+    "scl_lz77_wide_scratch_bytes": (_u64, [_u64]),
+    "scl_lz77_wide_replay_scratch_bytes": (_u64, [_u64, _u64]),
+    "scl_lz77_parse_wide": (_int, [C.POINTER(Lz77WideParseArgs), _vp]),
+    "scl_lz77_replay_wide": (_int, [C.POINTER(Lz77WideReplayArgs), _vp]),
+    "scl_lz77_wide_shape": (None, [_u32p, _u32p]),
+    "scl_lz77_wide_threshold": (_u64, []),
+    "scl_lz77_wide_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
     # LZ77: the entropy stage (scl_lz77_entropy.hip)
     "scl_lz77_entropy_encode_batch": (_int, [C.POINTER(Lz77EntropyEncodeArgs), _vp]),
     "scl_lz77_entropy_decode_batch": (_int, [C.POINTER(Lz77EntropyDecodeArgs), _vp]),

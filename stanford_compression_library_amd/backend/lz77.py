@@ -3,7 +3,10 @@ stage above it (csrc/scl_lz77_entropy.hip: sequences and literals <-> the refere
 
 Two call shapes, as in :mod:`.models`:
 
-* ``parse_host`` / ``replay_host`` -- one stream in host memory (what ``LZ77Encoder`` / ``LZ77Decoder`` use);
+* ``parse_host`` / ``replay_host`` -- one stream in host memory (what ``LZ77Encoder`` / ``LZ77Decoder`` use); from
+  ``wide_threshold()`` bytes on the library spreads the stream over the whole GPU (csrc/scl_lz77_wide.hip), with the same
+  results;
+* ``parse_wide`` / ``replay_wide`` -- that wide path on ONE stream resident in HBM: a :class:`ParsedBatch` of one stream;
 * ``parse_batch`` / ``replay_batch`` -- many independent streams resident in HBM, given as torch tensors;
   ``encode_batch`` / ``decode_batch`` turn their sequences and literals into block bits and back, ``compress_batch`` /
   ``decompress_batch`` do both steps.  No call loops over streams on the host.
@@ -155,6 +158,102 @@ def replay_batch(win, win_off, have, literal_count, match_length, match_offset, 
     with torch.cuda.device(dev):
         rc = L.scl_lz77_replay_batch(C.byref(a), _stream_handle(stream, dev))
     _lib.check(rc, "scl_lz77_replay_batch")
+    return out_len, status
+
+
+# ---- one large stream across the whole GPU (csrc/scl_lz77_wide.hip) ------------------------------------------------------------
+def wide_shape():
+    """-> (tile, cap): positions per tile and the cap of a scored extension, the kernels' compile-time shape"""
+    tile, cap = C.c_uint32(0), C.c_uint32(0)
+    _lib.load().scl_lz77_wide_shape(C.byref(tile), C.byref(cap))
+    return tile.value, cap.value
+
+
+def wide_threshold() -> int:
+    """block bytes from which ``parse_host`` / ``replay_host`` take the wide path"""
+    return int(_lib.load().scl_lz77_wide_threshold())
+
+
+def wide_scratch_bytes(n: int) -> int:
+    return int(_lib.load().scl_lz77_wide_scratch_bytes(int(n)))
+
+
+def wide_replay_scratch_bytes(n_seq: int, grow_bytes: int) -> int:
+    return int(_lib.load().scl_lz77_wide_replay_scratch_bytes(int(n_seq), int(grow_bytes)))
+
+
+def wide_kernel_names():
+    """-> (score, walk, resolve) kernel names as a kernel trace prints them"""
+    bufs = [C.create_string_buffer(128) for _ in range(3)]
+    _lib.check(_lib.load().scl_lz77_wide_kernel_names(*bufs, 128), "scl_lz77_wide_kernel_names")
+    return tuple(b.value.decode() for b in bufs)
+
+
+def parse_wide(win, start: int, min_match_length: int, max_matches: int, seq_cap: Optional[int] = None, scratch=None,
+               stream=None, out: Optional[ParsedBatch] = None, phases: int = 0) -> ParsedBatch:
+    """win: uint8 CUDA tensor, ONE window whose block starts at ``start``; 1 <= ``max_matches`` <= 64.  -> what
+    ``parse_batch`` returns for a batch of this one stream (``n_streams == 1``: ``encode_batch`` takes it as it is).
+    ``seq_cap`` defaults to ``default_seq_cap`` of the block; ``scratch``: a uint8 tensor of at least
+    ``wide_scratch_bytes(win.numel())`` bytes to reuse across calls; ``out``: a one-stream :class:`ParsedBatch` whose
+    buffers are written instead of new ones (its ``seq_cap`` holds); ``phases``: 0 = everything, else a mask of
+    ``lib.LZ77_WIDE_INDEX`` / ``_SCORE`` / ``_WALK`` / ``_EMIT`` run on the same scratch (for measurements)."""
+    import torch
+
+    L = _lib.load()
+    assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous() and win.dim() == 1
+    dev, n, start = win.device, int(win.numel()), int(start)
+    if out is not None:
+        seq_cap = out.seq_cap
+    if seq_cap is None:
+        seq_cap = default_seq_cap(n - start, min_match_length)
+    need = wide_scratch_bytes(n)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert scratch.numel() >= need
+    rows = lambda: torch.zeros((1, seq_cap), dtype=torch.int32, device=dev)  # noqa: E731
+    words = lambda: torch.zeros(1, dtype=torch.int32, device=dev)  # noqa: E731
+    if out is None:
+        out = ParsedBatch(rows(), rows(), rows(), torch.zeros(max(n, 1), dtype=torch.uint8, device=dev), words(), words(),
+                          words(), torch.full((1,), start, dtype=torch.int64, device=dev), int(seq_cap))
+    assert out.literal_count.shape == (1, out.seq_cap) and out.literals.numel() >= n
+    a = _lib.Lz77WideParseArgs(win.data_ptr(), n, start, int(min_match_length), int(max_matches), out.seq_cap, int(phases),
+                               out.literal_count.data_ptr(), out.match_length.data_ptr(), out.match_offset.data_ptr(),
+                               out.literals.data_ptr(), out.n_seq.data_ptr(), out.n_lit.data_ptr(), out.status.data_ptr(),
+                               scratch.data_ptr(), int(scratch.numel()))
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_parse_wide(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_parse_wide")
+    out._scratch = scratch  # the kernels read it asynchronously: it lives as long as the result
+    return out
+
+
+def replay_wide(win, have: int, literal_count, match_length, match_offset, n_seq: int, literals, n_lit: int, cap=None,
+                scratch=None, stream=None):
+    """Appends to ``win[:cap]`` (default: all of it) in place, which holds ``have`` bytes already: ONE stream's ``n_seq``
+    sequences (int32 tensors, the first ``n_seq`` entries of each) and ``n_lit`` literals from ``literals[0]`` on; the
+    counts are host integers, they size the launches.  -> (out_len, status): int32 [1] each, as ``replay_batch``."""
+    import torch
+
+    L = _lib.load()
+    assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous() and literals.dtype == torch.uint8
+    rows = tuple(t.reshape(-1) for t in (literal_count, match_length, match_offset))
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= int(n_seq) for t in rows)
+    assert literals.numel() >= int(n_lit)
+    dev, have, cap = win.device, int(have), int(win.numel() if cap is None else cap)
+    assert cap <= win.numel()
+    need = wide_replay_scratch_bytes(n_seq, max(cap - have, 0))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert scratch.numel() >= need
+    out_len = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    a = _lib.Lz77WideReplayArgs(win.data_ptr(), have, cap, rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(),
+                                int(n_seq), literals.data_ptr(), int(n_lit), out_len.data_ptr(), status.data_ptr(),
+                                scratch.data_ptr(), int(scratch.numel()))
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_replay_wide(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_replay_wide")
+    out_len._inputs = (rows, literals, scratch)  # read asynchronously: they live as long as the result
     return out_len, status
 
 

@@ -7,7 +7,9 @@ Drop-in for reference scl/compressors/lz77.py: ``LZ77Sequence`` (:115-124), ``Em
 * The LZ layer -- what the reference does with a dict of tuples and a byte-by-byte match loop -- is
   ``backend.lz77.parse_host`` / ``replay_host`` (csrc/scl_lz77.hip).  The coder objects keep their window
   across blocks on the host, as the reference does; every block hands the whole window to the device, which indexes it
-  anew (the batch API in ``backend.lz77`` is the one to use for many streams).
+  anew (the batch API in ``backend.lz77`` is the one to use for many streams).  From ``backend.lz77.wide_threshold()``
+  bytes of block on, and with ``max_num_matches_considered`` in 1..64, the library parses and replays the stream across the
+  whole GPU (csrc/scl_lz77_wide.hip) instead of on one wavefront: the same sequences, literals and bytes.
 * The entropy stage is the reference's layout: each stream of integers is coded with a Huffman code of its own empirical
   counts (``HuffmanEncoder`` / ``HuffmanDecoder``, i.e. the prefix-code kernels), the counts travel Elias-delta coded, sizes
   as 32-bit headers.  Binning, residual bits and headers are array operations on the host.

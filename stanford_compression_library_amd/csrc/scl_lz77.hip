@@ -9,13 +9,13 @@
 //   bitmap: one bit per position: it has a candidate (an equal gram at q <= p - L) -- parallel over positions;
 //   parse : ONE WAVEFRONT PER STREAM walks the stream: skip to the next set bit (4096 positions per step), score the
 //           candidates 64 at a time (lane j = the j-th most recent), longest wins, lowest lane on ties.
+// One LARGE stream has kernels of its own, scl_lz77_wide.hip; the *_host calls below choose.  The device code both share is
+// in scl_lz77_internal.h.
 // No workgroup waits on another (every dependency between workgroups is a kernel boundary), every loop is bounded by the
 // data, and reads and writes are checked against the buffers' sizes on any input.
 #include "scl_lz77_internal.h"
 
 namespace {
-
-__device__ __forceinline__ u32 lz_lane() { return threadIdx.x & (SCL_WAVE - 1); }
 
 // the stream that owns global position v: the last s with win_off[s] <= v if v < win_off[s + 1], else n_streams
 __device__ __forceinline__ u32 lz_stream_of(const u64 *win_off, u32 n_streams, u64 v) {
@@ -29,13 +29,6 @@ __device__ __forceinline__ u32 lz_stream_of(const u64 *win_off, u32 n_streams, u
     }
     if (n_streams == 0 || win_off[lo] > v || v >= win_off[lo + 1]) return n_streams;
     return lo;
-}
-
-// the L-gram at global position g as a little-endian integer; the caller guarantees g + L <= N
-__device__ __forceinline__ u64 lz_gram(const u8 *win, u64 g, u32 L) {
-    u64 k = 0;
-    for (u32 j = 0; j < L; ++j) k |= (u64)win[g + j] << (8 * j);
-    return k;
 }
 
 // digit of position v in pass `pass`: passes 0..L-1 read gram byte `pass`, later ones a byte of the stream number
@@ -65,17 +58,18 @@ __global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_histogram(const u8 
 }
 
 // exclusive scan of 256 values, one per thread; *total = their sum.  tmp: 256 words of LDS.
-__device__ __forceinline__ u32 lz_block_scan(u32 v, u32 *tmp, u32 *total) {
+template <class V>
+__device__ __forceinline__ V lz_block_scan(V v, V *tmp, V *total) {
     const u32 t = threadIdx.x;
     tmp[t] = v;
     __syncthreads();
     for (u32 d = 1; d < LZ_SCAN_THREADS; d <<= 1) {
-        const u32 add = t >= d ? tmp[t - d] : 0u;
+        const V add = t >= d ? tmp[t - d] : V(0);
         __syncthreads();
         tmp[t] += add;
         __syncthreads();
     }
-    const u32 incl = tmp[t];
+    const V incl = tmp[t];
     *total = tmp[LZ_SCAN_THREADS - 1];
     __syncthreads();
     return incl - v;
@@ -83,17 +77,18 @@ __device__ __forceinline__ u32 lz_block_scan(u32 v, u32 *tmp, u32 *total) {
 
 // the scan of the tile histograms in three kernels: every block scans its 2048 entries, one workgroup scans the block
 // sums, every block adds its offset
-__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_blocks(u32 *hist, u64 n, u32 *block_sums) {
-    __shared__ u32 tmp[LZ_SCAN_THREADS];
+template <class V>
+__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_blocks(V *hist, u64 n, V *block_sums) {
+    __shared__ V tmp[LZ_SCAN_THREADS];
     const u64 at = ((u64)blockIdx.x * LZ_SCAN_THREADS + threadIdx.x) * LZ_SCAN_PER_THREAD;
-    u32 v[LZ_SCAN_PER_THREAD], sum = 0;
+    V v[LZ_SCAN_PER_THREAD], sum = 0;
 #pragma unroll
     for (u32 j = 0; j < LZ_SCAN_PER_THREAD; ++j) {
-        v[j] = at + j < n ? hist[at + j] : 0u;
+        v[j] = at + j < n ? hist[at + j] : V(0);
         sum += v[j];
     }
-    u32 total;
-    u32 run = lz_block_scan(sum, tmp, &total);
+    V total;
+    V run = lz_block_scan(sum, tmp, &total);
 #pragma unroll
     for (u32 j = 0; j < LZ_SCAN_PER_THREAD; ++j) {
         if (at + j < n) hist[at + j] = run;
@@ -102,22 +97,24 @@ __global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_blocks(u32 *hist, u
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_block_sums(u32 *block_sums, u64 n) {
-    __shared__ u32 tmp[LZ_SCAN_THREADS];
-    u32 carry = 0;
+template <class V>
+__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_block_sums(V *block_sums, u64 n) {
+    __shared__ V tmp[LZ_SCAN_THREADS];
+    V carry = 0;
     for (u64 at = 0; at < n; at += LZ_SCAN_THREADS) {
         const u64 i = at + threadIdx.x;
-        const u32 v = i < n ? block_sums[i] : 0u;
-        u32 total;
-        const u32 ex = lz_block_scan(v, tmp, &total);
+        const V v = i < n ? block_sums[i] : V(0);
+        V total;
+        const V ex = lz_block_scan(v, tmp, &total);
         if (i < n) block_sums[i] = carry + ex;
         carry += total;
     }
 }
 
-__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_add(u32 *hist, u64 n, const u32 *block_sums) {
+template <class V>
+__global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_add(V *hist, u64 n, const V *block_sums) {
     const u64 at = ((u64)blockIdx.x * LZ_SCAN_THREADS + threadIdx.x) * LZ_SCAN_PER_THREAD;
-    const u32 add = block_sums[blockIdx.x];
+    const V add = block_sums[blockIdx.x];
 #pragma unroll
     for (u32 j = 0; j < LZ_SCAN_PER_THREAD; ++j)
         if (at + j < n) hist[at + j] += add;
@@ -214,49 +211,6 @@ __global__ __launch_bounds__(256) void lz77_candidate_bitmap(const u8 *win, u64 
 }
 
 // ---- parse -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 lz_readlane64(u64 v, u32 lane) {
-    const u32 lo = __builtin_amdgcn_readlane((int)(u32)v, (int)lane);
-    const u32 hi = __builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)lane);
-    return ((u64)hi << 32) | lo;
-}
-
-// first set bit in [from, to) of the bitmap, or `to`: 64 words per step, one per lane (wave-uniform result)
-__device__ __forceinline__ u64 lz_next_bit(const u64 *bitmap, u64 from, u64 to) {
-    if (from >= to) return to;
-    const u64 w_first = from >> 6, w_last = (to - 1) >> 6;
-    for (u64 wb = w_first; wb <= w_last; wb += SCL_WAVE) {
-        const u64 wi = wb + lz_lane();
-        u64 word = wi <= w_last ? bitmap[wi] : 0ull;
-        if (wi == w_first) word &= ~0ull << (from & 63);
-        if (wi == w_last && (to & 63)) word &= (1ull << (to & 63)) - 1;
-        const u64 hit = __ballot(word != 0);
-        if (hit) {
-            const u32 l = (u32)__builtin_ctzll(hit);
-            return (wb + l) * 64 + (u32)__builtin_ctzll(lz_readlane64(word, l));
-        }
-    }
-    return to;
-}
-
-__device__ __forceinline__ u64 lz_load8(const u8 *p) {
-    u64 v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-
-// largest l <= limit with a[0..l) == b[0..l), given that the first `known` bytes are equal; reads stay below a + limit
-// and b + limit
-__device__ __forceinline__ u32 lz_extend(const u8 *a, const u8 *b, u32 known, u32 limit) {
-    u32 len = known;
-    while (len + 8 <= limit) {
-        const u64 x = lz_load8(a + len) ^ lz_load8(b + len);
-        if (x) return len + ((u32)__builtin_ctzll(x) >> 3);
-        len += 8;
-    }
-    while (len < limit && a[len] == b[len]) ++len;
-    return len;
-}
-
 __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_parse(const u8 *win, u64 N, const u64 *win_off,
                                                                 const u32 *start, u32 n_streams, u32 L, u32 M,
                                                                 const u32 *order, const u32 *rank, const u64 *bitmap,
@@ -283,41 +237,8 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_parse(const u8 *win, u
             const u64 gp = lz_next_bit(bitmap, base + pos, g_stop);
             if (gp >= g_stop) break;
             const u32 p = (u32)(gp - base);
-            const u32 i = rank[gp];
-            const u64 key = lz_gram(win, gp, L);
-            // the newest occurrences may overlap p (q > p - L): at most L - 1, and they come first
-            bool near = false;
-            if (lane + 1 < L && lane < i) {
-                const u64 c = order[i - 1 - lane];
-                near = c >= base && c < gp && c + L > gp && lz_gram(win, c, L) == key;
-            }
-            const u32 skip = (u32)__popcll(__ballot(near));
-            u32 best_len = 0, best_q = 0;
-            for (u32 group = 0;; group += SCL_WAVE) {
-                const u32 nth = group + lane;  // this lane scores the nth most recent candidate
-                const u64 back = (u64)skip + nth;
-                bool ok = back < i && (M == 0 || nth < M);
-                u32 c = 0;
-                if (ok) {
-                    c = order[i - 1 - back];
-                    ok = c >= base && (u64)c + L <= gp && lz_gram(win, c, L) == key;
-                }
-                const u64 valid = __ballot(ok);
-                if (!(valid & 1ull)) break;
-                u64 score = 0;  // (length, 63 - lane): the maximum is the longest match, the lowest lane on ties
-                if (ok) score = ((u64)lz_extend(win + c, win + gp, L, n - p) << 6) | (63u - lane);
-                for (u32 d = 32; d; d >>= 1) {
-                    const u32 lo = __shfl_xor((u32)score, d), hi = __shfl_xor((u32)(score >> 32), d);
-                    const u64 other = ((u64)hi << 32) | lo;
-                    score = other > score ? other : score;
-                }
-                const u32 len = (u32)(score >> 6);
-                if (len > best_len) {  // an older group replaces only on strictly longer
-                    best_len = len;
-                    best_q = (u32)__builtin_amdgcn_readlane((int)c, (int)(63u - (u32)(score & 63)));
-                }
-                if (valid != ~0ull || (M != 0 && group + SCL_WAVE >= M)) break;
-            }
+            u32 best_q;
+            const u32 best_len = lz_score(win, base, gp, n - p, L, M, order, rank, &best_q);
             if (best_len == 0) {  // the bitmap promised a candidate: unreachable, and never a reason to spin
                 status |= SCL_ST_STATE;
                 break;
@@ -437,6 +358,17 @@ u32 lz_stream_passes(u64 n_streams) {  // bytes of a stream number; n_streams it
 
 }  // namespace
 
+template <class V>
+void lz77_scan_exclusive(V *data, u64 n, V *block_sums, hipStream_t st) {
+    const u32 blocks = (u32)((n + LZ_SCAN_BLOCK - 1) / LZ_SCAN_BLOCK);
+    if (!blocks) return;
+    hipLaunchKernelGGL(lz77_scan_blocks<V>, dim3(blocks), dim3(LZ_SCAN_THREADS), 0, st, data, n, block_sums);
+    hipLaunchKernelGGL(lz77_scan_block_sums<V>, dim3(1), dim3(LZ_SCAN_THREADS), 0, st, block_sums, (u64)blocks);
+    hipLaunchKernelGGL(lz77_scan_add<V>, dim3(blocks), dim3(LZ_SCAN_THREADS), 0, st, data, n, (const V *)block_sums);
+}
+template void lz77_scan_exclusive<u32>(u32 *, u64, u32 *, hipStream_t);
+template void lz77_scan_exclusive<u64>(u64 *, u64, u64 *, hipStream_t);
+
 extern "C" uint64_t scl_lz77_scratch_bytes(uint64_t total_bytes, uint64_t n_streams) {
     (void)n_streams;
     return lz77_scratch_layout(total_bytes).total;
@@ -483,11 +415,7 @@ extern "C" int scl_lz77_parse_batch(const scl_lz77_parse_args *a, void *stream) 
         for (u32 pass = 0; pass < passes; ++pass) {
             hipLaunchKernelGGL(lz77_sort_histogram, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, a->d_win, N,
                                a->d_win_off, n_streams, L, pass, in, hist, lay.n_tiles);
-            hipLaunchKernelGGL(lz77_scan_blocks, dim3((u32)lay.n_scan_blocks), dim3(LZ_SCAN_THREADS), 0, st, hist,
-                               lay.n_hist, sums);
-            hipLaunchKernelGGL(lz77_scan_block_sums, dim3(1), dim3(LZ_SCAN_THREADS), 0, st, sums, lay.n_scan_blocks);
-            hipLaunchKernelGGL(lz77_scan_add, dim3((u32)lay.n_scan_blocks), dim3(LZ_SCAN_THREADS), 0, st, hist,
-                               lay.n_hist, sums);
+            lz77_scan_exclusive(hist, lay.n_hist, sums, st);
             hipLaunchKernelGGL(lz77_sort_scatter, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, a->d_win, N,
                                a->d_win_off, n_streams, L, pass, in, out, pass + 1 == passes ? rank : nullptr, hist,
                                lay.n_tiles);
@@ -548,7 +476,9 @@ extern "C" int scl_lz77_parse_host(const uint8_t *h_window, uint64_t n, uint64_t
     SCL_REQUIRE(n < (1ull << 32) && start <= n && seq_cap < (1ull << 32), "%s: start <= n < 2^32 and seq_cap < 2^32", what);
     SCL_REQUIRE(lit_cap >= n - start, "%s: h_literals must hold the block (%llu bytes)", what,
                 (unsigned long long)(n - start));
-    const u64 scratch_bytes = scl_lz77_scratch_bytes(n, 1);
+    // a large block goes across the whole GPU (scl_lz77_wide.hip); the results are the same either way
+    const bool wide = n - start >= scl_lz77_wide_threshold() && max_matches >= 1 && max_matches <= 64;
+    const u64 scratch_bytes = wide ? scl_lz77_wide_scratch_bytes(n) : scl_lz77_scratch_bytes(n, 1);
     ScratchDev d_win, d_lit, d_seq, d_meta, d_scr;
     int rc;
     if ((rc = d_win.alloc(n)) || (rc = d_lit.alloc(n)) || (rc = d_seq.alloc(3 * seq_cap * 4)) ||
@@ -578,7 +508,28 @@ extern "C" int scl_lz77_parse_host(const uint8_t *h_window, uint64_t n, uint64_t
     a.d_status = &dm->status;
     a.d_scratch = d_scr.p;
     a.scratch_bytes = scratch_bytes;
-    if ((rc = scl_lz77_parse_batch(&a, nullptr))) return rc;
+    if (wide) {
+        scl_lz77_wide_parse_args w = {};
+        w.d_win = a.d_win;
+        w.n = n;
+        w.start = start;
+        w.min_match_length = min_match_length;
+        w.max_matches = max_matches;
+        w.seq_cap = a.seq_cap;
+        w.d_lit_count = a.d_lit_count;
+        w.d_match_len = a.d_match_len;
+        w.d_match_off = a.d_match_off;
+        w.d_literals = a.d_literals;
+        w.d_n_seq = a.d_n_seq;
+        w.d_n_lit = a.d_n_lit;
+        w.d_status = a.d_status;
+        w.d_scratch = a.d_scratch;
+        w.scratch_bytes = scratch_bytes;
+        rc = scl_lz77_parse_wide(&w, nullptr);
+    } else {
+        rc = scl_lz77_parse_batch(&a, nullptr);
+    }
+    if (rc) return rc;
     SCL_HIP_TRY(hipDeviceSynchronize());
     SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
     *n_seq = meta.n_seq;
@@ -602,10 +553,12 @@ extern "C" int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t c
                 "%s: null pointer argument", what);
     SCL_REQUIRE(cap < (1ull << 32) && have <= cap && n_seq < (1ull << 32) && n_lit < (1ull << 32),
                 "%s: have <= cap < 2^32, n_seq and n_lit < 2^32", what);
-    ScratchDev d_win, d_lit, d_seq, d_meta;
+    const bool wide = cap - have >= scl_lz77_wide_threshold();  // as in scl_lz77_parse_host
+    const u64 scratch_bytes = wide ? scl_lz77_wide_replay_scratch_bytes(n_seq, cap - have) : 0;
+    ScratchDev d_win, d_lit, d_seq, d_meta, d_scr;
     int rc;
     if ((rc = d_win.alloc(cap)) || (rc = d_lit.alloc(n_lit)) || (rc = d_seq.alloc(3 * n_seq * 4)) ||
-        (rc = d_meta.alloc(sizeof(LzMeta))))
+        (rc = d_meta.alloc(sizeof(LzMeta))) || (rc = d_scr.alloc(scratch_bytes)))
         return rc;
     LzMeta meta = {};
     meta.win_off[1] = cap;
@@ -639,7 +592,26 @@ extern "C" int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t c
     a.d_n_lit = &dm->n_lit;
     a.d_out_len = &dm->out_len;
     a.d_status = &dm->status;
-    if ((rc = scl_lz77_replay_batch(&a, nullptr))) return rc;
+    if (wide) {
+        scl_lz77_wide_replay_args w = {};
+        w.d_win = a.d_win;
+        w.have = have;
+        w.cap = cap;
+        w.d_lit_count = d_lc;
+        w.d_match_len = d_ml;
+        w.d_match_off = d_mo;
+        w.n_seq = n_seq;
+        w.d_literals = a.d_literals;
+        w.n_lit = n_lit;
+        w.d_out_len = a.d_out_len;
+        w.d_status = a.d_status;
+        w.d_scratch = d_scr.p;
+        w.scratch_bytes = scratch_bytes;
+        rc = scl_lz77_replay_wide(&w, nullptr);
+    } else {
+        rc = scl_lz77_replay_batch(&a, nullptr);
+    }
+    if (rc) return rc;
     SCL_HIP_TRY(hipDeviceSynchronize());
     SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
     *out_len = meta.out_len;

@@ -5,6 +5,13 @@ scaled to the batch.  Recorded, not gated: profiles/lz77_bench.txt.
 
     python tools/bench_lz77.py [--streams 4096] [--stream-kib 64] [--single-mib 16] [--steps 20] [--warmup 5]
                                [--single-steps N] [--single-warmup N] [--host-streams 64] [--out FILE]
+    python tools/bench_lz77.py --wide [--wide-kib 64,256,1024,4096,16384] [--out FILE]
+
+--wide times ONE stream on both paths in the same run -- the one-wave kernels (parse_batch / replay_batch of a batch of
+one) and the wide ones (parse_wide phase by phase, replay_wide) -- on the Markov source and on all-equal bytes, checks
+that both paths store the same sequences and literals and that the replay restores the input, and prints the ratios
+scl_lz77_wide_threshold() and the 10x gate at the largest size are read from.  The step count follows the time of a call:
+3 timed steps for a call of more than a second, up to 15 for short ones.
 
 Data: the first-order Markov source of bench_data.py over 16 symbols, one chain per stream (generated on the device).  The
 single stream is the first --single-mib MiB of the very same bytes, read as ONE window: its parse is one wavefront.
@@ -136,6 +143,93 @@ def run_shape(name, win, n_streams, stream_len, steps, warmup, dev, host_streams
     return lines
 
 
+def timed_to_fit(fn):
+    """median ms of fn: the first call is the warm-up and sets the number of timed steps"""
+    first = timed(fn, 1, 0)[0]
+    steps = 3 if first > 1000 else 7 if first > 50 else 15
+    ms = timed(fn, steps, 1 if first <= 1000 else 0)
+    return statistics.median(ms), steps
+
+
+def wide_shape_rows(source, win, dev):
+    """one stream of win.numel() bytes on both paths -> (lines, dict of medians in ms)"""
+    n = int(win.numel())
+    name = f"{source} 1 x {n >> 10} KiB"
+    win_off = torch.tensor([0, n], dtype=torch.int64, device=dev)
+    zero = torch.zeros(1, dtype=torch.int32, device=dev)
+    seq_cap = lz77.default_seq_cap(n, L)
+    scratch = torch.empty(lz77.scratch_bytes(n, 1), dtype=torch.uint8, device=dev)
+    one = lz77.parse_batch(win, win_off, zero, L, M, seq_cap, scratch=scratch)
+    wscratch = torch.empty(lz77.wide_scratch_bytes(n), dtype=torch.uint8, device=dev)
+    wide = lz77.parse_wide(win, 0, L, M, seq_cap=seq_cap, scratch=wscratch)
+    torch.cuda.synchronize()
+    n_seq, n_lit = int(one.n_seq[0]), int(one.n_lit[0])
+    same = bool(int(wide.n_seq[0]) == n_seq and int(wide.n_lit[0]) == n_lit and int(one.status[0]) == 0 and
+                int(wide.status[0]) == 0 and torch.equal(wide.literal_count[0, :n_seq], one.literal_count[0, :n_seq]) and
+                torch.equal(wide.match_length[0, :n_seq], one.match_length[0, :n_seq]) and
+                torch.equal(wide.match_offset[0, :n_seq], one.match_offset[0, :n_seq]) and
+                torch.equal(wide.literals[:n_lit], one.literals[:n_lit]))
+    out_one, out_wide = torch.zeros_like(win), torch.zeros_like(win)
+    rscratch = torch.empty(lz77.wide_replay_scratch_bytes(n_seq, n), dtype=torch.uint8, device=dev)
+
+    def parse_phase(mask):
+        return lambda: lz77.parse_wide(win, 0, L, M, scratch=wscratch, out=wide, phases=mask)
+
+    calls = (("one-wave index", lambda: lz77.parse_batch(win, win_off, zero, L, M, seq_cap, scratch=scratch, out=one,
+                                                         phases=lib.LZ77_INDEX)),
+             ("one-wave parse", lambda: lz77.parse_batch(win, win_off, zero, L, M, seq_cap, scratch=scratch, out=one,
+                                                         phases=lib.LZ77_PARSE)),
+             ("one-wave replay", lambda: lz77.replay_batch(out_one, win_off, zero, one.literal_count, one.match_length,
+                                                           one.match_offset, one.n_seq, one.literals, one.lit_off, one.n_lit)),
+             ("wide index", parse_phase(lib.LZ77_WIDE_INDEX)), ("wide score", parse_phase(lib.LZ77_WIDE_SCORE)),
+             ("wide walk", parse_phase(lib.LZ77_WIDE_WALK)), ("wide emit", parse_phase(lib.LZ77_WIDE_EMIT)),
+             ("wide replay", lambda: lz77.replay_wide(out_wide, 0, wide.literal_count, wide.match_length, wide.match_offset,
+                                                      n_seq, wide.literals, n_lit, scratch=rscratch)))
+    med, lines = {}, []
+    for what, fn in calls:
+        med[what], steps = timed_to_fit(fn)
+        lines.append(f"{name:26s} {what:16s}: median {med[what]:10.3f} ms over {steps:2d} steps  "
+                     f"{n / med[what] / 1e6:9.4f} GB/s of input")
+        print(lines[-1], flush=True)
+    torch.cuda.synchronize()
+    back = bool(torch.equal(out_one, win) and torch.equal(out_wide, win))
+    med["wide parse"] = med["wide score"] + med["wide walk"] + med["wide emit"]
+    lines.append(f"{name:26s} {n_seq} sequences, {n_lit} literals; wide parse = score + walk + emit = "
+                 f"{med['wide parse']:.3f} ms, the walk {100 * med['wide walk'] / med['wide parse']:.1f} % of it; one-wave / wide: "
+                 f"parse {med['one-wave parse'] / med['wide parse']:.2f}x, replay "
+                 f"{med['one-wave replay'] / med['wide replay']:.2f}x; same sequences and literals on both paths: "
+                 f"{'yes' if same else 'NO'}, round trip on both: {'ok' if back else 'FAILED'}")
+    print(lines[-1], flush=True)
+    return lines, med
+
+
+def run_wide(sizes_kib, dev):
+    tile, cap = lz77.wide_shape()
+    lines = [f"lz77 wide bench: ONE stream, one-wave kernels vs wide kernels in the same run; min_match_length {L}, "
+             f"max_num_matches_considered {M}, tile {tile}, cap {cap}, threshold {lz77.wide_threshold()} bytes, HIP events, "
+             f"{torch.cuda.get_device_name(0)}", f"kernels: {', '.join(lz77.wide_kernel_names())}"]
+    print("\n".join(lines), flush=True)
+    top = max(sizes_kib) << 10
+    markov = bench_data.markov1_chunks_device(16, max(top >> 16, 1), min(top, 1 << 16), 77, dev).reshape(-1)
+    sources = (("markov", markov), ("all-equal", torch.full((top,), 7, dtype=torch.uint8, device=dev)))
+    ratios = {}
+    for source, data in sources:
+        for kib in sizes_kib:
+            rows, med = wide_shape_rows(source, data[: kib << 10].contiguous(), dev)
+            lines += rows
+            ratios[(source, kib)] = (med["one-wave parse"] / med["wide parse"], med["one-wave replay"] / med["wide replay"])
+    kib = max(sizes_kib)
+    p, r = ratios[("markov", kib)]
+    lines.append(f"gate at {kib} KiB on the Markov source: wide parse {p:.1f}x, wide replay {r:.1f}x the one-wave path "
+                 f"(10x each is asked): {'met' if p >= 10 and r >= 10 else 'MISSED'}")
+    for what, i in (("parse", 0), ("replay", 1)):
+        ok = [k for k in sizes_kib if all(ratios[(s, j)][i] > 1 for s, _ in sources for j in sizes_kib if j >= k)]
+        lines.append(f"wide {what} is faster on both sources from {min(ok)} KiB on" if ok else
+                     f"wide {what} is not faster on both sources at the largest size")
+    print("\n".join(lines[-3:]), flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=4096)
@@ -147,9 +241,17 @@ def main():
     ap.add_argument("--single-warmup", type=int, default=None)
     ap.add_argument("--host-streams", type=int, default=64)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--wide-kib", default="64,256,1024,4096,16384")
     args = ap.parse_args()
     lib.require_device()
     dev = torch.device("cuda:0")
+    if args.wide:
+        text = "\n".join(run_wide([int(k) for k in args.wide_kib.split(",")], dev))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     stream_len = args.stream_kib << 10
     single_len = args.single_mib << 20
     assert single_len <= args.streams * stream_len
