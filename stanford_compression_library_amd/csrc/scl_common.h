@@ -51,6 +51,17 @@ static inline u32 scl_bit_width_u64(u64 x) {  // get_bit_width, bitarray_utils.p
 
 static inline u64 scl_round_up(u64 x, u64 a) { return (x + a - 1) / a * a; }
 
+// Carves one scratch buffer into parts: take(bytes) -> the part's byte offset; every part starts on a 256-byte boundary,
+// an empty one takes 256 bytes all the same.  `at` ends up as the bytes needed.
+struct SclCarver {
+    u64 at = 0;
+    u64 take(u64 bytes) {
+        const u64 here = at;
+        at += scl_round_up(bytes ? bytes : 1, 256);
+        return here;
+    }
+};
+
 // One model handle = one device: its tables live in the HBM of the device that was current at *_model_create.
 // The batch entry points launch on the CURRENT device, so they refuse a handle made on another one (SCL_E_PARAM)
 // instead of dereferencing a foreign device's pointers.  (scl_core.hip)

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "scl_common.h"
+#include "scl_scan.h"
 
 // ---- errors ---------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -186,7 +187,7 @@ __device__ __forceinline__ u64 cp_record_bytes(u32 nbits, int mode) {
 // pass 1: per-tile exclusive scan of record sizes -> d_off (tile-local), d_tile_sum
 __global__ void __launch_bounds__(CP_THREADS) cp_scan_tiles(const u32 *__restrict__ nbits, u64 n, int mode,
                                                            u64 *__restrict__ off, u64 *__restrict__ tile_sum) {
-    __shared__ u64 s_part[CP_THREADS];
+    __shared__ u64 s_wave[CP_THREADS / SCL_WAVE];
     const u64 base = (u64)blockIdx.x * CP_TILE + (u64)threadIdx.x * CP_ITEMS;
     u64 v[CP_ITEMS], run = 0;
     for (int i = 0; i < CP_ITEMS; ++i) {
@@ -194,47 +195,21 @@ __global__ void __launch_bounds__(CP_THREADS) cp_scan_tiles(const u32 *__restric
         v[i] = run;
         run += (idx < n) ? cp_record_bytes(nbits[idx], mode) : 0;
     }
-    s_part[threadIdx.x] = run;
-    __syncthreads();
-    // Hillis-Steele over the 256 per-thread sums
-    for (u32 d = 1; d < CP_THREADS; d <<= 1) {
-        u64 t = (threadIdx.x >= d) ? s_part[threadIdx.x - d] : 0;
-        __syncthreads();
-        s_part[threadIdx.x] += t;
-        __syncthreads();
-    }
-    const u64 excl = s_part[threadIdx.x] - run;
+    u64 total;
+    const u64 excl = scl_block_scan_excl<u64, CP_THREADS, SclScanSum>(run, s_wave, &total);
     for (int i = 0; i < CP_ITEMS; ++i) {
         u64 idx = base + i;
         if (idx < n) off[idx] = excl + v[i];
     }
-    if (threadIdx.x == CP_THREADS - 1) tile_sum[blockIdx.x] = s_part[threadIdx.x];
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
 // pass 2: one workgroup scans the tile sums in place (exclusive) and stores the grand total
 __global__ void __launch_bounds__(CP_THREADS) cp_scan_sums(u64 *__restrict__ tile_sum, u64 n_tiles,
                                                           u64 *__restrict__ total_out) {
-    __shared__ u64 s_part[CP_THREADS];
-    __shared__ u64 s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (u64 start = 0; start < n_tiles; start += CP_THREADS) {
-        u64 idx = start + threadIdx.x;
-        u64 mine = (idx < n_tiles) ? tile_sum[idx] : 0;
-        s_part[threadIdx.x] = mine;
-        __syncthreads();
-        for (u32 d = 1; d < CP_THREADS; d <<= 1) {
-            u64 t = (threadIdx.x >= d) ? s_part[threadIdx.x - d] : 0;
-            __syncthreads();
-            s_part[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (idx < n_tiles) tile_sum[idx] = s_carry + s_part[threadIdx.x] - mine;
-        __syncthreads();
-        if (threadIdx.x == CP_THREADS - 1) s_carry += s_part[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total_out = s_carry;
+    __shared__ u64 s_wave[CP_THREADS / SCL_WAVE];
+    const u64 total = scl_block_scan_array<u64, CP_THREADS, SclScanSum>(tile_sum, n_tiles, s_wave);
+    if (threadIdx.x == 0) *total_out = total;
 }
 
 // pass 3: add tile bases; entry n = total

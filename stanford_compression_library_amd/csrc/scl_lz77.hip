@@ -57,29 +57,11 @@ __global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_histogram(const u8 
     hist[(u64)threadIdx.x * n_tiles + blockIdx.x] = cnt[threadIdx.x];
 }
 
-// exclusive scan of 256 values, one per thread; *total = their sum.  tmp: 256 words of LDS.
-template <class V>
-__device__ __forceinline__ V lz_block_scan(V v, V *tmp, V *total) {
-    const u32 t = threadIdx.x;
-    tmp[t] = v;
-    __syncthreads();
-    for (u32 d = 1; d < LZ_SCAN_THREADS; d <<= 1) {
-        const V add = t >= d ? tmp[t - d] : V(0);
-        __syncthreads();
-        tmp[t] += add;
-        __syncthreads();
-    }
-    const V incl = tmp[t];
-    *total = tmp[LZ_SCAN_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
 // the scan of the tile histograms in three kernels: every block scans its 2048 entries, one workgroup scans the block
-// sums, every block adds its offset
+// sums, every block adds its offset (the scans across a workgroup: scl_scan.h)
 template <class V>
 __global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_blocks(V *hist, u64 n, V *block_sums) {
-    __shared__ V tmp[LZ_SCAN_THREADS];
+    __shared__ V s_wave[LZ_SCAN_THREADS / SCL_WAVE];
     const u64 at = ((u64)blockIdx.x * LZ_SCAN_THREADS + threadIdx.x) * LZ_SCAN_PER_THREAD;
     V v[LZ_SCAN_PER_THREAD], sum = 0;
 #pragma unroll
@@ -88,7 +70,7 @@ __global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_blocks(V *hist, u64
         sum += v[j];
     }
     V total;
-    V run = lz_block_scan(sum, tmp, &total);
+    V run = scl_block_scan_excl<V, LZ_SCAN_THREADS, SclScanSum>(sum, s_wave, &total);
 #pragma unroll
     for (u32 j = 0; j < LZ_SCAN_PER_THREAD; ++j) {
         if (at + j < n) hist[at + j] = run;
@@ -99,16 +81,8 @@ __global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_blocks(V *hist, u64
 
 template <class V>
 __global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_block_sums(V *block_sums, u64 n) {
-    __shared__ V tmp[LZ_SCAN_THREADS];
-    V carry = 0;
-    for (u64 at = 0; at < n; at += LZ_SCAN_THREADS) {
-        const u64 i = at + threadIdx.x;
-        const V v = i < n ? block_sums[i] : V(0);
-        V total;
-        const V ex = lz_block_scan(v, tmp, &total);
-        if (i < n) block_sums[i] = carry + ex;
-        carry += total;
-    }
+    __shared__ V s_wave[LZ_SCAN_THREADS / SCL_WAVE];
+    (void)scl_block_scan_array<V, LZ_SCAN_THREADS, SclScanSum>(block_sums, n, s_wave);
 }
 
 template <class V>

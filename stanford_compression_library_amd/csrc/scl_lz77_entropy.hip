@@ -23,20 +23,6 @@ namespace {
 #define LZE_STAGE_WORDS 96u  // 64 codewords of at most 43 bits behind at most 31 pending bits: 87 words
 #define LZE_MAX_GRID (1u << 20)
 
-__device__ __forceinline__ u32 lze_lane() { return threadIdx.x & (SCL_WAVE - 1); }
-
-__device__ __forceinline__ u32 lze_excl_scan(u32 v, u32 *total) {
-    const u32 lane = lze_lane();
-    u32 incl = v;
-#pragma unroll
-    for (u32 d = 1; d < SCL_WAVE; d <<= 1) {
-        const u32 up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    *total = __shfl(incl, SCL_WAVE - 1);
-    return incl - v;
-}
-
 __device__ __forceinline__ u64 lze_wave_sum(u64 v) {
 #pragma unroll
     for (u32 d = 32; d; d >>= 1) {
@@ -85,7 +71,7 @@ struct LzeWriter {
         slot = slot_;
         slot_bytes = slot_bytes_;
         pos = 0;
-        for (u32 w = lze_lane(); w < LZE_STAGE_WORDS; w += SCL_WAVE) stage[w] = 0;
+        for (u32 w = lz_lane(); w < LZE_STAGE_WORDS; w += SCL_WAVE) stage[w] = 0;
         __syncthreads();
     }
     __device__ __forceinline__ void store_word(u64 w, u32 v) {
@@ -93,7 +79,7 @@ struct LzeWriter {
     }
     __device__ __forceinline__ void append(u64 val, u32 len) {
         u32 total;
-        const u32 off = lze_excl_scan(len, &total);
+        const u32 off = scl_wave_scan_excl<u32, SclScanSum>(len, &total);
         if (total == 0) return;  // wave-uniform
         const u32 pend = (u32)(pos & 31);
         if (len) {
@@ -108,19 +94,19 @@ struct LzeWriter {
         __syncthreads();
         const u32 n_full = (pend + total) >> 5;
         const u64 first = pos >> 5;
-        for (u32 w = lze_lane(); w < n_full; w += SCL_WAVE) store_word(first + w, stage[w]);
+        for (u32 w = lz_lane(); w < n_full; w += SCL_WAVE) store_word(first + w, stage[w]);
         const u32 carry = stage[n_full];
         __syncthreads();
-        for (u32 w = lze_lane(); w <= n_full; w += SCL_WAVE) stage[w] = w == 0 ? carry : 0u;
+        for (u32 w = lz_lane(); w <= n_full; w += SCL_WAVE) stage[w] = w == 0 ? carry : 0u;
         __syncthreads();
         pos += total;
     }
     __device__ __forceinline__ void header(u32 v) {
-        const bool first = lze_lane() == 0;
+        const bool first = lz_lane() == 0;
         append(first ? v : 0u, first ? 32u : 0u);
     }
     __device__ __forceinline__ void finish() {  // the last partial word, zero bits behind the stream
-        if ((pos & 31) && lze_lane() == 0) store_word(pos >> 5, stage[0]);
+        if ((pos & 31) && lz_lane() == 0) store_word(pos >> 5, stage[0]);
     }
 };
 
@@ -144,7 +130,7 @@ __global__ __launch_bounds__(LZE_THREADS) void lz77_entropy_encode(
     __shared__ LzeBigTree big;
     __shared__ u32 stage[LZE_STAGE_WORDS];
     __shared__ u32 n_leaves[4], counts_size[4], values_size[4], flags;
-    const u32 lane = lze_lane();
+    const u32 lane = lz_lane();
     const u32 A = 32 + o;  // a sequence field's alphabet
 
     for (u64 s = blockIdx.x; s < n_streams; s += gridDim.x) {
@@ -332,7 +318,7 @@ __global__ __launch_bounds__(LZE_THREADS) void lz77_entropy_decode(
     __shared__ u32 hist[LZ_HUFF_MAX_K];
     __shared__ LzeBigTree tree;
     __shared__ u32 sh_m, sh_count, sh_status, sh_resid;
-    const u32 lane = lze_lane();
+    const u32 lane = lz_lane();
 
     for (u64 s = blockIdx.x; s < n_streams; s += gridDim.x) {
         const u64 at = bit_off[s], nbits = in_nbits[s], l_at = lit_off[s];
@@ -477,7 +463,7 @@ __global__ __launch_bounds__(LZE_THREADS) void lz77_entropy_decode(
                         const u32 b = live ? row[k0 + lane] : 0u;
                         const u32 log = b >= o ? b - o : 0u;
                         u32 total;
-                        const u32 off = lze_excl_scan(log, &total);
+                        const u32 off = scl_wave_scan_excl<u32, SclScanSum>(log, &total);
                         if (pos + total > nbits) {
                             status = SCL_ST_TRUNCATED;
                             break;

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "scl_common.h"
+#include "scl_scan.h"
 
 // ---- the index sort: a stable LSD radix sort of the POSITIONS, 8-bit digits ------------------------------------------
 // Nothing but the permutation moves: the digit of position v in gram pass d is the byte win[v + d] (0 past the buffer),
@@ -32,24 +33,19 @@ static inline Lz77Scratch lz77_scratch_layout(u64 N) {
     s.n_hist = 256 * s.n_tiles;
     s.n_scan_blocks = (s.n_hist + LZ_SCAN_BLOCK - 1) / LZ_SCAN_BLOCK;
     s.n_words = (N + 63) / 64;
-    u64 at = 0;
-    auto take = [&](u64 bytes) {
-        const u64 here = at;
-        at += scl_round_up(bytes ? bytes : 1, 256);
-        return here;
-    };
-    s.order_a = take(N * 4);
-    s.order_b = take(N * 4);
-    s.rank = take(N * 4);
-    s.bitmap = take(s.n_words * 8);
-    s.hist = take(s.n_hist * 4);
-    s.block_sums = take(s.n_scan_blocks * 4);
-    s.total = at;
+    SclCarver c;
+    s.order_a = c.take(N * 4);
+    s.order_b = c.take(N * 4);
+    s.rank = c.take(N * 4);
+    s.bitmap = c.take(s.n_words * 8);
+    s.hist = c.take(s.n_hist * 4);
+    s.block_sums = c.take(s.n_scan_blocks * 4);
+    s.total = c.at;
     return s;
 }
 
-// Exclusive scan of data[0..n) in place, three kernels on `st` (scl_lz77.hip); block_sums: ceil(n / LZ_SCAN_BLOCK) values.
-// V: u32 or u64.
+// Exclusive scan of data[0..n) in place, three kernels on `st` (scl_lz77.hip, over the workgroup scans of scl_scan.h);
+// block_sums: ceil(n / LZ_SCAN_BLOCK) values.  V: u32 or u64.
 template <class V>
 void lz77_scan_exclusive(V *data, u64 n, V *block_sums, hipStream_t st);
 

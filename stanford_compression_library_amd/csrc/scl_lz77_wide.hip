@@ -58,22 +58,17 @@ WideScratch wide_scratch_layout(u64 n) {
     WideScratch s;
     s.index = lz77_scratch_layout(n);
     s.n_tiles = (n + LZ_WIDE_TILE - 1) / LZ_WIDE_TILE;
-    u64 at = s.index.total;
-    auto take = [&](u64 bytes) {
-        const u64 here = at;
-        at += scl_round_up(bytes ? bytes : 1, 256);
-        return here;
-    };
-    s.slen = take(n * 4);
-    s.sq = take(n * 4);
-    s.exit = take(n * 4);
-    s.entry = take(s.n_tiles * 4);
-    s.cnt = take((s.n_tiles + 1) * 4);  // one entry more than tiles: the exclusive scan leaves the total there
-    s.msum = take((s.n_tiles + 1) * 4);
-    s.lend = take((s.n_tiles + 1) * 4);
-    s.sums = take(((s.n_tiles + 1 + LZ_SCAN_BLOCK - 1) / LZ_SCAN_BLOCK) * 4);
-    s.meta = take(sizeof(WideMeta));
-    s.total = at;
+    SclCarver c{s.index.total};
+    s.slen = c.take(n * 4);
+    s.sq = c.take(n * 4);
+    s.exit = c.take(n * 4);
+    s.entry = c.take(s.n_tiles * 4);
+    s.cnt = c.take((s.n_tiles + 1) * 4);  // one entry more than tiles: the exclusive scan leaves the total there
+    s.msum = c.take((s.n_tiles + 1) * 4);
+    s.lend = c.take((s.n_tiles + 1) * 4);
+    s.sums = c.take(((s.n_tiles + 1 + LZ_SCAN_BLOCK - 1) / LZ_SCAN_BLOCK) * 4);
+    s.meta = c.take(sizeof(WideMeta));
+    s.total = c.at;
     return s;
 }
 
@@ -90,18 +85,13 @@ struct ReplayScratch {
 
 ReplayScratch replay_scratch_layout(u64 n_seq, u64 grow) {
     ReplayScratch s;
-    u64 at = 0;
-    auto take = [&](u64 bytes) {
-        const u64 here = at;
-        at += scl_round_up(bytes ? bytes : 1, 256);
-        return here;
-    };
-    s.lit_sum = take((n_seq + 1) * 8);
-    s.all_sum = take((n_seq + 1) * 8);
-    s.sums = take(((n_seq + 1 + LZ_SCAN_BLOCK - 1) / LZ_SCAN_BLOCK) * 8);
-    s.root = take(grow * 4);
-    s.meta = take(sizeof(ReplayMeta));
-    s.total = at;
+    SclCarver c;
+    s.lit_sum = c.take((n_seq + 1) * 8);
+    s.all_sum = c.take((n_seq + 1) * 8);
+    s.sums = c.take(((n_seq + 1 + LZ_SCAN_BLOCK - 1) / LZ_SCAN_BLOCK) * 8);
+    s.root = c.take(grow * 4);
+    s.meta = c.take(sizeof(ReplayMeta));
+    s.total = c.at;
     return s;
 }
 
@@ -272,25 +262,8 @@ __global__ __launch_bounds__(256) void lz77w_tile_emit(const u8 *win, u32 n, u32
 
 // exclusive running maximum of a[0..n) in place, one workgroup
 __global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77w_scan_max(u32 *a, u64 n) {
-    __shared__ u32 tmp[LZ_SCAN_THREADS];
-    const u32 t = threadIdx.x;
-    u32 carry = 0;
-    for (u64 at = 0; at < n; at += LZ_SCAN_THREADS) {
-        const u64 i = at + t;
-        tmp[t] = i < n ? a[i] : 0u;
-        __syncthreads();
-        for (u32 d = 1; d < LZ_SCAN_THREADS; d <<= 1) {
-            const u32 other = t >= d ? tmp[t - d] : 0u;
-            __syncthreads();
-            if (other > tmp[t]) tmp[t] = other;
-            __syncthreads();
-        }
-        const u32 below = t ? tmp[t - 1] : 0u;
-        const u32 top = tmp[LZ_SCAN_THREADS - 1];
-        if (i < n) a[i] = below > carry ? below : carry;
-        if (top > carry) carry = top;
-        __syncthreads();
-    }
+    __shared__ u32 s_wave[LZ_SCAN_THREADS / SCL_WAVE];
+    (void)scl_block_scan_array<u32, LZ_SCAN_THREADS, SclScanMax>(a, n, s_wave);
 }
 
 // cnt[n_tiles], msum[n_tiles]: the totals.  n_lit of a block with too many sequences comes from lz77w_tile_emit.

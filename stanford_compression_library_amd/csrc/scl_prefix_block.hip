@@ -38,6 +38,7 @@
 
 #include "scl_entry.h"
 #include "scl_prefix_internal.h"
+#include "scl_scan.h"
 
 #define PFB_THREADS 256
 #define PFB_PER_THREAD 16u
@@ -55,30 +56,6 @@
 #define PFB_END_STATE 2u  // the codeword that starts at `end` walks into a missing child
 // one u32 per subsequence: start - i*S (0..31) | symbols << 6 (0..128) | how it ended << 15 | (end - i*S) << 17 (0..159)
 #define PFB_PACK(start_off, count, kind, end_off) ((start_off) | ((count) << 6) | ((kind) << 15) | ((end_off) << 17))
-
-// ---- block-wide exclusive scan (NT threads, all of them call) -------------------------------------------------------------
-template <typename T, int NT>
-__device__ __forceinline__ T pfb_block_scan(T v, T *s_wave /* [NT / 64] */, T &total) {
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (u32 o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (u32 i = 0; i < NT / 64; ++i) {
-        const T x = s_wave[i];
-        base += i < wave ? x : (T)0;
-        tot += x;
-    }
-    __syncthreads();  // s_wave may be written again
-    total = tot;
-    return base + incl - v;
-}
 
 // ---- encode ---------------------------------------------------------------------------------------------------------------
 struct PfbEncScratch {  // head of the encoder's scratch; u64 tile_bits[n_tiles] follows at byte 64
@@ -143,7 +120,7 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
     uint2 e[PFB_PER_THREAD];
     u32 bad = 0, total;
     const u32 bits = pfb_load_codes<SYM>(P, s_enc, sym, n, (u64)blockIdx.x * PFB_TILE + tid * PFB_PER_THREAD, e, bad);
-    (void)pfb_block_scan<u32, PFB_THREADS>(bits, s_wave, total);
+    (void)scl_block_scan_excl<u32, PFB_THREADS, SclScanSum>(bits, s_wave, &total);
     const int any_bad = __syncthreads_or((int)bad);
     if (tid == 0) {
         tile_bits[blockIdx.x] = total;
@@ -151,25 +128,11 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
     }
 }
 
-// ONE workgroup.  v[0..n) becomes its exclusive prefix sum; returns the total to every thread.
-__device__ __forceinline__ u64 pfb_scan_array(u64 *__restrict__ v, u64 n, u64 *s_wave) {
-    u64 carry = 0;
-    for (u64 base = 0; base < n; base += PFB_SCAN_THREADS) {
-        const u64 i = base + threadIdx.x;
-        const u64 x = i < n ? v[i] : 0;
-        u64 total;
-        const u64 ex = pfb_block_scan<u64, PFB_SCAN_THREADS>(x, s_wave, total);
-        if (i < n) v[i] = carry + ex;
-        carry += total;
-    }
-    return carry;
-}
-
 __global__ void __launch_bounds__(PFB_SCAN_THREADS)
     pfb_scan_tiles_kernel(u64 *__restrict__ tile_bits, u64 n_tiles, u64 out_cap_bytes, PfbEncScratch *__restrict__ head,
                           u64 *__restrict__ nbits, u32 *__restrict__ status) {
     __shared__ u64 s_wave[PFB_SCAN_THREADS / 64];
-    const u64 total = pfb_scan_array(tile_bits, n_tiles, s_wave);
+    const u64 total = scl_block_scan_array<u64, PFB_SCAN_THREADS, SclScanSum>(tile_bits, n_tiles, s_wave);
     if (threadIdx.x == 0) {
         const bool fits = (total + 7) / 8 <= out_cap_bytes;
         head->fits = fits ? 1u : 0u;
@@ -193,7 +156,7 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
     uint2 e[PFB_PER_THREAD];
     u32 bad = 0, tile_total;
     const u32 bits = pfb_load_codes<SYM>(P, s_enc, sym, n, (u64)blockIdx.x * PFB_TILE + tid * PFB_PER_THREAD, e, bad);
-    const u32 mine = pfb_block_scan<u32, PFB_THREADS>(bits, s_wave, tile_total);
+    const u32 mine = scl_block_scan_excl<u32, PFB_THREADS, SclScanSum>(bits, s_wave, &tile_total);
     const u64 base = tile_off[blockIdx.x];
     const u32 r = (u32)(base & 31u);
     // the thread's codewords are contiguous bits: whole words leave as they fill; the first and the last one are shared
@@ -425,7 +388,7 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
     __syncthreads();
     const u32 first_cut = s_first_cut;
     u64 total;
-    (void)pfb_block_scan<u64, PFB_THREADS>(active && tid <= first_cut ? (u64)count : 0ull, s_wave, total);
+    (void)scl_block_scan_excl<u64, PFB_THREADS, SclScanSum>(active && tid <= first_cut ? (u64)count : 0ull, s_wave, &total);
     if (tid == first_cut) sc.group_end[group] = ((group_bit + end) << 2) | kind;
     if (tid == 0) {
         sc.group_count[group] = total;
@@ -455,7 +418,7 @@ __global__ void __launch_bounds__(PFB_SCAN_THREADS)
     if (mine != PFB_NONE64) atomicMin(&s_first, (unsigned long long)mine);
     __syncthreads();
     const u64 last_group = s_first;
-    const u64 total = pfb_scan_array(sc.group_count, last_group + 1, s_wave);
+    const u64 total = scl_block_scan_array<u64, PFB_SCAN_THREADS, SclScanSum>(sc.group_count, last_group + 1, s_wave);
     if (threadIdx.x == 0) {
         const u64 cut = sc.group_end[last_group];
         const u64 end = cut == PFB_NONE64 ? in_nbits : cut >> 2;
@@ -505,7 +468,7 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
     __syncthreads();
     const u32 count = active && tid <= s_first_cut ? (packed >> 6) & 511u : 0u;
     u64 total;
-    u64 index = group_first + pfb_block_scan<u64, PFB_THREADS>((u64)count, s_wave, total);
+    u64 index = group_first + scl_block_scan_excl<u64, PFB_THREADS, SclScanSum>((u64)count, s_wave, &total);
     const u32 shift = (u32)(first_bit & 31u);
     u32 pos = tid * PFB_SUB + (packed & 63u);
     for (u32 k = 0; k < count && index < out_cap; ++k, ++index) {

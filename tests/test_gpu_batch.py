@@ -1076,6 +1076,39 @@ def test_compact_long_and_tiny_streams(framed, dev):
         assert np.array_equal(dense[offsets[c]:offsets[c + 1]], e), f"record {c} (len {lens[c]})"
 
 
+def test_compact_offsets_past_256_tiles_of_2048_records(dev):
+    """The offsets of scl_streams_compact are a scan in three kernels: every tile of 2048 records scans its sizes, ONE
+    workgroup scans the tile sums in trips of 256 with a carried prefix, every record adds its tile's base.  257 tiles
+    and one record more: the second trip of the one workgroup, a last tile of one record, and entry n (the total).  The
+    batch is made by hand -- 16-byte slots of random bytes, 0..128 of their bits a stream -- so the sizes come from the
+    host alone.  A striped batch launches the same three kernels, and slots of 16 bytes lie where the linear ones do."""
+    n, stride = 256 * 2048 + 2048 + 1, 16
+    rng = np.random.default_rng(61)
+    slots = rng.integers(0, 256, (n, stride), dtype=np.uint8)
+    nbits = rng.integers(0, 8 * stride + 1, n).astype(np.int64)
+    n_pad = (n + 63) // 64 * 64  # a striped batch holds whole waves of slots
+    data = torch.zeros(n_pad * stride + 16, dtype=torch.uint8, device=dev)
+    data[: n * stride] = torch.from_numpy(slots.reshape(-1)).to(dev)
+    make = lambda d, layout: models.EncodedBatch(  # noqa: E731
+        d, stride, torch.arange(n, dtype=torch.int64, device=dev) * (8 * stride),
+        torch.from_numpy(nbits.astype(np.int32)).to(dev), torch.zeros(n, dtype=torch.int32, device=dev), n, layout)
+    enc, striped = make(data[: n * stride + 16], "linear"), make(data, "striped")
+    dense_bytes = (nbits + 7) // 8
+    want_dense = np.concatenate([[0], np.cumsum(dense_bytes)])
+    want_framed = np.concatenate([[0], np.cumsum(4 + (nbits + 3 + 7) // 8)])
+    dense, offsets = models.compact(enc)
+    _, framed_offsets = models.compact(enc, framed=True)
+    assert np.array_equal(offsets.cpu().numpy(), want_dense), "dense offsets"
+    assert np.array_equal(framed_offsets.cpu().numpy(), want_framed), "framed offsets"
+    # every dense record: the slot's first ceil(nbits / 8) bytes, the bits behind the stream cleared
+    expect = slots[np.arange(stride)[None, :] < dense_bytes[:, None]]
+    cut = (nbits % 8 != 0)
+    expect[want_dense[1:][cut] - 1] &= (0xFF00 >> (nbits[cut] % 8)).astype(np.uint8)
+    assert np.array_equal(dense[: want_dense[-1]].cpu().numpy(), expect), "dense records"
+    dense_s, offsets_s = models.compact(striped)
+    assert torch.equal(offsets_s, offsets) and torch.equal(dense_s[: want_dense[-1]], dense[: want_dense[-1]]), "striped"
+
+
 def test_status_reporting_num_bits_out_kernels(dev):
     """scl_rans_fast_b.hip: a symbol outside the alphabet is flagged (KeyError in the reference), the other chunks
     are untouched, and a corrupted stream ends in a status bit, never in a crash."""

@@ -8,8 +8,8 @@ parse_batch on the same stream (rows, n_seq, literals, n_lit, status), replay_wi
 import numpy as np
 import pytest
 
-from lz77_helpers import ST_CAPACITY, markov1_stream, replay_restated
-from lz77_wide_helpers import all_cases, damage_cases, reference
+from lz77_helpers import ST_CAPACITY, markov1_long_stream, markov1_stream, replay_restated
+from lz77_wide_helpers import _noise, all_cases, damage_cases, reference
 from stanford_compression_library_amd.backend import lib as backend_lib
 from stanford_compression_library_amd.backend import lz77 as dev_lz77
 
@@ -164,6 +164,54 @@ def test_the_deepest_copy_chains(dev):
     seqs, lits = wide["rows"][: wide["n_seq"]], wide["literals"][: wide["n_lit"]]
     assert wide["status"] == 0 and wide["n_seq"] > len(w) // 8
     assert assert_replay(w[:0], seqs, lits, len(w), dev, "deep") == 0
+
+
+# ---- the carries of the scans (csrc/scl_scan.h): 2048 entries a scan block, 256 entries a trip of one workgroup ----------------
+SCAN_BLOCK, SCAN_TRIP = 2048, 256
+NOISE_TILES = ((255, 258), (2047, 2049))  # first and last tile of the stretches without a match
+
+
+def test_parse_across_the_carries_of_the_tile_scans(dev):
+    """2050 tiles: the sum scans of the per-tile sequence counts and matched bytes span two scan blocks, the running maximum
+    of the match ends takes nine trips.  The tiles on either side of trip border 256 and of scan block border 2048 have no
+    sequence of their own (noise over the Markov source), so what the tiles behind a border see -- where their literals
+    go, what the totals are -- can only be the carried prefix.  (There is no tile behind the second stretch: the window ends
+    in it, so the literal run to the end of the block and entry n_tiles, the totals, are what reads the second carry.)"""
+    n = (SCAN_BLOCK + 1) * T + 1
+    w = markov1_long_stream(n, 17)
+    rng = np.random.default_rng(44)
+    for first, last in NOISE_TILES:
+        w[first * T: (last + 1) * T] = _noise(rng, min((last + 1) * T, n) - first * T)
+    case = dict(name="carries", window=w, start=0, L=6, M=64)
+    wide, batch = parse_both(case, dev)
+    assert wide["status"] == 0 and batch["status"] == 0
+    assert_same_store(wide, batch, "carries")
+    n_seq, n_lit = wide["n_seq"], wide["n_lit"]
+    seqs, lits = wide["rows"][:n_seq], wide["literals"][:n_lit]
+    # the fixture: sequences on either side of both borders, none in the noise
+    assert n_seq > SCAN_BLOCK
+    ends = np.cumsum(seqs[:, 0] + seqs[:, 1])
+    tiles = (ends - seqs[:, 1]) // T  # the tile every sequence starts in
+    (a0, a1), (b0, b1) = NOISE_TILES
+    assert (tiles < SCAN_TRIP - 1).any() and ((tiles > a1) & (tiles < b0)).any()
+    assert not ((tiles >= a0) & (tiles <= a1)).any() and not (tiles >= b0).any()
+    assert n - int(ends[-1]) > (b1 - b0) * T and n_lit == n - int(seqs[:, 1].sum())
+    (got, out_len, status), (one, one_len, one_status) = replay_both(w[:0], seqs, lits, n, dev)
+    assert status == 0 and one_status == 0 and out_len == n and one_len == n
+    assert np.array_equal(got, w) and np.array_equal(one, w)
+
+
+def test_replay_across_the_carries_of_the_64_bit_scans(dev):
+    """258 scan blocks of sequences: the one workgroup that scans the block sums of the two 64-bit position scans takes a
+    second trip.  Every sequence is one literal and a match of 1..3 bytes at offset 1: the literal 2..4 times."""
+    n_seq = SCAN_TRIP * SCAN_BLOCK + SCAN_BLOCK + 1
+    lits = np.random.default_rng(45).integers(0, 256, n_seq).astype(np.uint8)
+    length = 1 + np.arange(n_seq) % 3
+    seqs = np.stack([np.ones(n_seq, np.int64), length, np.ones(n_seq, np.int64)], axis=1)
+    want = np.repeat(lits, 1 + length)
+    (got, out_len, status), (one, one_len, one_status) = replay_both(np.zeros(0, np.uint8), seqs, lits, want.size, dev)
+    assert status == 0 and out_len == want.size and np.array_equal(got, want)
+    assert one_status == 0 and one_len == want.size and np.array_equal(one, want)
 
 
 # ---- reuse -----------------------------------------------------------------------------------------------------------------

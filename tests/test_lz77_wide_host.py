@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from lz77_helpers import ST_CAPACITY, parse_restated, replay_restated
+from lz77_helpers import ST_CAPACITY, markov1_long_stream, markov1_stream, parse_restated, replay_restated
 from lz77_wide_helpers import (all_cases, cap_cases, damage_cases, parse_wide_restated, reference, replay_wide_restated,
                                sequence_positions, tile_cases)
 from stanford_compression_library_amd.backend import lib as backend_lib
@@ -166,3 +166,10 @@ def test_the_restated_replay_names_the_faults_as_the_rule_does():
     back, status, rounds = replay_wide_restated([], deep_seq, deep_lit)
     assert status == 0 and back.tolist() == next(c for c in CASES if c["name"] == "markov-L1-M1")["window"].tolist()
     assert rounds >= 3, "the deepest copy chains of the suite"
+
+
+def test_the_long_markov_source_is_the_markov_source():
+    """test_gpu_lz77_wide.py draws its 1 MiB window from markov1_long_stream: the same bytes, past a piece border too"""
+    n = (1 << 16) + 4097
+    assert np.array_equal(markov1_long_stream(n, 17), markov1_stream(n, 17))
+    assert np.array_equal(markov1_long_stream(300, 3), markov1_stream(300, 3))
