@@ -51,16 +51,13 @@ __device__ __forceinline__ u32 af_pk_sub(u32 a, u32 b) {
 // STAGED (round 4): completed words collect in 64 bytes of LDS per lane ([thread][64 bytes] at `lds_stage`) and leave as
 // whole 64-byte sectors, four back-to-back 16-byte stores -- for kernels that have the 16 KiB to spare.
 template <bool STAGED = false>
-struct AfWriterT {
-    u32 hi;    // pending bits, right-aligned (the oldest is the most significant), < 32 of them
-    u32 nacc;  // number of pending bits
+struct AfWriterT : SclFwdBits {  // the bit accumulator of scl_common.h; completed words go to emit()
     u32 *dst;
     u32 nwords;
     char *stage;
 
     __device__ __forceinline__ void init(u8 *slot, char *lds_stage = nullptr, u32 tid = 0) {
-        hi = 0;
-        nacc = 0;
+        SclFwdBits::init();
         nwords = 0;
         dst = reinterpret_cast<u32 *>(slot);
         stage = STAGED ? lds_stage + tid * 64 : nullptr;
@@ -85,35 +82,13 @@ struct AfWriterT {
         }
     }
     __device__ __forceinline__ void put(u32 v, u32 nb) {  // v < 2^nb, nb <= 32
-        // 32-bit arithmetic on purpose: see AnsFwdWriter::put (scl_ans_fast_io.h)
-        const u32 tot = nacc + nb;
-        if (tot >= 32) {
-            const u32 r = tot - 32;  // <= 31; nb - r = 32 - nacc
-            const u32 word = (r == 0) ? ((hi << (nb & 31)) | v) : ((hi << (nb - r)) | (v >> r));
-            emit(__builtin_bswap32(word));
-            hi = v & ((1u << r) - 1u);
-            nacc = r;
-        } else {
-            hi = (hi << nb) | v;
-            nacc = tot;
-        }
+        SclFwdBits::put(v, nb, [&](u32 word_be) { emit(word_be); });
     }
-    // put for the per-symbol field of the encoders (nb <= 32, nb = 0 allowed with v = 0): the pending bits and the field
-    // side by side in 64 bits, so that only the completed word is conditional -- no "which half" case split, no values
-    // merged after a branch (put above costs the lone wave ~8 register copies per symbol for those).
-    __device__ __forceinline__ void put_field(u32 v, u32 nb) {
-        const u32 tot = nacc + nb;                    // <= 63
-        const u64 wide = ((u64)hi << nb) | v;         // tot valid bits, right-aligned
-        nacc = tot & 31u;
-        if (tot >= 32) emit(__builtin_bswap32((u32)(wide >> nacc)));  // tot - 32 = tot & 31 here
-        hi = (u32)wide & ((1u << nacc) - 1u);
+    __device__ __forceinline__ void put_field(u32 v, u32 nb) {  // the per-symbol field: nb <= 32, nb = 0 allowed with v = 0
+        SclFwdBits::put_field(v, nb, [&](u32 word_be) { emit(word_be); });
     }
     __device__ __forceinline__ void put_run(u32 bit, u32 count) {
-        while (count >= 32) {
-            put(bit ? 0xFFFFFFFFu : 0u, 32);
-            count -= 32;
-        }
-        if (count) put(bit ? ((1u << count) - 1u) : 0u, count);
+        SclFwdBits::put_run(bit, count, [&](u32 word_be) { emit(word_be); }, [] {});
     }
     __device__ __forceinline__ u64 finish() {
         const u64 total = (u64)nwords * 32 + nacc;

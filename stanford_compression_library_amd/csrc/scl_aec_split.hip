@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(AS_THREADS)
 
     // =================================== writer role =====================================================================
     // 64-bit window hi:lo, `cnt` pending bits bottom-aligned (cnt < 32 between symbols); a field is at most 31 bits, so
-    // the window never holds more than 62.  32-bit shifts only (see AnsFwdWriter::put, scl_ans_fast_io.h).  A completed
+    // the window never holds more than 62.  32-bit shifts only (see SclFwdBits::put, scl_common.h).  A completed
     // big-endian word goes straight to the slot (4-byte stores; the stream is a third of the input and L2 merges them).
     // Round 6 staged the words in LDS (the 2 KiB the totals vacated) and stored whole 32-byte sectors: the same streams,
     // but the writer role -- one of three that pace each other -- grew by a tenth and the kernel went from 4.7 to 5.05 ms

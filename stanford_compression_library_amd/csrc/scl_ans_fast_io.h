@@ -1,5 +1,19 @@
-// scl_ans_fast_io.h -- line-granular stream I/O shared by the rANS and tANS fast kernels (same stream layout:
-// produced back to front, read front to back).  Internal to csrc/.
+// scl_ans_fast_io.h -- lane-per-chunk stream I/O of the tuned coder kernels.  Internal to csrc/.
+//
+// Who uses what:
+//   rANS (scl_rans_fast.hip)       AnsBackWriterL / S / T out, AnsBitReaderW / T in, CoopLineStore for the symbols
+//   rANS-b8, tANS (scl_rans_fast_b.hip, scl_tans_fast.hip)   AnsBackWriter out, AnsBitReader in, CoopLineStore
+//   range (scl_range_fast.hip)     scl_flush_rows under RgOutT, scl_transpose8 in RgOut, AnsBitReaderW / T in
+//   static arithmetic (scl_aec_static.hip)   AnsFwdWriter out, AnsBitReader<.., ZERO_PAST_END> in
+//   prefix codes (scl_prefix.hip)  AnsFwdWriter<.., BOUNDED> out, AnsBitReader in
+// rANS / tANS streams are produced back to front and read front to back; the others grow front to back.
+//
+// The pieces, each defined once:
+//   AnsBackWindow   64-bit window of the back writers L / S / T (push, put32, the hand-written check of L and T)
+//   scl_flush_rows  the wave's row-by-row store of striped pieces (AnsBackWriterT, RgOutT)
+//   AnsLineFeed     128-byte lines -> registers -> [word][thread] ring, of the linear readers (AnsBitReader, AnsBitReaderW)
+//   AnsRingCursor   window-less read position over that ring (AnsBitReaderW, AnsBitReaderT, whose feed is AnsPieceFeed)
+//   SclFwdBits      (scl_common.h) the forward bit accumulator (AnsFwdWriter, AfWriterT of scl_aec_lane_io.h)
 //
 // Memory granularity rule (profiles/r01_v2_pmc_summary.txt -> r01_v3): with one lane per 4 KiB chunk a CU owns
 // 1024 open cache lines for input and 1024 for output -- more than L1 and, per XCD, the whole L2 -- so a lane
@@ -140,23 +154,91 @@ struct AnsBackWriter {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-// Round-2 back writer: 64-bit bit window -> per-lane LDS ring of 64 words -> whole 128-byte lines stored by quads.
+// The bit window of the round-2 / round-6 back writers (AnsBackWriterL, S, T; D is the writer, which owns the ring and
+// supplies check<RING_OFF>(lds, bits)).
 //
-// (1) Bits.  The pending bits are the TOP n bits of a 64-bit window hi:lo, newest on top:
+// The pending bits are the TOP n bits of a 64-bit window hi:lo, newest on top:
 //       push(x, k):  lo = alignbit(hi, lo, k);  hi = alignbit(x, hi, k);  n += k
-//     v_alignbit takes the low k bits of its first operand by itself: no field extraction (v_bfe), no merging of two
-//     fields, no shift of the field to its place in an accumulator.  check() every two symbols (n <= 32 + 2*13 < 64):
-//     n >= 33 means the oldest 32 bits, alignbit(hi, lo, 64 - n), are a complete word; the rest of the window stays
-//     where it is (top-aligned), n -= 32.  The counter is room = 32 - n, unsigned: the subtraction that accounts for a
-//     pair of symbols borrows exactly when n reaches 33 (no compare instruction), and the wrapped value's low 5 bits are
-//     the word's shift amount (v_alignbit reads 5 bits: (32 - n) mod 32 = 64 - n for 33 <= n <= 63).
-// (2) Ring.  256 bytes per lane, [thread][word]: the two halves are two 128-byte line buffers holding words in MEMORY
+// v_alignbit takes the low k bits of its first operand by itself: no field extraction (v_bfe), no merging of two
+// fields, no shift of the field to its place in an accumulator.  check() every two symbols (n <= 32 + 2*13 < 64):
+// n >= 33 means the oldest 32 bits, alignbit(hi, lo, 64 - n), are a complete word; the rest of the window stays
+// where it is (top-aligned), n -= 32.  The counter is room = 32 - n, unsigned: the subtraction that accounts for a
+// pair of symbols borrows exactly when n reaches 33 (no compare instruction), and the wrapped value's low 5 bits are
+// the word's shift amount (v_alignbit reads 5 bits: (32 - n) mod 32 = 64 - n for 33 <= n <= 63).
+template <class D>
+struct AnsBackWindow {
+    u32 hi, lo;   // the window
+    u32 room;     // 32 - (number of pending bits), as an unsigned counter: a push that BORROWS completed a word
+
+    __device__ __forceinline__ void window_init() {
+        hi = lo = 0;
+        room = 32;
+    }
+    // the low k bits of v go in front of the stream; k < 32, bits of v above bit k are ignored
+    __device__ __forceinline__ void push(u32 v, u32 k) {
+        lo = __builtin_amdgcn_alignbit(hi, lo, k);
+        hi = __builtin_amdgcn_alignbit(v, hi, k);
+    }
+    // push() in two halves (round 5): what two pushes of k0 and k1 bits move from hi into lo is what ONE funnel shift of the
+    // hi of before by k0 + k1 moves (k0 + k1 < 32) -- so a pair of symbols updates hi twice and lo once: three v_alignbit
+    // instead of four
+    __device__ __forceinline__ void push_hi(u32 v, u32 k) { hi = __builtin_amdgcn_alignbit(v, hi, k); }
+    __device__ __forceinline__ void fold_lo(u32 hi_before, u32 bits) { lo = __builtin_amdgcn_alignbit(hi_before, lo, bits); }
+    template <u32 RING_OFF>
+    __device__ __forceinline__ void put32(char *lds, u32 v, u32 w) {  // any w <= 32 (header fields)
+        D &d = *static_cast<D *>(this);
+        if (w > 16) {
+            push(v, 16);
+            d.template check<RING_OFF>(lds, 16);
+            push(v >> 16, w - 16);
+            d.template check<RING_OFF>(lds, w - 16);
+        } else {
+            push(v, w);
+            d.template check<RING_OFF>(lds, w);
+        }
+    }
+    // check() of the writers whose ring is LANE_BYTES = 128 or 256 bytes per lane, LANE_BYTES-aligned, so that the write
+    // ADDRESS is the only ring state: wa = ((wa - 4) & (LANE_BYTES - 1)) | base (AnsBackWriterL, AnsBackWriterT).
+    // Account for the `bits` (<= 26) pushed since the last call.  The subtraction's borrow IS the test "33 or more bits
+    // pending" (v_sub_co_u32 + a branch on VCC: no separate compare); the wrapped counter's low 5 bits are the shift that
+    // brings the oldest 32 bits down: (32 - n) mod 32 = 64 - n for 33 <= n <= 63.
+    // RING_OFF: byte offset of the rings in the workgroup's LDS block (an immediate of the ds_write).  The block is
+    // written by hand: the compiler's version of the same seven instructions carries an s_cbranch_execz that skips them
+    // when no lane completed a word -- practically never, with 64 lanes -- and every instruction on this path, which the
+    // whole wave runs for every pair of symbols, is ~2.5 % of the kernel (0.575 -> 0.556 ms).  LDS instructions of a wave
+    // execute in order, so the flush rounds' reads see these writes; the compiler, which does not know of them, can only
+    // wait too long for its own LDS operations, never too short.
+    template <u32 LANE_BYTES, u32 RING_OFF>
+    __device__ __forceinline__ void check_pow2(u32 &wa, u32 base, u32 bits) {
+        static_assert((LANE_BYTES & (LANE_BYTES - 1u)) == 0, "the ring offset wraps with an AND");
+        u32 w, t;
+        u64 sv;
+        asm volatile(
+            "v_sub_co_u32 %[room], vcc, %[room], %[bits]\n\t"
+            "s_and_saveexec_b64 %[sv], vcc\n\t"
+            "v_alignbit_b32 %[w], %[hi], %[lo], %[room]\n\t"
+            "v_add_u32 %[t], %[step], %[wa]\n\t"  // (wa - 4) mod LANE_BYTES, with the AND below
+            "v_perm_b32 %[w], 0, %[w], %[sel]\n\t"
+            "v_add_u32 %[room], 32, %[room]\n\t"
+            "ds_write_b32 %[wa], %[w] offset:%[off]\n\t"
+            "v_and_or_b32 %[wa], %[t], %[mask], %[base]\n\t"
+            "s_or_b64 exec, exec, %[sv]"
+            : [room] "+v"(room), [wa] "+v"(wa), [w] "=&v"(w), [t] "=&v"(t), [sv] "=&s"(sv)
+            : [bits] "v"(bits), [hi] "v"(hi), [lo] "v"(lo), [sel] "s"(0x00010203u), [mask] "s"(LANE_BYTES - 1u),
+              [base] "v"(base), [step] "n"(LANE_BYTES - 4u), [off] "i"(RING_OFF)
+            : "vcc", "memory");
+    }
+};
+
+// Round-2 back writer: the 64-bit bit window above -> per-lane LDS ring of 64 words -> whole 128-byte lines stored by quads.
+//
+// (1) Ring.  256 bytes per lane, [thread][word]: the two halves are two 128-byte line buffers holding words in MEMORY
 //     order (the stream grows downwards, so the write offset walks 124, 120, .. 0, 252, .. 128, 124, ..).  The ring is
 //     256-byte aligned, so the write ADDRESS is the only state: wa = ((wa - 4) & 255) | base.  A lane's scattered 4-byte
 //     writes now collide in the banks (bank = word index mod 32, whatever the lane), which ds_write_b32 mostly hides
 //     (measured: no slower than the conflict-free [word][thread] layout of round 1); what the layout buys is that a
 //     16-byte piece of a line is ONE aligned ds_read_b128 -- for any lane.
-// (3) Stores.  What bounds a lane-per-chunk coder on this chip is the SHAPE of its write requests: with the same
+// (2) Stores.  What bounds a lane-per-chunk coder on this chip is the SHAPE of its write requests: with the same
 //     lines, the same bytes and no arithmetic at all, lanes storing their own lines (8 x 16 bytes) take 0.58 ms per GiB
 //     batch, four lanes per 64-byte half line 0.52, eight lanes per whole line 0.42 (tools/ubench/linecopy3.hip; the read
 //     shape makes no difference).  The round-1 encoder (0.59 ms) sat exactly on the first figure.  So a line is stored by
@@ -173,15 +255,18 @@ __device__ __forceinline__ u32 scl_quad_bcast(u32 v) {  // value of lane R of th
     return (u32)__builtin_amdgcn_mov_dpp((int)v, R * 0x55, 0xF, 0xF, true);
 }
 template <int THREADS>
-struct AnsBackWriterL {
+struct AnsBackWriterL : AnsBackWindow<AnsBackWriterL<THREADS>> {
+    typedef AnsBackWindow<AnsBackWriterL<THREADS>> Win;
+    using Win::hi;
+    using Win::lo;
+    using Win::room;
+    using Win::push;
     static constexpr u32 FLUSH_MASK = 3;   // the encoder's flush points: every (FLUSH_MASK + 1) x 16 symbols
     static constexpr u32 FLUSH_PHASE = 1;  // ... after block 1 (mod 4) of a line
     static constexpr u32 WG_PER_CU = 2;    // 64 KiB of rings + the 4 KiB table per 256 lanes
     static constexpr bool STRIPED = false;
     static constexpr u32 LANE_BYTES = 256;                   // one 256-byte ring per lane, 256-byte aligned
     static constexpr u32 RING_BYTES = THREADS * LANE_BYTES;  // placed at LDS offset 0 of the workgroup
-    u32 hi, lo;   // the window
-    u32 room;     // 32 - (number of pending bits), as an unsigned counter: a push that BORROWS completed a word
     u32 wa;       // LDS byte address (from the ring base) of the word that completes next: base | offset 0..252
     u32 th4;      // ring offset of the FIRST word (highest address) of the oldest unflushed line
     u32 base;     // tid * LANE_BYTES (low 8 bits zero)
@@ -197,63 +282,15 @@ struct AnsBackWriterL {
     __device__ __forceinline__ u32 pend4() const { return (th4 - wa) & 255u; }  // 4 * completed words not yet stored (< 256)
 
     __device__ __forceinline__ void init(u32 tid, u32 slot_end_off) {
-        hi = lo = 0;
-        room = 32;
+        Win::window_init();
         base = tid * LANE_BYTES;
         th4 = (124u + rot_of(tid)) & 255u;
         wa = base | th4;
         goff = goff0 = slot_end_off;
     }
-    // the low k bits of v go in front of the stream; k < 32, bits of v above bit k are ignored
-    __device__ __forceinline__ void push(u32 v, u32 k) {
-        lo = __builtin_amdgcn_alignbit(hi, lo, k);
-        hi = __builtin_amdgcn_alignbit(v, hi, k);
-    }
-    // push() in two halves (round 5): what two pushes of k0 and k1 bits move from hi into lo is what ONE funnel shift of the
-    // hi of before by k0 + k1 moves (k0 + k1 < 32) -- so a pair of symbols updates hi twice and lo once: three v_alignbit
-    // instead of four
-    __device__ __forceinline__ void push_hi(u32 v, u32 k) { hi = __builtin_amdgcn_alignbit(v, hi, k); }
-    __device__ __forceinline__ void fold_lo(u32 hi_before, u32 bits) { lo = __builtin_amdgcn_alignbit(hi_before, lo, bits); }
-    // account for the `bits` (<= 26) pushed since the last call.  The subtraction's borrow IS the test "33 or more bits
-    // pending" (v_sub_co_u32 + a branch on VCC: no separate compare); the wrapped counter's low 5 bits are the shift that
-    // brings the oldest 32 bits down: (32 - n) mod 32 = 64 - n for 33 <= n <= 63.
-    // RING_OFF: byte offset of the rings in the workgroup's LDS block (an immediate of the ds_write).  The block is
-    // written by hand: the compiler's version of the same seven instructions carries an s_cbranch_execz that skips them
-    // when no lane completed a word -- practically never, with 64 lanes -- and every instruction on this path, which the
-    // whole wave runs for every pair of symbols, is ~2.5 % of the kernel (0.575 -> 0.556 ms).  LDS instructions of a wave
-    // execute in order, so the flush rounds' reads see these writes; the compiler, which does not know of them, can only
-    // wait too long for its own LDS operations, never too short.
     template <u32 RING_OFF>
-    __device__ __forceinline__ void check(char *lds, u32 bits) {
-        u32 w, t;
-        u64 sv;
-        asm volatile(
-            "v_sub_co_u32 %[room], vcc, %[room], %[bits]\n\t"
-            "s_and_saveexec_b64 %[sv], vcc\n\t"
-            "v_alignbit_b32 %[w], %[hi], %[lo], %[room]\n\t"
-            "v_add_u32 %[t], 0xfc, %[wa]\n\t"
-            "v_perm_b32 %[w], 0, %[w], %[sel]\n\t"
-            "v_add_u32 %[room], 32, %[room]\n\t"
-            "ds_write_b32 %[wa], %[w] offset:%[off]\n\t"
-            "v_and_or_b32 %[wa], %[t], %[m255], %[base]\n\t"
-            "s_or_b64 exec, exec, %[sv]"
-            : [room] "+v"(room), [wa] "+v"(wa), [w] "=&v"(w), [t] "=&v"(t), [sv] "=&s"(sv)
-            : [bits] "v"(bits), [hi] "v"(hi), [lo] "v"(lo), [sel] "s"(0x00010203u), [m255] "s"(255u), [base] "v"(base),
-              [off] "i"(RING_OFF)
-            : "vcc", "memory");
-        (void)lds;
-    }
-    template <u32 RING_OFF>
-    __device__ __forceinline__ void put32(char *lds, u32 v, u32 w) {  // any w <= 32 (header fields)
-        if (w > 16) {
-            push(v, 16);
-            check<RING_OFF>(lds, 16);
-            push(v >> 16, w - 16);
-            check<RING_OFF>(lds, w - 16);
-        } else {
-            push(v, w);
-            check<RING_OFF>(lds, w);
-        }
+    __device__ __forceinline__ void check(char *, u32 bits) {  // see AnsBackWindow::check_pow2
+        Win::template check_pow2<LANE_BYTES, RING_OFF>(wa, base, bits);
     }
     template <int R>
     __device__ __forceinline__ void quad_round(const char *lds, u8 *wg_out, u32 f, u32 qbase, u32 j16) const {
@@ -329,15 +366,18 @@ struct AnsBackWriterL {
 // at the same steps and write the same ring offset; with a lane stride of 192 bytes and no rotation that is 2 of the
 // 32 banks.  The launch code keeps such tables on AnsBackWriterL (whose rings are rotated per lane).
 template <int THREADS>
-struct AnsBackWriterS {
+struct AnsBackWriterS : AnsBackWindow<AnsBackWriterS<THREADS>> {
+    typedef AnsBackWindow<AnsBackWriterS<THREADS>> Win;
+    using Win::hi;
+    using Win::lo;
+    using Win::room;
+    using Win::push;
     static constexpr u32 FLUSH_MASK = 1;
     static constexpr u32 FLUSH_PHASE = 0;  // after blocks 0, 2, 4, 6 of a line: none just before its end (see the kernel)
     static constexpr u32 WG_PER_CU = 3;
     static constexpr bool STRIPED = false;
     static constexpr u32 LANE_BYTES = 192;
     static constexpr u32 RING_BYTES = THREADS * LANE_BYTES;
-    u32 hi, lo;   // the window
-    u32 room;     // 32 - (number of pending bits): a push that BORROWS completed a word
     u32 wo;       // ring offset (0..188) of the word that completes next; its LDS address is base + wo
     u32 rhi, rlo; // ring offsets (0, 64 or 128) of the slots holding the upper / lower half of the oldest unflushed line
     u32 base;     // tid * LANE_BYTES
@@ -350,22 +390,15 @@ struct AnsBackWriterS {
         return t + ((u32)((int)t >> 31) & LANE_BYTES);
     }
     __device__ __forceinline__ void init(u32 tid, u32 slot_end_off) {
-        hi = lo = 0;
-        room = 32;
+        Win::window_init();
         base = tid * LANE_BYTES;
         rhi = 128;
         rlo = 64;
         wo = 188u;
         goff = goff0 = slot_end_off;
     }
-    __device__ __forceinline__ void push(u32 v, u32 k) {  // the low k bits of v go in front of the stream; k < 32
-        lo = __builtin_amdgcn_alignbit(hi, lo, k);
-        hi = __builtin_amdgcn_alignbit(v, hi, k);
-    }
-    __device__ __forceinline__ void push_hi(u32 v, u32 k) { hi = __builtin_amdgcn_alignbit(v, hi, k); }  // see AnsBackWriterL
-    __device__ __forceinline__ void fold_lo(u32 hi_before, u32 bits) { lo = __builtin_amdgcn_alignbit(hi_before, lo, bits); }
     template <u32 RING_OFF>
-    __device__ __forceinline__ void check(char *lds, u32 bits) {  // as AnsBackWriterL::check, by hand for the same reason
+    __device__ __forceinline__ void check(char *lds, u32 bits) {  // as AnsBackWindow::check_pow2, by hand for the same reason
         u32 w, t;
         u64 sv;
         asm volatile(
@@ -383,18 +416,6 @@ struct AnsBackWriterS {
             : [bits] "v"(bits), [hi] "v"(hi), [lo] "v"(lo), [sel] "s"(0x00010203u), [base] "v"(base), [off] "i"(RING_OFF)
             : "vcc", "memory");
         (void)lds;
-    }
-    template <u32 RING_OFF>
-    __device__ __forceinline__ void put32(char *lds, u32 v, u32 w) {  // any w <= 32 (header fields)
-        if (w > 16) {
-            push(v, 16);
-            check<RING_OFF>(lds, 16);
-            push(v >> 16, w - 16);
-            check<RING_OFF>(lds, w - 16);
-        } else {
-            push(v, w);
-            check<RING_OFF>(lds, w);
-        }
     }
     template <int R>
     __device__ __forceinline__ void quad_round(const char *lds, u8 *wg_out, u32 f, u32 qj, u32 j16) const {
@@ -469,25 +490,68 @@ struct AnsBackWriterS {
 // another for correctness, so ragged batches and partial waves take the same path.  The logical position of every bit is what it was -- `bit_offset` /
 // `nbits` keep their meaning -- only the mapping to memory changes (scl_stripe_byte below; the decoder's reader and
 // scl_streams_compact undo it).
-//   * bit window, check(): as AnsBackWriterL (the asm block differs in the ring constants only);
+//   * bit window, check(): AnsBackWindow, the check_pow2 of AnsBackWriterL with LANE_BYTES = 128;
 //   * ring: 32 words per lane, [thread][word], words in MEMORY order inside 16-byte pieces, rotated by 16 * (lane mod 8)
 //     bytes against lockstep tables; flush points 32 symbols apart (<= 13 new words on top of the <= 18 a lane may keep);
-//   * flush(): the wave stores the next row when every lane holds a complete piece (see the comment there).
+//   * flush point: the wave stores the next row when every lane holds a complete piece (scl_flush_rows, below).
 __device__ __forceinline__ u64 scl_stripe_byte(u64 logical_byte, u64 stride) {
     // logical byte address in a batch of slots of `stride` bytes (a multiple of 16) -> physical byte address
     const u64 slot = logical_byte / stride, b = logical_byte - slot * stride;
     return (slot >> 6) * (stride << 6) + (b >> 4) * 1024u + ((slot & 63u) << 4) + (b & 15u);
 }
+// Flush point of a writer over WAVE-STRIPED slots (AnsBackWriterT below, RgOutT in scl_range_fast.hip).  Any subset of the
+// wave may call; the lanes present act together.  Lanes complete their 16-byte pieces at data-dependent times; a piece stored
+// the moment it is complete makes every 128-byte line arrive in two or three partial writes (measured: +0.13 ms per GiB
+// batch, worse than the L writer).  So the wave stores ROW BY ROW: the next row goes out when EVERY lane present holds a
+// complete piece -- one instruction, 64 adjacent pieces, eight whole lines when the lanes are where i.i.d. data keeps them:
+// in step to within a piece or two, which the ring absorbs (a lane may leave a flush point holding up to `guard` units of
+// complete words).  A lane beyond that stores its own oldest pieces -- partial lines; lanes that drift apart for good (very
+// different statistics from chunk to chunk) all end up there, at the cost of the unsynchronised form (+3 %), never of
+// correctness.
+// W supplies: pending() -- complete words not yet stored, in units of which W::PIECE make a piece; store_row<R>(ctx...) --
+// store piece R (0 = oldest) of the complete ones, updating nothing; rows_done(m) -- m pieces have left.
+template <class W, class... CTX>
+__device__ __forceinline__ void scl_flush_rows(W &w, u32 guard, CTX... ctx) {
+    const u32 p = w.pending();
+    const u64 all = __builtin_amdgcn_ballot_w64(true);
+    if (__builtin_amdgcn_ballot_w64(p >= W::PIECE) == all) {
+        w.template store_row<0>(ctx...);
+        if (__builtin_amdgcn_ballot_w64(p >= 2u * W::PIECE) == all) {
+            w.template store_row<1>(ctx...);
+            if (__builtin_amdgcn_ballot_w64(p >= 3u * W::PIECE) == all) {
+                w.template store_row<2>(ctx...);
+                if (__builtin_amdgcn_ballot_w64(p >= 4u * W::PIECE) == all) {
+                    w.template store_row<3>(ctx...);
+                    w.rows_done(4);
+                } else {
+                    w.rows_done(3);
+                }
+            } else {
+                w.rows_done(2);
+            }
+        } else {
+            w.rows_done(1);
+        }
+    }
+    while (w.pending() > guard) {
+        w.template store_row<0>(ctx...);
+        w.rows_done(1);
+    }
+}
 template <int THREADS>
-struct AnsBackWriterT {
+struct AnsBackWriterT : AnsBackWindow<AnsBackWriterT<THREADS>> {
+    typedef AnsBackWindow<AnsBackWriterT<THREADS>> Win;
+    using Win::hi;
+    using Win::lo;
+    using Win::room;
+    using Win::push;
     static constexpr u32 FLUSH_MASK = 1;   // the encoder's flush points: every 32 symbols
     static constexpr u32 FLUSH_PHASE = 0;  // after blocks 0, 2, 4, 6 of a line: none just before its end (see the kernel)
     static constexpr u32 WG_PER_CU = 4;    // 32 KiB of rings + the 4 KiB table per 256 lanes
     static constexpr u32 LANE_BYTES = 128;
     static constexpr u32 RING_BYTES = THREADS * LANE_BYTES;
     static constexpr bool STRIPED = true;
-    u32 hi, lo;   // the window
-    u32 room;     // 32 - (number of pending bits): a push that BORROWS completed a word
+    static constexpr u32 PIECE = 16;  // pending() counts bytes
     u32 wa;       // LDS byte address (from the ring base) of the word that completes next: base | offset 0..124
     u32 th4;      // ring offset of the FIRST word (highest address) of the oldest unflushed piece (= 12 mod 16)
     u32 base;     // tid * LANE_BYTES
@@ -498,50 +562,15 @@ struct AnsBackWriterT {
 
     // out_stride: bytes per logical slot (a multiple of 16; 256 lanes * out_stride < 2^32)
     __device__ __forceinline__ void init(u32 tid, u32 out_stride) {
-        hi = lo = 0;
-        room = 32;
+        Win::window_init();
         base = tid * LANE_BYTES;
         th4 = (124u + 16u * (tid & 7u)) & 127u;
         wa = base | th4;
         goff = goff0 = ((tid >> 6) + 1u) * (out_stride << 6) - 1024u + ((tid & 63u) << 4);
     }
-    __device__ __forceinline__ void push(u32 v, u32 k) {  // the low k bits of v go in front of the stream; k < 32
-        lo = __builtin_amdgcn_alignbit(hi, lo, k);
-        hi = __builtin_amdgcn_alignbit(v, hi, k);
-    }
-    __device__ __forceinline__ void push_hi(u32 v, u32 k) { hi = __builtin_amdgcn_alignbit(v, hi, k); }  // see AnsBackWriterL
-    __device__ __forceinline__ void fold_lo(u32 hi_before, u32 bits) { lo = __builtin_amdgcn_alignbit(hi_before, lo, bits); }
     template <u32 RING_OFF>
-    __device__ __forceinline__ void check(char *lds, u32 bits) {  // as AnsBackWriterL::check, by hand for the same reason
-        u32 w, t;
-        u64 sv;
-        asm volatile(
-            "v_sub_co_u32 %[room], vcc, %[room], %[bits]\n\t"
-            "s_and_saveexec_b64 %[sv], vcc\n\t"
-            "v_alignbit_b32 %[w], %[hi], %[lo], %[room]\n\t"
-            "v_add_u32 %[t], 0x7c, %[wa]\n\t"
-            "v_perm_b32 %[w], 0, %[w], %[sel]\n\t"
-            "v_add_u32 %[room], 32, %[room]\n\t"
-            "ds_write_b32 %[wa], %[w] offset:%[off]\n\t"
-            "v_and_or_b32 %[wa], %[t], %[m127], %[base]\n\t"
-            "s_or_b64 exec, exec, %[sv]"
-            : [room] "+v"(room), [wa] "+v"(wa), [w] "=&v"(w), [t] "=&v"(t), [sv] "=&s"(sv)
-            : [bits] "v"(bits), [hi] "v"(hi), [lo] "v"(lo), [sel] "s"(0x00010203u), [m127] "s"(127u), [base] "v"(base),
-              [off] "i"(RING_OFF)
-            : "vcc", "memory");
-        (void)lds;
-    }
-    template <u32 RING_OFF>
-    __device__ __forceinline__ void put32(char *lds, u32 v, u32 w) {  // any w <= 32 (header fields)
-        if (w > 16) {
-            push(v, 16);
-            check<RING_OFF>(lds, 16);
-            push(v >> 16, w - 16);
-            check<RING_OFF>(lds, w - 16);
-        } else {
-            push(v, w);
-            check<RING_OFF>(lds, w);
-        }
+    __device__ __forceinline__ void check(char *, u32 bits) {  // see AnsBackWindow::check_pow2
+        Win::template check_pow2<LANE_BYTES, RING_OFF>(wa, base, bits);
     }
     // piece r (0 = oldest) of the complete ones this lane holds -> its row; nothing is updated (see rows_done)
     template <u32 R>
@@ -557,42 +586,11 @@ struct AnsBackWriterT {
         goff -= 1024u * m;
         th4 = (th4 - 16u * m) & 127u;
     }
-    // Flush point (any subset of the wave may call; the lanes present act together).  Lanes complete their pieces at
-    // data-dependent times; a piece stored the moment it is complete makes every 128-byte line arrive in two or three
-    // partial writes (measured: +0.13 ms per GiB batch, worse than the L writer).  So the wave stores ROW BY ROW: the next
-    // row goes out when EVERY lane present holds a complete piece -- one instruction, 64 adjacent pieces, eight whole lines
-    // when the lanes are where i.i.d. data keeps them: in step to within a piece or two, which the ring absorbs (a lane may
-    // leave a flush point holding up to `guard` bytes of complete words).  A lane beyond that stores its own oldest pieces
-    // -- partial lines; lanes that drift apart for good (very different statistics from chunk to chunk) all end up there,
-    // at the cost of the unsynchronised form (+3 %), never of correctness: the ring cannot reach 32 words.
-    // guard: 4 * (31 - the most words 32 symbols can complete): 72 for <= 13 bits per symbol, 60 for <= 16
-    __device__ __forceinline__ void flush(char *lds, u8 *wg_out, u32 guard) {
-        const u32 p = pend4();
-        const u64 all = __builtin_amdgcn_ballot_w64(true);
-        if (__builtin_amdgcn_ballot_w64(p >= 16u) == all) {
-            store_row<0>(lds, wg_out);
-            if (__builtin_amdgcn_ballot_w64(p >= 32u) == all) {
-                store_row<1>(lds, wg_out);
-                if (__builtin_amdgcn_ballot_w64(p >= 48u) == all) {
-                    store_row<2>(lds, wg_out);
-                    if (__builtin_amdgcn_ballot_w64(p >= 64u) == all) {
-                        store_row<3>(lds, wg_out);
-                        rows_done(4);
-                    } else {
-                        rows_done(3);
-                    }
-                } else {
-                    rows_done(2);
-                }
-            } else {
-                rows_done(1);
-            }
-        }
-        while (pend4() > guard) {
-            store_row<0>(lds, wg_out);
-            rows_done(1);
-        }
-    }
+    // The flush point is scl_flush_rows(*this, guard, lds, wg_out), called by the kernel itself (a member that forwards to it
+    // is one more level of inlining, which moved the register allocation of every striped encoder).
+    // guard: 4 * (31 - the most words 32 symbols can complete): 72 for <= 13 bits per symbol, 60 for <= 16 -- the ring cannot
+    // reach 32 words
+    __device__ __forceinline__ u32 pending() const { return pend4(); }
     __device__ __forceinline__ void flush_all(char *lds, u8 *wg_out) {  // per lane
         while (pend4() >= 16u) {
             store_row<0>(lds, wg_out);
@@ -702,167 +700,15 @@ struct Line128 {
     }
 };
 
+// Line feed of the linear readers (AnsBitReader, AnsBitReaderW): whole 128-byte lines of the stream are prefetched into
+// registers, byte-swapped and moved into the [word][thread] ring of 32 words one 64-byte half at a time.
 // ZERO_PAST_END: bits after the last bit of the stream read as 0 whatever the buffer holds there (the arithmetic
 // decoder's state register looks 32 bits ahead, arithmetic_coding.py:222-229, :258-261); the ANS decoders never
 // look at what they do not consume and leave it off.
-template <int THREADS, bool ZERO_PAST_END = false>
-struct AnsBitReader {
-    static constexpr u32 RING_BYTES = 32u * THREADS * 4u;
-    u32 wabs;      // ZERO_PAST_END: index (from the buffer start) of the next word that enters the ring
-    u32 end_word;  //                index of the word holding the first bit after the stream
-    u32 end_mask;  //                bits of that word which still belong to the stream
-    const uint4 *base;
-    u64 n_blocks16;  // readable 16-byte blocks
-    u64 next_line;   // index of the next 128-byte line to prefetch
-    uint4 pf[8];     // prefetched line: its two 64-byte halves enter the ring one at a time
-    u32 stage;       // 0: the lower half of pf is next, 1: the upper half
-    u32 ra;          // LDS byte address of the next ring word to read (thread column, wraps inside the ring)
-    u32 wa;          // LDS byte address of the ring half that is filled next
-    u32 nwr;         // words written to the ring (the words READ follow from it and the two ring positions: nrd())
-    u32 A, B;        // 64-bit window, big-endian words
-    u32 sh;          // lookahead = low32((A:B) >> sh); sh in [0,31].  Unsigned on purpose: advance() takes the BORROW of
-                     // its subtraction as "the window crossed a word" (v_sub_co + branch on VCC, no compare)
-    u32 bias;        // consumed bits = 32*nrd() - sh - bias
-
-    __device__ __forceinline__ void load_line(u64 j) {  // whole 128-byte line: one HBM burst instead of two
-        // Every line but the buffer's last is readable as a whole: ONE comparison and eight loads off one address.  (Eight
-        // separately bounds-checked loads -- compare, zero default, branch, each -- were 70 instructions per line, a fifth
-        // of the rANS decoder's vector instructions.)
-        // (not for ZERO_PAST_END users: the static-model arithmetic decoder sits at its register limit and spills with it)
-        if (!ZERO_PAST_END && j * 8 + 8 <= n_blocks16) {
-            const uint4 *p = base + j * 8;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) pf[i] = p[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const u64 idx = j * 8 + i;
-                pf[i] = (idx < n_blocks16) ? base[idx] : make_uint4(0, 0, 0, 0);
-            }
-        }
-    }
-    __device__ __forceinline__ void push_half(char *lds, const uint4 &q0, const uint4 &q1, const uint4 &q2,
-                                              const uint4 &q3) {
-        char *r = lds + wa;
-        const uint4 blk[4] = {q0, q1, q2, q3};
-        if (ZERO_PAST_END && wabs + 16 > end_word) {  // the half that holds the end of the stream, or lies past it
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const u32 w4[4] = {blk[i].x, blk[i].y, blk[i].z, blk[i].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const u32 wi = wabs + 4 * i + j;
-                    const u32 keep = (wi < end_word) ? 0xFFFFFFFFu : (wi == end_word ? end_mask : 0u);
-                    *reinterpret_cast<u32 *>(r + (4 * i + j) * THREADS * 4) = __builtin_bswap32(w4[j]) & keep;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                *reinterpret_cast<u32 *>(r + (4 * i + 0) * THREADS * 4) = __builtin_bswap32(blk[i].x);
-                *reinterpret_cast<u32 *>(r + (4 * i + 1) * THREADS * 4) = __builtin_bswap32(blk[i].y);
-                *reinterpret_cast<u32 *>(r + (4 * i + 2) * THREADS * 4) = __builtin_bswap32(blk[i].z);
-                *reinterpret_cast<u32 *>(r + (4 * i + 3) * THREADS * 4) = __builtin_bswap32(blk[i].w);
-            }
-        }
-        if (ZERO_PAST_END) wabs += 16;
-        wa ^= 16 * THREADS * 4;
-        nwr += 16;
-    }
-    __device__ __forceinline__ u32 next_word(const char *lds) {
-        const u32 v = *reinterpret_cast<const u32 *>(lds + ra);
-        ra = (ra + THREADS * 4) & (RING_BYTES - 1);
-        return v;
-    }
-    // words still ahead of the reader, minus one, in ring-address units: `wa` is the half that is filled next, i.e.
-    // the row after the newest word; the reader never runs dry, so a distance of 0 rows means 32
-    __device__ __forceinline__ u32 ahead_m1() const { return (wa - ra - THREADS * 4) & (RING_BYTES - 1); }
-    __device__ __forceinline__ u32 nrd() const { return nwr - (ahead_m1() / (THREADS * 4) + 1); }
-    // call at least every 16 symbols (<= 6 words consumed in between)
-    __device__ __forceinline__ void maybe_refill(char *lds) {
-        if (ahead_m1() < 16 * THREADS * 4) {  // 16 words or fewer ahead: the reader has left the older half
-            if (stage == 0) {
-                push_half(lds, pf[0], pf[1], pf[2], pf[3]);
-                stage = 1;
-            } else {
-                push_half(lds, pf[4], pf[5], pf[6], pf[7]);
-                stage = 0;
-                load_line(next_line++);
-            }
-        }
-    }
-    __device__ __forceinline__ void init(const u8 *in, u64 in_size_bytes, u64 bit_off, char *lds, u32 tid,
-                                         u32 nbits = 0) {
-        base = reinterpret_cast<const uint4 *>(in);
-        n_blocks16 = in_size_bytes >> 4;
-        const u64 j0 = bit_off >> 10;
-        if (ZERO_PAST_END) {  // (streams and buffers are below 2^37 bits: word indices fit 32 bits)
-            const u64 end = bit_off + nbits;
-            wabs = (u32)(j0 * 32);
-            end_word = (u32)(end >> 5);
-            end_mask = ~(0xFFFFFFFFu >> (end & 31u)) & (0u - (u32)((end & 31u) != 0));
-        }
-        wa = tid * 4;
-        nwr = 0;
-        load_line(j0);
-        push_half(lds, pf[0], pf[1], pf[2], pf[3]);
-        push_half(lds, pf[4], pf[5], pf[6], pf[7]);
-        load_line(j0 + 1);
-        next_line = j0 + 2;
-        stage = 0;
-        const u32 w0 = (u32)(bit_off >> 5) & 31u;
-        ra = tid * 4 + w0 * THREADS * 4;
-        // a stream that starts in the upper half of its line has fewer than 17 words ahead of it: top the ring
-        // up before the first word is read (the lower half of the ring is already behind the read position)
-        maybe_refill(lds);
-        const u32 pos = (u32)bit_off & 31u;
-        const u32 first = next_word(lds);
-        if (pos == 0) {
-            A = 0;
-            B = first;
-            sh = 0;
-        } else {
-            A = first;
-            B = next_word(lds);
-            sh = 32 - pos;
-        }
-        bias = 32 * nrd() - sh;  // consumed == 0 here
-    }
-    __device__ __forceinline__ u32 consumed() const { return 32 * nrd() - sh - bias; }
-    __device__ __forceinline__ u32 look() const { return __builtin_amdgcn_alignbit(A, B, sh); }
-    __device__ __forceinline__ u32 look(const char *) const { return look(); }
-    __device__ __forceinline__ void advance(const char *lds, u32 nb) {  // nb <= 32
-        if (__builtin_usub_overflow(sh, nb, &sh)) {
-            A = B;
-            B = next_word(lds);
-            sh += 32;
-        }
-    }
-    __device__ __forceinline__ u32 get(const char *lds, u32 w) {  // 1 <= w <= 32
-        const u32 v = look() >> (32 - w);
-        advance(lds, w);
-        return v;
-    }
-};
-
-// Round-4 reader: no bit window in registers.  AnsBitReader keeps two ring words (A, B) in registers and advances
-// them under a branch that the whole wave runs for every pair of symbols (some lane always crosses a word: 5 VALU + 2 SALU
-// + the branch per pair).  Here the lookahead of a pair is read straight out of the ring by BIT POSITION: the two words
-// around the position (two conflict-free ds_read_b32 of the lane's column) and one v_alignbit -- no branch, no window to
-// shift, two VALU instructions less per pair (the rANS decoder issues 12.8 VALU per symbol at 77-80 % of one per four
-// clocks: instruction COUNT is what bounds it).
-//   N = -(bits consumed since bit 0 of the lane's first 128-byte line): v_alignbit reads its low five bits, which is the
-//       shift that brings the position's bit to the top -- for a position on a word boundary that shift is 0 and the
-//       result is the SECOND word, so the first word read is the one holding the bit BEFORE the position:
-//   P = (position - 1) << RSH: P & ROWMASK is that word's ring row (byte address without the thread column).
-// Same ring, same line-granular refill and the same call cadence as AnsBitReader.
-template <int THREADS, bool ZERO_PAST_END = false>
-struct AnsBitReaderW {
+template <int THREADS, bool ZERO_PAST_END>
+struct AnsLineFeed {
     static constexpr u32 RING_BYTES = 32u * THREADS * 4u;
     static constexpr u32 ROW = THREADS * 4u;
-    static constexpr u32 RSH = THREADS == 1024 ? 7u : (THREADS == 512 ? 6u : (THREADS == 256 ? 5u : 4u));  // log2(ROW) - 5
-    static constexpr u32 ROWMASK = 31u * ROW;
-    static_assert((32u << RSH) == ROW, "THREADS must be 128, 256, 512 or 1024");
     u32 wabs;      // ZERO_PAST_END: index (from the buffer start) of the next word that enters the ring
     u32 end_word;  //                index of the word holding the first bit after the stream
     u32 end_mask;  //                bits of that word which still belong to the stream
@@ -872,10 +718,6 @@ struct AnsBitReaderW {
     uint4 pf[8];     // prefetched line: its two 64-byte halves enter the ring one at a time
     u32 stage;       // 0: the lower half of pf is next, 1: the upper half
     u32 wa;          // LDS byte address of the ring half that is filled next
-    u32 N, P;        // see above
-    u32 col;         // tid * 4
-    u32 rowA;        // LDS byte address of the first word the last look() read: rows from here on are still needed
-    u32 start;       // bit position at init
 
     __device__ __forceinline__ void load_line(u64 j) {  // whole 128-byte line: one HBM burst instead of two
         // Every line but the buffer's last is readable as a whole: ONE comparison and eight loads off one address.  (Eight
@@ -921,14 +763,56 @@ struct AnsBitReaderW {
         if (ZERO_PAST_END) wabs += 16;
         wa ^= 16 * ROW;
     }
-    // rows from the first one still needed up to the newest, minus one, in ring-address units.  The writer may fill the
-    // half at `wa` once at most 16 rows are left ahead of rowA: that half then lies wholly behind the reader.  A check
-    // that finds 17 rows and does nothing still leaves 4 after the <= 13 words of the next 32 symbols -- the position's
-    // two words and one to spare.
-    __device__ __forceinline__ u32 ahead_m1() const { return (wa - rowA - ROW) & (RING_BYTES - 1); }
-    // call at least every 32 symbols of <= 13 bits
+    // The stream starts at bit `bit_off` of the buffer and has `nbits` bits; returns the index j0 of its first line.  The
+    // reader then fills the ring with that line and requests the next one itself (those six lines, inside this function,
+    // cost the static arithmetic decoder -- at its register limit -- its register allocation).
+    __device__ __forceinline__ u64 feed_open(const u8 *in, u64 in_size_bytes, u64 bit_off, u32 nbits) {
+        base = reinterpret_cast<const uint4 *>(in);
+        n_blocks16 = in_size_bytes >> 4;
+        const u64 j0 = bit_off >> 10;
+        if (ZERO_PAST_END) {  // (streams and buffers are below 2^37 bits: word indices fit 32 bits)
+            const u64 end = bit_off + nbits;
+            wabs = (u32)(j0 * 32);
+            end_word = (u32)(end >> 5);
+            end_mask = ~(0xFFFFFFFFu >> (end & 31u)) & (0u - (u32)((end & 31u) != 0));
+        }
+        return j0;
+    }
+};
+
+template <int THREADS, bool ZERO_PAST_END = false>
+struct AnsBitReader : AnsLineFeed<THREADS, ZERO_PAST_END> {
+    typedef AnsLineFeed<THREADS, ZERO_PAST_END> Feed;
+    using Feed::RING_BYTES;
+    using Feed::load_line;
+    using Feed::next_line;
+    using Feed::pf;
+    using Feed::stage;
+    using Feed::wa;
+    u32 ra;          // LDS byte address of the next ring word to read (thread column, wraps inside the ring)
+    u32 nwr;         // words written to the ring (the words READ follow from it and the two ring positions: nrd())
+    u32 A, B;        // 64-bit window, big-endian words
+    u32 sh;          // lookahead = low32((A:B) >> sh); sh in [0,31].  Unsigned on purpose: advance() takes the BORROW of
+                     // its subtraction as "the window crossed a word" (v_sub_co + branch on VCC, no compare)
+    u32 bias;        // consumed bits = 32*nrd() - sh - bias
+
+    __device__ __forceinline__ void push_half(char *lds, const uint4 &q0, const uint4 &q1, const uint4 &q2,
+                                              const uint4 &q3) {
+        Feed::push_half(lds, q0, q1, q2, q3);
+        nwr += 16;
+    }
+    __device__ __forceinline__ u32 next_word(const char *lds) {
+        const u32 v = *reinterpret_cast<const u32 *>(lds + ra);
+        ra = (ra + THREADS * 4) & (RING_BYTES - 1);
+        return v;
+    }
+    // words still ahead of the reader, minus one, in ring-address units: `wa` is the half that is filled next, i.e.
+    // the row after the newest word; the reader never runs dry, so a distance of 0 rows means 32
+    __device__ __forceinline__ u32 ahead_m1() const { return (wa - ra - THREADS * 4) & (RING_BYTES - 1); }
+    __device__ __forceinline__ u32 nrd() const { return nwr - (ahead_m1() / (THREADS * 4) + 1); }
+    // call at least every 16 symbols (<= 6 words consumed in between)
     __device__ __forceinline__ void maybe_refill(char *lds) {
-        if (ahead_m1() < 16 * ROW) {
+        if (ahead_m1() < 16 * THREADS * 4) {  // 16 words or fewer ahead: the reader has left the older half
             if (stage == 0) {
                 push_half(lds, pf[0], pf[1], pf[2], pf[3]);
                 stage = 1;
@@ -941,31 +825,84 @@ struct AnsBitReaderW {
     }
     __device__ __forceinline__ void init(const u8 *in, u64 in_size_bytes, u64 bit_off, char *lds, u32 tid,
                                          u32 nbits = 0) {
-        base = reinterpret_cast<const uint4 *>(in);
-        n_blocks16 = in_size_bytes >> 4;
-        const u64 j0 = bit_off >> 10;
-        if (ZERO_PAST_END) {  // (streams and buffers are below 2^37 bits: word indices fit 32 bits)
-            const u64 end = bit_off + nbits;
-            wabs = (u32)(j0 * 32);
-            end_word = (u32)(end >> 5);
-            end_mask = ~(0xFFFFFFFFu >> (end & 31u)) & (0u - (u32)((end & 31u) != 0));
-        }
-        col = tid * 4;
-        wa = col;
+        const u64 j0 = Feed::feed_open(in, in_size_bytes, bit_off, nbits);
+        wa = tid * 4;
+        nwr = 0;
         load_line(j0);
         push_half(lds, pf[0], pf[1], pf[2], pf[3]);
         push_half(lds, pf[4], pf[5], pf[6], pf[7]);
         load_line(j0 + 1);
         next_line = j0 + 2;
         stage = 0;
-        start = (u32)bit_off & 1023u;
+        const u32 w0 = (u32)(bit_off >> 5) & 31u;
+        ra = tid * 4 + w0 * THREADS * 4;
+        // a stream that starts in the upper half of its line has fewer than 17 words ahead of it: top the ring
+        // up before the first word is read (the lower half of the ring is already behind the read position)
+        maybe_refill(lds);
+        const u32 pos = (u32)bit_off & 31u;
+        const u32 first = next_word(lds);
+        if (pos == 0) {
+            A = 0;
+            B = first;
+            sh = 0;
+        } else {
+            A = first;
+            B = next_word(lds);
+            sh = 32 - pos;
+        }
+        bias = 32 * nrd() - sh;  // consumed == 0 here
+    }
+    __device__ __forceinline__ u32 consumed() const { return 32 * nrd() - sh - bias; }
+    __device__ __forceinline__ u32 look() const { return __builtin_amdgcn_alignbit(A, B, sh); }
+    __device__ __forceinline__ u32 look(const char *) const { return look(); }
+    __device__ __forceinline__ void advance(const char *lds, u32 nb) {  // nb <= 32
+        if (__builtin_usub_overflow(sh, nb, &sh)) {
+            A = B;
+            B = next_word(lds);
+            sh += 32;
+        }
+    }
+    __device__ __forceinline__ u32 get(const char *lds, u32 w) {  // 1 <= w <= 32
+        const u32 v = look() >> (32 - w);
+        advance(lds, w);
+        return v;
+    }
+};
+
+// Window-less read position over the [word][thread] ring of 32 words (round 4; AnsBitReaderW, AnsBitReaderT).  FEED fills
+// the ring and supplies `wa`, the LDS byte address of the row filled next; it is the base so that its fields stay in
+// front of the cursor's (the order the readers' registers were tuned with).  AnsBitReader keeps two
+// ring words (A, B) in registers and advances them under a branch that the whole wave runs for every pair of symbols (some
+// lane always crosses a word: 5 VALU + 2 SALU + the branch per pair).  Here the lookahead of a pair is read straight out of
+// the ring by BIT POSITION: the two words around the position (two conflict-free ds_read_b32 of the lane's column) and one
+// v_alignbit -- no branch, no window to shift, two VALU instructions less per pair (the rANS decoder issues 12.8 VALU per
+// symbol at 77-80 % of one per four clocks: instruction COUNT is what bounds it).
+//   N = -(bits consumed since bit 0 of the lane's first line or piece): v_alignbit reads its low five bits, which is the
+//       shift that brings the position's bit to the top -- for a position on a word boundary that shift is 0 and the
+//       result is the SECOND word, so the first word read is the one holding the bit BEFORE the position:
+//   P = (position - 1) << RSH: P & ROWMASK is that word's ring row (byte address without the thread column).
+template <int THREADS, class FEED>
+struct AnsRingCursor : FEED {
+    using FEED::RING_BYTES;
+    using FEED::ROW;
+    using FEED::wa;
+    static constexpr u32 RSH = THREADS == 1024 ? 7u : (THREADS == 512 ? 6u : (THREADS == 256 ? 5u : 4u));  // log2(ROW) - 5
+    static constexpr u32 ROWMASK = 31u * ROW;
+    static_assert((32u << RSH) == ROW, "THREADS must be 128, 256, 512 or 1024");
+    u32 N, P;        // see above
+    u32 col;         // tid * 4
+    u32 rowA;        // LDS byte address of the first word the last look() read: rows from here on are still needed
+    u32 start;       // bit position at init (inside the first line or piece loaded)
+
+    // the position is bit `start_` of the ring's row 0 (col is set)
+    __device__ __forceinline__ void seek(u32 start_) {
+        start = start_;
         N = 0u - start;
         P = (start - 1u) << RSH;
         rowA = ((start >> 5) * ROW) | col;  // the word of the position itself (the one before it is never needed again)
-        // a stream that starts in the upper half of its line has fewer than 17 words ahead of it: top the ring up before
-        // the first word is read (the lower half of the ring is already behind the read position)
-        maybe_refill(lds);
     }
+    // rows from the first one still needed up to the newest, minus one, in ring-address units
+    __device__ __forceinline__ u32 ahead_m1() const { return (wa - rowA - ROW) & (RING_BYTES - 1); }
     __device__ __forceinline__ u32 consumed() const { return (0u - N) - start; }
     // the 32 bits at the position (the ring always holds the two words around it)
     __device__ __forceinline__ u32 look(const char *lds) {
@@ -989,8 +926,57 @@ struct AnsBitReaderW {
     }
 };
 
-// Round-6 reader for WAVE-STRIPED slots (the layout AnsBackWriterT writes; scl_stripe_byte).  Same windowless look() /
-// advance() as AnsBitReaderW over the same [word][thread] ring of 32 words -- what changes is the refill: the unit is the
+// Round-4 reader: the line feed of AnsBitReader under the window-less cursor above.  Same ring, same line-granular refill
+// and the same call cadence as AnsBitReader.
+template <int THREADS, bool ZERO_PAST_END = false>
+struct AnsBitReaderW : AnsRingCursor<THREADS, AnsLineFeed<THREADS, ZERO_PAST_END>> {
+    typedef AnsLineFeed<THREADS, ZERO_PAST_END> Feed;
+    typedef AnsRingCursor<THREADS, Feed> Cursor;
+    using Cursor::ROW;
+    using Cursor::RING_BYTES;
+    using Cursor::ahead_m1;
+    using Cursor::col;
+    using Feed::load_line;
+    using Feed::next_line;
+    using Feed::pf;
+    using Feed::stage;
+    using Feed::wa;
+
+    // call at least every 32 symbols of <= 13 bits.  The writer may fill the half at `wa` once at most 16 rows are left ahead
+    // of rowA: that half then lies wholly behind the reader.  A check that finds 17 rows and does nothing still leaves 4
+    // after the <= 13 words of the next 32 symbols -- the position's two words and one to spare.
+    __device__ __forceinline__ void maybe_refill(char *lds) {
+        if (ahead_m1() < 16 * ROW) {
+            if (stage == 0) {
+                Feed::push_half(lds, pf[0], pf[1], pf[2], pf[3]);
+                stage = 1;
+            } else {
+                Feed::push_half(lds, pf[4], pf[5], pf[6], pf[7]);
+                stage = 0;
+                load_line(next_line++);
+            }
+        }
+    }
+    __device__ __forceinline__ void init(const u8 *in, u64 in_size_bytes, u64 bit_off, char *lds, u32 tid,
+                                         u32 nbits = 0) {
+        const u64 j0 = Feed::feed_open(in, in_size_bytes, bit_off, nbits);
+        col = tid * 4;
+        wa = col;
+        load_line(j0);
+        Feed::push_half(lds, pf[0], pf[1], pf[2], pf[3]);
+        Feed::push_half(lds, pf[4], pf[5], pf[6], pf[7]);
+        load_line(j0 + 1);
+        next_line = j0 + 2;
+        stage = 0;
+        Cursor::seek((u32)bit_off & 1023u);
+        // a stream that starts in the upper half of its line has fewer than 17 words ahead of it: top the ring up before
+        // the first word is read (the lower half of the ring is already behind the read position)
+        maybe_refill(lds);
+    }
+};
+
+// Round-6 reader for WAVE-STRIPED slots (the layout AnsBackWriterT writes; scl_stripe_byte).  The window-less cursor of
+// AnsBitReaderW (AnsRingCursor) over the same [word][thread] ring of 32 words -- what changes is the refill: the unit is the
 // 16-byte PIECE, not the 128-byte line.  Piece q of lane l lives at wave_slot + 1024 q + 16 l, so when the lanes of a wave
 // fetch "their next piece" the addresses of neighbouring lanes are adjacent -- lanes within the same row read ONE
 // contiguous run -- where the linear layout made every lane's load touch a different line (64 lines per instruction).
@@ -1010,23 +996,16 @@ struct AnsBitReaderW {
 // requests that follow go out back to back.  The requests, their order and what enters the ring are untouched; no wait is
 // written by hand.  Headline decode 3 % faster (profiles/ans_refill_codegen.txt, profiles/ans_refill_timing.txt).
 // ONE_WAIT = false keeps the refill as the compiler makes it (the any-total range decoder, which would take one more register).
-template <int THREADS, bool ONE_WAIT = true>
-struct AnsBitReaderT {
+template <int THREADS>
+struct AnsPieceFeed {  // the ring and the prefetch registers of AnsBitReaderT
     static constexpr u32 RING_BYTES = 32u * THREADS * 4u;
     static constexpr u32 ROW = THREADS * 4u;
-    static constexpr u32 RSH = THREADS == 1024 ? 7u : (THREADS == 512 ? 6u : (THREADS == 256 ? 5u : 4u));  // log2(ROW) - 5
-    static constexpr u32 ROWMASK = 31u * ROW;
-    static_assert((32u << RSH) == ROW, "THREADS must be 128, 256, 512 or 1024");
     const u8 *wbase;  // the wave's striped slot + 16 * lane
     u32 goff;         // byte offset (from wbase) of the next piece to request
     u32 glast;        // ... of the lane's last piece
     uint4 pf[4];      // pieces requested at the previous refill point
     u32 npf;          // how many of them
     u32 wa;           // LDS byte address of the ring row filled next (a multiple of four rows | col)
-    u32 N, P;         // as AnsBitReaderW
-    u32 col;          // tid * 4
-    u32 rowA;         // LDS byte address of the first word the last look() read
-    u32 start;        // bit position at init (inside the first piece loaded: < 128)
 
     __device__ __forceinline__ uint4 fetch() {
         const uint4 q = *reinterpret_cast<const uint4 *>(wbase + goff);
@@ -1041,7 +1020,23 @@ struct AnsBitReaderT {
         *reinterpret_cast<u32 *>(r + 3 * ROW) = __builtin_bswap32(q.w);
         wa = (wa + 4 * ROW) & (RING_BYTES - 1);
     }
-    __device__ __forceinline__ u32 ahead_m1() const { return (wa - rowA - ROW) & (RING_BYTES - 1); }
+};
+template <int THREADS, bool ONE_WAIT = true>
+struct AnsBitReaderT : AnsRingCursor<THREADS, AnsPieceFeed<THREADS>> {
+    typedef AnsPieceFeed<THREADS> Feed;
+    typedef AnsRingCursor<THREADS, Feed> Cursor;
+    using Cursor::RSH;
+    using Cursor::ahead_m1;
+    using Cursor::col;
+    using Feed::fetch;
+    using Feed::glast;
+    using Feed::goff;
+    using Feed::npf;
+    using Feed::pf;
+    using Feed::push_piece;
+    using Feed::wa;
+    using Feed::wbase;
+
     // call at least every 32 symbols of <= 13 bits
     __device__ __forceinline__ void maybe_refill(char *lds) {
         // touch all four prefetch registers HERE, unconditionally (the idiom of rf_encode16): the compiler then waits for
@@ -1075,41 +1070,23 @@ struct AnsBitReaderT {
         for (int i = 0; i < 8; ++i) push_piece(lds, q[i]);  // wa is back at row 0: the ring is full
         npf = 0;
         if (ONE_WAIT) pf[0] = pf[1] = pf[2] = pf[3] = make_uint4(0, 0, 0, 0);  // maybe_refill names them before the first request
-        start = rel & 127u;
-        N = 0u - start;
-        P = (start - 1u) << RSH;
-        rowA = ((start >> 5) * ROW) | col;
-    }
-    __device__ __forceinline__ u32 consumed() const { return (0u - N) - start; }
-    __device__ __forceinline__ u32 look(const char *lds) {
-        const u32 a = (P & ROWMASK) | col;
-        const u32 b = ((P + ROW) & ROWMASK) | col;
-        rowA = a;
-        const u32 A = *reinterpret_cast<const u32 *>(lds + a);
-        const u32 B = *reinterpret_cast<const u32 *>(lds + b);
-        return __builtin_amdgcn_alignbit(A, B, N);
-    }
-    __device__ __forceinline__ void advance(const char *, u32 nb) {
-        N -= nb;
-        asm("v_lshl_add_u32 %0, %1, %2, %0" : "+v"(P) : "v"(nb), "n"(RSH));
-    }
-    __device__ __forceinline__ u32 get(const char *lds, u32 w) {  // 1 <= w <= 32
-        const u32 v = look(lds) >> (32 - w);
-        advance(lds, w);
-        return v;
+        Cursor::seek(rel & 127u);
     }
 };
 
-// Forward twin of AnsBackWriter for streams that grow front to back (arithmetic coder): completed big-endian
-// words go to the per-lane LDS ring ([word][thread], at LDS offset 0) and leave for memory as whole 128-byte lines
-// (the first 64-byte half waits in registers), so that a lane only ever stores whole, aligned lines.
+// Forward twin of AnsBackWriter for streams that grow front to back (static arithmetic coder, prefix codes): the bit
+// accumulator of scl_common.h (SclFwdBits) in front of a word ring that leaves for memory as whole lines.  Completed
+// big-endian words go to the per-lane LDS ring ([word][thread], at LDS offset 0) and leave as whole 128-byte lines -- the
+// first 64-byte half waits in registers (`held`) until the second is ready -- so that a lane only ever stores whole,
+// aligned lines.
 // BOUNDED (the prefix-code encoder, scl_prefix.hip): the slot holds `cap` bytes (a multiple of 16); a line or tail that
-// would cross it is not stored and sets `overflow`, the bit count still comes out whole -- as RgOut (scl_range_fast.hip).
+// would cross it is not stored and sets `overflow`, the bit count still comes out whole.
+// RgOut (scl_range_fast.hip) keeps a ring of the same kind under its byte accumulator, as a copy: the two writers list the
+// ring's fields in different orders, that order decides how the fields are split into registers, and with either order
+// for both the other's kernels came out with another register allocation (profiles/io_refactor_codegen.txt).
 template <int THREADS, bool BOUNDED = false>
-struct AnsFwdWriter {
+struct AnsFwdWriter : SclFwdBits {
     static constexpr u32 RING_BYTES = 32u * THREADS * 4u;
-    u32 hi;    // pending bits, right-aligned (the oldest is the most significant), < 32 of them
-    u32 nacc;  // number of pending bits
     u32 ra;    // LDS byte address of the ring word that completes next
     u32 fa;    // LDS byte address of the oldest unflushed word
     u32 pend;  // completed words not yet stored to memory
@@ -1123,8 +1100,7 @@ struct AnsFwdWriter {
     __device__ __forceinline__ void init(u32 tid, u8 *slot_, u64 cap_ = 0) {
         cap = cap_;
         overflow = 0;
-        hi = 0;
-        nacc = 0;
+        SclFwdBits::init();
         ra = tid * 4;
         fa = tid * 4;
         pend = 0;
@@ -1133,39 +1109,16 @@ struct AnsFwdWriter {
         have_held = 0;
         held[0] = held[1] = held[2] = held[3] = make_uint4(0, 0, 0, 0);
     }
-    __device__ __forceinline__ void put(char *lds, u32 v, u32 w) {  // v < 2^w, w <= 32
-        const u32 tot = nacc + w;
-        if (tot >= 32) {
-            const u32 r = tot - 32;  // <= 31
-            // 32-bit arithmetic on purpose.  The obvious (u32)(t >> r) on a 64-bit t compiled to v_lshrrev_b64 with
-            // a just-computed VGPR shift amount and, at full occupancy, stored a wrong word about once in 10^8
-            // (tools/stress_fast_kernels.py: ~3 words per 1 GiB encode held the bits accumulated BEFORE this call);
-            // this form has been stress-tested clean.  w - r = 32 - nacc is in [1, 32); r == 0 means w == 32 - nacc.
-            const u32 word = (r == 0) ? ((hi << (w & 31)) | v) : ((hi << (w - r)) | (v >> r));
-            *reinterpret_cast<u32 *>(lds + ra) = __builtin_bswap32(word);
-            ra = (ra + THREADS * 4) & (RING_BYTES - 1);
-            ++pend;
-            hi = v & ((1u << r) - 1u);
-            nacc = r;
-        } else {
-            hi = (hi << w) | v;  // tot < 32, so w < 32
-            nacc = tot;
-        }
+    __device__ __forceinline__ void push_word(char *lds, u32 word_be) {
+        *reinterpret_cast<u32 *>(lds + ra) = word_be;
+        ra = (ra + THREADS * 4) & (RING_BYTES - 1);
+        ++pend;
     }
-    // put for the per-symbol field of the arithmetic encoders (w <= 32; w = 0 allowed with v = 0): pending bits and field side
-    // by side in 64 bits, only the completed word is conditional -- no case split on which half the word comes from and no
-    // values merged after a branch.  (The round-1 fault blamed on this 64-bit form was a register spill --
-    // profiles/r03_fwd_writer_fault_analysis.txt; no kernel spills now, tests/test_no_scratch.py.)
-    __device__ __forceinline__ void put_field(char *lds, u32 v, u32 w) {
-        const u32 tot = nacc + w;              // <= 63
-        const u64 wide = ((u64)hi << w) | v;   // tot valid bits, right-aligned
-        nacc = tot & 31u;
-        if (tot >= 32) {
-            *reinterpret_cast<u32 *>(lds + ra) = __builtin_bswap32((u32)(wide >> nacc));  // tot - 32 = tot & 31 here
-            ra = (ra + THREADS * 4) & (RING_BYTES - 1);
-            ++pend;
-        }
-        hi = (u32)wide & ((1u << nacc) - 1u);
+    __device__ __forceinline__ void put(char *lds, u32 v, u32 w) {  // v < 2^w, w <= 32
+        SclFwdBits::put(v, w, [&](u32 word_be) { push_word(lds, word_be); });
+    }
+    __device__ __forceinline__ void put_field(char *lds, u32 v, u32 w) {  // the per-symbol field: w = 0 allowed with v = 0
+        SclFwdBits::put_field(v, w, [&](u32 word_be) { push_word(lds, word_be); });
     }
     // 16 pending words leave the ring at a time; call after at most 16 new words
     __device__ __forceinline__ void maybe_flush(char *lds) {
@@ -1204,12 +1157,7 @@ struct AnsFwdWriter {
         }
     }
     __device__ __forceinline__ void put_run(char *lds, u32 bit, u32 count) {  // `count` copies of `bit`
-        while (count >= 32) {
-            put(lds, bit ? 0xFFFFFFFFu : 0u, 32);
-            maybe_flush(lds);
-            count -= 32;
-        }
-        if (count) put(lds, bit ? ((1u << count) - 1u) : 0u, count);
+        SclFwdBits::put_run(bit, count, [&](u32 word_be) { push_word(lds, word_be); }, [&] { maybe_flush(lds); });
     }
     __device__ __forceinline__ u64 finish(char *lds) {  // returns the stream length in bits
         maybe_flush(lds);

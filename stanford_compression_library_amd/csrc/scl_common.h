@@ -311,6 +311,61 @@ struct FwdBitWriter {
     }
 };
 
+// The bit accumulator of the tuned forward writers (AnsFwdWriter in scl_ans_fast_io.h: words to an LDS ring; AfWriterT in
+// scl_aec_lane_io.h: words to the slot or a staging sector).  At most 31 pending bits in one register; a completed word is
+// handed, big-endian, to the owner's `sink(u32 word_be)` before the pending bits are updated.
+struct SclFwdBits {
+    u32 hi;    // pending bits, right-aligned (the oldest is the most significant), < 32 of them
+    u32 nacc;  // number of pending bits
+
+    __device__ __forceinline__ void init() {
+        hi = 0;
+        nacc = 0;
+    }
+    template <class SINK>
+    __device__ __forceinline__ void put(u32 v, u32 w, SINK &&sink) {  // v < 2^w, w <= 32
+        const u32 tot = nacc + w;
+        if (tot >= 32) {
+            const u32 r = tot - 32;  // <= 31
+            // 32-bit arithmetic on purpose.  The obvious (u32)(t >> r) on a 64-bit t compiled to v_lshrrev_b64 with
+            // a just-computed VGPR shift amount and, at full occupancy, stored a wrong word about once in 10^8
+            // (tools/stress_fast_kernels.py: ~3 words per 1 GiB encode held the bits accumulated BEFORE this call);
+            // this form has been stress-tested clean.  w - r = 32 - nacc is in [1, 32); r == 0 means w == 32 - nacc.
+            const u32 word = (r == 0) ? ((hi << (w & 31)) | v) : ((hi << (w - r)) | (v >> r));
+            sink(__builtin_bswap32(word));
+            hi = v & ((1u << r) - 1u);
+            nacc = r;
+        } else {
+            hi = (hi << w) | v;  // tot < 32, so w < 32
+            nacc = tot;
+        }
+    }
+    // put for the per-symbol field of the arithmetic and prefix encoders (w <= 32; w = 0 allowed with v = 0): pending bits and
+    // field side by side in 64 bits, only the completed word is conditional -- no case split on which half the word comes
+    // from and no values merged after a branch (put above costs a lone wave ~8 register copies per symbol for those).  (The
+    // round-1 fault blamed on this 64-bit form was a register spill -- profiles/r03_fwd_writer_fault_analysis.txt; no kernel
+    // spills now, tests/test_no_scratch.py.)
+    template <class SINK>
+    __device__ __forceinline__ void put_field(u32 v, u32 w, SINK &&sink) {
+        const u32 tot = nacc + w;             // <= 63
+        const u64 wide = ((u64)hi << w) | v;  // tot valid bits, right-aligned
+        nacc = tot & 31u;
+        if (tot >= 32) sink(__builtin_bswap32((u32)(wide >> nacc)));  // tot - 32 = tot & 31 here
+        hi = (u32)wide & ((1u << nacc) - 1u);
+    }
+    // `count` copies of `bit`; `word_done()` after every whole word of the run (an owner that must drain its buffer every
+    // so many words does so there)
+    template <class SINK, class DONE>
+    __device__ __forceinline__ void put_run(u32 bit, u32 count, SINK &&sink, DONE &&word_done) {
+        while (count >= 32) {
+            put(bit ? 0xFFFFFFFFu : 0u, 32, sink);
+            word_done();
+            count -= 32;
+        }
+        if (count) put(bit ? ((1u << count) - 1u) : 0u, count, sink);
+    }
+};
+
 // Forward reader over an arbitrary bit range [pos, end) of a buffer.
 struct BitReader {
     const u8 *base;

@@ -14,7 +14,7 @@
 
 #include <type_traits>
 
-#include "scl_ans_fast_io.h"  // scl_transpose8: the 8 x 8 register transpose behind the cooperative line store
+#include "scl_ans_fast_io.h"  // scl_flush_rows under RgOutT, scl_transpose8 in RgOut, AnsBitReaderW / T
 #include "scl_range_internal.h"
 
 #define RGE_THREADS 256
@@ -177,12 +177,15 @@ struct RgOut {
 // at wave_slot + (b / 16) * 1024 + 16 l + b % 16, so piece q of the 64 lanes of a wave is one contiguous kilobyte).  What the
 // cooperative line store above buys only for lanes in lockstep (uniform bytes), this buys for any table: a lane keeps
 // 16-byte pieces, not 128-byte lines, and the WAVE stores the next row when every lane present holds a complete piece (four
-// nested ballots per flush point; AnsBackWriterT has the argument) -- 64 adjacent pieces per store instruction, no transpose,
+// nested ballots per flush point; scl_flush_rows has the argument) -- 64 adjacent pieces per store instruction, no transpose,
 // no 64-byte half line held in registers.  A lane holding more than 15 words when it leaves a flush point (32 ring words - the
 // 16 that 16 symbols can complete) stores its own oldest pieces.  Streams grow front to back: rows ascend.
+// (The byte accumulator acc / cnt / put_bytes stays a copy of RgOut's: as a common base of the two it moved RgOut's fields
+// and with them the instruction order of every linear encoder -- profiles/io_refactor_codegen.txt.)
 struct RgOutT {
     static constexpr bool STRIPED = true;
     static constexpr u32 ROW = RGE_THREADS * 4;
+    static constexpr u32 PIECE = 4;  // pending() counts words
     u64 acc;   // as RgOut
     u32 cnt;
     u32 ra;    // LDS byte address of the ring word written next
@@ -213,6 +216,7 @@ struct RgOutT {
             ++pend;
         }
     }
+    __device__ __forceinline__ u32 pending() const { return pend; }
     // piece R (0 = oldest) of the complete ones -> its row; nothing is updated (rows_done)
     template <u32 R>
     __device__ __forceinline__ void store_row(char *lds) {
@@ -232,35 +236,8 @@ struct RgOutT {
         fa = (fa + 4u * m * ROW) & (RGE_RING_BYTES - 1);
         pend -= 4u * m;
     }
-    // call at least every 16 symbols (<= 16 new words)
-    template <bool COOP_UNUSED = false>
-    __device__ __forceinline__ void maybe_flush(char *lds) {
-        const u32 p = pend;
-        const u64 all = __builtin_amdgcn_ballot_w64(true);
-        if (__builtin_amdgcn_ballot_w64(p >= 4u) == all) {
-            store_row<0>(lds);
-            if (__builtin_amdgcn_ballot_w64(p >= 8u) == all) {
-                store_row<1>(lds);
-                if (__builtin_amdgcn_ballot_w64(p >= 12u) == all) {
-                    store_row<2>(lds);
-                    if (__builtin_amdgcn_ballot_w64(p >= 16u) == all) {
-                        store_row<3>(lds);
-                        rows_done(4);
-                    } else {
-                        rows_done(3);
-                    }
-                } else {
-                    rows_done(2);
-                }
-            } else {
-                rows_done(1);
-            }
-        }
-        while (pend > 15u) {
-            store_row<0>(lds);
-            rows_done(1);
-        }
-    }
+    // The flush point is scl_flush_rows(o, 15u, lds), called by the kernel itself (RG_FLUSH): at least every 16 symbols
+    // (<= 16 new words); a lane may leave with 15 words (32 ring words - those 16).
     __device__ __forceinline__ u64 finish(char *lds) {  // returns total bytes
         while (pend >= 4u) {
             store_row<0>(lds);
@@ -418,6 +395,15 @@ __device__ __forceinline__ uint2 rg_entry(const char *tab, u32 a) {
     return *reinterpret_cast<const uint2 *>(tab + a);
 }
 
+// flush point of either writer (o, lds, MODE and OUT are the caller's)
+#define RG_FLUSH()                                        \
+    do {                                                  \
+        if constexpr (OUT::STRIPED)                       \
+            scl_flush_rows(o, 15u, lds);                  \
+        else                                              \
+            o.template maybe_flush<RG_UNI(MODE)>(lds);    \
+    } while (0)
+
 template <int MODE, typename OUT>
 __device__ __forceinline__ void rg_encode16(const uint4 v, u32 &low, u32 &range, OUT &o, u32 &bad, char *lds,
                                             const char *tab, const RgDivM &md) {
@@ -459,7 +445,7 @@ __device__ __forceinline__ void rg_encode16(const uint4 v, u32 &low, u32 &range,
             }
         }
     }
-    o.template maybe_flush<RG_UNI(MODE)>(lds);
+    RG_FLUSH();
 }
 
 // OUT: RgOut (linear slots) or RgOutT (wave-striped slots, ABI 8: `out` then holds round_up(n_chunks, 64) slots)
@@ -534,9 +520,9 @@ __global__ void __launch_bounds__(RGE_THREADS, 4) range_encode_fast_kernel(Range
         u32 bytes, nb, z0 = 0, zn = 0;
         rg_encode_symbol<MODE>(low, range, rg_entry<MODE>(tab, a), md, bytes, nb, z0, zn, o, lds);
         o.put_bytes(lds, bytes, nb);
-        if ((i & 15u) == 15u) o.template maybe_flush<RG_UNI(MODE)>(lds);
+        if ((i & 15u) == 15u) RG_FLUSH();
     }
-    o.template maybe_flush<RG_UNI(MODE)>(lds);
+    RG_FLUSH();
     o.put_bytes(lds, low, 32);  // flush :181-186: the four bytes of low, most significant first
     const u64 total_bytes = o.finish(lds);
     out_bit_off[c] = c * out_stride * 8;
@@ -547,101 +533,6 @@ __global__ void __launch_bounds__(RGE_THREADS, 4) range_encode_fast_kernel(Range
 // ---------------------------------------------------------------------------------------------------
 // decode
 // ---------------------------------------------------------------------------------------------------
-struct RgIn {  // forward bit reader over a per-lane LDS word ring (same scheme as the rANS fast decoder)
-    const uint4 *base;
-    u64 n_blocks16, next64;
-    uint4 pf[4];
-    u32 ra, wa, nrd, nwr;
-    u32 A, B;
-    int sh;
-    u32 bias;
-
-    __device__ __forceinline__ void load64(u64 j) {
-        // one bounds test for the whole 64-byte block (all but the buffer's last are readable whole): the four separately
-        // tested loads were 36 instructions per refill, run by the whole wave whenever any lane refills
-        if (j * 4 + 4 <= n_blocks16) {
-            const uint4 *p = base + j * 4;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pf[i] = p[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const u64 idx = j * 4 + i;
-                pf[i] = (idx < n_blocks16) ? base[idx] : make_uint4(0, 0, 0, 0);
-            }
-        }
-    }
-    __device__ __forceinline__ void push_pf(char *lds) {
-        char *r = lds + wa;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<u32 *>(r + (4 * i + 0) * RGD_THREADS * 4) = __builtin_bswap32(pf[i].x);
-            *reinterpret_cast<u32 *>(r + (4 * i + 1) * RGD_THREADS * 4) = __builtin_bswap32(pf[i].y);
-            *reinterpret_cast<u32 *>(r + (4 * i + 2) * RGD_THREADS * 4) = __builtin_bswap32(pf[i].z);
-            *reinterpret_cast<u32 *>(r + (4 * i + 3) * RGD_THREADS * 4) = __builtin_bswap32(pf[i].w);
-        }
-        wa ^= 16 * RGD_THREADS * 4;
-        nwr += 16;
-    }
-    __device__ __forceinline__ u32 next_word(const char *lds) {
-        const u32 v = *reinterpret_cast<const u32 *>(lds + ra);
-        ra = (ra + RGD_THREADS * 4) & (RGD_RING_BYTES - 1);
-        ++nrd;
-        return v;
-    }
-    // call at least every 4 symbols (a symbol consumes <= 4 bytes: 4 words in between)
-    __device__ __forceinline__ void maybe_refill(char *lds) {
-        if (nwr - nrd <= 16) {
-            push_pf(lds);
-            load64(next64++);
-        }
-    }
-    __device__ __forceinline__ void init(const u8 *in, u64 in_size_bytes, u64 bit_off, char *lds, u32 tid) {
-        base = reinterpret_cast<const uint4 *>(in);
-        n_blocks16 = in_size_bytes >> 4;
-        const u64 j0 = bit_off >> 9;
-        wa = tid * 4;
-        nwr = 0;
-        load64(j0);
-        push_pf(lds);
-        load64(j0 + 1);
-        push_pf(lds);
-        load64(j0 + 2);
-        next64 = j0 + 3;
-        const u32 w0 = (u32)(bit_off >> 5) & 15u;
-        ra = tid * 4 + w0 * RGD_THREADS * 4;
-        nrd = w0;
-        const u32 pos = (u32)bit_off & 31u;
-        const u32 first = next_word(lds);
-        if (pos == 0) {
-            A = 0;
-            B = first;
-            sh = 0;
-        } else {
-            A = first;
-            B = next_word(lds);
-            sh = 32 - (int)pos;
-        }
-        bias = 32 * nrd - (u32)sh;
-    }
-    __device__ __forceinline__ u32 consumed() const { return 32 * nrd - (u32)sh - bias; }
-    __device__ __forceinline__ u32 look() const { return __builtin_amdgcn_alignbit(A, B, (u32)sh); }
-    __device__ __forceinline__ u32 look(const char *) const { return look(); }
-    __device__ __forceinline__ void advance(const char *lds, u32 nb) {  // nb <= 32
-        sh -= (int)nb;
-        if (sh < 0) {
-            A = B;
-            B = next_word(lds);
-            sh += 32;
-        }
-    }
-    __device__ __forceinline__ u32 get32(const char *lds) {
-        const u32 v = look();
-        advance(lds, 32);
-        return v;
-    }
-};
-
 // floor(d / r) for any d < 2^32 and r >= 1, exactly: trunc((d + 0.5) * x) in binary64 with x = 1 / r good to 2^-42
 // (v_rcp_f32 of the rounded divisor, 2^-21, squared by one Newton step on the exact divisor).  (d + 0.5) / r is at
 // least 0.5 / r away from an integer, the error of the product is below (d + 0.5) / r * 2^-41 -- less than that for

@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(RF_THREADS, (EncOut::STRIPED && CHECK_SYM) ? 3
 #define RF_FLUSH()                                   \
     do {                                             \
         if constexpr (EncOut::STRIPED) {             \
-            o.flush(lds, wg_out, NB_T == 1 ? 72u : 60u); \
+            scl_flush_rows(o, NB_T == 1 ? 72u : 60u, lds, wg_out); \
         } else {                                     \
             if (coop_out)                            \
                 o.flush_quad(lds, wg_out, threadIdx.x); \

@@ -660,7 +660,7 @@ def test_random_models_fast_paths_vs_oracle(seed, dev):
 def test_tuned_kernels_full_occupancy_stress(mode, dev):
     """1 GiB batches, three times: every tuned kernel family against the any-parameter kernels word for word
     (encode) and against the input (decode).  A timing-dependent fault of about 3 wrong words per GiB in an
-    earlier forward writer (64-bit shift with a just-computed amount, see AnsFwdWriter::put) was only visible at
+    earlier forward writer (64-bit shift with a just-computed amount, see SclFwdBits::put) was only visible at
     this scale; nothing smaller would have caught it."""
     n_chunks, chunk_len = 262144, 4096
     if mode == "fixed":

@@ -1,6 +1,6 @@
 """Stress the arithmetic-coder fast kernels at full occupancy: N full-size encodes compared word for word with the
 any-parameter kernel's streams, and every decode compared with the input (rare, timing-dependent faults -- see the
-note in AnsFwdWriter::put -- only show up at this scale).  MODEL=fixed|order1, NCHUNKS, REPS."""
+note in SclFwdBits::put -- only show up at this scale).  MODEL=fixed|order1, NCHUNKS, REPS."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
