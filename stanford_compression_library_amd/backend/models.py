@@ -257,6 +257,23 @@ class _DeviceModel:
                             torch.empty(n_chunks, dtype=torch.int32, device=device),
                             torch.empty(n_chunks, dtype=torch.int32, device=device), n_chunks, layout)
 
+    # -- the argument lists of the batch entry points, from the model to d_status (include/scl_hip.h), for chunks a..b of
+    # whole-batch tensors: every pointer is moved to chunk a, so the bit offsets written or read count from there ----------
+    def _encode_args(self, sym, lens, out: EncodedBatch, a: int, b: int) -> list:
+        """rows a..b of ``sym`` (their lengths in ``lens``, or None) -> slots a..b of ``out``"""
+        return [self._h, sym.data_ptr() + a * sym.stride(0) * sym.element_size(), sym.stride(0),
+                lens.data_ptr() + 4 * a if lens is not None else None, sym.shape[1], b - a,
+                out.data.data_ptr() + a * out.stride, out.stride, out.bit_offset.data_ptr() + 8 * a,
+                out.nbits.data_ptr() + 4 * a, out.status.data_ptr() + 4 * a]
+
+    def _decode_args(self, data, in_bytes: int, bit_offset, nbits, chunk_cap: int, out, a: int, b: int) -> list:
+        """streams a..b inside ``data`` (``in_bytes``: its size, or the slot stride of striped slots) -> rows a..b of
+        ``out`` = (sym, lens, consumed, status)"""
+        sym, lens, used, status = out
+        return [self._h, data.data_ptr(), in_bytes, bit_offset.data_ptr() + 8 * a, nbits.data_ptr() + 4 * a, b - a,
+                sym.data_ptr() + a * sym.stride(0) * sym.element_size(), sym.stride(0), int(chunk_cap),
+                lens.data_ptr() + 4 * a, used.data_ptr() + 4 * a, status.data_ptr() + 4 * a]
+
     def encode_batch(self, sym, lens=None, out_stride: Optional[int] = None, stream=None,
                      out: Optional[EncodedBatch] = None, any_parameter_kernels: bool = False,
                      layout: Optional[str] = None) -> EncodedBatch:
@@ -277,11 +294,8 @@ class _DeviceModel:
         assert out.n_chunks == n_chunks
         striped = out.layout == "striped"
         assert not (striped and any_parameter_kernels), "striped slots are written by the tuned kernels only"
-        stride, data, bit_off, nbits, status = out.stride, out.data, out.bit_offset, out.nbits, out.status
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        args = [self._h, sym.data_ptr(), sym.stride(0), lens.data_ptr() if lens is not None else None,
-                chunk_len, n_chunks, data.data_ptr(), stride, bit_off.data_ptr(), nbits.data_ptr(),
-                status.data_ptr()]
+        args = self._encode_args(sym, lens, out, 0, n_chunks)
         if self._needs_scratch:
             scratch, nbytes = self._scratch(n_chunks, dev)
             args += [scratch.data_ptr() if scratch is not None else None, nbytes]
@@ -298,15 +312,13 @@ class _DeviceModel:
         those chunks count from SLOT a, i.e. from ``out.data.data_ptr() + a * out.stride``."""
         import torch
 
-        n_rows, chunk_len = sym.shape
+        n_rows = sym.shape[0]
         assert 0 <= a <= b <= n_rows == out.n_chunks and sym.stride(1) == 1
         striped = out.layout == "striped"
         assert not striped or a % 64 == 0, "striped slots: a sub-batch starts on a multiple of 64 chunks"
         assert sym.stride(0) % 16 == 0 and sym.data_ptr() % 16 == 0, "rows must start on 16-byte boundaries"
         assert not self.wide, "the overlapped pipeline carries uint8 symbols"
-        args = [self._h, sym.data_ptr() + a * sym.stride(0), sym.stride(0), None, chunk_len, b - a,
-                out.data.data_ptr() + a * out.stride, out.stride, out.bit_offset.data_ptr() + 8 * a,
-                out.nbits.data_ptr() + 4 * a, out.status.data_ptr() + 4 * a]
+        args = self._encode_args(sym, None, out, a, b)
         if self._needs_scratch:
             scratch, nbytes = self._scratch(b - a, sym.device)
             args += [scratch.data_ptr() if scratch is not None else None, nbytes]
@@ -342,15 +354,13 @@ class _DeviceModel:
         n_chunks = int(bit_offset.numel())
         dev = data.device
         sym, lens, used, status = out if out is not None else self.alloc_decoded(n_chunks, chunk_cap, dev)
-        out_stride = sym.stride(0)
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         striped = striped_stride is not None
         assert not (striped and any_parameter_kernels), "striped slots are read by the tuned kernels only"
         # (a striped reader walks whole wave-slots: the buffer must hold round_up(n_chunks, 64) slots)
         assert not striped or data.numel() >= (n_chunks + 63) // 64 * 64 * int(striped_stride), "striped buffer too short"
-        args = [self._h, data.data_ptr(), int(striped_stride) if striped else data.numel(), bit_offset.data_ptr(),
-                nbits.data_ptr(), n_chunks,
-                sym.data_ptr(), out_stride, int(chunk_cap), lens.data_ptr(), used.data_ptr(), status.data_ptr()]
+        args = self._decode_args(data, int(striped_stride) if striped else data.numel(), bit_offset, nbits, chunk_cap,
+                                 (sym, lens, used, status), 0, n_chunks)
         if self._needs_scratch:
             scratch, nbytes = self._scratch(n_chunks, dev)
             args += [scratch.data_ptr() if scratch is not None else None, nbytes]
@@ -668,10 +678,8 @@ class AecModel(_DeviceModel):
             out = self.alloc_encoded(n_chunks, chunk_len, sym.device, out_stride)
         st = stream if stream is not None else torch.cuda.current_stream(sym.device).cuda_stream
         with torch.cuda.device(sym.device):
-            rc = self._sym_fn("encode_batch_resume")(
-                self._h, sym.data_ptr(), sym.stride(0), lens.data_ptr() if lens is not None else None, chunk_len,
-                n_chunks, out.data.data_ptr(), out.stride, out.bit_offset.data_ptr(), out.nbits.data_ptr(),
-                out.status.data_ptr(), state.data_ptr(), state.numel(), n_coders, st)
+            rc = self._sym_fn("encode_batch_resume")(*self._encode_args(sym, lens, out, 0, n_chunks), state.data_ptr(),
+                                                     state.numel(), n_coders, st)
         _lib.check(rc, "scl_aec_encode_batch_resume")
         return out
 
@@ -685,8 +693,7 @@ class AecModel(_DeviceModel):
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             rc = self._sym_fn("decode_batch_resume")(
-                self._h, data.data_ptr(), data.numel(), bit_offset.data_ptr(), nbits.data_ptr(), n_chunks,
-                sym.data_ptr(), sym.stride(0), int(chunk_cap), lens.data_ptr(), used.data_ptr(), status.data_ptr(),
+                *self._decode_args(data, data.numel(), bit_offset, nbits, chunk_cap, (sym, lens, used, status), 0, n_chunks),
                 state.data_ptr(), state.numel(), n_coders, st)
         _lib.check(rc, "scl_aec_decode_batch_resume")
         return sym[:, :chunk_cap], lens, used, status

@@ -595,76 +595,7 @@ static bool aec_wide_dense_forced() {
     return e && e[0] == 'd';
 }
 
-// ---- the tuned kernel families of the byte entry points ---------------------------------------------------------------
-// In priority order: the FIRST family that serves the model and can take the call's rows runs it; the any-parameter
-// kernels follow the table.  The row relay, scl_aec_fast_path and both dispatches walk it.
-struct AecFamily {
-    const char *name;  // for comments and error text
-    bool (*served)(const scl_aec_model *m, u64 max_symbols);
-    // what the kernels need of the rows, beyond what holds for every tuned family (encode: slots of scl_aec_slot_bytes;
-    // decode: at least one whole 32-bit word of input).  in_ok: d_in is 16-byte aligned
-    bool (*enc_rows_ok)(const SclEncodeArgs<u8> &a, const scl_aec_model *m);
-    bool (*dec_rows_ok)(const SclDecodeArgs<u8> &a, const scl_aec_model *m, bool in_ok);
-    u64 (*zero_bytes)(const scl_aec_model *m, u64 n_chunks);  // scratch the kernels need zero-filled; null: they use none
-    void (*encode)(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
-    void (*decode)(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
-};
-
-// rows start on `align`-byte boundaries and hold `row` bytes rounded up to it
-static bool aec_rows(const void *p, u64 stride, u64 align, u64 row) {
-    return (((uintptr_t)p | stride) & (align - 1)) == 0 && stride >= scl_round_up(row, align);
-}
-static bool aec_enc_rows4(const SclEncodeArgs<u8> &a, const scl_aec_model *) {
-    return aec_rows(a.d_sym, a.sym_stride, 4, a.chunk_len);
-}
-static bool aec_dec_rows4(const SclDecodeArgs<u8> &a, const scl_aec_model *, bool) {
-    return aec_rows(a.d_out_sym, a.out_stride, 4, a.out_cap);
-}
-static bool aec_wide_sparse_ok(const scl_aec_model *m, u64 n) { return aec_wide_ok(m, n) && !aec_wide_dense_forced(); }
-static bool aec_wide_dense_ok(const scl_aec_model *m, u64 n) { return aec_wide_ok(m, n) && aec_wide_dense_forced(); }
-
-static const AecFamily aec_families[] = {
-    // small-alphabet adaptive models: cumulative context rows in LDS, closed-form renormalisation (scl_aec_fast.hip; the
-    // encoder with a chunk's work split over three waves, scl_aec_split.hip)
-    {"fast/split", aec_fast_ok,
-     [](const SclEncodeArgs<u8> &a, const scl_aec_model *) {
-         return aec_rows(a.d_sym, a.sym_stride, 16, a.chunk_len) && (a.out_stride & 63) == 0;
-     },
-     [](const SclDecodeArgs<u8> &a, const scl_aec_model *, bool in_ok) {
-         return in_ok && aec_rows(a.d_out_sym, a.out_stride, 16, a.out_cap);
-     },
-     nullptr, aec_fast_encode_launch, aec_fast_decode_launch},
-    // adaptive i.i.d. model on a large alphabet: two-level cumulative table per lane in LDS (scl_aec_iid.hip)
-    {"iid", aec_iid_ok, aec_enc_rows4, aec_dec_rows4, nullptr, aec_iid_encode_launch, aec_iid_decode_launch},
-    // static model: shared table in LDS, line-granular I/O, 32-bit byte offsets into the input (scl_aec_static.hip)
-    {"static", [](const scl_aec_model *m, u64) { return aec_static_ok(m); },
-     [](const SclEncodeArgs<u8> &a, const scl_aec_model *) {
-         return aec_rows(a.d_sym, a.sym_stride, 16, 0) && (a.out_stride & 15) == 0;
-     },
-     [](const SclDecodeArgs<u8> &a, const scl_aec_model *, bool in_ok) {
-         return in_ok && a.in_size_bytes < (1ull << 34) && aec_rows(a.d_out_sym, a.out_stride, 16, a.out_cap);
-     },
-     nullptr, aec_static_encode_launch, aec_static_decode_launch},
-    // order-k on a large alphabet: one table line per symbol while a context is young (scl_aec_sparse.hip) ...
-    {"sparse", aec_wide_sparse_ok, aec_enc_rows4, aec_dec_rows4, aec_sparse_zero_bytes, aec_sparse_encode_launch,
-     aec_sparse_decode_launch},
-    // ... or, under SCL_AEC_WIDE=dense, the two-level rows in device memory, tuned arithmetic, lookups issued ahead
-    // (scl_aec_wide.hip: u16 cells)
-    {"wide", aec_wide_dense_ok, aec_enc_rows4, aec_dec_rows4, aec_wide_scratch_bytes, aec_wide_encode_launch,
-     aec_wide_decode_launch},
-};
-
-static bool aec_tuned_serves(const scl_aec_model *m, u64 max_symbols) {
-    for (const AecFamily &f : aec_families)
-        if (f.served(m, max_symbols)) return true;
-    return false;
-}
-
-extern "C" int scl_aec_fast_path(const scl_aec_model *m, uint64_t max_symbols) {
-    return (m && aec_tuned_serves(m, max_symbols)) ? 1 : 0;
-}
-
-// d_scratch / scratch_bytes of a batch call
+// d_scratch / scratch_bytes of a batch call: what the byte entry points hand to the walk over the families (`call`)
 struct AecScratch {
     void *p;
     u64 bytes;
@@ -680,6 +611,88 @@ static int aec_prepare_scratch(const scl_aec_model *m, u64 n_chunks, AecScratch 
     return SCL_OK;
 }
 
+// ---- the tuned kernel families of the byte entry points (scl_entry.h: SclFamily) ----------------------------------------
+// In priority order: the FIRST family that serves the model and can take the call runs it; the any-parameter kernels
+// follow the table.  scl_aec_fast_path and both batch calls walk it.  No family has a capacity check (an encoder's slots
+// are at least scl_aec_slot_bytes) and the readers load whole 32-bit words (at least one of input).
+//
+// rows start on `align`-byte boundaries and hold `row` bytes rounded up to it
+static bool aec_rows(const void *p, u64 stride, u64 align, u64 row) {
+    return (((uintptr_t)p | stride) & (align - 1)) == 0 && stride >= scl_round_up(row, align);
+}
+static bool aec_slot_fits(const scl_aec_model *m, const SclEncodeArgs<u8> &a) {
+    return a.out_stride >= scl_aec_slot_bytes(m, a.chunk_len);
+}
+static bool aec_in_word(const scl_aec_model *, const SclDecodeArgs<u8> &a) { return a.in_size_bytes >= 4; }
+static bool aec_in_line(const scl_aec_model *m, const SclDecodeArgs<u8> &a) { return aec_in_word(m, a) && scl_in_aligned(m, a); }
+static bool aec_enc_rows4(const scl_aec_model *, const SclEncodeArgs<u8> &a) {
+    return aec_rows(a.d_sym, a.sym_stride, 4, a.chunk_len);
+}
+static bool aec_dec_rows4(const scl_aec_model *, const SclDecodeArgs<u8> &a) {
+    return aec_rows(a.d_out_sym, a.out_stride, 4, a.out_cap);
+}
+static bool aec_dec_rows16(const scl_aec_model *, const SclDecodeArgs<u8> &a) {
+    return aec_rows(a.d_out_sym, a.out_stride, 16, a.out_cap);
+}
+
+// A family's launchers: LAUNCH is its entry point in scl_aec_*.hip; ZERO_BYTES (null: the kernels use no scratch) says how
+// much of the call's scratch they need zero-filled -- unless the model's counts fit LDS, where nobody touches the scratch.
+template <auto LAUNCH, auto ZERO_BYTES, class ARGS>
+static int aec_family_launch(const scl_aec_model *m, const ARGS &a, hipStream_t st, void *call, u64 max_symbols) {
+    const AecScratch scratch = *(const AecScratch *)call;
+    if constexpr (!std::is_null_pointer_v<decltype(ZERO_BYTES)>)
+        if (!aec_use_lds(m, max_symbols))
+            if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st, ZERO_BYTES(m, a.n_chunks))) return rc;
+    LAUNCH(m, a, st, (u32 *)scratch.p);
+    return SCL_OK;
+}
+template <auto LAUNCH, auto ZERO_BYTES = nullptr>
+static int aec_family_encode(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, void *call) {
+    return aec_family_launch<LAUNCH, ZERO_BYTES>(m, a, st, call, a.chunk_len);
+}
+template <auto LAUNCH, auto ZERO_BYTES = nullptr>
+static int aec_family_decode(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, void *call) {
+    return aec_family_launch<LAUNCH, ZERO_BYTES>(m, a, st, call, a.out_cap);
+}
+
+static const SclFamily<scl_aec_model> aec_families[] = {
+    // small-alphabet adaptive models: cumulative context rows in LDS, closed-form renormalisation (scl_aec_fast.hip; the
+    // encoder with a chunk's work split over three waves, scl_aec_split.hip)
+    {"fast/split", [](const scl_aec_model *m, u64 n, bool tuned) { return tuned && aec_fast_ok(m, n); }, aec_slot_fits,
+     aec_in_line,
+     [](const scl_aec_model *, const SclEncodeArgs<u8> &a) {
+         return aec_rows(a.d_sym, a.sym_stride, 16, a.chunk_len) && (a.out_stride & 63) == 0;
+     },
+     aec_dec_rows16, aec_family_encode<aec_fast_encode_launch>, aec_family_decode<aec_fast_decode_launch>, nullptr},
+    // adaptive i.i.d. model on a large alphabet: two-level cumulative table per lane in LDS (scl_aec_iid.hip)
+    {"iid", [](const scl_aec_model *m, u64 n, bool tuned) { return tuned && aec_iid_ok(m, n); }, aec_slot_fits, aec_in_word,
+     aec_enc_rows4, aec_dec_rows4, aec_family_encode<aec_iid_encode_launch>, aec_family_decode<aec_iid_decode_launch>,
+     nullptr},
+    // static model: shared table in LDS, line-granular I/O, 32-bit byte offsets into the input (scl_aec_static.hip)
+    {"static", [](const scl_aec_model *m, u64, bool tuned) { return tuned && aec_static_ok(m); }, aec_slot_fits,
+     [](const scl_aec_model *m, const SclDecodeArgs<u8> &a) { return aec_in_line(m, a) && a.in_size_bytes < (1ull << 34); },
+     [](const scl_aec_model *, const SclEncodeArgs<u8> &a) {
+         return aec_rows(a.d_sym, a.sym_stride, 16, 0) && (a.out_stride & 15) == 0;
+     },
+     aec_dec_rows16, aec_family_encode<aec_static_encode_launch>, aec_family_decode<aec_static_decode_launch>, nullptr},
+    // order-k on a large alphabet: one table line per symbol while a context is young (scl_aec_sparse.hip) ...
+    {"sparse", [](const scl_aec_model *m, u64 n, bool tuned) { return tuned && aec_wide_ok(m, n) && !aec_wide_dense_forced(); },
+     aec_slot_fits, aec_in_word, aec_enc_rows4, aec_dec_rows4,
+     aec_family_encode<aec_sparse_encode_launch, aec_sparse_zero_bytes>,
+     aec_family_decode<aec_sparse_decode_launch, aec_sparse_zero_bytes>, nullptr},
+    // ... or, under SCL_AEC_WIDE=dense, the two-level rows in device memory, tuned arithmetic, lookups issued ahead
+    // (scl_aec_wide.hip: u16 cells)
+    {"wide", [](const scl_aec_model *m, u64 n, bool tuned) { return tuned && aec_wide_ok(m, n) && aec_wide_dense_forced(); },
+     aec_slot_fits, aec_in_word, aec_enc_rows4, aec_dec_rows4,
+     aec_family_encode<aec_wide_encode_launch, aec_wide_scratch_bytes>,
+     aec_family_decode<aec_wide_decode_launch, aec_wide_scratch_bytes>, nullptr},
+};
+
+// (the model's answer, whatever the thread's any-parameter switch says)
+extern "C" int scl_aec_fast_path(const scl_aec_model *m, uint64_t max_symbols) {
+    return (m && scl_first_served(aec_families, m, max_symbols, true)) ? 1 : 0;
+}
+
 // the any-parameter kernels: a lane's model in LDS (lds: byte symbols only, aec_use_lds) or in `cells` (scratch, or the
 // state a *_resume call carries on, with its contexts in ctx_state), 64-bit arithmetic for PRECISION above 32
 template <class SYM>
@@ -690,7 +703,6 @@ static int aec_encode_any(const scl_aec_model *m, bool lds, const SclEncodeArgs<
     if constexpr (sizeof(SYM) == 1)
         if (lds) kernel = wide ? aec_encode_kernel<true, true> : aec_encode_kernel<true, false>;
     scl_launch_encode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a, cells, ctx_state);
-    SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
@@ -702,54 +714,31 @@ static int aec_decode_any(const scl_aec_model *m, bool lds, const SclDecodeArgs<
     if constexpr (sizeof(SYM) == 1)
         if (lds) kernel = wide ? aec_decode_kernel<true, true> : aec_decode_kernel<true, false>;
     scl_launch_decode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a, cells, ctx_state);
-    SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
-// the byte batch calls, after their argument checks
-static int aec_encode_bytes(const scl_aec_model *m, const SclEncodeArgs<u8> &args, AecScratch scratch, hipStream_t st) {
-    if (args.n_chunks == 0) return SCL_OK;
-    SclEncodeArgs<u8> a = args;
-    // (the tuned kernels have no capacity check)
-    const bool tuned = !scl_force_generic() && a.out_stride >= scl_aec_slot_bytes(m, a.chunk_len);
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
-    if (tuned && aec_tuned_serves(m, a.chunk_len))
-        if (int rc = relay.in(a, st)) return rc;
-    const bool lds = aec_use_lds(m, a.chunk_len);
-    for (const AecFamily &f : aec_families) {
-        if (!tuned || !f.served(m, a.chunk_len) || !f.enc_rows_ok(a, m)) continue;
-        if (f.zero_bytes && !lds)
-            if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st, f.zero_bytes(m, a.n_chunks))) return rc;
-        f.encode(m, a, st, (u32 *)scratch.p);
-        SCL_HIP_TRY(hipGetLastError());
-        return SCL_OK;
-    }
-    if (!lds)
-        if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
-    return aec_encode_any(m, lds, a, (u32 *)scratch.p, nullptr, st);
+// the batch calls without a state to resume: the families for byte symbols, else the any-parameter kernels with a lane's
+// model in LDS where it fits (byte symbols only) or in the call's scratch, which is checked and prepared here
+template <class SYM>
+static int aec_encode_fresh(const char *what, const scl_aec_model *m, const SclEncodeArgs<SYM> &args, AecScratch scratch,
+                            hipStream_t st) {
+    return scl_encode_batch(what, aec_families, m, args, st, &scratch, [&](const SclEncodeArgs<SYM> &a, const RowRelay &) -> int {
+        const bool lds = sizeof(SYM) == 1 && aec_use_lds(m, a.chunk_len);
+        if (!lds)
+            if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
+        return aec_encode_any(m, lds, a, (u32 *)scratch.p, nullptr, st);
+    });
 }
 
-static int aec_decode_bytes(const scl_aec_model *m, const SclDecodeArgs<u8> &args, AecScratch scratch, hipStream_t st) {
-    if (args.n_chunks == 0) return SCL_OK;
-    SclDecodeArgs<u8> a = args;
-    const bool tuned = !scl_force_generic() && a.in_size_bytes >= 4;  // the tuned readers load whole 32-bit words
-    const bool in_ok = ((uintptr_t)a.d_in & 15) == 0;
-    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
-    if (tuned && aec_tuned_serves(m, a.out_cap) && in_ok)
-        if (int rc = relay.out_begin(a, st)) return rc;
-    const bool lds = aec_use_lds(m, a.out_cap);
-    for (const AecFamily &f : aec_families) {
-        if (!tuned || !f.served(m, a.out_cap) || !f.dec_rows_ok(a, m, in_ok)) continue;
-        if (f.zero_bytes && !lds)
-            if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st, f.zero_bytes(m, a.n_chunks))) return rc;
-        f.decode(m, a, st, (u32 *)scratch.p);
-        SCL_HIP_TRY(hipGetLastError());
-        return relay.out_end(a);
-    }
-    if (!lds)
-        if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
-    if (int rc = aec_decode_any(m, lds, a, (u32 *)scratch.p, nullptr, st)) return rc;
-    return relay.out_end(a);
+template <class SYM>
+static int aec_decode_fresh(const char *what, const scl_aec_model *m, const SclDecodeArgs<SYM> &args, AecScratch scratch,
+                            hipStream_t st) {
+    return scl_decode_batch(what, aec_families, m, args, st, &scratch, [&](const SclDecodeArgs<SYM> &a, const RowRelay &) -> int {
+        const bool lds = sizeof(SYM) == 1 && aec_use_lds(m, a.out_cap);
+        if (!lds)
+            if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
+        return aec_decode_any(m, lds, a, (u32 *)scratch.p, nullptr, st);
+    });
 }
 
 extern "C" int scl_aec_encode_batch(const scl_aec_model *m, const uint8_t *d_sym, uint64_t sym_stride,
@@ -758,8 +747,7 @@ extern "C" int scl_aec_encode_batch(const scl_aec_model *m, const uint8_t *d_sym
                                     uint32_t *d_status, void *d_scratch, uint64_t scratch_bytes, void *stream) {
     const SclEncodeArgs<u8> a = {d_sym, sym_stride, d_lens, chunk_len, n_chunks,
                                  d_out, out_stride, d_out_bit_offset, d_out_nbits, d_status};
-    if (int rc = scl_check_encode("aec_encode_batch", SCL_ROWS_U8, m, a)) return rc;
-    return aec_encode_bytes(m, a, {d_scratch, scratch_bytes}, (hipStream_t)stream);
+    return aec_encode_fresh("aec_encode_batch", m, a, {d_scratch, scratch_bytes}, (hipStream_t)stream);
 }
 
 extern "C" int scl_aec_decode_batch(const scl_aec_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
@@ -769,8 +757,7 @@ extern "C" int scl_aec_decode_batch(const scl_aec_model *m, const uint8_t *d_in,
                                     void *stream) {
     const SclDecodeArgs<u8> a = {d_in, in_size_bytes, d_bit_offset, d_in_nbits, n_chunks, d_out_sym,
                                  out_stride, out_cap, d_out_lens, d_consumed, d_status};
-    if (int rc = scl_check_decode("aec_decode_batch", SCL_ROWS_U8, m, a)) return rc;
-    return aec_decode_bytes(m, a, {d_scratch, scratch_bytes}, (hipStream_t)stream);
+    return aec_decode_fresh("aec_decode_batch", m, a, {d_scratch, scratch_bytes}, (hipStream_t)stream);
 }
 
 // ---- coder state carried across blocks (quirk Q4) -----------------------------------------------------------
@@ -927,33 +914,29 @@ static int aec_resume_state(const char *what, const scl_aec_model *m, u64 n_chun
 template <class SYM>
 static int aec_encode_cells(const char *what, const scl_aec_model *m, const SclEncodeArgs<SYM> &a, AecScratch scratch,
                             const AecResume *resume, hipStream_t st) {
+    if (!resume || (m && m->dev.kind == SCL_MODEL_FIXED)) return aec_encode_fresh(what, m, a, scratch, st);
     if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, a)) return rc;
-    u32 *cells = (u32 *)scratch.p;
+    u32 *cells = nullptr;
     u64 *ctx_state = nullptr;
-    if (resume && m->dev.kind != SCL_MODEL_FIXED)
-        if (int rc = aec_resume_state(what, m, a.n_chunks, *resume, cells, ctx_state)) return rc;
-    if constexpr (sizeof(SYM) == 1)
-        if (!ctx_state) return aec_encode_bytes(m, a, scratch, st);
+    if (int rc = aec_resume_state(what, m, a.n_chunks, *resume, cells, ctx_state)) return rc;
     if (a.n_chunks == 0) return SCL_OK;
-    if (!ctx_state)
-        if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
-    return aec_encode_any(m, false, a, cells, ctx_state, st);
+    if (int rc = aec_encode_any(m, false, a, cells, ctx_state, st)) return rc;
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
 }
 
 template <class SYM>
 static int aec_decode_cells(const char *what, const scl_aec_model *m, const SclDecodeArgs<SYM> &a, AecScratch scratch,
                             const AecResume *resume, hipStream_t st) {
+    if (!resume || (m && m->dev.kind == SCL_MODEL_FIXED)) return aec_decode_fresh(what, m, a, scratch, st);
     if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, a)) return rc;
-    u32 *cells = (u32 *)scratch.p;
+    u32 *cells = nullptr;
     u64 *ctx_state = nullptr;
-    if (resume && m->dev.kind != SCL_MODEL_FIXED)
-        if (int rc = aec_resume_state(what, m, a.n_chunks, *resume, cells, ctx_state)) return rc;
-    if constexpr (sizeof(SYM) == 1)
-        if (!ctx_state) return aec_decode_bytes(m, a, scratch, st);
+    if (int rc = aec_resume_state(what, m, a.n_chunks, *resume, cells, ctx_state)) return rc;
     if (a.n_chunks == 0) return SCL_OK;
-    if (!ctx_state)
-        if (int rc = aec_prepare_scratch(m, a.n_chunks, scratch, st)) return rc;
-    return aec_decode_any(m, false, a, cells, ctx_state, st);
+    if (int rc = aec_decode_any(m, false, a, cells, ctx_state, st)) return rc;
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
 }
 
 extern "C" int scl_aec_encode_batch_resume(const scl_aec_model *m, const uint8_t *d_sym, uint64_t sym_stride,

@@ -1,5 +1,6 @@
-// scl_entry.h -- what every coder's C entry points share: the argument checks of the batch calls, the prologue of the
-// wave-striped calls and the single-chunk host drivers.  Host code only; included by scl_{rans,tans,range,aec}.hip.
+// scl_entry.h -- what every coder's C entry points share: the argument checks of the batch calls, the walk over a coder's
+// table of tuned kernel families that chooses the kernels (and names them), the prologue of the wave-striped calls and
+// the single-chunk host drivers.  Host code only; included by scl_{rans,tans,range,prefix,aec}.hip.
 #pragma once
 
 #include <type_traits>
@@ -43,6 +44,135 @@ int scl_check_decode(const char *what, SclRows rows, const MODEL *m, const SclDe
     SCL_REQUIRE(((uintptr_t)a.d_in & 3) == 0 && (rows == SCL_ROWS_U8 || ((uintptr_t)a.d_out_sym & 1) == 0),
                 "%s: d_in must be 4-byte aligned%s", what, rows == SCL_ROWS_U8 ? "" : ", d_out_sym 2-byte aligned");
     return SCL_OK;
+}
+
+// ---- kernel choice of the batch entry points ---------------------------------------------------------------------------
+// A coder lists its tuned kernel families in priority order; the batch calls (scl_encode_batch / scl_decode_batch below)
+// and the calls that only report the choice (scl_first_served, scl_kernel_names) read the same list.  MODEL: the coder's
+// handle.  Byte symbols only: uint16 symbols run the coder's any-parameter kernels.
+template <class MODEL>
+struct SclFamily {
+    const char *name;  // for comments and error text
+    // Does the family serve the model?  max_symbols: the longest chunk (chunk_len / out_cap).  tuned: the calling thread
+    // lets the tuned kernels run (!scl_force_generic(); the calls that report the MODEL pass true).  Environment switches
+    // that move a model from one family to another are read in here.
+    bool (*served)(const MODEL *m, u64 max_symbols, bool tuned);
+    // what the kernels need of the call that re-laying its rows cannot give ...
+    bool (*enc_call_ok)(const MODEL *m, const SclEncodeArgs<u8> &a);
+    bool (*dec_call_ok)(const MODEL *m, const SclDecodeArgs<u8> &a);
+    // ... and of the rows, once the relay has run
+    bool (*enc_rows_ok)(const MODEL *m, const SclEncodeArgs<u8> &a);
+    bool (*dec_rows_ok)(const MODEL *m, const SclDecodeArgs<u8> &a);
+    // start the kernels; `call`: what the coder's entry point handed to the walk (the arithmetic coder's scratch)
+    int (*encode)(const MODEL *m, const SclEncodeArgs<u8> &a, hipStream_t st, void *call);
+    int (*decode)(const MODEL *m, const SclDecodeArgs<u8> &a, hipStream_t st, void *call);
+    // the two kernels of a batch of n_chunks aligned, equally long rows, as rocprofv3 prints them (null: the coder has no
+    // *_kernel_names call)
+    void (*names)(const MODEL *m, u64 n_chunks, char *enc, char *dec, size_t cap);
+};
+
+// predicates most families share
+template <class MODEL>
+bool scl_any_call(const MODEL *, const SclEncodeArgs<u8> &) { return true; }
+template <class MODEL>
+bool scl_in_aligned(const MODEL *, const SclDecodeArgs<u8> &a) { return ((uintptr_t)a.d_in & 15) == 0; }
+template <class MODEL>
+bool scl_sym_rows_aligned(const MODEL *, const SclEncodeArgs<u8> &a) { return scl_rows_aligned(a.d_sym, a.sym_stride); }
+template <class MODEL>
+bool scl_out_rows_aligned(const MODEL *, const SclDecodeArgs<u8> &a) { return scl_rows_aligned(a.d_out_sym, a.out_stride); }
+
+static inline void scl_put_names(char *enc, char *dec, size_t cap, const char *enc_name, const char *dec_name) {
+    if (enc) snprintf(enc, cap, "%s", enc_name);
+    if (dec) snprintf(dec, cap, "%s", dec_name);
+}
+
+// the family that runs a batch of aligned rows in slots of the coder's size: the first that serves the model, or null
+template <class MODEL, size_t N>
+const SclFamily<MODEL> *scl_first_served(const SclFamily<MODEL> (&families)[N], const MODEL *m, u64 max_symbols, bool tuned) {
+    for (const SclFamily<MODEL> &f : families)
+        if (f.served(m, max_symbols, tuned)) return &f;
+    return nullptr;
+}
+
+// the body of a *_kernel_names call (any_enc / any_dec: the coder's any-parameter kernels)
+template <class MODEL, size_t N>
+int scl_kernel_names(const char *what, const SclFamily<MODEL> (&families)[N], const MODEL *m, u64 n_chunks, char *enc,
+                     char *dec, u64 cap, const char *any_enc, const char *any_dec) {
+    SCL_REQUIRE(m && (enc || dec) && cap >= 96, "%s: null argument or a buffer below 96 bytes", what);
+    if (const SclFamily<MODEL> *f = scl_first_served(families, m, 0, !scl_force_generic()))
+        f->names(m, n_chunks, enc, dec, (size_t)cap);
+    else
+        scl_put_names(enc, dec, (size_t)cap, any_enc, any_dec);
+    return SCL_OK;
+}
+
+// The body of every *_encode_batch / *_decode_batch call on linear slots: the argument checks, nothing to do for an empty
+// batch, then the FIRST family that serves the model and can take the call runs it.  Rows that do not start on 16-byte
+// boundaries are re-laid first (RowRelay) if and only if some family that serves the model could then take them; a
+// decoder's rows are copied back at the end.  any(a, relay) starts the coder's any-parameter kernels on the arguments as
+// the walk leaves them (relay.failed: rows had to be re-laid and the scratch could not be had) when no family took the
+// call, and for uint16 symbols.
+template <class MODEL, size_t N, class SYM, class ANY>
+int scl_encode_batch(const char *what, const SclFamily<MODEL> (&families)[N], const MODEL *m, const SclEncodeArgs<SYM> &args,
+                     hipStream_t st, void *call, ANY any) {
+    static_assert(N <= 32, "one bit per family");
+    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, args)) return rc;
+    if (args.n_chunks == 0) return SCL_OK;
+    SclEncodeArgs<SYM> a = args;
+    RowRelay relay;
+    if constexpr (sizeof(SYM) == 1) {
+        const bool tuned = !scl_force_generic();
+        u32 takes = 0;  // bit i: family i serves the model and the call has what it needs
+        for (size_t i = 0; i < N; ++i)
+            if (families[i].served(m, a.chunk_len, tuned) && families[i].enc_call_ok(m, a)) takes |= 1u << i;
+        if (takes)
+            if (int rc = relay.in(a, st)) return rc;
+        for (size_t i = 0; i < N; ++i) {
+            if (!(takes >> i & 1) || !families[i].enc_rows_ok(m, a)) continue;
+            if (int rc = families[i].encode(m, a, st, call)) return rc;
+            SCL_HIP_TRY(hipGetLastError());
+            return SCL_OK;
+        }
+    }
+    if (int rc = any(a, relay)) return rc;
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+template <class MODEL, size_t N, class SYM, class ANY>
+int scl_decode_batch(const char *what, const SclFamily<MODEL> (&families)[N], const MODEL *m, const SclDecodeArgs<SYM> &args,
+                     hipStream_t st, void *call, ANY any) {
+    static_assert(N <= 32, "one bit per family");
+    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, args)) return rc;
+    if (args.n_chunks == 0) return SCL_OK;
+    SclDecodeArgs<SYM> a = args;
+    RowRelay relay;
+    if constexpr (sizeof(SYM) == 1) {
+        const bool tuned = !scl_force_generic();
+        u32 takes = 0;
+        for (size_t i = 0; i < N; ++i)
+            if (families[i].served(m, a.out_cap, tuned) && families[i].dec_call_ok(m, a)) takes |= 1u << i;
+        if (takes)
+            if (int rc = relay.out_begin(a, st)) return rc;
+        for (size_t i = 0; i < N; ++i) {
+            if (!(takes >> i & 1) || !families[i].dec_rows_ok(m, a)) continue;
+            if (int rc = families[i].decode(m, a, st, call)) return rc;
+            SCL_HIP_TRY(hipGetLastError());
+            return relay.out_end(a);
+        }
+    }
+    if (int rc = any(a, relay)) return rc;
+    SCL_HIP_TRY(hipGetLastError());
+    return relay.out_end(a);
+}
+
+// The slot of the rANS and tANS coders (scl_rans_slot_bytes / scl_tans_slot_bytes): header, final state and the worst case
+// of every symbol, whole bytes plus the word the writers store past the stream's end, in lines of 128 bytes.
+template <class MODEL>
+u64 scl_ans_slot_bytes(const MODEL *m, u64 n_symbols) {
+    if (!m) return 0;
+    const u64 bits = (u64)m->dev.size_bits + m->dev.nsb + n_symbols * (u64)m->max_bits_per_symbol;
+    return scl_round_up((bits + 7) / 8 + 4, 128);
 }
 
 // ---- wave-striped slots (ABI version 8): the body of every *_batch_striped call, after its argument checks ------------

@@ -393,24 +393,40 @@ extern "C" int scl_prefix_model_create(const uint32_t *h_code, const uint8_t *h_
     return SCL_OK;
 }
 
+// ---- the tuned kernel family of the byte entry points (scl_entry.h: SclFamily) -------------------------------------------
+// The encoder checks its capacity (any slot will do); the tuned reader loads whole 16-byte blocks of the input.
+static const SclFamily<scl_prefix_model> prefix_families[] = {
+    {"prefix_fast", [](const scl_prefix_model *m, u64, bool tuned) { return tuned && m->fast; },
+     scl_any_call<scl_prefix_model>,
+     [](const scl_prefix_model *m, const SclDecodeArgs<u8> &a) { return scl_in_aligned(m, a) && a.in_size_bytes % 16 == 0; },
+     scl_sym_rows_aligned<scl_prefix_model>, scl_out_rows_aligned<scl_prefix_model>,
+     [](const scl_prefix_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         scl_launch_encode(prefix_encode_fast_kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
+         return SCL_OK;
+     },
+     [](const scl_prefix_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         scl_launch_decode(prefix_decode_fast_kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
+         return SCL_OK;
+     },
+     [](const scl_prefix_model *, u64, char *enc, char *dec, size_t cap) {
+         scl_put_names(enc, dec, cap, "prefix_encode_fast_kernel", "prefix_decode_fast_kernel");
+     }},
+};
+
 extern "C" int scl_prefix_model_info(const scl_prefix_model *m, scl_prefix_info *info) {
     SCL_REQUIRE(m && info, "prefix_model_info: null argument");
     info->K = m->dev.K;
     info->min_len = m->dev.min_len;
     info->max_len = m->dev.max_len;
     info->lut_bits = m->dev.lut_bits;
-    info->fast_path = m->fast;
+    info->fast_path = scl_first_served(prefix_families, m, 0, true) ? 1 : 0;  // the model's, whatever the thread's switch says
     info->device = m->device;
     return SCL_OK;
 }
 
 extern "C" int scl_prefix_kernel_names(const scl_prefix_model *m, uint64_t n_chunks, char *enc, char *dec, uint64_t cap) {
-    SCL_REQUIRE(m && (enc || dec) && cap >= 96, "prefix_kernel_names: null argument or a buffer below 96 bytes");
-    (void)n_chunks;
-    const bool f = !scl_force_generic() && m->fast;
-    if (enc) snprintf(enc, (size_t)cap, "%s", f ? "prefix_encode_fast_kernel" : "prefix_encode_kernel");
-    if (dec) snprintf(dec, (size_t)cap, "%s", f ? "prefix_decode_fast_kernel" : "prefix_decode_kernel");
-    return SCL_OK;
+    return scl_kernel_names("prefix_kernel_names", prefix_families, m, n_chunks, enc, dec, cap, "prefix_encode_kernel",
+                            "prefix_decode_kernel");
 }
 
 extern "C" uint64_t scl_prefix_slot_bytes(const scl_prefix_model *m, uint64_t n_symbols) {
@@ -422,47 +438,18 @@ extern "C" uint64_t scl_prefix_slot_bytes(const scl_prefix_model *m, uint64_t n_
 // ---- batch entry points: one body for uint8 symbols (the tuned kernels first) and uint16 symbols ------------------------
 template <class SYM>
 static int prefix_encode(const char *what, const scl_prefix_model *m, const SclEncodeArgs<SYM> &args, hipStream_t st) {
-    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, args)) return rc;
-    if (args.n_chunks == 0) return SCL_OK;
-    SclEncodeArgs<SYM> a = args;
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernel
-    const SclGrid g = {(u32)((a.n_chunks + 255) / 256), 256};
-    if constexpr (sizeof(SYM) == 1) {
-        const bool tuned = !scl_force_generic() && m->fast;
-        if (tuned)
-            if (int rc = relay.in(a, st)) return rc;
-        if (tuned && scl_rows_aligned(a.d_sym, a.sym_stride)) {
-            scl_launch_encode(prefix_encode_fast_kernel, g, st, m->dev, a);
-            SCL_HIP_TRY(hipGetLastError());
-            return SCL_OK;
-        }
-    }
-    scl_launch_encode(prefix_encode_kernel<SYM>, g, st, m->dev, a);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return scl_encode_batch(what, prefix_families, m, args, st, nullptr, [&](const SclEncodeArgs<SYM> &a, const RowRelay &) -> int {
+        scl_launch_encode(prefix_encode_kernel<SYM>, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
+        return SCL_OK;
+    });
 }
 
 template <class SYM>
 static int prefix_decode(const char *what, const scl_prefix_model *m, const SclDecodeArgs<SYM> &args, hipStream_t st) {
-    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, args)) return rc;
-    if (args.n_chunks == 0) return SCL_OK;
-    SclDecodeArgs<SYM> a = args;
-    RowRelay relay;  // output rows the tuned kernel cannot store to go through aligned scratch and are copied back
-    const SclGrid g = {(u32)((a.n_chunks + 255) / 256), 256};
-    if constexpr (sizeof(SYM) == 1) {
-        // the tuned reader loads whole 16-byte blocks of the input
-        const bool tuned = !scl_force_generic() && m->fast && ((uintptr_t)a.d_in & 15) == 0 && a.in_size_bytes % 16 == 0;
-        if (tuned)
-            if (int rc = relay.out_begin(a, st)) return rc;
-        if (tuned && scl_rows_aligned(a.d_out_sym, a.out_stride)) {
-            scl_launch_decode(prefix_decode_fast_kernel, g, st, m->dev, a);
-            SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(a);
-        }
-    }
-    scl_launch_decode(prefix_decode_kernel<SYM>, g, st, m->dev, a);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(a);
+    return scl_decode_batch(what, prefix_families, m, args, st, nullptr, [&](const SclDecodeArgs<SYM> &a, const RowRelay &) -> int {
+        scl_launch_decode(prefix_decode_kernel<SYM>, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
+        return SCL_OK;
+    });
 }
 
 extern "C" int scl_prefix_encode_batch(const scl_prefix_model *m, const uint8_t *d_sym, uint64_t sym_stride,

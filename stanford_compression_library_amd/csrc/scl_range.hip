@@ -230,7 +230,26 @@ extern "C" void scl_range_model_destroy(scl_range_model *m) {
     delete m;
 }
 
-extern "C" int scl_range_fast_path(const scl_range_model *m) { return (m && m->fast) ? 1 : 0; }
+// ---- the tuned kernel family of the byte entry points (scl_entry.h: SclFamily) -------------------------------------------
+// scl_range_fast.hip.  The encoder checks its capacity (any slot will do); the decoder loads 16-byte lines.
+static const SclFamily<scl_range_model> range_families[] = {
+    {"range_fast", [](const scl_range_model *m, u64, bool tuned) { return tuned && m->fast; }, scl_any_call<scl_range_model>,
+     scl_in_aligned<scl_range_model>, scl_sym_rows_aligned<scl_range_model>, scl_out_rows_aligned<scl_range_model>,
+     [](const scl_range_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         range_fast_encode_launch(m, a, st);
+         return SCL_OK;
+     },
+     [](const scl_range_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         range_fast_decode_launch(m, a, st);
+         return SCL_OK;
+     },
+     nullptr},
+};
+
+// (the model's answer, whatever the thread's any-parameter switch says)
+extern "C" int scl_range_fast_path(const scl_range_model *m) {
+    return (m && scl_first_served(range_families, m, 0, true)) ? 1 : 0;
+}
 
 extern "C" uint64_t scl_range_slot_bytes(const scl_range_model *m, uint64_t n_symbols) {
     if (!m) return 0;
@@ -243,50 +262,22 @@ extern "C" uint64_t scl_range_slot_bytes(const scl_range_model *m, uint64_t n_sy
 // 65536: the any-parameter kernels) --------------------------------------------------------------------------------------
 template <class SYM>
 static int range_encode(const char *what, const scl_range_model *m, const SclEncodeArgs<SYM> &args, hipStream_t st) {
-    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, args)) return rc;
-    if (args.n_chunks == 0) return SCL_OK;
-    SclEncodeArgs<SYM> a = args;
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
-    if constexpr (sizeof(SYM) == 1) {
-        const bool tuned = !scl_force_generic();
-        if (tuned && m->fast)
-            if (int rc = relay.in(a, st)) return rc;
-        if (tuned && m->fast && scl_rows_aligned(a.d_sym, a.sym_stride)) {
-            range_fast_encode_launch(m, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return SCL_OK;
-        }
-    }
-    auto kernel = m->dev.P <= 32 ? range_encode_kernel<u32, SYM> : range_encode_kernel<u64, SYM>;
-    scl_launch_encode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return scl_encode_batch(what, range_families, m, args, st, nullptr, [&](const SclEncodeArgs<SYM> &a, const RowRelay &) -> int {
+        auto kernel = m->dev.P <= 32 ? range_encode_kernel<u32, SYM> : range_encode_kernel<u64, SYM>;
+        scl_launch_encode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
+        return SCL_OK;
+    });
 }
 
 template <class SYM>
 static int range_decode(const char *what, const scl_range_model *m, const SclDecodeArgs<SYM> &args, hipStream_t st) {
-    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, args)) return rc;
-    if (args.n_chunks == 0) return SCL_OK;
-    SclDecodeArgs<SYM> a = args;
-    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
-    RangeDev dev = m->dev;
-    if constexpr (sizeof(SYM) == 1) {
-        const bool tuned = !scl_force_generic();
-        const bool in_ok = ((uintptr_t)a.d_in & 15) == 0;
-        if (tuned && m->fast && in_ok)
-            if (int rc = relay.out_begin(a, st)) return rc;
-        if (tuned && m->fast && in_ok && scl_rows_aligned(a.d_out_sym, a.out_stride)) {
-            range_fast_decode_launch(m, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(a);
-        }
-    } else {
-        dev.d_slot2sym = nullptr;  // a table of BYTES: the u16 kernels search the cumulative counts
-    }
-    auto kernel = m->dev.P <= 32 ? range_decode_kernel<u32, SYM> : range_decode_kernel<u64, SYM>;
-    scl_launch_decode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, dev, a);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(a);
+    return scl_decode_batch(what, range_families, m, args, st, nullptr, [&](const SclDecodeArgs<SYM> &a, const RowRelay &) -> int {
+        RangeDev dev = m->dev;
+        if (sizeof(SYM) != 1) dev.d_slot2sym = nullptr;  // a table of BYTES: the u16 kernels search the cumulative counts
+        auto kernel = m->dev.P <= 32 ? range_decode_kernel<u32, SYM> : range_decode_kernel<u64, SYM>;
+        scl_launch_decode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, dev, a);
+        return SCL_OK;
+    });
 }
 
 extern "C" int scl_range_encode_batch(const scl_range_model *m, const uint8_t *d_sym, uint64_t sym_stride,

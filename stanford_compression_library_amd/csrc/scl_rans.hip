@@ -245,6 +245,46 @@ extern "C" void scl_rans_model_destroy(scl_rans_model *m) {
     delete m;
 }
 
+extern "C" uint64_t scl_rans_slot_bytes(const scl_rans_model *m, uint64_t n_symbols) { return scl_ans_slot_bytes(m, n_symbols); }
+
+// ---- the tuned kernel families of the byte entry points (scl_entry.h: SclFamily) ----------------------------------------
+// Neither has a capacity check: an encoder's slots are at least scl_rans_slot_bytes.  The decoders load 16-byte lines.
+static bool rans_slot_fits(const scl_rans_model *m, const SclEncodeArgs<u8> &a) {
+    return a.out_stride >= scl_rans_slot_bytes(m, a.chunk_len);
+}
+
+static const SclFamily<scl_rans_model> rans_families[] = {
+    // scl_rans_fast.hip: NUM_BITS_OUT = 1 and, within their bounds, 4 / 8 / 16; a workgroup's 256 slots within 32-bit offsets
+    {"rans_fast", [](const scl_rans_model *m, u64, bool tuned) { return tuned && m->fast; },
+     [](const scl_rans_model *m, const SclEncodeArgs<u8> &a) { return rans_slot_fits(m, a) && a.out_stride < (1ull << 24); },
+     scl_in_aligned<scl_rans_model>, scl_sym_rows_aligned<scl_rans_model>, scl_out_rows_aligned<scl_rans_model>,
+     [](const scl_rans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         rans_fast_encode_launch(m, a, st);
+         return SCL_OK;
+     },
+     [](const scl_rans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         rans_fast_decode_launch(m, a, st);
+         return SCL_OK;
+     },
+     [](const scl_rans_model *m, u64 n_chunks, char *enc, char *dec, size_t cap) {
+         rans_fast_kernel_names(m, n_chunks, enc, dec, cap);
+     }},
+    // scl_rans_fast_b.hip: NUM_BITS_OUT = 2 and what those bounds exclude
+    {"rans_fastb", [](const scl_rans_model *m, u64, bool tuned) { return tuned && m->fastb; }, rans_slot_fits,
+     scl_in_aligned<scl_rans_model>, scl_sym_rows_aligned<scl_rans_model>, scl_out_rows_aligned<scl_rans_model>,
+     [](const scl_rans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         rans_fastb_encode_launch(m, a, st);
+         return SCL_OK;
+     },
+     [](const scl_rans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         rans_fastb_decode_launch(m, a, st);
+         return SCL_OK;
+     },
+     [](const scl_rans_model *, u64, char *enc, char *dec, size_t cap) {
+         scl_put_names(enc, dec, cap, "rans_encode_fastb_kernel", "rans_decode_fastb_kernel");
+     }},
+};
+
 extern "C" int scl_rans_model_info(const scl_rans_model *m, scl_rans_info *info) {
     SCL_REQUIRE(m && info, "rans_model_info: null argument");
     info->M = m->dev.M;
@@ -255,7 +295,7 @@ extern "C" int scl_rans_model_info(const scl_rans_model *m, scl_rans_info *info)
     info->size_bits = m->dev.size_bits;
     info->num_bits_out = m->dev.b;
     info->max_bits_per_symbol = m->max_bits_per_symbol;
-    info->fast_path = m->fast | m->fastb;
+    info->fast_path = scl_first_served(rans_families, m, 0, true) ? 1 : 0;  // the model's, whatever the thread's switch says
     info->device = m->device;
     return SCL_OK;
 }
@@ -267,90 +307,38 @@ extern "C" int scl_rans_model_info(const scl_rans_model *m, scl_rans_info *info)
 // SCL_RANS_ENC_WRITER and want to know that the switch took).
 extern "C" int scl_rans_encoder_kind(const scl_rans_model *m, uint64_t n_chunks) {
     if (!m) return 0;
-    if (scl_force_generic()) return 'G';
-    if (m->fast) return rf_use_slot_writer(m, n_chunks) ? 'S' : 'L';
-    return m->fastb ? 'B' : 'G';
+    const SclFamily<scl_rans_model> *f = scl_first_served(rans_families, m, 0, !scl_force_generic());
+    if (!f) return 'G';
+    if (f != &rans_families[0]) return 'B';
+    return rf_use_slot_writer(m, n_chunks) ? 'S' : 'L';
 }
 
 // (ABI 6) the two kernels a batch of n_chunks aligned, equally long rows would run, named the way rocprofv3 prints them
 // (template arguments included for the tuned kernels; the any-parameter kernels by their function name) -- so that a
 // bench line's "kernel" fields can be matched mechanically against a committed kernel-trace summary.
 extern "C" int scl_rans_kernel_names(const scl_rans_model *m, uint64_t n_chunks, char *enc, char *dec, uint64_t cap) {
-    SCL_REQUIRE(m && (enc || dec) && cap >= 96, "rans_kernel_names: null argument or a buffer below 96 bytes");
-    if (!scl_force_generic() && m->fast) {
-        rans_fast_kernel_names(m, n_chunks, enc, dec, (size_t)cap);
-        return SCL_OK;
-    }
-    const bool b = !scl_force_generic() && m->fastb;
-    if (enc) snprintf(enc, (size_t)cap, "%s", b ? "rans_encode_fastb_kernel" : "rans_encode_generic");
-    if (dec) snprintf(dec, (size_t)cap, "%s", b ? "rans_decode_fastb_kernel" : "rans_decode_generic");
-    return SCL_OK;
-}
-
-extern "C" uint64_t scl_rans_slot_bytes(const scl_rans_model *m, uint64_t n_symbols) {
-    if (!m) return 0;
-    const u64 bits = (u64)m->dev.size_bits + m->dev.nsb + n_symbols * (u64)m->max_bits_per_symbol;
-    return scl_round_up((bits + 7) / 8 + 4, 128);
+    return scl_kernel_names("rans_kernel_names", rans_families, m, n_chunks, enc, dec, cap, "rans_encode_generic",
+                            "rans_decode_generic");
 }
 
 // ---- batch entry points: one body for uint8 symbols (the tuned kernels first) and uint16 symbols (alphabets up to
 // 65536: the any-parameter kernels) --------------------------------------------------------------------------------------
 template <class SYM>
 static int rans_encode(const char *what, const scl_rans_model *m, const SclEncodeArgs<SYM> &args, hipStream_t st) {
-    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, args)) return rc;
-    if (args.n_chunks == 0) return SCL_OK;
-    SclEncodeArgs<SYM> a = args;
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
-    if constexpr (sizeof(SYM) == 1) {
-        const bool tuned = !scl_force_generic();
-        const bool fits = a.out_stride >= scl_rans_slot_bytes(m, a.chunk_len);  // the tuned kernels have no capacity check
-        if (tuned && (m->fast || m->fastb) && fits)
-            if (int rc = relay.in(a, st)) return rc;
-        const bool rows_ok = scl_rows_aligned(a.d_sym, a.sym_stride);
-        if (tuned && m->fast && rows_ok && fits && a.out_stride < (1ull << 24)) {  // 256 slots within 32-bit offsets
-            rans_fast_encode_launch(m, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return SCL_OK;
-        }
-        if (tuned && m->fastb && rows_ok && fits) {
-            rans_fastb_encode_launch(m, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return SCL_OK;
-        }
-    }
-    auto kernel = m->state32 ? rans_encode_generic<u32, SYM> : rans_encode_generic<u64, SYM>;
-    scl_launch_encode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return scl_encode_batch(what, rans_families, m, args, st, nullptr, [&](const SclEncodeArgs<SYM> &a, const RowRelay &) -> int {
+        auto kernel = m->state32 ? rans_encode_generic<u32, SYM> : rans_encode_generic<u64, SYM>;
+        scl_launch_encode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
+        return SCL_OK;
+    });
 }
 
 template <class SYM>
 static int rans_decode(const char *what, const scl_rans_model *m, const SclDecodeArgs<SYM> &args, hipStream_t st) {
-    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, args)) return rc;
-    if (args.n_chunks == 0) return SCL_OK;
-    SclDecodeArgs<SYM> a = args;
-    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
-    if constexpr (sizeof(SYM) == 1) {
-        const bool tuned = !scl_force_generic();
-        const bool in_ok = ((uintptr_t)a.d_in & 15) == 0;
-        if (tuned && (m->fast || m->fastb) && in_ok)
-            if (int rc = relay.out_begin(a, st)) return rc;
-        const bool rows_ok = in_ok && scl_rows_aligned(a.d_out_sym, a.out_stride);
-        if (tuned && m->fast && rows_ok) {
-            rans_fast_decode_launch(m, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(a);
-        }
-        if (tuned && m->fastb && rows_ok) {
-            rans_fastb_decode_launch(m, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(a);
-        }
-    }
-    auto kernel = m->state32 ? rans_decode_generic<u32, SYM> : rans_decode_generic<u64, SYM>;
-    scl_launch_decode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(a);
+    return scl_decode_batch(what, rans_families, m, args, st, nullptr, [&](const SclDecodeArgs<SYM> &a, const RowRelay &) -> int {
+        auto kernel = m->state32 ? rans_decode_generic<u32, SYM> : rans_decode_generic<u64, SYM>;
+        scl_launch_decode(kernel, {(u32)((a.n_chunks + 255) / 256), 256}, st, m->dev, a);
+        return SCL_OK;
+    });
 }
 
 extern "C" int scl_rans_encode_batch(const scl_rans_model *m, const uint8_t *d_sym, uint64_t sym_stride,

@@ -333,6 +333,55 @@ extern "C" void scl_tans_model_destroy(scl_tans_model *m) {
     delete m;
 }
 
+extern "C" uint64_t scl_tans_slot_bytes(const scl_tans_model *m, uint64_t n_symbols) { return scl_ans_slot_bytes(m, n_symbols); }
+
+// ---- the tuned kernel families of the byte entry points (scl_entry.h: SclFamily) ----------------------------------------
+// A model the table-free rANS kernels can serve (m->rans: same stream, no tables) runs on them, its LDS-table kernels
+// (scl_tans_fast.hip) behind them -- unless SCL_TANS_KERNELS=table puts those first.  A model WITHOUT lookup tables has
+// no any-parameter kernels: the rANS kernels serve it even while the calling thread keeps the tuned kernels out.
+// No family has a capacity check: an encoder's slots are at least the serving model's slot.  The decoders load 16-byte lines.
+static bool tans_table_served(const scl_tans_model *m, u64, bool tuned) { return tuned && m->fast; }
+static bool tans_slot_fits(const scl_tans_model *m, const SclEncodeArgs<u8> &a) {
+    return a.out_stride >= scl_tans_slot_bytes(m, a.chunk_len);
+}
+static int tans_table_encode(const scl_tans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, void *) {
+    tans_fast_encode_launch(m, a, st);
+    return SCL_OK;
+}
+static int tans_table_decode(const scl_tans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, void *) {
+    tans_fast_decode_launch(m, a, st);
+    return SCL_OK;
+}
+static void tans_table_names(const scl_tans_model *, u64, char *enc, char *dec, size_t cap) {
+    scl_put_names(enc, dec, cap, "tans_encode_fast_kernel", "tans_decode_fast_kernel");
+}
+
+static const SclFamily<scl_tans_model> tans_families[] = {
+    {"tans_fast, asked for by SCL_TANS_KERNELS=table",
+     [](const scl_tans_model *m, u64 n, bool tuned) { return tans_table_served(m, n, tuned) && tans_table_kernels_forced(); },
+     tans_slot_fits, scl_in_aligned<scl_tans_model>, scl_sym_rows_aligned<scl_tans_model>,
+     scl_out_rows_aligned<scl_tans_model>, tans_table_encode, tans_table_decode, tans_table_names},
+    // rans_fast on the companion model: a workgroup's 256 slots within 32-bit offsets
+    {"rans_fast", [](const scl_tans_model *m, u64, bool tuned) { return (tuned || !m->tables) && m->rans; },
+     [](const scl_tans_model *m, const SclEncodeArgs<u8> &a) {
+         return a.out_stride >= scl_rans_slot_bytes(m->rans, a.chunk_len) && a.out_stride < (1ull << 24);
+     },
+     scl_in_aligned<scl_tans_model>, scl_sym_rows_aligned<scl_tans_model>, scl_out_rows_aligned<scl_tans_model>,
+     [](const scl_tans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         rans_fast_encode_launch(m->rans, a, st);
+         return SCL_OK;
+     },
+     [](const scl_tans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, void *) -> int {
+         rans_fast_decode_launch(m->rans, a, st);
+         return SCL_OK;
+     },
+     [](const scl_tans_model *m, u64 n_chunks, char *enc, char *dec, size_t cap) {
+         rans_fast_kernel_names(m->rans, n_chunks, enc, dec, cap);
+     }},
+    {"tans_fast", tans_table_served, tans_slot_fits, scl_in_aligned<scl_tans_model>, scl_sym_rows_aligned<scl_tans_model>,
+     scl_out_rows_aligned<scl_tans_model>, tans_table_encode, tans_table_decode, tans_table_names},
+};
+
 extern "C" int scl_tans_model_info(const scl_tans_model *m, scl_rans_info *info) {
     SCL_REQUIRE(m && info, "tans_model_info: null argument");
     info->M = m->dev.M;
@@ -343,15 +392,10 @@ extern "C" int scl_tans_model_info(const scl_tans_model *m, scl_rans_info *info)
     info->size_bits = m->dev.size_bits;
     info->num_bits_out = 1;
     info->max_bits_per_symbol = m->max_bits_per_symbol;
-    info->fast_path = (m->fast || m->rans) ? 1u : m->dev.lds_tables;
+    // the model's, whatever the thread's switch says: a tuned family, or any-parameter kernels with their tables in LDS
+    info->fast_path = scl_first_served(tans_families, m, 0, true) ? 1u : m->dev.lds_tables;
     info->device = m->device;
     return SCL_OK;
-}
-
-extern "C" uint64_t scl_tans_slot_bytes(const scl_tans_model *m, uint64_t n_symbols) {
-    if (!m) return 0;
-    const u64 bits = (u64)m->dev.size_bits + m->dev.nsb + n_symbols * (u64)m->max_bits_per_symbol;
-    return scl_round_up((bits + 7) / 8 + 4, 128);
 }
 
 extern "C" int scl_tans_model_tables(const scl_tans_model *m, uint32_t *h_enc, uint32_t *h_nbits, uint32_t *h_thresh,
@@ -372,17 +416,8 @@ extern "C" int scl_tans_model_tables(const scl_tans_model *m, uint32_t *h_enc, u
 // (ABI 6) as scl_rans_kernel_names: a tANS model the table-free rANS kernels can serve runs on them (same stream) unless
 // SCL_TANS_KERNELS=table is set
 extern "C" int scl_tans_kernel_names(const scl_tans_model *m, uint64_t n_chunks, char *enc, char *dec, uint64_t cap) {
-    SCL_REQUIRE(m && (enc || dec) && cap >= 96, "tans_kernel_names: null argument or a buffer below 96 bytes");
-    const bool tuned = !scl_force_generic();
-    const bool table_first = m->fast && tans_table_kernels_forced();
-    if ((tuned || !m->tables) && m->rans && !(table_first && tuned)) {
-        rans_fast_kernel_names(m->rans, n_chunks, enc, dec, (size_t)cap);
-        return SCL_OK;
-    }
-    const bool f = tuned && m->fast;
-    if (enc) snprintf(enc, (size_t)cap, "%s", f ? "tans_encode_fast_kernel" : "tans_encode_kernel");
-    if (dec) snprintf(dec, (size_t)cap, "%s", f ? "tans_decode_fast_kernel" : "tans_decode_kernel");
-    return SCL_OK;
+    return scl_kernel_names("tans_kernel_names", tans_families, m, n_chunks, enc, dec, cap, "tans_encode_kernel",
+                            "tans_decode_kernel");
 }
 
 // ---- wave-striped slots (ABI version 8): tANS models the table-free rANS kernels serve, on their striped form ----------
@@ -426,83 +461,36 @@ extern "C" int scl_tans_decode_batch_striped(const scl_tans_model *m, const uint
 // 65536: lookup tables in device memory) -----------------------------------------------------------------------------
 template <class SYM>
 static int tans_encode(const char *what, const scl_tans_model *m, const SclEncodeArgs<SYM> &args, hipStream_t st) {
-    if (int rc = scl_check_encode(what, scl_rows_of<SYM>(), m, args)) return rc;
-    if (args.n_chunks == 0) return SCL_OK;
-    SclEncodeArgs<SYM> a = args;
-    RowRelay relay;  // rows that do not start on 16-byte boundaries are re-laid for the tuned kernels
-    if constexpr (sizeof(SYM) == 1) {
-        const bool tuned = !scl_force_generic();
-        const bool table_first = m->fast && tans_table_kernels_forced();  // else the table-free kernels when the model has them
-        if ((tuned || !m->tables) && (m->fast || m->rans))
-            if (int rc = relay.in(a, st)) return rc;
-        const bool rows_ok = scl_rows_aligned(a.d_sym, a.sym_stride);
-        const bool fast_ok = tuned && m->fast && rows_ok && a.out_stride >= scl_tans_slot_bytes(m, a.chunk_len);
-        // same stream from the table-free rANS kernels (32-bit slot offsets per workgroup)
-        const bool rans_ok = (tuned || !m->tables) && m->rans && rows_ok &&
-                             a.out_stride >= scl_rans_slot_bytes(m->rans, a.chunk_len) && a.out_stride < (1ull << 24);
-        if (rans_ok && !(table_first && fast_ok)) {
-            rans_fast_encode_launch(m->rans, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return SCL_OK;
-        }
-        if (fast_ok) {
-            tans_fast_encode_launch(m, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return SCL_OK;
-        }
+    return scl_encode_batch(what, tans_families, m, args, st, nullptr, [&](const SclEncodeArgs<SYM> &a, const RowRelay &relay) -> int {
         if (!m->tables && relay.failed) {  // the rows WERE the problem, and the scratch to re-lay them could not be had
             scl_set_error("%s: out of device memory re-laying unaligned symbol rows (hipMallocAsync failed) and this "
                           "model has no lookup tables for the any-parameter kernels", what);
             return SCL_E_ALLOC;
         }
-    }
-    SCL_REQUIRE(m->tables, "%s: this model has no lookup tables (RANGE_FACTOR*M > 2^26)%s", what,
-                sizeof(SYM) == 1 ? "; it needs 16-byte aligned symbol rows and slots of scl_tans_slot_bytes" : "");
-    if (int rc = tans_ensure_tables(m)) return rc;
-    const u32 lds = sizeof(SYM) == 1 ? (768 + (m->dev.lds_tables ? m->dev.L : 0)) * sizeof(u32) : 16;
-    scl_launch_encode(tans_encode_kernel<SYM>, {(u32)((a.n_chunks + 255) / 256), 256, lds}, st, m->dev, a);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+        SCL_REQUIRE(m->tables, "%s: this model has no lookup tables (RANGE_FACTOR*M > 2^26)%s", what,
+                    sizeof(SYM) == 1 ? "; it needs 16-byte aligned symbol rows and slots of scl_tans_slot_bytes" : "");
+        if (int rc = tans_ensure_tables(m)) return rc;
+        const u32 lds = sizeof(SYM) == 1 ? (768 + (m->dev.lds_tables ? m->dev.L : 0)) * sizeof(u32) : 16;
+        scl_launch_encode(tans_encode_kernel<SYM>, {(u32)((a.n_chunks + 255) / 256), 256, lds}, st, m->dev, a);
+        return SCL_OK;
+    });
 }
 
 template <class SYM>
 static int tans_decode(const char *what, const scl_tans_model *m, const SclDecodeArgs<SYM> &args, hipStream_t st) {
-    if (int rc = scl_check_decode(what, scl_rows_of<SYM>(), m, args)) return rc;
-    if (args.n_chunks == 0) return SCL_OK;
-    SclDecodeArgs<SYM> a = args;
-    RowRelay relay;  // output rows the tuned kernels cannot store to go through aligned scratch and are copied back
-    if constexpr (sizeof(SYM) == 1) {
-        const bool tuned = !scl_force_generic();
-        const bool in_ok = ((uintptr_t)a.d_in & 15) == 0;
-        if ((tuned || !m->tables) && (m->fast || m->rans) && in_ok)
-            if (int rc = relay.out_begin(a, st)) return rc;
-        const bool table_first = m->fast && tans_table_kernels_forced();
-        const bool bufs_ok = in_ok && scl_rows_aligned(a.d_out_sym, a.out_stride);
-        const bool fast_ok = tuned && m->fast && bufs_ok;
-        const bool rans_ok = (tuned || !m->tables) && m->rans && bufs_ok;
-        if (rans_ok && !(table_first && fast_ok)) {
-            rans_fast_decode_launch(m->rans, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(a);
-        }
-        if (fast_ok) {
-            tans_fast_decode_launch(m, a, st);
-            SCL_HIP_TRY(hipGetLastError());
-            return relay.out_end(a);
-        }
+    return scl_decode_batch(what, tans_families, m, args, st, nullptr, [&](const SclDecodeArgs<SYM> &a, const RowRelay &relay) -> int {
         if (!m->tables && relay.failed) {
             scl_set_error("%s: out of device memory re-laying unaligned output rows (hipMallocAsync failed) and this "
                           "model has no lookup tables for the any-parameter kernels", what);
             return SCL_E_ALLOC;
         }
-    }
-    SCL_REQUIRE(m->tables, "%s: this model has no lookup tables (RANGE_FACTOR*M > 2^26)%s", what,
-                sizeof(SYM) == 1 ? "; it needs 16-byte aligned buffers" : "");
-    if (int rc = tans_ensure_tables(m)) return rc;
-    const u32 lds = (m->dev.lds_tables ? 2 * m->dev.L : 4) * sizeof(u32);
-    scl_launch_decode(tans_decode_kernel<SYM>, {(u32)((a.n_chunks + 255) / 256), 256, lds}, st, m->dev, a);
-    SCL_HIP_TRY(hipGetLastError());
-    return relay.out_end(a);
+        SCL_REQUIRE(m->tables, "%s: this model has no lookup tables (RANGE_FACTOR*M > 2^26)%s", what,
+                    sizeof(SYM) == 1 ? "; it needs 16-byte aligned buffers" : "");
+        if (int rc = tans_ensure_tables(m)) return rc;
+        const u32 lds = (m->dev.lds_tables ? 2 * m->dev.L : 4) * sizeof(u32);
+        scl_launch_decode(tans_decode_kernel<SYM>, {(u32)((a.n_chunks + 255) / 256), 256, lds}, st, m->dev, a);
+        return SCL_OK;
+    });
 }
 
 extern "C" int scl_tans_encode_batch(const scl_tans_model *m, const uint8_t *d_sym, uint64_t sym_stride,

@@ -144,6 +144,15 @@ def test_aec_family_on_aligned_odd_and_declined_rows(name, dev):
     moved.copy_(enc_a.data)
     assert moved.data_ptr() % 16 == 4
     check(*model.decode_batch(moved, enc_a.bit_offset, enc_a.nbits, CHUNK_LEN), "input at base + 4")
+    # (d) both at once: the families whose readers load words take the moved input once the odd rows are re-laid, the others
+    # leave the call to the any-parameter kernels
+    buf, rows = _odd_rows(dev)
+    outs = tuple(torch.zeros(N_CHUNKS, dtype=torch.int32, device=dev) for _ in range(3))
+    check(*model.decode_batch(moved, enc_a.bit_offset, enc_a.nbits, CHUNK_LEN, out=(rows,) + outs), "input at base + 4, odd rows")
+    got = rows.cpu().numpy()
+    for c in range(N_CHUNKS):
+        assert (got[c, lens[c]:] == FILL).all(), f"chunk {c}: bytes behind the decoded symbols were written"
+    assert (buf[:1].cpu().numpy() == FILL).all() and (buf[1 + N_CHUNKS * ODD_STRIDE:].cpu().numpy() == FILL).all()
 
 
 def test_orderk256_with_dense_rows_forced():
