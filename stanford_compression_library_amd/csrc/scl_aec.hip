@@ -538,20 +538,17 @@ extern "C" int scl_aec_model_create(int model_kind, const uint32_t *h_freq_init,
     m->dev.total0 = (u32)tot;
     ::memcpy(m->h_freq, freq, (K < 256 ? K : 256) * sizeof(u32));
     const u64 tab_entries = K > 256 ? K : 256;
-    hipError_t e = hipMalloc((void **)&m->d_freq, tab_entries * sizeof(u32));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_cum, tab_entries * sizeof(u32));
-    if (e == hipSuccess) e = hipMemcpy(m->d_freq, freq, K * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_cum, cum, K * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess && model_kind == SCL_MODEL_IID && K > 16 && K <= 256) {
+    const char *what = "aec_model_create: device table upload";
+    int rc = scl_upload(&m->d_freq, freq, K, what, tab_entries);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_cum, cum, K, what, tab_entries);
+    if (rc == SCL_OK && model_kind == SCL_MODEL_IID && K > 16 && K <= 256) {
         u32 init[136];
         aec_iid_build_init(freq, K, init);
-        e = hipMalloc((void **)&m->d_iid_init, sizeof(init));
-        if (e == hipSuccess) e = hipMemcpy(m->d_iid_init, init, sizeof(init), hipMemcpyHostToDevice);
+        rc = scl_upload(&m->d_iid_init, init, 136, what);
     }
-    if (e != hipSuccess) {
-        scl_set_error("aec_model_create: device table upload failed: %s", hipGetErrorString(e));
+    if (rc != SCL_OK) {
         scl_aec_model_destroy(m);
-        return SCL_E_HIP;
+        return rc;
     }
     m->dev.d_freq = m->d_freq;
     m->dev.d_cum = m->d_cum;

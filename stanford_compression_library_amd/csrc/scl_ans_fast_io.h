@@ -7,6 +7,7 @@
 //   static arithmetic (scl_aec_static.hip)   AnsFwdWriter out, AnsBitReader<.., ZERO_PAST_END> in
 //   prefix codes (scl_prefix.hip)  AnsFwdWriter<.., BOUNDED> out, AnsBitReader in
 // rANS / tANS streams are produced back to front and read front to back; the others grow front to back.
+// (What stands around the symbol step of the three ANS decoders -- header, loops, epilogue -- is scl_ans_frame.h.)
 //
 // The pieces, each defined once:
 //   AnsBackWindow   64-bit window of the back writers L / S / T (push, put32, the hand-written check of L and T)

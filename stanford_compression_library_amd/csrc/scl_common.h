@@ -51,6 +51,20 @@ static inline u32 scl_bit_width_u64(u64 x) {  // get_bit_width, bitarray_utils.p
 
 static inline u64 scl_round_up(u64 x, u64 a) { return (x + a - 1) / a * a; }
 
+// One device table of a model: allocates max(n, n_alloc, 1) entries at *d and copies the n entries of h there (n = 0:
+// allocation only).  SCL_E_HIP with "<what> failed: ..." as the error otherwise; *d is then null or allocated, and the
+// model's destroy function, which frees what the model owns, takes care of it.
+template <class T>
+int scl_upload(T **d, const T *h, u64 n, const char *what, u64 n_alloc = 0) {
+    const u64 cap = n_alloc > n ? n_alloc : n;
+    hipError_t e = hipMalloc((void **)d, (cap ? cap : 1) * sizeof(T));
+    if (e == hipSuccess && n) e = hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) return SCL_OK;
+    (void)hipGetLastError();  // reported here: a later launch check must not find it
+    scl_set_error("%s failed: %s", what, hipGetErrorString(e));
+    return SCL_E_HIP;
+}
+
 // Carves one scratch buffer into parts: take(bytes) -> the part's byte offset; every part starts on a 256-byte boundary,
 // an empty one takes 256 bytes all the same.  `at` ends up as the bytes needed.
 struct SclCarver {

@@ -372,18 +372,14 @@ extern "C" int scl_prefix_model_create(const uint32_t *h_code, const uint8_t *h_
     m->dev.len_gcd = len_gcd;
     m->dev.n_deep = fast ? n_deep : 0;
     m->fast = fast ? 1 : 0;
-    hipError_t e = hipMalloc((void **)&m->d_enc, enc.size() * sizeof(uint2));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_nodes, nodes.size() * sizeof(uint2));
-    if (e == hipSuccess && fast) e = hipMalloc((void **)&m->d_lut, lut.size() * sizeof(u16));
-    if (e == hipSuccess && fast) e = hipMalloc((void **)&m->d_deep, deep.size() * sizeof(u32));
-    if (e == hipSuccess) e = hipMemcpy(m->d_enc, enc.data(), enc.size() * sizeof(uint2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_nodes, nodes.data(), nodes.size() * sizeof(uint2), hipMemcpyHostToDevice);
-    if (e == hipSuccess && fast) e = hipMemcpy(m->d_lut, lut.data(), lut.size() * sizeof(u16), hipMemcpyHostToDevice);
-    if (e == hipSuccess && fast) e = hipMemcpy(m->d_deep, deep.data(), deep.size() * sizeof(u32), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("prefix_model_create: device table upload failed: %s", hipGetErrorString(e));
+    const char *what = "prefix_model_create: device table upload";
+    int rc = scl_upload(&m->d_enc, enc.data(), enc.size(), what);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_nodes, nodes.data(), nodes.size(), what);
+    if (rc == SCL_OK && fast) rc = scl_upload(&m->d_lut, lut.data(), lut.size(), what);
+    if (rc == SCL_OK && fast) rc = scl_upload(&m->d_deep, deep.data(), deep.size(), what);
+    if (rc != SCL_OK) {
         scl_prefix_model_destroy(m);
-        return SCL_E_HIP;
+        return rc;
     }
     m->dev.d_enc = m->d_enc;
     m->dev.d_nodes = m->d_nodes;

@@ -198,21 +198,14 @@ extern "C" int scl_range_model_create(const uint32_t *h_freq, uint32_t K, uint32
         for (u32 s = 0; s < K; ++s)
             for (u32 j = 0; j < h_freq[s]; ++j) slot2sym[cum[s] + j] = (u8)s;
     const u64 tab_entries = K > 256 ? K : 256;
-    hipError_t e = hipMalloc((void **)&m->d_freq, tab_entries * sizeof(u32));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_cum, tab_entries * sizeof(u32));
-    if (e == hipSuccess && lut) e = hipMalloc((void **)&m->d_slot2sym, M);
-    if (e == hipSuccess) e = hipMemcpy(m->d_freq, h_freq, K * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_cum, cum, K * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess && lut) e = hipMemcpy(m->d_slot2sym, slot2sym, M, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("range_model_create: device table upload failed: %s", hipGetErrorString(e));
-        scl_range_model_destroy(m);
-        return SCL_E_HIP;
-    }
+    const char *what = "range_model_create: device table upload";
+    int rc = scl_upload(&m->d_freq, h_freq, K, what, tab_entries);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_cum, cum, K, what, tab_entries);
+    if (rc == SCL_OK && lut) rc = scl_upload(&m->d_slot2sym, slot2sym, M, what);
     m->dev.d_freq = m->d_freq;
     m->dev.d_cum = m->d_cum;
     m->dev.d_slot2sym = m->d_slot2sym;
-    const int rc = K <= 256 ? range_fast_build_tables(m, h_freq, cum) : SCL_OK;
+    if (rc == SCL_OK && K <= 256) rc = range_fast_build_tables(m, h_freq, cum);
     if (rc != SCL_OK) {
         scl_range_model_destroy(m);
         return rc;

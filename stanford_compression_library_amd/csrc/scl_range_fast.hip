@@ -841,12 +841,8 @@ int range_fast_build_tables(scl_range_model *m, const u32 *h_freq, const u32 *h_
         const u32 src = s < D.K ? s : 0;
         tab[s] = make_uint2(h_cum[src], h_freq[src]);
     }
-    hipError_t e = hipMalloc((void **)&m->d_enc_tab, 256 * sizeof(uint2));
-    if (e == hipSuccess) e = hipMemcpy(m->d_enc_tab, tab.data(), 256 * sizeof(uint2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("range_model_create: fast-path table upload failed: %s", hipGetErrorString(e));
-        return SCL_E_HIP;
-    }
+    const int rc = scl_upload(&m->d_enc_tab, tab.data(), 256, "range_model_create: fast-path table upload");
+    if (rc != SCL_OK) return rc;
     m->fdev.K = D.K;
     m->fdev.m_log2 = D.m_log2;
     m->fdev.M = D.M;

@@ -22,6 +22,7 @@
 
 #include "scl_entry.h"
 
+#include "scl_ans_frame.h"
 #include "scl_rans_internal.h"
 
 // =====================================================================================================
@@ -82,9 +83,7 @@ __global__ void __launch_bounds__(256) rans_encode_generic(RansDev P, const SYM 
     w.put(n, P.size_bits);
     const u64 total = w.finish();
     if (w.overflow) st |= SCL_ST_CAPACITY;
-    out_bit_off[c] = (c + 1) * out_stride * 8 - total;
-    out_nbits[c] = (u32)total;
-    if (status) status[c] = st;
+    ans_encode_results(total, st, c, out_stride, out_bit_off, out_nbits, status);
 }
 
 template <typename ST, typename SYM = u8>
@@ -206,19 +205,13 @@ static int rans_model_build(const u32 *h_freq, u32 K, u64 RF, u32 b, u32 size_bi
         m->max_bits_per_symbol = kb;
     }
     const u64 tab_entries = K > 256 ? K : 256;
-    hipError_t e = hipMalloc((void **)&m->d_freq, tab_entries * sizeof(u32));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_cum, tab_entries * sizeof(u32));
-    if (e == hipSuccess) e = hipMemcpy(m->d_freq, h_freq, K * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_cum, cum, K * sizeof(u32), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("rans_model_create: device table upload failed: %s", hipGetErrorString(e));
-        scl_rans_model_destroy(m);
-        return SCL_E_HIP;
-    }
+    const char *what = "rans_model_create: device table upload";
+    int rc = scl_upload(&m->d_freq, h_freq, K, what, tab_entries);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_cum, cum, K, what, tab_entries);
     m->dev.d_freq = m->d_freq;
     m->dev.d_cum = m->d_cum;
     // the tuned kernels carry symbols as bytes: alphabets above 256 run the any-parameter kernels (*_u16 entry points)
-    int rc = K <= 256 ? rans_fast_build_tables(m, h_freq, cum) : SCL_OK;
+    if (rc == SCL_OK && K <= 256) rc = rans_fast_build_tables(m, h_freq, cum);
     if (rc == SCL_OK && !m->fast && K <= 256) rc = rans_fastb_build_tables(m, h_freq, cum);
     if (rc != SCL_OK) {
         scl_rans_model_destroy(m);

@@ -31,7 +31,7 @@
 
 #include <stdlib.h>
 
-#include "scl_ans_fast_io.h"
+#include "scl_ans_frame.h"
 #include "scl_rans_internal.h"
 
 #define RF_THREADS 256
@@ -293,10 +293,7 @@ __global__ void __launch_bounds__(RF_THREADS, (EncOut::STRIPED && CHECK_SYM) ? 3
     u32 st = (CHECK_SYM && (bad & 0x80808080u)) ? SCL_ST_SYMBOL : 0u;
     if (P.size_bits < 32 && (n >> P.size_bits)) st |= SCL_ST_SIZE;
     o.template put32<RF_RING_OFF>(lds, n, P.size_bits);
-    const u64 total = o.finish(lds, wg_out);
-    out_bit_off[c] = (c + 1) * out_stride * 8 - total;
-    out_nbits[c] = (u32)total;
-    if (status) status[c] = st;
+    ans_encode_results(o.finish(lds, wg_out), st, c, out_stride, out_bit_off, out_nbits, status);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -312,9 +309,7 @@ __global__ void __launch_bounds__(RF_THREADS, (EncOut::STRIPED && CHECK_SYM) ? 3
 // {f | sym << 24, slot - c}: v_mad_u32_u24 ignores the symbol byte, so no field needs extracting.
 // Workgroup size: 1024 lanes (one workgroup per CU, 4 waves per SIMD) for batches that fill the chip that way
 // (>= 256 workgroups); smaller batches take 256-lane workgroups so that they spread over all CUs instead of running 4
-// waves per SIMD on a quarter of them (65 536 chunks: decode 0.48 -> see DESIGN.md).
-#define RD_THREADS 1024
-#define RD_THREADS_SMALL 256
+// waves per SIMD on a quarter of them (65 536 chunks: decode 0.48 -> see DESIGN.md): ans_wide_workgroups, scl_ans_frame.h.
 
 // decode one symbol: state update + renormalisation from the 32-bit lookahead `lk` (bits are consumed from
 // its top); returns the first table word (symbol in byte 3) and the number of bits used.
@@ -409,36 +404,52 @@ __device__ __forceinline__ u32 rf_decode_symbol(u32 &x, u32 &lk, u32 &used, cons
 // a check that found 17 words ahead and did nothing still leaves 4); the line loop asks after every second block,
 // because a check costs the wave BOTH refill bodies (some lane is always at either stage: 2 x 16 byte swaps and ring
 // writes, plus the loads) whether or not a given lane needed one.
-template <int ML_T, int CB_T, bool REFILL = true, int NB_T = 1, typename DecIn>
-__device__ __forceinline__ uint4 rf_decode16(u32 &x, DecIn &r, char *lds, const char *tab, u32 ml_rt, u32 cb_rt,
-                                             const RfGenM &rf_gen) {
-    u32 ow[4];
-#pragma unroll
-    for (int d = 3; d >= 0; --d) {
-        u32 pr[2] = {0u, 0u};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            u32 lk = r.look(lds);
-            u32 ua, ub;
-            const u32 ea = rf_decode_symbol<ML_T, CB_T, NB_T>(x, lk, ua, tab, ml_rt, cb_rt, rf_gen);
-            const u32 eb = rf_decode_symbol<ML_T, CB_T, NB_T>(x, lk, ub, tab, ml_rt, cb_rt, rf_gen);
-            // two symbols use at most 2*m <= 24 bits of the 32-bit lookahead (2 x 16 for NUM_BITS_OUT > 1: the second
-            // symbol's three don't-care bits are whatever follows); the top-aligned variants report their shift, 3 more
-            // per symbol than they read
-            r.advance(lds, ((ML_T >= 0 && CB_T == 3) || NB_T != 1) ? ua + ub - 6u : ua + ub);
-            // the symbol bytes of a pair with ONE v_perm (the earlier symbol is the more significant byte), the two pairs
-            // of a word with another: three instead of four per four symbols
-            u32 p = __builtin_amdgcn_perm(ea, eb, 0x0c0c0703u);  // 0 : 0 : ea >> 24 : eb >> 24
-            // the chain through x is serial anyway; without this fence the compiler sinks all the byte inserts
-            // of a 64-symbol iteration to its end, keeps every table word alive until then and spills
-            asm volatile("" : "+v"(p) : : "memory");
-            pr[h] = p;
-        }
-        ow[d] = __builtin_amdgcn_perm(pr[0], pr[1], 0x05040100u);
+template <int ML_T, int CB_T, int NB_T>
+struct RfDecStep {  // STEP of ans_decode_rows (scl_ans_frame.h)
+    static constexpr bool SPARSE_REFILL = NB_T == 1;  // ring check every 32 symbols (<= 13 bits each), every 16 for
+                                                      // NUM_BITS_OUT > 1 (<= 16 bits each)
+    static constexpr u32 XSH = ((ML_T >= 0 && CB_T == 3) || NB_T != 1) ? 3u : 0u;  // top-aligned state, see rf_decode_symbol
+    const char *tab;
+    u32 ml_rt, cb_rt;
+    const RfGenM &rf_gen;
+
+    template <typename DecIn>
+    __device__ __forceinline__ u8 symbol(u32 &x, DecIn &r, char *lds) const {
+        u32 used, lk1 = r.look(lds);
+        const u32 e = rf_decode_symbol<ML_T, CB_T, NB_T>(x, lk1, used, tab, ml_rt, cb_rt, rf_gen);
+        r.advance(lds, used - XSH);
+        return (u8)(e >> 24);
     }
-    if (REFILL) r.maybe_refill(lds);
-    return make_uint4(ow[0], ow[1], ow[2], ow[3]);
-}
+    template <bool REFILL, typename DecIn>
+    __device__ __forceinline__ uint4 block16(u32 &x, DecIn &r, char *lds) const {
+        u32 ow[4];
+#pragma unroll
+        for (int d = 3; d >= 0; --d) {
+            u32 pr[2] = {0u, 0u};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                u32 lk = r.look(lds);
+                u32 ua, ub;
+                const u32 ea = rf_decode_symbol<ML_T, CB_T, NB_T>(x, lk, ua, tab, ml_rt, cb_rt, rf_gen);
+                const u32 eb = rf_decode_symbol<ML_T, CB_T, NB_T>(x, lk, ub, tab, ml_rt, cb_rt, rf_gen);
+                // two symbols use at most 2*m <= 24 bits of the 32-bit lookahead (2 x 16 for NUM_BITS_OUT > 1: the second
+                // symbol's three don't-care bits are whatever follows); the top-aligned variants report their shift, 3 more
+                // per symbol than they read
+                r.advance(lds, ua + ub - 2 * XSH);
+                // the symbol bytes of a pair with ONE v_perm (the earlier symbol is the more significant byte), the two pairs
+                // of a word with another: three instead of four per four symbols
+                u32 p = __builtin_amdgcn_perm(ea, eb, 0x0c0c0703u);  // 0 : 0 : ea >> 24 : eb >> 24
+                // the chain through x is serial anyway; without this fence the compiler sinks all the byte inserts
+                // of a 64-symbol iteration to its end, keeps every table word alive until then and spills
+                asm volatile("" : "+v"(p) : : "memory");
+                pr[h] = p;
+            }
+            ow[d] = __builtin_amdgcn_perm(pr[0], pr[1], 0x05040100u);
+        }
+        if (REFILL) r.maybe_refill(lds);
+        return make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    }
+};
 
 // STRIPED: the input is in wave-striped slots (AnsBackWriterT / AnsBitReaderT, scl_ans_fast_io.h); `in_size_bytes` then
 // carries the slot stride and stream c lies in slot c.
@@ -458,7 +469,6 @@ __global__ void __launch_bounds__(THREADS) rans_decode_fast_kernel(RansFastDev P
     char *lds = s_lds + 4096 * 8;
     const char *tab = s_lds;
     const u32 M = P.M;
-    constexpr u32 XSH = ((ML_T >= 0 && CB_T == 3) || NB_T != 1) ? 3u : 0u;  // top-aligned state, see rf_decode_symbol
     for (u32 i = threadIdx.x; i < M; i += THREADS) {
         const uint2 v = P.d_dec_tab[i];
         reinterpret_cast<uint2 *>(s_lds)[i] = v;
@@ -467,75 +477,19 @@ __global__ void __launch_bounds__(THREADS) rans_decode_fast_kernel(RansFastDev P
     const u64 c = (u64)blockIdx.x * THREADS + threadIdx.x;
     if (c >= n_chunks) return;
     const u32 avail = in_nbits[c];
-    u32 st = 0;
-    if (avail < P.size_bits + P.nsb) {  // header does not fit
-        out_lens[c] = 0;
-        consumed[c] = P.size_bits + P.nsb;
-        if (status) status[c] = SCL_ST_TRUNCATED;
-        return;
-    }
+    if (ans_decode_refuse(P, avail, c, out_lens, consumed, status)) return;
     DecIn r;
-    if constexpr (STRIPED)
-        r.init(in, in_size_bytes, c, bit_off[c], lds, threadIdx.x);
-    else
-        r.init(in, in_size_bytes, bit_off[c], lds, threadIdx.x);
-    u32 n = r.get(lds, P.size_bits);
-    u32 x = r.get(lds, P.nsb);
-    x <<= XSH;
-    out_lens[c] = n;
-    if (n > out_cap) {
-        st |= SCL_ST_CAPACITY;
-        n = 0;
-    }
-    const u32 st_header = st;
-    const u32 ml_rt = P.m_log2, cb_rt = (ML_T == 0 && CB_T == 3) ? 3u - (32 - P.nsb) : 32 - P.nsb;  // see rf_decode_symbol
+    u32 n, x, st;
+    ans_decode_open<STRIPED>(P, r, lds, in, in_size_bytes, bit_off, c, out_cap, n, x, st, out_lens);
+    typedef RfDecStep<ML_T, CB_T, NB_T> Step;
+    x <<= Step::XSH;
     RfGenM rf_gen;
     rf_gen.inv_m = 1.0 / (double)P.M;
     rf_gen.m = NB_T != 1 ? P.dec_sadd : P.M;   // NUM_BITS_OUT > 1: b - 1 - cbl and ~(b - 1), see rf_decode_symbol
     rf_gen.l = NB_T != 1 ? P.dec_notb : P.L;
-    u8 *dst = out_sym + c * out_stride;
-
-    // symbols come out last-first (rANS.py:291): the ragged head of the last 16-byte block ...
-    u32 i = n;
-    while (i & 15u) {
-        u32 used, lk1 = r.look(lds);
-        const u32 e = rf_decode_symbol<ML_T, CB_T, NB_T>(x, lk1, used, tab, ml_rt, cb_rt, rf_gen);
-        r.advance(lds, used - XSH);
-        dst[--i] = (u8)(e >> 24);
-        if ((i & 3u) == 0) r.maybe_refill(lds);
-    }
-    // ... whole 16-byte blocks up to a line boundary ...
-    while (i & 127u) {
-        const uint4 v = rf_decode16<ML_T, CB_T, true, NB_T>(x, r, lds, tab, ml_rt, cb_rt, rf_gen);
-        i -= 16;
-        *reinterpret_cast<uint4 *>(dst + i) = v;
-    }
-    // ... then one full 128-byte line per iteration, eight registers: stored cooperatively by the wave when every
-    // lane is here with the same position (CoopLineStore, scl_ans_fast_io.h), else as a burst of eight 16-byte stores
-    CoopLineStore cs;
-    cs.init(out_sym, c, out_stride, i);
-#pragma nounroll
-    while (i) {
-        uint4 a[8];
-#pragma unroll
-        for (int b = 7; b >= 0; --b)
-            // ring check every 32 symbols (<= 13 bits each), every 16 for NUM_BITS_OUT > 1 (<= 16 bits each)
-            a[b] = ((b & 1) && NB_T == 1) ? rf_decode16<ML_T, CB_T, false, NB_T>(x, r, lds, tab, ml_rt, cb_rt, rf_gen)
-                                          : rf_decode16<ML_T, CB_T, true, NB_T>(x, r, lds, tab, ml_rt, cb_rt, rf_gen);
-        i -= 128;
-        if (cs.on) {
-            cs.store(a, i);
-        } else {
-            uint4 *p = reinterpret_cast<uint4 *>(dst + i);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) p[b] = a[b];
-        }
-    }
-    const u32 used_bits = r.consumed();
-    if (used_bits > avail) st |= SCL_ST_TRUNCATED;
-    else if (st_header == 0 && (x >> XSH) != P.L) st |= SCL_ST_STATE;  // assert state == INITIAL_STATE (rANS.py:295)
-    consumed[c] = used_bits;
-    if (status) status[c] = st;
+    const Step step = {tab, P.m_log2, (ML_T == 0 && CB_T == 3) ? 3u - (32 - P.nsb) : 32 - P.nsb, rf_gen};
+    ans_decode_rows(step, x, r, lds, n, out_sym, c, out_stride);
+    ans_decode_close(r.consumed(), avail, st, x >> Step::XSH, P.L, c, consumed, status);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -545,6 +499,28 @@ static u32 ceil_log2_u32(u32 v) {
     u32 s = 0;
     while ((1ull << s) < v) ++s;
     return s;
+}
+
+// The end of both table builders: uploads the encoder's entries and the decode slot table, fills what every form of the
+// kernels reads from m->fdev and marks the model as served.
+static int rf_publish_tables(scl_rans_model *m, const std::vector<uint4> &enc, const u32 *h_freq, const u32 *h_cum) {
+    const RansDev &D = m->dev;
+    std::vector<uint2> dec(D.M);
+    ans_fill_dec_slots(dec.data(), h_freq, h_cum, D.K);
+    const char *what = "rans_model_create: fast-path table upload";
+    int rc = scl_upload(&m->d_enc_tab, enc.data(), enc.size(), what);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_dec_tab, dec.data(), dec.size(), what);
+    if (rc != SCL_OK) return rc;
+    m->fdev.K = D.K;
+    m->fdev.nsb = D.nsb;
+    m->fdev.size_bits = D.size_bits;
+    m->fdev.m_log2 = D.m_log2;
+    m->fdev.L = (u32)D.L;
+    m->fdev.M = (u32)D.M;
+    m->fdev.d_enc_tab = m->d_enc_tab;
+    m->fdev.d_dec_tab = m->d_dec_tab;
+    m->fast = 1;
+    return SCL_OK;
 }
 
 // Decides whether the model qualifies and uploads the two tables.  Returns SCL_OK also when the model
@@ -563,15 +539,11 @@ static int rans_fast_build_tables_b(scl_rans_model *m, const u32 *h_freq, const 
     if (r + b > 24 || D.nsb != r + D.m_log2 + b) return SCL_OK;
     const u32 M = (u32)D.M, nsb = D.nsb;
     std::vector<uint4> enc(256);
-    std::vector<uint2> dec(M);
     for (u32 s = 0; s < 256; ++s) {
         const u32 src = s < D.K ? s : 0;  // out-of-alphabet symbols are flagged, entry 0 keeps the lane sane
         const u32 f = h_freq[src], c = h_cum[src];
-        const u64 a1 = ((u64)D.RF * f) << b;  // max_shrunk_state + 1 (rANS.py:112)
-        u32 k_lo = 0, k_hi = 0;
-        while ((D.L >> (k_lo * b)) >= a1) ++k_lo;
-        while ((m->H >> (k_hi * b)) >= a1) ++k_hi;
-        if (k_hi > k_lo + 1 || (k_lo + 1) * b > 16) return SCL_OK;
+        u32 k_lo;
+        if (!ans_release_groups(D.L, m->H, ((u64)D.RF * f) << b, b, 16, &k_lo)) return SCL_OK;
         // floor(x / (f 2^(b k_lo))) = (x rcp) >> (E + b k_lo) for every x < 2^nsb: rcp = ceil(2^E / f) with E = nsb +
         // ceil(log2 f) (the error x (rcp f - 2^E) / (f 2^(E + b k_lo)) stays below 1 / (f 2^(b k_lo)))
         const u32 E = nsb + ceil_log2_u32(f);
@@ -579,32 +551,13 @@ static int rans_fast_build_tables_b(scl_rans_model *m, const u32 *h_freq, const 
         if ((rcp >> 32) != 0 || E + b * k_lo < 32 || E + b * k_lo - 32 > 31) return SCL_OK;
         enc[s] = make_uint4((u32)rcp, M - f, c, (E + b * k_lo - 32) | ((b * k_lo) << 8));
     }
-    for (u32 s = 0; s < D.K; ++s)
-        for (u32 j = 0; j < h_freq[s]; ++j) dec[h_cum[s] + j] = make_uint2(h_freq[s] | (s << 24), j);
-    hipError_t e = hipMalloc((void **)&m->d_enc_tab, 256 * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_dec_tab, M * sizeof(uint2));
-    if (e == hipSuccess) e = hipMemcpy(m->d_enc_tab, enc.data(), 256 * sizeof(uint4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_dec_tab, dec.data(), M * sizeof(uint2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("rans_model_create: fast-path table upload failed: %s", hipGetErrorString(e));
-        return SCL_E_HIP;
-    }
     m->enc_lockstep = 0;
-    m->fdev.K = D.K;
-    m->fdev.nsb = nsb;
-    m->fdev.size_bits = D.size_bits;
-    m->fdev.m_log2 = D.m_log2;
-    m->fdev.L = (u32)D.L;
-    m->fdev.M = M;
     m->fdev.enc_msh = ((r + b) << 16) | (b << 24);
     m->fdev.b = b;
     const u32 cbl = 32 - scl_bit_width_u64(D.L);
     m->fdev.dec_sadd = b - 1 - cbl;  // (mod 2^32: added to a count of leading zeros >= cbl - b + 1)
     m->fdev.dec_notb = ~(b - 1);
-    m->fdev.d_enc_tab = m->d_enc_tab;
-    m->fdev.d_dec_tab = m->d_dec_tab;
-    m->fast = 1;
-    return SCL_OK;
+    return rf_publish_tables(m, enc, h_freq, h_cum);
 }
 
 int rans_fast_build_tables(scl_rans_model *m, const u32 *h_freq, const u32 *h_cum) {
@@ -631,7 +584,6 @@ int rans_fast_build_tables(scl_rans_model *m, const u32 *h_freq, const u32 *h_cu
     const u32 C = r + 2 * mp + 2;
     const u32 enc_msh = ((C >= 33) ? (C - 32) : (1u | ((33 - C) << 8))) | (r << 16);
     std::vector<uint4> enc(256);
-    std::vector<uint2> dec(M);
     bool foldable = true;
     u64 fixed_k_mass[32] = {0};  // total frequency of the symbols that ALWAYS release k bits (k_hi == k_lo), per k
     for (u32 s = 0; s < 256; ++s) {
@@ -667,27 +619,8 @@ int rans_fast_build_tables(scl_rans_model *m, const u32 *h_freq, const u32 *h_cu
     u64 top_mass = 0;
     for (u32 k = 0; k < 32; ++k) top_mass = fixed_k_mass[k] > top_mass ? fixed_k_mass[k] : top_mass;
     m->enc_lockstep = (4 * top_mass >= 3 * (u64)M) ? 1u : 0u;
-    for (u32 s = 0; s < D.K; ++s)
-        for (u32 j = 0; j < h_freq[s]; ++j) dec[h_cum[s] + j] = make_uint2(h_freq[s] | (s << 24), j);
-    hipError_t e = hipMalloc((void **)&m->d_enc_tab, 256 * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_dec_tab, M * sizeof(uint2));
-    if (e == hipSuccess) e = hipMemcpy(m->d_enc_tab, enc.data(), 256 * sizeof(uint4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_dec_tab, dec.data(), M * sizeof(uint2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("rans_model_create: fast-path table upload failed: %s", hipGetErrorString(e));
-        return SCL_E_HIP;
-    }
-    m->fdev.K = D.K;
-    m->fdev.nsb = nsb;
-    m->fdev.size_bits = D.size_bits;
-    m->fdev.m_log2 = D.m_log2;
-    m->fdev.L = (u32)D.L;
-    m->fdev.M = M;
     m->fdev.enc_msh = enc_msh_final;
-    m->fdev.d_enc_tab = m->d_enc_tab;
-    m->fdev.d_dec_tab = m->d_dec_tab;
-    m->fast = 1;
-    return SCL_OK;
+    return rf_publish_tables(m, enc, h_freq, h_cum);
 }
 
 // Which writer.  At equal occupancy the two run within noise of each other (the third wave per SIMD that AnsBackWriterS
@@ -744,10 +677,9 @@ static RfEncChoice rf_encode_choice(const scl_rans_model *m, u64 n_chunks, bool 
 }
 
 void rans_fast_encode_launch(const scl_rans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, bool striped) {
-    const u32 blocks = (u32)((a.n_chunks + RF_THREADS - 1) / RF_THREADS);
     const RfEncChoice ch = rf_encode_choice(m, a.n_chunks, striped);
 #define RF_LAUNCH_ENC_K(OUT, CHECK, MSH, R, NB) \
-    scl_launch_encode(rans_encode_fast_kernel<OUT, CHECK, MSH, R, NB>, {blocks, RF_THREADS}, st, m->fdev, a)
+    scl_launch_encode(rans_encode_fast_kernel<OUT, CHECK, MSH, R, NB>, ans_grid(a.n_chunks, RF_THREADS), st, m->fdev, a)
 #define RF_LAUNCH_ENC_W(CHECK, MSH, R, NB)                  \
     do {                                                    \
         if (ch.striped)                                     \
@@ -784,8 +716,7 @@ struct RfDecChoice {
 };
 static RfDecChoice rf_decode_choice(const scl_rans_model *m, u64 n_chunks) {
     RfDecChoice c;
-    // up to 2 x 256 small workgroups are resident at once (64 KiB of LDS each): beyond that the 1024-lane form wins
-    c.threads = n_chunks > 2ull * 256 * RD_THREADS_SMALL ? RD_THREADS : RD_THREADS_SMALL;
+    c.threads = ans_wide_workgroups(n_chunks) ? ANS_THREADS_WIDE : ANS_THREADS_SMALL;
     c.nb = m->fdev.b != 1 ? 0 : 1;
     if (m->fdev.b != 1)  // NUM_BITS_OUT in {4, 8, 16}
         c.ml = 0, c.cb = 0;
@@ -814,9 +745,8 @@ void rans_fast_kernel_names(const scl_rans_model *m, u64 n_chunks, char *enc, ch
 
 void rans_fast_decode_launch(const scl_rans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, bool striped) {
     const RfDecChoice ch = rf_decode_choice(m, a.n_chunks);
-#define RF_LAUNCH_DEC_K(ML, CB, TH, NB, ST)                                                                          \
-    scl_launch_decode(rans_decode_fast_kernel<ML, CB, TH, NB, ST>, {(u32)((a.n_chunks + TH - 1) / TH), TH}, st, m->fdev, \
-                      a)
+#define RF_LAUNCH_DEC_K(ML, CB, TH, NB, ST) \
+    scl_launch_decode(rans_decode_fast_kernel<ML, CB, TH, NB, ST>, ans_grid(a.n_chunks, TH), st, m->fdev, a)
 #define RF_LAUNCH_DEC_T(ML, CB, TH, NB)                     \
     do {                                                    \
         if (striped)                                        \
@@ -826,10 +756,10 @@ void rans_fast_decode_launch(const scl_rans_model *m, const SclDecodeArgs<u8> &a
     } while (0)
 #define RF_LAUNCH_DEC(ML, CB, NB)                           \
     do {                                                    \
-        if (ch.threads == RD_THREADS)                       \
-            RF_LAUNCH_DEC_T(ML, CB, RD_THREADS, NB);        \
+        if (ch.threads == ANS_THREADS_WIDE)                 \
+            RF_LAUNCH_DEC_T(ML, CB, ANS_THREADS_WIDE, NB);  \
         else                                                \
-            RF_LAUNCH_DEC_T(ML, CB, RD_THREADS_SMALL, NB);  \
+            RF_LAUNCH_DEC_T(ML, CB, ANS_THREADS_SMALL, NB); \
     } while (0)
     if (ch.nb == 0)
         RF_LAUNCH_DEC(0, 0, 0);

@@ -16,14 +16,12 @@
 //    sh = (max(d, 0) + b - 1) & ~(b - 1) bits in one 64-bit shift.
 #include <vector>
 
-#include "scl_ans_fast_io.h"
+#include "scl_ans_frame.h"
 #include "scl_rans_internal.h"
 
 #define RB_THREADS 256
 #define RB_RING_BYTES (32 * RB_THREADS * 4)
 typedef AnsBackWriter<RB_THREADS> EncOutB;
-#define RBD_THREADS 1024      // batches that fill the chip with one 1024-lane workgroup per CU
-#define RBD_THREADS_SMALL 256  // smaller ones spread over all CUs instead (see scl_rans_fast.hip)
 
 // ---------------------------------------------------------------------------------------------------
 // encode
@@ -112,6 +110,8 @@ __global__ void __launch_bounds__(RB_THREADS, 4) rans_encode_fastb_kernel(RansFa
     if (P.size_bits < 32 && (n >> P.size_bits)) st |= SCL_ST_SIZE;
     o.put32(lds, n, P.size_bits);
     const u64 total = o.finish(lds);
+    // (not ans_encode_results: handing these three stores to a function changes this kernel's registers and measured
+    // 2.5 % slower on 65 536 chunks, profiles/ans_frame_codegen.txt)
     out_bit_off[c] = (c + 1) * out_stride * 8 - total;
     out_nbits[c] = (u32)total;
     if (status) status[c] = st;
@@ -121,37 +121,42 @@ __global__ void __launch_bounds__(RB_THREADS, 4) rans_encode_fastb_kernel(RansFa
 // decode
 // ---------------------------------------------------------------------------------------------------
 // One workgroup of 1024 lanes per CU: slot table {f | sym << 24, slot - c} at LDS offset 0 (32 KiB), word ring behind it.
-template <typename DecInB>
-__device__ __forceinline__ u32 rb_decode_symbol(u32 &x, DecInB &r, char *lds, const char *tab, u32 m_log2, u32 cbl,
-                                                u32 bm1) {
-    const uint2 e = *reinterpret_cast<const uint2 *>(tab + ((x << 3) & (((1u << m_log2) - 1u) << 3)));
-    const u32 xn = __umul24(x >> m_log2, e.x) + e.y;  // v_mad_u32_u24 reads the low 24 bits (f) of e.x
-    // missing bits d = bit_width(L) - bit_width(xn) = clz(xn) - cbl; groups of b bits: sh = b ceil(max(d, 0) / b)
-    const int d = (int)__builtin_clz(xn) - (int)cbl;
-    const u32 sh = ((u32)max(d, 0) + bm1) & ~bm1;
-    x = (u32)(((((u64)xn) << 32) | r.look()) << sh >> 32);  // sh <= 27: one 64-bit shift, sh = 0 included
-    r.advance(lds, sh);
-    return e.x;
-}
+struct RbDecStep {  // STEP of ans_decode_rows (scl_ans_frame.h)
+    static constexpr bool SPARSE_REFILL = false;  // block16 tops the ring up itself, after every four symbols
+    const char *tab;
+    u32 m_log2, cbl, bm1;
 
-template <typename DecInB>
-__device__ __forceinline__ uint4 rb_decode16(u32 &x, DecInB &r, char *lds, const char *tab, u32 m_log2, u32 cbl,
-                                             u32 bm1) {
-    u32 ow[4];
-#pragma unroll
-    for (int d = 3; d >= 0; --d) {
-        u32 o = 0;
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const u32 e = rb_decode_symbol(x, r, lds, tab, m_log2, cbl, bm1);
-            o = __builtin_amdgcn_perm(o, e, 0x06050403u);  // o = (o << 8) | (e >> 24)
-        }
-        r.maybe_refill(lds);  // <= 4 words consumed by four symbols
-        asm volatile("" : "+v"(o) : : "memory");
-        ow[d] = o;
+    template <typename DecInB>
+    __device__ __forceinline__ u32 entry(u32 &x, DecInB &r, char *lds) const {  // one symbol; returns the first table word
+        const uint2 e = *reinterpret_cast<const uint2 *>(tab + ((x << 3) & (((1u << m_log2) - 1u) << 3)));
+        const u32 xn = __umul24(x >> m_log2, e.x) + e.y;  // v_mad_u32_u24 reads the low 24 bits (f) of e.x
+        // missing bits d = bit_width(L) - bit_width(xn) = clz(xn) - cbl; groups of b bits: sh = b ceil(max(d, 0) / b)
+        const int d = (int)__builtin_clz(xn) - (int)cbl;
+        const u32 sh = ((u32)max(d, 0) + bm1) & ~bm1;
+        x = (u32)(((((u64)xn) << 32) | r.look()) << sh >> 32);  // sh <= 27: one 64-bit shift, sh = 0 included
+        r.advance(lds, sh);
+        return e.x;
     }
-    return make_uint4(ow[0], ow[1], ow[2], ow[3]);
-}
+    template <typename DecInB>
+    __device__ __forceinline__ u8 symbol(u32 &x, DecInB &r, char *lds) const { return (u8)(entry(x, r, lds) >> 24); }
+    template <bool REFILL, typename DecInB>
+    __device__ __forceinline__ uint4 block16(u32 &x, DecInB &r, char *lds) const {
+        u32 ow[4];
+#pragma unroll
+        for (int d = 3; d >= 0; --d) {
+            u32 o = 0;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const u32 e = entry(x, r, lds);
+                o = __builtin_amdgcn_perm(o, e, 0x06050403u);  // o = (o << 8) | (e >> 24)
+            }
+            r.maybe_refill(lds);  // <= 4 words consumed by four symbols
+            asm volatile("" : "+v"(o) : : "memory");
+            ow[d] = o;
+        }
+        return make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    }
+};
 
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) rans_decode_fastb_kernel(RansFastBDev P, const u8 *__restrict__ in,
@@ -171,59 +176,13 @@ __global__ void __launch_bounds__(THREADS) rans_decode_fastb_kernel(RansFastBDev
     const u64 c = (u64)blockIdx.x * THREADS + threadIdx.x;
     if (c >= n_chunks) return;
     const u32 avail = in_nbits[c];
-    u32 st = 0;
-    if (avail < P.size_bits + P.nsb) {  // header does not fit
-        out_lens[c] = 0;
-        consumed[c] = P.size_bits + P.nsb;
-        if (status) status[c] = SCL_ST_TRUNCATED;
-        return;
-    }
+    if (ans_decode_refuse(P, avail, c, out_lens, consumed, status)) return;
     DecInB r;
-    r.init(in, in_size_bytes, bit_off[c], lds, threadIdx.x);
-    u32 n = r.get(lds, P.size_bits);
-    u32 x = r.get(lds, P.nsb);
-    out_lens[c] = n;
-    if (n > out_cap) {
-        st |= SCL_ST_CAPACITY;
-        n = 0;
-    }
-    const u32 st_header = st;
-    const u32 m_log2 = P.m_log2, cbl = P.cbl, bm1 = P.b - 1;
-    u8 *dst = out_sym + c * out_stride;
-
-    // symbols come out last-first (rANS.py:291): ragged head, 16-byte blocks up to a line boundary, then whole lines
-    u32 i = n;
-    while (i & 15u) {
-        const u32 e = rb_decode_symbol(x, r, lds, tab, m_log2, cbl, bm1);
-        dst[--i] = (u8)(e >> 24);
-        if ((i & 3u) == 0) r.maybe_refill(lds);
-    }
-    while (i & 127u) {
-        const uint4 v = rb_decode16(x, r, lds, tab, m_log2, cbl, bm1);
-        i -= 16;
-        *reinterpret_cast<uint4 *>(dst + i) = v;
-    }
-    CoopLineStore cs;  // whole waves of equally long chunks store cooperatively (scl_ans_fast_io.h)
-    cs.init(out_sym, c, out_stride, i);
-#pragma nounroll
-    while (i) {
-        uint4 a[8];
-#pragma unroll
-        for (int b = 7; b >= 0; --b) a[b] = rb_decode16(x, r, lds, tab, m_log2, cbl, bm1);
-        i -= 128;
-        if (cs.on) {
-            cs.store(a, i);
-        } else {
-            uint4 *p = reinterpret_cast<uint4 *>(dst + i);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) p[b] = a[b];
-        }
-    }
-    const u32 used_bits = r.consumed();
-    if (used_bits > avail) st |= SCL_ST_TRUNCATED;
-    else if (st_header == 0 && x != P.L) st |= SCL_ST_STATE;  // assert state == INITIAL_STATE (rANS.py:295)
-    consumed[c] = used_bits;
-    if (status) status[c] = st;
+    u32 n, x, st;
+    ans_decode_open<false>(P, r, lds, in, in_size_bytes, bit_off, c, out_cap, n, x, st, out_lens);
+    const RbDecStep step = {tab, P.m_log2, P.cbl, P.b - 1};
+    ans_decode_rows(step, x, r, lds, n, out_sym, c, out_stride);
+    ans_decode_close(r.consumed(), avail, st, x, P.L, c, consumed, status);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -247,10 +206,8 @@ int rans_fastb_build_tables(scl_rans_model *m, const u32 *h_freq, const u32 *h_c
         const u32 src = s < D.K ? s : 0;  // out-of-alphabet symbols are flagged, entry 0 keeps the lane sane
         const u32 f = h_freq[src], c = h_cum[src];
         const u64 a1 = ((u64)D.RF * f) << b;  // max_shrunk_state + 1 (rANS.py:112)
-        u32 k_lo = 0, k_hi = 0;
-        while ((D.L >> (k_lo * b)) >= a1) ++k_lo;
-        while ((m->H >> (k_hi * b)) >= a1) ++k_hi;
-        if (k_hi > k_lo + 1 || (k_lo + 1) * b > 31) return SCL_OK;  // the first cannot happen (H < L 2^b)
+        u32 k_lo;
+        if (!ans_release_groups(D.L, m->H, a1, b, 31, &k_lo)) return SCL_OK;
         u64 thresh = a1 << (k_lo * b);
         if (thresh > 0x7FFFFFFFull) thresh = 0x7FFFFFFFull;  // never reached by x <= H < 2^31: always "below"
         const double inv_f = 1.0 / (double)f;
@@ -263,18 +220,12 @@ int rans_fastb_build_tables(scl_rans_model *m, const u32 *h_freq, const u32 *h_c
         enc[s] = make_uint4((u32)bits64, (u32)(bits64 >> 32), (u32)thresh, c);
         aux[s] = (M - f) | (((k_lo + 1) * b) << 24);
     }
-    for (u32 s = 0; s < D.K; ++s)
-        for (u32 j = 0; j < h_freq[s]; ++j) dec[h_cum[s] + j] = make_uint2(h_freq[s] | (s << 24), j);
-    hipError_t e = hipMalloc((void **)&m->d_encb_tab, 256 * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_encb_aux, 256 * sizeof(u32));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_decb_tab, M * sizeof(uint2));
-    if (e == hipSuccess) e = hipMemcpy(m->d_encb_tab, enc.data(), 256 * sizeof(uint4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_encb_aux, aux.data(), 256 * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_decb_tab, dec.data(), M * sizeof(uint2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("rans_model_create: fast-path (NUM_BITS_OUT > 1) table upload failed: %s", hipGetErrorString(e));
-        return SCL_E_HIP;
-    }
+    ans_fill_dec_slots(dec.data(), h_freq, h_cum, D.K);
+    const char *what = "rans_model_create: fast-path (NUM_BITS_OUT > 1) table upload";
+    int rc = scl_upload(&m->d_encb_tab, enc.data(), 256, what);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_encb_aux, aux.data(), 256, what);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_decb_tab, dec.data(), M, what);
+    if (rc != SCL_OK) return rc;
     RansFastBDev &F = m->fbdev;
     F.K = D.K;
     F.nsb = D.nsb;
@@ -292,7 +243,7 @@ int rans_fastb_build_tables(scl_rans_model *m, const u32 *h_freq, const u32 *h_c
 }
 
 void rans_fastb_encode_launch(const scl_rans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st) {
-    const SclGrid g = {(u32)((a.n_chunks + RB_THREADS - 1) / RB_THREADS), RB_THREADS};
+    const SclGrid g = ans_grid(a.n_chunks, RB_THREADS);
     if (m->fbdev.K < 256)
         scl_launch_encode(rans_encode_fastb_kernel<true>, g, st, m->fbdev, a);
     else
@@ -300,11 +251,8 @@ void rans_fastb_encode_launch(const scl_rans_model *m, const SclEncodeArgs<u8> &
 }
 
 void rans_fastb_decode_launch(const scl_rans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st) {
-    if (a.n_chunks > 2ull * 256 * RBD_THREADS_SMALL)  // more than two 256-lane workgroups per CU: the 1024-lane form
-        scl_launch_decode(rans_decode_fastb_kernel<RBD_THREADS>,
-                          {(u32)((a.n_chunks + RBD_THREADS - 1) / RBD_THREADS), RBD_THREADS}, st, m->fbdev, a);
+    if (ans_wide_workgroups(a.n_chunks))
+        scl_launch_decode(rans_decode_fastb_kernel<ANS_THREADS_WIDE>, ans_grid(a.n_chunks, ANS_THREADS_WIDE), st, m->fbdev, a);
     else
-        scl_launch_decode(rans_decode_fastb_kernel<RBD_THREADS_SMALL>,
-                          {(u32)((a.n_chunks + RBD_THREADS_SMALL - 1) / RBD_THREADS_SMALL), RBD_THREADS_SMALL}, st,
-                          m->fbdev, a);
+        scl_launch_decode(rans_decode_fastb_kernel<ANS_THREADS_SMALL>, ans_grid(a.n_chunks, ANS_THREADS_SMALL), st, m->fbdev, a);
 }

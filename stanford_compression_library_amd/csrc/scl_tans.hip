@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "scl_entry.h"
+#include "scl_ans_frame.h"
 #include "scl_tans_internal.h"
 #include "scl_rans_internal.h"
 
@@ -125,9 +126,7 @@ __global__ void __launch_bounds__(256) tans_encode_kernel(TansDev P, const SYM *
     w.put(n, P.size_bits);
     const u64 total = w.finish();
     if (w.overflow) st |= SCL_ST_CAPACITY;
-    out_bit_off[c] = (c + 1) * out_stride * 8 - total;
-    out_nbits[c] = (u32)total;
-    if (status) status[c] = st;
+    ans_encode_results(total, st, c, out_stride, out_bit_off, out_nbits, status);
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------
@@ -203,18 +202,15 @@ static int tans_ensure_tables(const scl_tans_model *cm) {
     if (m->built) return SCL_OK;
     const u64 L = m->dev.L;
     const u32 K = m->dev.K;
-    hipError_t e = hipSuccess;
     u32 **tabs[] = {&m->d_enc, &m->d_dec_sym, &m->d_dec_xs};
     for (u32 **p : tabs)
-        if (e == hipSuccess && !*p) e = hipMalloc((void **)p, L * sizeof(u32));
-    if (e == hipSuccess) {
-        const u32 n_thr = (u32)(L > K ? L : K);
-        hipLaunchKernelGGL(tans_build_tables, dim3((n_thr + 255) / 256), dim3(256), 0, 0, K, m->dev.M, m->dev.RF,
-                           m->dev.m_log2, m->dev.nsb, m->d_freq, m->d_cum, m->d_enc, m->d_nbits, m->d_thresh,
-                           m->d_dec_sym, m->d_dec_xs);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
+        if (!*p && scl_upload<u32>(p, nullptr, 0, "tans: device table allocation", L) != SCL_OK) return SCL_E_HIP;
+    const u32 n_thr = (u32)(L > K ? L : K);
+    hipLaunchKernelGGL(tans_build_tables, dim3((n_thr + 255) / 256), dim3(256), 0, 0, K, m->dev.M, m->dev.RF,
+                       m->dev.m_log2, m->dev.nsb, m->d_freq, m->d_cum, m->d_enc, m->d_nbits, m->d_thresh,
+                       m->d_dec_sym, m->d_dec_xs);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         (void)hipGetLastError();
         scl_set_error("tans: device table build (%llu entries) failed: %s", (unsigned long long)L, hipGetErrorString(e));
@@ -286,21 +282,15 @@ extern "C" int scl_tans_model_create(const uint32_t *h_freq, uint32_t K, uint64_
         }
         m->max_bits_per_symbol = kb;
     }
-    hipError_t e = hipSuccess;
-    auto alloc = [&](u32 **p, u64 n) {
-        if (e == hipSuccess) e = hipMalloc((void **)p, (n ? n : 1) * sizeof(u32));
-    };
     const u64 tab_entries = K > 256 ? K : 256;
-    alloc(&m->d_freq, tab_entries);
-    alloc(&m->d_cum, tab_entries);
-    alloc(&m->d_nbits, tab_entries);
-    alloc(&m->d_thresh, tab_entries);
-    if (e == hipSuccess) e = hipMemcpy(m->d_freq, h_freq, K * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_cum, cum, K * sizeof(u32), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("tans_model_create: device table upload failed: %s", hipGetErrorString(e));
+    const char *what = "tans_model_create: device table upload";
+    int rc = scl_upload(&m->d_freq, h_freq, K, what, tab_entries);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_cum, cum, K, what, tab_entries);
+    if (rc == SCL_OK) rc = scl_upload<u32>(&m->d_nbits, nullptr, 0, what, tab_entries);  // filled by tans_build_tables
+    if (rc == SCL_OK) rc = scl_upload<u32>(&m->d_thresh, nullptr, 0, what, tab_entries);
+    if (rc != SCL_OK) {
         scl_tans_model_destroy(m);
-        return SCL_E_HIP;
+        return rc;
     }
     m->dev.d_freq = m->d_freq;
     m->dev.d_cum = m->d_cum;
@@ -311,7 +301,7 @@ extern "C" int scl_tans_model_create(const uint32_t *h_freq, uint32_t K, uint64_
     // 2^26 entries) are only built if somebody asks for them (scl_tans_model_tables, or rows the tuned kernels
     // cannot take) -- tans_ensure_tables.
     const bool small = m->tables && L <= 8192;  // LDS-sized tables are built at once (the tuned table kernels need them)
-    int rc = (m->tables && (!m->rans || small)) ? tans_ensure_tables(m) : SCL_OK;
+    rc = (m->tables && (!m->rans || small)) ? tans_ensure_tables(m) : SCL_OK;
     if (rc == SCL_OK && m->tables && (!m->rans || small) && K <= 256) rc = tans_fast_build_tables(m, h_freq, cum);
     if (rc != SCL_OK) {
         scl_tans_model_destroy(m);

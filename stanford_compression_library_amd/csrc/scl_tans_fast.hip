@@ -13,13 +13,8 @@
 //                       expand_state_num_bits_table is clz.
 #include <vector>
 
-#include "scl_ans_fast_io.h"
+#include "scl_ans_frame.h"
 #include "scl_tans_internal.h"
-
-// Workgroup size: 1024 lanes (one workgroup per CU, tables staged once) for batches that fill the chip that way;
-// batches of up to 131 072 chunks take 256-lane workgroups so that they spread over all CUs (see scl_rans_fast.hip).
-#define TF_THREADS 1024
-#define TF_THREADS_SMALL 256
 
 struct TfSym {
     u32 bits, k;
@@ -126,44 +121,57 @@ __global__ void __launch_bounds__(THREADS) tans_encode_fast_kernel(TansFastDev P
     if (P.size_bits < 32 && (n >> P.size_bits)) st |= SCL_ST_SIZE;
     o.put32(lds, n, P.size_bits);
     const u64 total = o.finish(lds);
+    // (not ans_encode_results: see rans_encode_fastb_kernel)
     out_bit_off[c] = (c + 1) * out_stride * 8 - total;
     out_nbits[c] = (u32)total;
     if (status) status[c] = st;
 }
 
-// decode one symbol from the 32-bit lookahead (bits consumed from its top); returns the table word
-__device__ __forceinline__ u32 tf_decode_symbol(u32 &x, u32 lk, u32 &used, const char *tab, u32 idx_mask, u32 cb) {
-    const u32 e = *reinterpret_cast<const u32 *>(tab + ((x << 2) & idx_mask));  // base_decode_step_table[x]
-    const u32 xs = e >> 8;
-    const u32 cl = (u32)__builtin_clz(xs);                     // xs >= RANGE_FACTOR > 0
-    const u32 y = __builtin_amdgcn_alignbit(xs, lk, 32 - cl);  // (xs << cl) | (lk >> (32 - cl))
-    x = y >> cb;                                               // nb = NUM_STATE_BITS - bit_width(xs) new bits
-    used = cl - cb;
-    return e;
-}
+struct TfDecStep {  // STEP of ans_decode_rows (scl_ans_frame.h)
+    static constexpr bool SPARSE_REFILL = false;  // the ring is topped up after every block of 16
+    const char *tab;
+    u32 idx_mask, cb;
 
-template <typename TfIn>
-__device__ __forceinline__ uint4 tf_decode16(u32 &x, TfIn &r, char *lds, const char *tab, u32 idx_mask, u32 cb) {
-    u32 ow[4];
-#pragma unroll
-    for (int d = 3; d >= 0; --d) {
-        u32 o = 0;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const u32 lk = r.look();
-            u32 ua, ub;
-            const u32 ea = tf_decode_symbol(x, lk, ua, tab, idx_mask, cb);
-            const u32 eb = tf_decode_symbol(x, lk << ua, ub, tab, idx_mask, cb);
-            r.advance(lds, ua + ub);  // <= 2*13 bits of the 32-bit lookahead
-            o = __builtin_amdgcn_perm(o, ea, 0x06050400u);  // o = (o << 8) | (ea & 0xFF)
-            o = __builtin_amdgcn_perm(o, eb, 0x06050400u);
-            asm volatile("" : "+v"(o) : : "memory");
-        }
-        ow[d] = o;
+    // one symbol from the 32-bit lookahead (bits consumed from its top); returns the table word
+    __device__ __forceinline__ u32 entry(u32 &x, u32 lk, u32 &used) const {
+        const u32 e = *reinterpret_cast<const u32 *>(tab + ((x << 2) & idx_mask));  // base_decode_step_table[x]
+        const u32 xs = e >> 8;
+        const u32 cl = (u32)__builtin_clz(xs);                     // xs >= RANGE_FACTOR > 0
+        const u32 y = __builtin_amdgcn_alignbit(xs, lk, 32 - cl);  // (xs << cl) | (lk >> (32 - cl))
+        x = y >> cb;                                               // nb = NUM_STATE_BITS - bit_width(xs) new bits
+        used = cl - cb;
+        return e;
     }
-    r.maybe_refill(lds);
-    return make_uint4(ow[0], ow[1], ow[2], ow[3]);
-}
+    template <typename TfIn>
+    __device__ __forceinline__ u8 symbol(u32 &x, TfIn &r, char *lds) const {
+        u32 used;
+        const u32 e = entry(x, r.look(), used);
+        r.advance(lds, used);
+        return (u8)e;
+    }
+    template <bool REFILL, typename TfIn>
+    __device__ __forceinline__ uint4 block16(u32 &x, TfIn &r, char *lds) const {
+        u32 ow[4];
+#pragma unroll
+        for (int d = 3; d >= 0; --d) {
+            u32 o = 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const u32 lk = r.look();
+                u32 ua, ub;
+                const u32 ea = entry(x, lk, ua);
+                const u32 eb = entry(x, lk << ua, ub);
+                r.advance(lds, ua + ub);  // <= 2*13 bits of the 32-bit lookahead
+                o = __builtin_amdgcn_perm(o, ea, 0x06050400u);  // o = (o << 8) | (ea & 0xFF)
+                o = __builtin_amdgcn_perm(o, eb, 0x06050400u);
+                asm volatile("" : "+v"(o) : : "memory");
+            }
+            ow[d] = o;
+        }
+        r.maybe_refill(lds);
+        return make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    }
+};
 
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) tans_decode_fast_kernel(TansFastDev P, const u8 *__restrict__ in,
@@ -185,63 +193,17 @@ __global__ void __launch_bounds__(THREADS) tans_decode_fast_kernel(TansFastDev P
     const u64 c = (u64)blockIdx.x * THREADS + threadIdx.x;
     if (c >= n_chunks) return;
     const u32 avail = in_nbits[c];
-    u32 st = 0;
-    if (avail < P.size_bits + P.nsb) {
-        out_lens[c] = 0;
-        consumed[c] = P.size_bits + P.nsb;
-        if (status) status[c] = SCL_ST_TRUNCATED;
-        return;
-    }
+    if (ans_decode_refuse(P, avail, c, out_lens, consumed, status)) return;
     TfIn r;
-    r.init(in, in_size_bytes, bit_off[c], lds, threadIdx.x);
-    u32 n = r.get(lds, P.size_bits);
-    u32 x = r.get(lds, P.nsb);
-    out_lens[c] = n;
-    if (x < P.L || x >= 2 * P.L) {  // KeyError on base_decode_step_table in the reference
-        st |= SCL_ST_STATE;
+    u32 n, x, st;
+    ans_decode_open<false>(P, r, lds, in, in_size_bytes, bit_off, c, out_cap, n, x, st, out_lens);
+    if (x < P.L || x >= 2 * P.L) {  // KeyError on base_decode_step_table in the reference: nothing is decoded, and the
+        st = SCL_ST_STATE;          // chunk reports that alone, as tans_decode_kernel does (st was 0 or SCL_ST_CAPACITY)
         n = 0;
     }
-    if (n > out_cap) {
-        st |= SCL_ST_CAPACITY;
-        n = 0;
-    }
-    const u32 st_header = st;
-    const u32 idx_mask = (P.L - 1) << 2, cb = 32 - P.nsb;
-    u8 *dst = out_sym + c * out_stride;
-    u32 i = n;
-    while (i & 15u) {
-        u32 used;
-        const u32 e = tf_decode_symbol(x, r.look(), used, tab, idx_mask, cb);
-        r.advance(lds, used);
-        dst[--i] = (u8)e;
-        if ((i & 3u) == 0) r.maybe_refill(lds);
-    }
-    while (i & 127u) {
-        const uint4 v = tf_decode16(x, r, lds, tab, idx_mask, cb);
-        i -= 16;
-        *reinterpret_cast<uint4 *>(dst + i) = v;
-    }
-    CoopLineStore cs;  // whole waves of equally long chunks store cooperatively (scl_ans_fast_io.h)
-    cs.init(out_sym, c, out_stride, i);
-#pragma nounroll
-    while (i) {  // one full 128-byte line per iteration
-        uint4 a[8];
-#pragma unroll
-        for (int b = 7; b >= 0; --b) a[b] = tf_decode16(x, r, lds, tab, idx_mask, cb);
-        i -= 128;
-        if (cs.on) {
-            cs.store(a, i);
-        } else {
-            uint4 *p = reinterpret_cast<uint4 *>(dst + i);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) p[b] = a[b];
-        }
-    }
-    const u32 used_bits = r.consumed();
-    if (used_bits > avail) st |= SCL_ST_TRUNCATED;
-    else if (st_header == 0 && x != P.L) st |= SCL_ST_STATE;  // assert state == INITIAL_STATE (tANS.py:277)
-    consumed[c] = used_bits;
-    if (status) status[c] = st;
+    const TfDecStep step = {tab, (P.L - 1) << 2, 32 - P.nsb};
+    ans_decode_rows(step, x, r, lds, n, out_sym, c, out_stride);
+    ans_decode_close(r.consumed(), avail, st, x, P.L, c, consumed, status);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -253,11 +215,11 @@ int tans_fast_build_tables(scl_tans_model *m, const u32 *h_freq, const u32 *h_cu
     if (D.L > 8192 || D.K < 1 || D.nsb > 14) return SCL_OK;
     const u32 L = D.L;
     std::vector<u32> enc(L), nbits(D.K), thresh(D.K), dsym(L), dxs(L);
-    hipError_t e = hipMemcpy(enc.data(), m->d_enc, L * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(nbits.data(), m->d_nbits, D.K * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(thresh.data(), m->d_thresh, D.K * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(dsym.data(), m->d_dec_sym, L * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(dxs.data(), m->d_dec_xs, L * 4, hipMemcpyDeviceToHost);
+    SCL_HIP_TRY(hipMemcpy(enc.data(), m->d_enc, L * 4, hipMemcpyDeviceToHost));
+    SCL_HIP_TRY(hipMemcpy(nbits.data(), m->d_nbits, D.K * 4, hipMemcpyDeviceToHost));
+    SCL_HIP_TRY(hipMemcpy(thresh.data(), m->d_thresh, D.K * 4, hipMemcpyDeviceToHost));
+    SCL_HIP_TRY(hipMemcpy(dsym.data(), m->d_dec_sym, L * 4, hipMemcpyDeviceToHost));
+    SCL_HIP_TRY(hipMemcpy(dxs.data(), m->d_dec_xs, L * 4, hipMemcpyDeviceToHost));
     std::vector<uint4> fsym(256);
     std::vector<u16> fenc(L);
     std::vector<u32> fdec(L);
@@ -273,16 +235,11 @@ int tans_fast_build_tables(scl_tans_model *m, const u32 *h_freq, const u32 *h_cu
         fenc[i] = (u16)enc[i];
         fdec[i] = (dxs[i] << 8) | dsym[i];
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_fenc_sym, 256 * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_fenc_tab, L * sizeof(u16));
-    if (e == hipSuccess) e = hipMalloc((void **)&m->d_fdec_tab, L * sizeof(u32));
-    if (e == hipSuccess) e = hipMemcpy(m->d_fenc_sym, fsym.data(), 256 * sizeof(uint4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_fenc_tab, fenc.data(), L * sizeof(u16), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->d_fdec_tab, fdec.data(), L * sizeof(u32), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        scl_set_error("tans_model_create: fast-path table upload failed: %s", hipGetErrorString(e));
-        return SCL_E_HIP;
-    }
+    const char *what = "tans_model_create: fast-path table upload";
+    int rc = scl_upload(&m->d_fenc_sym, fsym.data(), 256, what);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_fenc_tab, fenc.data(), L, what);
+    if (rc == SCL_OK) rc = scl_upload(&m->d_fdec_tab, fdec.data(), L, what);
+    if (rc != SCL_OK) return rc;
     m->fdev.K = D.K;
     m->fdev.L = L;
     m->fdev.nsb = D.nsb;
@@ -295,19 +252,15 @@ int tans_fast_build_tables(scl_tans_model *m, const u32 *h_freq, const u32 *h_cu
 }
 
 void tans_fast_encode_launch(const scl_tans_model *m, const SclEncodeArgs<u8> &a, hipStream_t st) {
-    if (a.n_chunks > 2ull * 256 * TF_THREADS_SMALL)
-        scl_launch_encode(tans_encode_fast_kernel<TF_THREADS>,
-                          {(u32)((a.n_chunks + TF_THREADS - 1) / TF_THREADS), TF_THREADS}, st, m->fdev, a);
+    if (ans_wide_workgroups(a.n_chunks))
+        scl_launch_encode(tans_encode_fast_kernel<ANS_THREADS_WIDE>, ans_grid(a.n_chunks, ANS_THREADS_WIDE), st, m->fdev, a);
     else
-        scl_launch_encode(tans_encode_fast_kernel<TF_THREADS_SMALL>,
-                          {(u32)((a.n_chunks + TF_THREADS_SMALL - 1) / TF_THREADS_SMALL), TF_THREADS_SMALL}, st, m->fdev, a);
+        scl_launch_encode(tans_encode_fast_kernel<ANS_THREADS_SMALL>, ans_grid(a.n_chunks, ANS_THREADS_SMALL), st, m->fdev, a);
 }
 
 void tans_fast_decode_launch(const scl_tans_model *m, const SclDecodeArgs<u8> &a, hipStream_t st) {
-    if (a.n_chunks > 2ull * 256 * TF_THREADS_SMALL)
-        scl_launch_decode(tans_decode_fast_kernel<TF_THREADS>,
-                          {(u32)((a.n_chunks + TF_THREADS - 1) / TF_THREADS), TF_THREADS}, st, m->fdev, a);
+    if (ans_wide_workgroups(a.n_chunks))
+        scl_launch_decode(tans_decode_fast_kernel<ANS_THREADS_WIDE>, ans_grid(a.n_chunks, ANS_THREADS_WIDE), st, m->fdev, a);
     else
-        scl_launch_decode(tans_decode_fast_kernel<TF_THREADS_SMALL>,
-                          {(u32)((a.n_chunks + TF_THREADS_SMALL - 1) / TF_THREADS_SMALL), TF_THREADS_SMALL}, st, m->fdev, a);
+        scl_launch_decode(tans_decode_fast_kernel<ANS_THREADS_SMALL>, ans_grid(a.n_chunks, ANS_THREADS_SMALL), st, m->fdev, a);
 }

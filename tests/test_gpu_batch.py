@@ -1005,10 +1005,80 @@ def test_cooperative_line_store_full_and_partial_waves(name, n, dev):
         assert np.array_equal(np.asarray(o_sym), dec[c, :lens[c]])
 
 
+_T86 = np.array([3, 1, 7, 2, 19, 40, 5, 9], dtype=np.int64)  # total 86 (tests/test_gpu_decoder_fuzz.py): the ML_T < 0 decoder
+# decoder -> (model, table, slot layout, oracle arguments of orc.rans_encode, environment, the decode kernel that must serve it)
+FRAME_DECODERS = {
+    "rans_b1_linear": (lambda f: models.RansModel(f.tolist(), 1 << 16, 1, 32), None, "linear", dict(RF=1 << 16), {},
+                       "rans_decode_fast_kernel<12, 3, 256, 1, false>"),
+    "rans_b1_striped": (lambda f: models.RansModel(f.tolist(), 1 << 16, 1, 32), None, "striped", dict(RF=1 << 16), {},
+                        "rans_decode_fast_kernel<12, 3, 256, 1, true>"),
+    "rans_total86": (lambda f: models.RansModel(f.tolist(), 1 << 16, 1, 32), _T86, "linear", dict(RF=1 << 16), {},
+                     "rans_decode_fast_kernel<-1, 0, 256, 1, false>"),
+    "rans_b8": (lambda f: models.RansModel(f.tolist(), 1 << 8, 8, 32), None, "linear", dict(RF=1 << 8, b=8), {},
+                "rans_decode_fast_kernel<0, 0, 256, 0, false>"),
+    "rans_b2": (lambda f: models.RansModel(f.tolist(), 1 << 8, 2, 32), None, "linear", dict(RF=1 << 8, b=2), {},
+                "rans_decode_fastb_kernel"),
+    "tans_table": (lambda f: models.TansModel(f.tolist(), 1, 32), None, "linear", dict(RF=1), {"SCL_TANS_KERNELS": "table"},
+                   "tans_decode_fast_kernel"),
+}
+
+
+@pytest.mark.parametrize("name", list(FRAME_DECODERS))
+def test_ans_decode_frame(name, dev, monkeypatch):
+    """What stands around the symbol step of every tuned ANS decoder (scl_ans_frame.h: header exit, ragged head, 16-byte
+    blocks, cooperative line loop, status epilogue), on each decoder that uses it.  One launch of 64 x 3 + 19 chunks: a wave
+    of 64 equal chunks of 256 symbols (cooperative store, two lines); a wave whose lengths sit on every loop boundary (not
+    cooperating); a wave of 64 equal chunks of 128 where one lane's stream is too short for its header (the header exit
+    inside a would-be cooperating wave); a partial wave of 19 equal chunks of 256."""
+    make_model, table, layout, o_args, env, kernel = FRAME_DECODERS[name]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    freq = bench_data.t256_table() if table is None else table
+    model = make_model(freq)
+    edges = [0, 1, 15, 16, 17, 112, 127, 128, 129, 143, 144, 255, 256, 257]
+    lens = np.array([256] * 64 + [edges[i % len(edges)] for i in range(64)] + [128] * 64 + [256] * 19, dtype=np.int32)
+    n_chunks, cap, cut = lens.size, 272, 128 + 37
+    assert model.info().fast_path and model.kernel_names(n_chunks, layout)[1].startswith(kernel)
+    sym = bench_data.iid_chunks_host(freq, n_chunks, cap, seed=4242)
+    d_lens = torch.from_numpy(lens).to(dev)
+    enc = model.encode_batch(torch.from_numpy(sym).to(dev), lens=d_lens, layout=layout)
+    avail = enc.nbits.clone()
+    avail[cut] = 10
+    got = []
+    for generic in (False, True):
+        out = model.alloc_decoded(n_chunks, cap, dev)
+        out[0].fill_(0xA5)
+        if generic:
+            res = model.decode_batch(enc.linear_data(), enc.bit_offset, avail, cap, out=out, any_parameter_kernels=True)
+        else:
+            res = model.decode_batch(enc.data, enc.bit_offset, avail, cap, out=out,
+                                     striped_stride=enc.stride if layout == "striped" else None)
+        torch.cuda.synchronize()
+        got.append([t.cpu().numpy() for t in res])
+    dec, dlens, used, status = got[0]
+    nbits = enc.nbits.cpu().numpy()
+    want_lens = lens.copy()
+    want_lens[cut] = 0
+    assert np.array_equal(dlens, want_lens)
+    assert status[cut] == backend_lib.ST_TRUNCATED and not np.delete(status, cut).any() and not enc.status.cpu().numpy().any()
+    assert np.array_equal(np.delete(used, cut), np.delete(nbits, cut))
+    for c in range(n_chunks):
+        assert np.array_equal(dec[c, :want_lens[c]], sym[c, :want_lens[c]]), f"chunk {c}"
+        assert (dec[c, want_lens[c]:] == 0xA5).all(), f"chunk {c}: bytes beyond the chunk were written"
+    for what, a, b in zip(("symbols", "lengths", "consumed bits", "status"), got[0], got[1]):
+        assert np.array_equal(a, b), f"tuned and any-parameter decoders differ in {what}"
+    if layout == "linear":
+        data, offs = enc.data.cpu().numpy(), enc.bit_offset.cpu().numpy()
+        for c in (0, 63, 64, 65, 70, 77, 127, 128, cut, 191, 192, n_chunks - 1):
+            rb, rn = orc.rans_encode(sym[c, :lens[c]], freq, **o_args)
+            assert int(nbits[c]) == rn and np.array_equal(_stream_bits(data, offs[c], rn), np.unpackbits(rb)[:rn]), f"chunk {c}"
+
+
 @pytest.mark.parametrize("seed", range(int(os.environ.get("SCL_RANDOM_SEEDS", 16))))
 def test_random_models_num_bits_out_vs_oracle(seed, dev):
-    """NUM_BITS_OUT in {2, 4, 8, 16} (the reference's own sweep uses 8, rANS.py:366-379) on the tuned kernels of
-    scl_rans_fast_b.hip: random power-of-two tables, RANGE_FACTOR as large as H < 2^31 and RF 2^b <= 2^24 allow (or
+    """NUM_BITS_OUT in {2, 4, 8, 16} (the reference's own sweep uses 8, rANS.py:366-379) on the tuned kernels -- b = 2, and
+    what scl_rans_fast.hip excludes, on scl_rans_fast_b.hip; b in {4, 8, 16} within their bounds on scl_rans_fast.hip:
+    random power-of-two tables, RANGE_FACTOR as large as H < 2^31 and RF 2^b <= 2^24 allow (or
     small), ragged chunks, symbols from the table and from a uniform distribution; streams equal to the oracle's,
     decode equal to the input with the exact bit count -- and the same through the any-parameter kernels."""
     rng = np.random.default_rng(31000 + seed)

@@ -9,7 +9,10 @@ Every library's first round trip is verified against the input.  Printed per cas
 the per-round means, the spread (max - min over the rounds), and per round the result-against-first-library differences.
 
 Cases: the headline batch (rANS, t256, 262 144 x 4096, striped), the same on tANS, configs[1] (65 536 chunks, linear slots),
-configs[2] (range coder, uniform bytes, striped), and the headline on linear slots."""
+configs[2] (range coder, uniform bytes, striped), the headline on linear slots; and, on linear slots, what else runs on the
+frame of scl_ans_frame.h: rANS NUM_BITS_OUT = 8 (b8) and = 2 (b2, scl_rans_fast_b.hip), the tANS table kernels (tanstab:
+SCL_TANS_KERNELS=table for the case), rANS on a table of total 86 (t86) -- each also as a 65 536-chunk batch (*_64k), which
+runs the 256-lane forms."""
 import argparse
 import os
 import sys
@@ -52,6 +55,13 @@ CASES = {
                  "striped"),
     "linear": ("rANS t256 262144 x 4096 linear", lambda: models.RansModel(t256.tolist(), 1 << 16, 1, 32), t256, 262144, "linear"),
 }
+t86 = np.array([3, 1, 7, 2, 19, 40, 5, 9], dtype=np.int64)
+for tag, n in (("", 262144), ("_64k", 65536)):
+    CASES["b8" + tag] = (f"rANS b=8 RF=2^8 t256 {n} x 4096 linear", lambda: models.RansModel(t256.tolist(), 1 << 8, 8, 32), t256, n, "linear")
+    CASES["b2" + tag] = (f"rANS b=2 RF=2^8 t256 {n} x 4096 linear", lambda: models.RansModel(t256.tolist(), 1 << 8, 2, 32), t256, n, "linear")
+    CASES["tanstab" + tag] = (f"tANS table kernels RF=1 t256 {n} x 4096 linear", lambda: models.TansModel(t256.tolist(), 1, 32), t256, n, "linear",
+                              {"SCL_TANS_KERNELS": "table"})
+    CASES["t86" + tag] = (f"rANS total 86 {n} x 4096 linear", lambda: models.RansModel(t86.tolist(), 1 << 16, 1, 32), t86, n, "linear")
 chunk_len = 4096
 
 
@@ -77,7 +87,9 @@ def time_case(model, sym, enc, dec, reps):
 
 
 for key in args.cases.split(","):
-    title, make, freq, n_chunks, layout = CASES[key]
+    title, make, freq, n_chunks, layout = CASES[key][:5]
+    env = CASES[key][5] if len(CASES[key]) > 5 else {}
+    os.environ.update(env)  # read by the library at every call
     ms = [with_lib(i, make) for i in range(len(handles))]
     sym = bench_data.iid_chunks_device(freq, n_chunks, chunk_len, seed=1, device=dev)
     enc = ms[0].alloc_encoded(n_chunks, chunk_len, dev, layout=layout)
@@ -99,12 +111,15 @@ for key in args.cases.split(","):
     res = np.array(res)  # [lib][round][enc, dec, rt, dec behind dec]
     names = ("encode", "decode", "round trip", "decode behind decode")
     for i, p in enumerate(args.libs):
-        med, spread = np.median(res[i], axis=0), res[i].max(axis=0) - res[i].min(axis=0)
-        print(f"  {os.path.basename(p):28s} " + "  ".join(f"{n} {m:.4f} (spread {s:.4f})" for n, m, s in zip(names, med, spread)) + " ms")
+        med, lo, hi = np.median(res[i], axis=0), res[i].min(axis=0), res[i].max(axis=0)
+        print(f"  {os.path.basename(p):28s} " + "  ".join(f"{n} {m:.4f} ({a:.4f} .. {b:.4f}, spread {b - a:.4f})"
+                                                            for n, m, a, b in zip(names, med, lo, hi)) + " ms")
     for i in range(1, len(ms)):
         d = res[i] - res[0]
         for k, n in enumerate(names):
             print(f"  {os.path.basename(args.libs[i])} - {os.path.basename(args.libs[0])}, {n}, per round: "
                   + " ".join(f"{x:+.4f}" for x in d[:, k]) + f"   median {np.median(d[:, k]):+.4f} ms ({100 * np.median(d[:, k]) / np.median(res[0][:, k]):+.2f} %)")
+    for k in env:
+        del os.environ[k]
     del sym, enc, dec, ms
     torch.cuda.empty_cache()
