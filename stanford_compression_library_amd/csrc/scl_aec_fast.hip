@@ -31,11 +31,9 @@
 //    straight to the slot (4-byte stores, L2 merges them); symbols arrive four per 32-bit load, one word ahead,
 //    the load unconditional so that it is not waited for at once.
 #include <stdlib.h>
-#include <type_traits>
 
 #include "scl_aec_internal.h"
-#include "scl_aec_math.h"
-#include "scl_aec_lane_io.h"
+#include "scl_aec_frame.h"
 
 #define AF_THREADS 256
 #define AF_CTX_BYTES (AF_THREADS * 32)      // one 32-byte row of every thread
@@ -46,55 +44,70 @@
 #define AF_LUT_BYTES 512
 #define AF_LDS_BYTES (AF_LUT_BASE + AF_LUT_BYTES)
 
-struct AfRow {
-    uint4 a, b;
-};
-
 // LDS image of one workgroup: rows (exclusive cumulative counts, 32 bytes per context and thread), row totals,
 // and the update masks LUT[s][j] = (j > s)
 __device__ __forceinline__ void af_setup_tables(char *lds, const AecFastDev &P, u32 tid) {
-    if (tid < 128) {
-        const u32 s = tid >> 3, r = tid & 7;  // register r holds elements 2r, 2r+1
-        const u32 v = ((2 * r > s) ? 1u : 0u) | ((2 * r + 1 > s) ? 0x10000u : 0u);
-        *reinterpret_cast<u32_lds *>(lds + AF_LUT_BASE + s * 32 + r * 4) = v;
-    }
-    const uint4 a = make_uint4(P.initX[0], P.initX[1], P.initX[2], P.initX[3]);
-    const uint4 b = make_uint4(P.initX[4], P.initX[5], P.initX[6], P.initX[7]);
+    af_fill_mask_rows(lds + AF_LUT_BASE, tid, [](u32 j, u32 s) { return j > s; });
+    const AfRow init = {make_uint4(P.initX[0], P.initX[1], P.initX[2], P.initX[3]),
+                        make_uint4(P.initX[4], P.initX[5], P.initX[6], P.initX[7])};
     for (u32 c = 0; c < P.nctx; ++c) {
-        *reinterpret_cast<uint4_lds *>(lds + c * AF_CTX_BYTES + tid * 32) = a;
-        *reinterpret_cast<uint4_lds *>(lds + c * AF_CTX_BYTES + tid * 32 + 16) = b;
+        af_row_store(lds, c * AF_CTX_BYTES + tid * 32, init);
         *reinterpret_cast<u32_lds *>(lds + AF_TOT_BASE + c * (AF_THREADS * 4) + tid * 4) = P.total0;
     }
     __syncthreads();
 }
 
-__device__ __forceinline__ AfRow af_row_load(const char *lds, u32 rowbase) {
-    AfRow R;
-    R.a = *reinterpret_cast<const uint4_lds *>(lds + rowbase);
-    R.b = *reinterpret_cast<const uint4_lds *>(lds + rowbase + 16);
-    return R;
-}
-// update_model with the mask row already loaded
-__device__ __forceinline__ void af_row_store_updated(const AfRow &R, const uint4 &ia, const uint4 &ib, char *lds,
-                                                     u32 rowbase, u32 totaddr) {
-    *reinterpret_cast<uint4_lds *>(lds + rowbase) =
-        make_uint4(af_pk_add(R.a.x, ia.x), af_pk_add(R.a.y, ia.y), af_pk_add(R.a.z, ia.z), af_pk_add(R.a.w, ia.w));
-    *reinterpret_cast<uint4_lds *>(lds + rowbase + 16) =
-        make_uint4(af_pk_add(R.b.x, ib.x), af_pk_add(R.b.y, ib.y), af_pk_add(R.b.z, ib.z), af_pk_add(R.b.w, ib.w));
-    __hip_atomic_fetch_add(reinterpret_cast<u32 *>(lds + totaddr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// update_model: count[s] += 1  <=>  X[j] += 1 for j > s, total += 1
-__device__ __forceinline__ AfRow af_row_update(const AfRow &R, char *lds, u32 rowbase, u32 totaddr, u32 s) {
-    const uint4 ia = *reinterpret_cast<const uint4_lds *>(lds + AF_LUT_BASE + s * 32);
-    const uint4 ib = *reinterpret_cast<const uint4_lds *>(lds + AF_LUT_BASE + s * 32 + 16);
-    AfRow o;
-    o.a = make_uint4(af_pk_add(R.a.x, ia.x), af_pk_add(R.a.y, ia.y), af_pk_add(R.a.z, ia.z), af_pk_add(R.a.w, ia.w));
-    o.b = make_uint4(af_pk_add(R.b.x, ib.x), af_pk_add(R.b.y, ib.y), af_pk_add(R.b.z, ib.z), af_pk_add(R.b.w, ib.w));
-    *reinterpret_cast<uint4_lds *>(lds + rowbase) = o.a;
-    *reinterpret_cast<uint4_lds *>(lds + rowbase + 16) = o.b;
-    __hip_atomic_fetch_add(reinterpret_cast<u32 *>(lds + totaddr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return o;
-}
+// The encoder's model stage (af_lane_encode), split in two so that the arithmetic of the previous symbol runs while the
+// LDS reads are in flight: issue = freqs_current lookup for symbol s (loads only), finish = update_model (:118) and 1/T.
+// Everything the arithmetic of a symbol needs (c, d, T, 1/T) is ready one iteration ahead.
+template <bool ORDER1>
+struct AfEncModel {
+    const AecFastDev &P;
+    char *lds;
+    u32 tid;
+    u32 ctx = 0;
+    u32 c_nx = 0, d_nx = 1, T_nx = 1;
+    double x_nx = 1.0;
+    u32 m_rowbase = 0, m_totaddr = 0, m_s = 0, m_draw = 0;
+    AfRow m_R, m_M;
+    __device__ __forceinline__ AfEncModel(const AecFastDev &P_, char *lds_, u32 tid_) : P(P_), lds(lds_), tid(tid_) {}
+    __device__ __forceinline__ void issue(u32 s) {
+        m_rowbase = ctx * AF_CTX_BYTES + tid * 32;
+        m_totaddr = AF_TOT_BASE + ctx * (AF_THREADS * 4) + tid * 4;
+        m_s = s;
+        const u32 ea = m_rowbase + 2 * s;
+        c_nx = *reinterpret_cast<const u16_lds *>(lds + ea);
+        m_draw = *reinterpret_cast<const u16_lds *>(lds + ea + 2);
+        T_nx = *reinterpret_cast<const u32_lds *>(lds + m_totaddr);
+        m_R = af_row_load(lds, m_rowbase);
+        m_M = af_row_load(lds, AF_LUT_BASE + s * 32);
+        ctx = af_next_ctx<ORDER1>(P, ctx, s);
+    }
+    __device__ __forceinline__ void finish() {
+        // update_model: count[s] += 1  <=>  X[j] += 1 for j > s, total += 1
+        af_row_store(lds, m_rowbase, af_row_add(m_R, m_M));
+        __hip_atomic_fetch_add(reinterpret_cast<u32 *>(lds + m_totaddr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        d_nx = (m_s == 15) ? T_nx : m_draw;
+        x_nx = af_recip((double)T_nx);
+    }
+    // arithmetic stage: shrink_range (:58-78) and the renormalisation loops (:126-150) of one symbol, in the first forms
+    // (af_shrink, af_renorm_counts): this kernel is the second implementation the tests compare the split encoder against
+    template <class Emit>
+    __device__ __forceinline__ void code(AfWriter &wr, u32 &low, u32 &hm, u32 &pending, u32 cc, u32 dd, u32 TT, double xx,
+                                         Emit emit) {
+        af_shrink(low, hm, cc, dd, TT, xx);
+        u32 k, m;
+        const bool edge = af_renorm_counts(low, hm, k, m);
+        if (__builtin_expect(edge || (k + pending > 32), 0)) {
+            af_renorm_literal_enc(low, hm, pending, emit);
+        } else {
+            af_put_common(wr, low, k, m, pending);
+            const u32 kt = k + m;  // <= 31
+            low = (low << kt) & 0x7FFFFFFFu;
+            hm = (hm << kt) | ((1u << kt) - 1u) | AF_HALF;
+        }
+    }
+};
 
 template <bool ORDER1>
 __global__ void __launch_bounds__(AF_THREADS)
@@ -106,105 +119,11 @@ __global__ void __launch_bounds__(AF_THREADS)
     af_setup_tables(lds, P, tid);
     const u64 chunk = (u64)blockIdx.x * AF_THREADS + tid;
     if (chunk >= n_chunks) return;
-    const u32 n = lens ? lens[chunk] : chunk_len;
-    const u32 *src = reinterpret_cast<const u32 *>(sym + chunk * sym_stride);
     AfWriter wr;
     wr.init(out + chunk * out_stride);
-    wr.put(af_header_value(n, P.size_bits), P.size_bits);  // :92-99
-    u32 st = af_header_status(n, P.size_bits);
-    u32 low = 0, hm = 0xFFFFFFFFu;
-    u32 pending = 0;  // E3 steps not yet resolved (<= 32 * n < 2^20)
-    u32 ctx = 0;
-    u32 nextw = 0;
-    const u32 last_word = n ? (n - 1) >> 2 : 0;
-    u32 c_nx = 0, d_nx = 1, T_nx = 1;
-    double x_nx = 1.0;
-
-    // model stage, split in two so that the arithmetic of the previous symbol runs while the LDS reads are in
-    // flight: model_issue = freqs_current lookup for symbol s (loads only), model_finish = update_model (:118)
-    // and 1/T.  Everything the arithmetic of a symbol needs (c, d, T, 1/T) is ready one iteration ahead.
-    u32 m_rowbase = 0, m_totaddr = 0, m_s = 0, m_draw = 0;
-    AfRow m_R;
-    uint4 m_ia, m_ib;
-    auto model_issue = [&](u32 s) {
-        m_rowbase = ctx * AF_CTX_BYTES + tid * 32;
-        m_totaddr = AF_TOT_BASE + ctx * (AF_THREADS * 4) + tid * 4;
-        m_s = s;
-        const u32 ea = m_rowbase + 2 * s;
-        c_nx = *reinterpret_cast<const u16_lds *>(lds + ea);
-        m_draw = *reinterpret_cast<const u16_lds *>(lds + ea + 2);
-        T_nx = *reinterpret_cast<const u32_lds *>(lds + m_totaddr);
-        m_R = af_row_load(lds, m_rowbase);
-        m_ia = *reinterpret_cast<const uint4_lds *>(lds + AF_LUT_BASE + s * 32);
-        m_ib = *reinterpret_cast<const uint4_lds *>(lds + AF_LUT_BASE + s * 32 + 16);
-        ctx = af_next_ctx<ORDER1>(P, ctx, s);
-    };
-    auto model_finish = [&]() {
-        af_row_store_updated(m_R, m_ia, m_ib, lds, m_rowbase, m_totaddr);
-        d_nx = (m_s == 15) ? T_nx : m_draw;
-        x_nx = af_recip((double)T_nx);
-    };
-    // one step of the literal loops, and the termination: `bit`, then `pending` copies of its inverse
-    auto emit = [&](u32 bit) {
-        wr.put(bit, 1);
-        wr.put_run(bit ^ 1u, pending);
-    };
-    // arithmetic stage: shrink_range (:58-78) and the renormalisation loops (:126-150) of one symbol
-    auto code = [&](u32 cc, u32 dd, u32 TT, double xx) {
-        af_shrink(low, hm, cc, dd, TT, xx);
-        u32 k, m;
-        const bool edge = af_renorm_counts(low, hm, k, m);
-        if (__builtin_expect(edge || (k + pending > 32), 0)) {
-            af_renorm_literal_enc(low, hm, pending, emit);
-        } else {
-            if (k > 0) {
-                // b0, then `pending` copies of !b0, then the other k-1 common bits
-                const u32 top = low >> (32 - k);
-                const u32 b0 = top >> (k - 1);
-                const u32 rest = top & ((1u << (k - 1)) - 1u);
-                const u32 pat = (1u << pending) - (b0 ^ 1u);  // pending <= 31 here
-                wr.put((pat << (k - 1)) | rest, k + pending);
-                pending = 0;
-            }
-            pending += m;
-            const u32 kt = k + m;  // <= 31
-            low = (low << kt) & 0x7FFFFFFFu;
-            hm = (hm << kt) | ((1u << kt) - 1u) | AF_HALF;
-        }
-    };
-
-    // Before the first symbol (c, d, T, 1/T) = (0, 1, 1, 1.0) makes the arithmetic stage a no-op (d == T keeps
-    // high, low += 0, nothing to renormalise), so every symbol runs the same body and one more `code` drains it.
-    const u32 n_words = (n + 3) >> 2;
-    if (n > 0) nextw = src[0];
-    for (u32 w = 0; w < n_words; ++w) {
-        // four symbols per 32-bit load, one word ahead.  The load is unconditional with its index clamped into
-        // the chunk and sits where nothing has to be merged with it: a load under a lane-dependent or periodic
-        // condition is copied into the loop-carried register at once, i.e. waited for at once (~1 us each).
-        u32 word = nextw;
-        nextw = src[min(w + 1, last_word)];
-        const u32 cnt = min(4u, n - 4 * w);
-#pragma unroll 1
-        for (u32 j = 0; j < cnt; ++j) {
-            u32 s = word & 0xFFu;
-            word >>= 8;
-            if (s >= P.K) {
-                st |= SCL_ST_SYMBOL;
-                s = 0;
-            }
-            const u32 cc = c_nx, dd = d_nx, TT = T_nx;
-            const double xx = x_nx;
-            model_issue(s);        // this symbol: LDS reads in flight ...
-            code(cc, dd, TT, xx);  // ... while the previous symbol is coded
-            model_finish();
-        }
-    }
-    code(c_nx, d_nx, T_nx, x_nx);
-    af_terminate(low, pending, emit);  // :153-159
-    const u64 total = wr.finish();
-    out_bit_off[chunk] = chunk * out_stride * 8;
-    out_nbits[chunk] = (u32)total;
-    if (status) status[chunk] = st;
+    AfEncModel<ORDER1> mdl(P, lds, tid);
+    const AfEncoded e = af_lane_encode(mdl, wr, P.K, P.size_bits, sym, sym_stride, lens, chunk_len, chunk);
+    af_encode_results(e.total, e.st, chunk, out_stride, out_bit_off, out_nbits, status);
 }
 
 // ---- decoder (round 4) ---------------------------------------------------------------------------------------------
@@ -229,44 +148,23 @@ __device__ __forceinline__ void ad_setup_tables(char *lds, const AecFastDev &P, 
         const u32 hi = (r < 7) ? (P.initX[r + 1] & 0xFFFFu) : P.total0;    // X[2r + 2]
         y[r] = lo | (hi << 16);
     }
-    const uint4 a = make_uint4(y[0], y[1], y[2], y[3]);
-    const uint4 b = make_uint4(y[4], y[5], y[6], y[7]);
-    for (u32 c = 0; c < P.nctx; ++c) {
-        *reinterpret_cast<uint4_lds *>(lds + AD_ROW_BASE + c * AF_CTX_BYTES + tid * 32) = a;
-        *reinterpret_cast<uint4_lds *>(lds + AD_ROW_BASE + c * AF_CTX_BYTES + tid * 32 + 16) = b;
-    }
+    const AfRow init = {make_uint4(y[0], y[1], y[2], y[3]), make_uint4(y[4], y[5], y[6], y[7])};
+    for (u32 c = 0; c < P.nctx; ++c) af_row_store(lds, AD_ROW_BASE + c * AF_CTX_BYTES + tid * 32, init);
     __syncthreads();
 }
 
+// One symbol of the decoder (af_lane_decode): decode_step_core (:177-201) and update_model.
 template <bool ORDER1>
-__global__ void __launch_bounds__(AF_THREADS)
-    aec_fast_decode_kernel(AecFastDev P, const u8 *__restrict__ in, u64 in_size_bytes,
-                           const u64 *__restrict__ bit_off, const u32 *__restrict__ in_nbits, u64 n_chunks,
-                           u8 *__restrict__ out_sym, u64 out_stride, u32 out_cap, u32 *__restrict__ out_lens,
-                           u32 *__restrict__ consumed, u32 *__restrict__ status) {
-    __shared__ __attribute__((aligned(16))) char lds[AD_LDS_BYTES];
-    const u32 tid = threadIdx.x;
-    ad_setup_tables(lds, P, tid);
-    const u64 chunk = (u64)blockIdx.x * AF_THREADS + tid;
-    if (chunk >= n_chunks) return;
-    const u32 nbits = in_nbits[chunk];
-    AfReader rd;
-    rd.init(in, in_size_bytes, bit_off[chunk], nbits);
-    u32 st;
-    const u32 n = af_decode_length(rd.get(P.size_bits), st, nbits, P.size_bits, out_cap, chunk, out_lens, consumed, status);
-    if (n == 0) return;
-    AfSymOut so;
-    so.init(lds + AD_OUT_BASE, tid, out_sym + chunk * out_stride);
-    u32 state = rd.get(32);
-    u32 low = 0, hm = 0xFFFFFFFFu;
+struct AdStep {
+    const AecFastDev &P;
+    char *lds;
+    u32 lane_m2;  // two bytes before the lane's row of context 0
+    u32 row_m2;   // the same for the current context: carried from symbol to symbol
     u32 ctx = 0;
-    AfRow R = af_row_load(lds, AD_ROW_BASE + tid * 32);
-    const u32 lane_m2 = AD_ROW_BASE + tid * 32 - 2;  // two bytes before the lane's row of context 0
-    u32 row_m2 = lane_m2;                            // the same for the current context: carried from symbol to symbol
-    // One symbol: decode_step_core (:177-201), update_model, symbol out.  The loop runs it for all but the last symbol of the
-    // chunk, the last one follows the loop without a renormalisation (the reference breaks before it, :242-243): a single
-    // exit test per iteration.
-    auto step = [&](u32 i) {
+    AfRow R;
+    __device__ __forceinline__ AdStep(const AecFastDev &P_, char *lds_, u32 tid)
+        : P(P_), lds(lds_), lane_m2(AD_ROW_BASE + tid * 32 - 2), row_m2(lane_m2), R(af_row_load(lds_, AD_ROW_BASE + tid * 32)) {}
+    __device__ __forceinline__ u32 operator()(u32 &low, u32 &hm, u32 state) {
         // T = Y[15] < 2^15, as float (one SDWA conversion out of the packed pair) and as double (from the float): both exact
         float Tf;
         asm("v_cvt_f32_u32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(Tf) : "v"(R.b.w));
@@ -278,9 +176,8 @@ __global__ void __launch_bounds__(AF_THREADS)
         const u32 tgt = (u32)(num * xr);
         // s = #{j : Y[j] <= target}; Y[15] = T > target, so s <= 15, and entries past the alphabet hold T as well, so
         // s <= K - 1
-        const u32 Y[8] = {R.a.x, R.a.y, R.a.z, R.a.w, R.b.x, R.b.y, R.b.z, R.b.w};
-        u32 msk[8];
-        const u32 s = min(af_pk_search16(Y, tgt, msk), P.K - 1);
+        AfRow M;
+        const u32 s = min(af_row_search(R, tgt, M), P.K - 1);
         // c = Y[s - 1], d = Y[s]: two u16 reads, issued before the row is rewritten; s = 0 reads the two bytes in front of
         // the row, masked away below.  All addresses of the step hang off "row - 2": one add fewer than with "row" and "- 2".
         const u32 ea_m2 = row_m2 + 2 * s;
@@ -289,10 +186,7 @@ __global__ void __launch_bounds__(AF_THREADS)
         asm("" : "+v"(ea_d));  // hides that the two reads are adjacent (the compiler would merge them into one unaligned read)
         u32 d_raw = *reinterpret_cast<const u16_lds *>(lds + ea_d + 2);
         // update_model: Y[j] += 1 for j >= s, i.e. minus the search's masks
-        *reinterpret_cast<uint4_lds *>(lds + row_m2 + 2) =
-            make_uint4(af_pk_sub(Y[0], msk[0]), af_pk_sub(Y[1], msk[1]), af_pk_sub(Y[2], msk[2]), af_pk_sub(Y[3], msk[3]));
-        *reinterpret_cast<uint4_lds *>(lds + row_m2 + 18) =
-            make_uint4(af_pk_sub(Y[4], msk[4]), af_pk_sub(Y[5], msk[5]), af_pk_sub(Y[6], msk[6]), af_pk_sub(Y[7], msk[7]));
+        af_row_store(lds, row_m2 + 2, af_row_sub(R, M));
         ctx = af_next_ctx<ORDER1>(P, ctx, s);
         // next symbol's row: issued now, needed only after the arithmetic below
         asm("v_lshl_add_u32 %0, %1, 13, %2" : "=v"(row_m2) : "v"(ctx), "v"(lane_m2));  // ctx * AF_CTX_BYTES + lane_m2, one op
@@ -303,69 +197,26 @@ __global__ void __launch_bounds__(AF_THREADS)
         double xT = af_recip_fd(T2, Td);
         asm volatile("" : "+v"(xT));
         asm volatile("" : "+v"(c_raw), "+v"(d_raw));
-        const u32 c = c_raw & ~msk[0];
+        const u32 c = c_raw & ~M.a.x;
         af_shrink2_d(low, hm, (double)c, (double)d_raw, xT);
-        so.put(s, i);  // four to a word, sixteen words to a 64-byte sector (AfSymOut)
-    };
-    // ---- renormalisation, :245-275; UNCHECKED selects the reader's refill (AfReader::next_word) ----
-    auto renorm = [&](auto unchecked) {
-        constexpr bool UC = decltype(unchecked)::value;
-        u32 k, m, nlow, nhm;
-        const bool edge = af_renorm2_dec(low, hm, k, m, nlow, nhm);
-        if (__builtin_expect(edge, 0)) {
-            af_renorm_literal_dec(low, hm, state, [&] { return rd.get<UC>(1); });
-        } else {
-            const u32 kt = k + m;  // <= 31
-            state = af_state_shift_in<UC>(rd, state, k, kt);
-            low = nlow;
-            hm = nhm;
-        }
-    };
-    // The symbol index i is the same for every lane still at work (they start together and only drop out), so it lives in a
-    // scalar register.  Stretches: as many symbols as EVERY working lane can decode without reaching the last word of its
-    // stream (and has left to decode) run with the unchecked refill and a scalar trip count; the last symbols of the chunks
-    // -- and everything, in a wave that holds a very short stream -- run in the checked loop below.
-    u32 i = 0;
-    for (;;) {
-        const bool at_work = i + 1 < n;
-        const u32 mine = at_work ? min(rd.safe_symbols(), n - 1 - i) : 0xFFFFFFFFu;
-        const u32 cnt = __builtin_amdgcn_readfirstlane(af_wave_min(mine));
-        if (cnt == 0xFFFFFFFFu || cnt < 16) break;
-        if (at_work) {
-            const u32 *before = rd.ptr;
-            // four symbols per trip once the index is a multiple of four: which byte of the output word a symbol fills, and
-            // when the word is complete, are then known at compile time (AfSymOut::put: no scalar compare-and-branch per
-            // symbol), and the trip count is tested once per four
-            u32 u = 0;
-            for (; u < cnt && ((i + u) & 3u); ++u) {
-                step(i + u);
-                renorm(std::true_type{});
-            }
-            for (; u + 4 <= cnt; u += 4) {
-                const u32 base = i + u;
-                __builtin_assume((base & 3u) == 0);
-#pragma unroll
-                for (u32 q = 0; q < 4; ++q) {
-                    step(base + q);
-                    renorm(std::true_type{});
-                }
-            }
-            for (; u < cnt; ++u) {
-                step(i + u);
-                renorm(std::true_type{});
-            }
-            rd.settle(before);
-        }
-        i += cnt;
+        return s;
     }
-    for (; i + 1 < n; ++i) {
-        step(i);
-        renorm(std::false_type{});
-    }
-    step(n - 1);
-    so.finish(n);
-    consumed[chunk] = af_consumed_bits(low, hm, state, rd.position());  // :277-282
-    if (status) status[chunk] = st;
+};
+
+template <bool ORDER1>
+__global__ void __launch_bounds__(AF_THREADS)
+    aec_fast_decode_kernel(AecFastDev P, const u8 *__restrict__ in, u64 in_size_bytes,
+                           const u64 *__restrict__ bit_off, const u32 *__restrict__ in_nbits, u64 n_chunks,
+                           u8 *__restrict__ out_sym, u64 out_stride, u32 out_cap, u32 *__restrict__ out_lens,
+                           u32 *__restrict__ consumed, u32 *__restrict__ status) {
+    __shared__ __attribute__((aligned(16))) char lds[AD_LDS_BYTES];
+    ad_setup_tables(lds, P, threadIdx.x);
+    AfLaneDec f;
+    if (af_lane_dec_done<AF_THREADS>(f, P.size_bits, in, in_size_bytes, bit_off, in_nbits, n_chunks, out_cap, out_lens, consumed,
+                                     status))
+        return;
+    AdStep<ORDER1> step(P, lds, threadIdx.x);
+    af_lane_decode(step, f, lds + AD_OUT_BASE, out_sym + f.chunk * out_stride, consumed, status);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------
@@ -387,17 +238,9 @@ void aec_fast_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, 
         aec_split_encode_launch(m, a, st);
         return;
     }
-    const SclGrid g = {(u32)((a.n_chunks + AF_THREADS - 1) / AF_THREADS), AF_THREADS};
-    if (m->dev.k == 1)
-        scl_launch_encode(aec_fast_encode_kernel<true>, g, st, aec_fast_dev(m), a);
-    else
-        scl_launch_encode(aec_fast_encode_kernel<false>, g, st, aec_fast_dev(m), a);
+    AEC_LAUNCH_ORDER1(m, scl_launch_encode, aec_fast_encode_kernel, aec_grid(a.n_chunks, AF_THREADS), st, aec_fast_dev(m), a);
 }
 
 void aec_fast_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *) {
-    const SclGrid g = {(u32)((a.n_chunks + AF_THREADS - 1) / AF_THREADS), AF_THREADS};
-    if (m->dev.k == 1)
-        scl_launch_decode(aec_fast_decode_kernel<true>, g, st, aec_fast_dev(m), a);
-    else
-        scl_launch_decode(aec_fast_decode_kernel<false>, g, st, aec_fast_dev(m), a);
+    AEC_LAUNCH_ORDER1(m, scl_launch_decode, aec_fast_decode_kernel, aec_grid(a.n_chunks, AF_THREADS), st, aec_fast_dev(m), a);
 }

@@ -54,6 +54,17 @@ void aec_iid_build_init(const u32 *h_freq, u32 K, u32 *out136);
 void aec_iid_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
 void aec_iid_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch);
 
+// ---- launch shapes of the tuned families ------------------------------------------------------------------------------
+// one lane per chunk, workgroups of `threads` lanes; the split encoder: `per_group` chunks to a workgroup of `threads`
+static inline SclGrid aec_grid(u64 n_chunks, u32 threads) { return {(u32)((n_chunks + threads - 1) / threads), threads}; }
+static inline SclGrid aec_grid_groups(u64 n_chunks, u32 per_group, u32 threads) { return {aec_grid(n_chunks, per_group).blocks, threads}; }
+// kernels templated on ORDER1 (the context of an order-1 model is the previous symbol: no multiply, no modulo)
+#define AEC_LAUNCH_ORDER1(m, LAUNCH, KERNEL, ...)                   \
+    do {                                                            \
+        if ((m)->dev.k == 1) LAUNCH(KERNEL<true>, __VA_ARGS__);     \
+        else LAUNCH(KERNEL<false>, __VA_ARGS__);                    \
+    } while (0)
+
 // ---- small-alphabet adaptive models (aec_fast_ok): what scl_aec_fast.hip's and scl_aec_split.hip's kernels take ----------
 struct AecFastDev {
     u32 K;          // alphabet size 2..16

@@ -1,5 +1,5 @@
-// scl_aec_lane_io.h -- per-lane stream I/O and packed-u16 helpers of the arithmetic-coder kernels that keep a
-// private model per lane in LDS (scl_aec_fast.hip: order-k rows, scl_aec_iid.hip: two-level i.i.d. table).
+// scl_aec_lane_io.h -- per-lane stream I/O, packed-u16 helpers, rows and mask rows of the arithmetic-coder kernels that keep
+// a private model per lane in LDS (scl_aec_fast.hip: order-k rows, scl_aec_iid.hip: two-level i.i.d. table).
 // These kernels run one wave per SIMD (LDS-bound occupancy), so few lines are open per CU and plain 4-byte
 // accesses are merged by L2; the high-occupancy kernels use the line-granular I/O of scl_ans_fast_io.h instead.
 // Internal to csrc/.
@@ -44,6 +44,54 @@ __device__ __forceinline__ u32 af_pk_search16(const u32 (&e)[8], u32 t, u32 (&m)
 }
 __device__ __forceinline__ u32 af_pk_sub(u32 a, u32 b) {
     return __builtin_bit_cast(u32, (u16x2)(__builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)));
+}
+
+// ---- one row of 16 packed u16 counts (32 bytes of LDS) in eight registers, and the rows of update masks -----------------
+struct AfRow {
+    uint4 a, b;
+};
+__device__ __forceinline__ AfRow af_row_load(const char *lds, u32 rowbase) {
+    AfRow R;
+    R.a = *reinterpret_cast<const uint4_lds *>(lds + rowbase);
+    R.b = *reinterpret_cast<const uint4_lds *>(lds + rowbase + 16);
+    return R;
+}
+__device__ __forceinline__ void af_row_store(char *lds, u32 rowbase, const AfRow &R) {
+    *reinterpret_cast<uint4_lds *>(lds + rowbase) = R.a;
+    *reinterpret_cast<uint4_lds *>(lds + rowbase + 16) = R.b;
+}
+// update_model on a row: count[s] += 1 is "+ mask row" for the encoders (masks of ones from the LUT below), "- mask row"
+// for the decoders (the search's masks of 0xFFFF)
+__device__ __forceinline__ AfRow af_row_add(const AfRow &R, const AfRow &M) {
+    AfRow o;
+    o.a = make_uint4(af_pk_add(R.a.x, M.a.x), af_pk_add(R.a.y, M.a.y), af_pk_add(R.a.z, M.a.z), af_pk_add(R.a.w, M.a.w));
+    o.b = make_uint4(af_pk_add(R.b.x, M.b.x), af_pk_add(R.b.y, M.b.y), af_pk_add(R.b.z, M.b.z), af_pk_add(R.b.w, M.b.w));
+    return o;
+}
+__device__ __forceinline__ AfRow af_row_sub(const AfRow &R, const AfRow &M) {
+    AfRow o;
+    o.a = make_uint4(af_pk_sub(R.a.x, M.a.x), af_pk_sub(R.a.y, M.a.y), af_pk_sub(R.a.z, M.a.z), af_pk_sub(R.a.w, M.a.w));
+    o.b = make_uint4(af_pk_sub(R.b.x, M.b.x), af_pk_sub(R.b.y, M.b.y), af_pk_sub(R.b.z, M.b.z), af_pk_sub(R.b.w, M.b.w));
+    return o;
+}
+// af_pk_search16 over a row in registers
+__device__ __forceinline__ u32 af_row_search(const AfRow &R, u32 t, AfRow &M) {
+    const u32 e[8] = {R.a.x, R.a.y, R.a.z, R.a.w, R.b.x, R.b.y, R.b.z, R.b.w};
+    u32 m[8];
+    const u32 cnt = af_pk_search16(e, t, m);
+    M.a = make_uint4(m[0], m[1], m[2], m[3]);
+    M.b = make_uint4(m[4], m[5], m[6], m[7]);
+    return cnt;
+}
+// The 512-byte LUT of sixteen mask rows at `lut`: element j of row s is on(j, s) ? 1 : 0 (register r of a row holds elements
+// 2r and 2r + 1).  Called by the whole workgroup (at least 128 lanes) ahead of its barrier.
+template <class PRED>
+__device__ __forceinline__ void af_fill_mask_rows(char *lut, u32 tid, PRED on) {
+    if (tid < 128) {
+        const u32 s = tid >> 3, r = tid & 7;
+        const u32 v = (on(2 * r, s) ? 1u : 0u) | (on(2 * r + 1, s) ? 0x10000u : 0u);
+        *reinterpret_cast<u32_lds *>(lut + s * 32 + r * 4) = v;
+    }
 }
 
 // ---- forward bit writer: completed big-endian words go straight to the slot (4-byte stores; the stream is a

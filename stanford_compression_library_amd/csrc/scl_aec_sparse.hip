@@ -28,8 +28,7 @@
 // The decoder has no order in the list to search by: it bisects.  With u = target - s, "s + (symbols below s) <= target"
 // reads (symbols below target - u) <= u, u in 0..n: five steps of one packed count each.
 #include "scl_aec_internal.h"
-#include "scl_aec_math.h"
-#include "scl_aec_lane_io.h"
+#include "scl_aec_frame.h"
 
 #define AP_THREADS 64       // one wave per workgroup: the staging area below is 17 KiB, nine workgroups fit a CU
 // words of entries per line (two u16 entries each; 15 = the whole line but its header).  Measured on one box: the encoder
@@ -73,28 +72,8 @@ __device__ __forceinline__ u32 ap_count_gt(const ApLine &L, u32 v) {
     const u32 a = af_pk_add(a0, a1);  // minus the count, per half
     return (u32)(-((int32_t)(a << 16) >> 16) - ((int32_t)a >> 16));
 }
-__device__ __forceinline__ u32 ap_next_ctx(const AecSparseDev &P, u32 ctx, u32 s) {  // past_k[1:] + [s], :146-151
-    if (P.k == 0) return 0;
-    if (P.k == 1) return s;
-    return (u32)(((u64)ctx * P.K + s) % P.ctx_mod);
-}
 
 // ---- the dense rows of contexts that have outgrown their line (layout of scl_aec_wide.hip, u16 cells) ---------------
-struct ApRow16 {
-    u32 v[16];
-};
-__device__ __forceinline__ ApRow16 ap_load16(const u16 *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    const uint4 a = q[0], b = q[1];
-    const u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    ApRow16 r;
-#pragma unroll
-    for (u32 j = 0; j < 8; ++j) {
-        r.v[2 * j] = w[j] & 0xFFFFu;
-        r.v[2 * j + 1] = w[j] >> 16;
-    }
-    return r;
-}
 // The context leaves its line: its dense row (u16 cells: 16 block totals, then the counts) is built in LDS -- a byte per
 // cell, every count is at most 32 here -- and written out whole with plain 16-byte stores: no atomics on device memory, so
 // this lane's later plain loads of the row see it without any fence (the row has never been read in this launch, and
@@ -139,31 +118,6 @@ __device__ __forceinline__ void ap_move_to_dense(const ApLine &L, u32 *line, u16
     }
     line[0] = AP_DENSE;
 }
-// (c, f, T) of symbol s from a dense row: one round trip for the two pieces
-struct ApCft {
-    u32 c, f, T, fb;  // fb = the symbol's block total (count - 1 units), for the update
-};
-__device__ __forceinline__ ApCft ap_dense_lookup(const u16 *row, u32 K, u32 s) {
-    const ApRow16 bt = ap_load16(row);
-    const ApRow16 cb = ap_load16(row + 16 + (s & ~15u));
-    const u32 b = s >> 4, w = s & 15u;
-    u32 below = 0, tot = 0, fs = 0, fb = 0;
-#pragma unroll
-    for (u32 j = 0; j < 16; ++j) {
-        tot += bt.v[j];
-        below += (j < b) ? bt.v[j] : 0u;
-        below += (j < w) ? cb.v[j] : 0u;
-        fs = (j == w) ? cb.v[j] : fs;
-        fb = (j == b) ? bt.v[j] : fb;
-    }
-    ApCft r;
-    r.c = s + below;
-    r.f = 1 + fs;
-    r.T = K + tot;
-    r.fb = fb;
-    return r;
-}
-
 // ---- encoder ----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(AP_THREADS)
     aec_sparse_encode_kernel(AecSparseDev P, const u8 *__restrict__ sym, u64 sym_stride, const u32 *__restrict__ lens,
@@ -174,7 +128,6 @@ __global__ void __launch_bounds__(AP_THREADS)
     const u64 chunk = (u64)blockIdx.x * AP_THREADS + threadIdx.x;
     if (chunk >= n_chunks) return;
     const u32 n = lens ? lens[chunk] : chunk_len;
-    const u32 *src = reinterpret_cast<const u32 *>(sym + chunk * sym_stride);
     u32 *lines = scratch + chunk * (16ull * P.ctx_mod);
     u16 *dense = reinterpret_cast<u16 *>(scratch + P.dense_base) + chunk * ((u64)P.ctx_mod * P.row_cells);
     AfWriter wr;
@@ -184,41 +137,11 @@ __global__ void __launch_bounds__(AP_THREADS)
     u32 low = 0, hm = 0xFFFFFFFFu;
     u32 pending = 0;  // E3 steps not yet resolved
 
-    // one step of the literal loops, and the termination: `bit`, then `pending` copies of its inverse
-    auto emit = [&](u32 bit) {
-        wr.put(bit, 1);
-        wr.put_run(bit ^ 1u, pending);
-    };
-    // arithmetic stage: shrink_range (:58-78) and the renormalisation loops (:126-150) of one symbol
-    auto code = [&](u32 cc, u32 dd, double xx) {
-        af_shrink2(low, hm, cc, dd, xx);
-        u32 k, m, nlow, nhm;
-        const bool edge = af_renorm2(low, hm, k, m, nlow, nhm);
-        if (__builtin_expect(edge || (k + pending > 32), 0)) {
-            af_renorm_literal_enc(low, hm, pending, emit);
-        } else {
-            if (k > 0) {
-                const u32 top = low >> (32 - k);
-                const u32 b0 = top >> (k - 1);
-                const u32 rest = top & ((1u << (k - 1)) - 1u);
-                const u32 pat = (1u << pending) - (b0 ^ 1u);  // pending <= 31 here
-                wr.put((pat << (k - 1)) | rest, k + pending);
-                pending = 0;
-            }
-            pending += m;
-            low = nlow;
-            hm = nhm;
-        }
-    };
-
     // symbol i's line is in flight since the previous iteration; what symbol i - 1 added to it (it was counted after the
-    // line was issued) is patched into the results.  Symbols arrive four per 32-bit load, two words ahead.
-    const u32 last_word = n ? (n - 1) >> 2 : 0;
-    u32 word_a = src[0], word_b = src[min(1u, last_word)];
+    // line was issued) is patched into the results.
+    AfSymFeed feed;
+    u32 s_cur = feed.first(sym + chunk * sym_stride, n, P.K, st);
     u32 ctx = 0;
-    u32 s_cur = word_a & 0xFFu;
-    if (n > 0 && s_cur >= P.K) st |= SCL_ST_SYMBOL;
-    s_cur = (s_cur >= P.K) ? 0u : s_cur;
     ApLine L = ap_load_line(lines);
     u32 p_ctx = 0xFFFFFFFFu, p_s = 0;  // the symbol counted while this line was in flight (none yet)
     u32 c_pv = 0, d_pv = 1;            // (c, d, T) = (0, 1, 1): the arithmetic stage is a no-op before the first symbol
@@ -226,18 +149,11 @@ __global__ void __launch_bounds__(AP_THREADS)
     for (u32 i = 0; i < n; ++i) {
         const u32 s = s_cur;
         // next symbol: its line is issued now, before this symbol is counted
-        const u32 inx = i + 1;
-        if ((inx & 3u) == 0) {
-            word_a = word_b;
-            word_b = src[min((inx >> 2) + 1, last_word)];
-        }
-        u32 s_nx = (word_a >> (8 * (inx & 3u))) & 0xFFu;
-        if (inx < n && s_nx >= P.K) st |= SCL_ST_SYMBOL;
-        s_nx = (s_nx >= P.K) ? 0u : s_nx;  // also past the end of the chunk: the line read for it is never used
-        const u32 ctx_nx = ap_next_ctx(P, ctx, s);
+        const u32 s_nx = feed.next(i + 1, n, P.K, st);
+        const u32 ctx_nx = af_next_ctx_k(P, ctx, s);
         const ApLine L_nx = ap_load_line(lines + 16ull * ctx_nx);
         // meanwhile: the arithmetic of the previous symbol
-        code(c_pv, d_pv, x_pv);
+        af_code_symbol(wr, low, hm, pending, c_pv, d_pv, x_pv);
         // freqs_current of this symbol (:118), then update_model (:143-160)
         u32 *line = lines + 16ull * ctx;
         u16 *row = dense + (u64)ctx * P.row_cells;
@@ -247,9 +163,9 @@ __global__ void __launch_bounds__(AP_THREADS)
         if (__builtin_expect(L.w[0] == AP_DENSE || cnt > (2 * AP_WORDS_ENC), 0)) {
             // dense -- when the line was read, or since the previous symbol (whose move the line in hand has not seen):
             // everything counted so far is in the row, read now
-            const ApCft r = ap_dense_lookup(row, P.K, s);
-            c = r.c, f = r.f, T = r.T;
-            row[16 + s] = (u16)r.f;  // plain stores (visible to this lane's later loads), cells hold count - 1
+            const AfRowCounts r = af_row_counts(af_load16(row), af_load16(row + 16 + (s & ~15u)), s);
+            c = s + r.below, f = 1 + r.fs, T = P.K + r.tot;
+            row[16 + s] = (u16)f;  // plain stores (visible to this lane's later loads), cells hold count - 1
             row[s >> 4] = (u16)(r.fb + 1);
         } else {
             const u32 g0 = ap_count_gt<AP_WORDS_ENC>(L, s) + ((same && p_s + 1 > s) ? 1u : 0u);
@@ -273,12 +189,9 @@ __global__ void __launch_bounds__(AP_THREADS)
         s_cur = s_nx;
         L = L_nx;
     }
-    code(c_pv, d_pv, x_pv);
-    af_terminate(low, pending, emit);  // :153-159
-    const u64 total = wr.finish();
-    out_bit_off[chunk] = chunk * out_stride * 8;
-    out_nbits[chunk] = (u32)total;
-    if (status) status[chunk] = st;
+    af_code_symbol(wr, low, hm, pending, c_pv, d_pv, x_pv);
+    af_terminate(low, pending, [&](u32 bit) { af_emit(wr, bit, pending); });  // :153-159
+    af_encode_results(wr.finish(), st, chunk, out_stride, out_bit_off, out_nbits, status);
 }
 
 // ---- decoder ----------------------------------------------------------------------------------------------------------
@@ -295,6 +208,8 @@ __global__ void __launch_bounds__(AP_THREADS)
     rd.init(in, in_size_bytes, bit_off[chunk], nbits);
     // This kernel's own text of af_decode_length and, below, of af_renorm_literal_dec (scl_aec_math.h): with the helpers it
     // came out longer and measurably slower (profiles/aec_fold_timing.txt).  Keep the copies in step with the helpers.
+    // Likewise af_row_find and AfSymWord (scl_aec_frame.h, as the wide decoder uses them): + 0.2 % at the edge of the parents'
+    // own spread (profiles/aec_frame_timing.txt); with its own text the kernel is the parent's byte for byte.
     u32 st = 0;
     u32 n = rd.get(P.size_bits);
     if (nbits < P.size_bits) {
@@ -328,8 +243,8 @@ __global__ void __launch_bounds__(AP_THREADS)
         const double xr = af_recip((double)(hm - low) + 1.0);  // issued before the line arrives
         u32 s, c, f, T;
         if (__builtin_expect(L.w[0] == AP_DENSE, 0)) {
-            // the two-level search of scl_aec_wide.hip: block totals, then the block the target lands in
-            const ApRow16 bt = ap_load16(row);
+            // the two-level search of the wide decoder (af_row_find): block totals, then the block the target lands in
+            const AfCells16 bt = af_load16(row);
             u32 tot = 0;
 #pragma unroll
             for (u32 j = 0; j < 16; ++j) tot += bt.v[j];
@@ -346,7 +261,7 @@ __global__ void __launch_bounds__(AP_THREADS)
                 fb = take ? bt.v[j] : fb;
                 run += 16 + bt.v[j];
             }
-            const ApRow16 cb = ap_load16(row + 16 + 16 * b);
+            const AfCells16 cb = af_load16(row + 16 + 16 * b);
             const u32 wmax = min(15u, P.K - 1 - 16 * b);
             u32 w = 0, fs = cb.v[0];
             c = g;
@@ -394,7 +309,7 @@ __global__ void __launch_bounds__(AP_THREADS)
         // (c, f) of this symbol and the arithmetic come out of the line in hand while it travels
         const ApLine Lc = L;
         const bool was_dense = Lc.w[0] == AP_DENSE;
-        ctx = ap_next_ctx(P, ctx, s);
+        ctx = af_next_ctx_k(P, ctx, s);
         L = ap_load_line(lines + 16ull * ctx);
         if (!was_dense) {
             const u32 cnt = Lc.w[0];
@@ -470,11 +385,9 @@ static AecSparseDev aec_sparse_dev(const scl_aec_model *m, u64 n_chunks) {
 u64 aec_sparse_zero_bytes(const scl_aec_model *m, u64 n_chunks) { return 64ull * m->dev.ctx_mod * n_chunks; }
 
 void aec_sparse_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *d_scratch) {
-    const SclGrid g = {(u32)((a.n_chunks + AP_THREADS - 1) / AP_THREADS), AP_THREADS};
-    scl_launch_encode(aec_sparse_encode_kernel, g, st, aec_sparse_dev(m, a.n_chunks), a, d_scratch);
+    scl_launch_encode(aec_sparse_encode_kernel, aec_grid(a.n_chunks, AP_THREADS), st, aec_sparse_dev(m, a.n_chunks), a, d_scratch);
 }
 
 void aec_sparse_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *d_scratch) {
-    const SclGrid g = {(u32)((a.n_chunks + AP_THREADS - 1) / AP_THREADS), AP_THREADS};
-    scl_launch_decode(aec_sparse_decode_kernel, g, st, aec_sparse_dev(m, a.n_chunks), a, d_scratch);
+    scl_launch_decode(aec_sparse_decode_kernel, aec_grid(a.n_chunks, AP_THREADS), st, aec_sparse_dev(m, a.n_chunks), a, d_scratch);
 }

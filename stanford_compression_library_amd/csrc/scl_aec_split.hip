@@ -36,8 +36,7 @@
 // Writer side.  64-bit window of 32-bit halves, one field of <= 31 bits per symbol (b0, pending x !b0, k - 1 more
 // bits); k + pending > 31 and the termination take the bit-run path.
 #include "scl_aec_internal.h"
-#include "scl_aec_math.h"
-#include "scl_aec_lane_io.h"
+#include "scl_aec_frame.h"
 
 #define AS_LANES 64                    // chunks per workgroup: one wave per role, four workgroups per CU (40 KiB of LDS each)
 #define AS_THREADS (3 * AS_LANES)      // wave 0: model role, wave 1: coder role, wave 2: writer role
@@ -79,12 +78,8 @@ __global__ void __launch_bounds__(AS_THREADS)
     const u32 n = live ? (lens ? lens[chunk] : chunk_len) : 0u;
 
     // ---- tables, LUT, the longest chunk of the workgroup ----------------------------------------------------------
-    if (tid < 128) {
-        const u32 s = tid >> 3, r = tid & 7;  // addend of word r (counts 2r, 2r + 1) for symbol s: [j > s]
-        // (count 0 of a row is its total: + 1 for every symbol)
-        const u32 v = ((2 * r > s || r == 0) ? 1u : 0u) | ((2 * r + 1 > s) ? 0x10000u : 0u);
-        *reinterpret_cast<u32_lds *>(lds + AS_LUT_BASE + s * 32 + r * 4) = v;
-    }
+    // addend rows: [j > s] for symbol s; count 0 of a row is its total: + 1 for every symbol
+    af_fill_mask_rows(lds + AS_LUT_BASE, tid, [](u32 j, u32 s) { return j > s || j == 0; });
     if (tid == 0) *reinterpret_cast<u32_lds *>(lds + AS_RED_BASE) = 0;
     if (role == 0) {
         for (u32 c = 0; c < P.nctx; ++c) {
@@ -321,16 +316,10 @@ __global__ void __launch_bounds__(AS_THREADS)
     });
     const u64 total = (u64)nwords * 32 + cnt;
     if (cnt) dst[nwords] = __builtin_bswap32(wlo << (32 - cnt));
-    out_bit_off[chunk] = chunk * out_stride * 8;
-    out_nbits[chunk] = (u32)total;
-    if (status) status[chunk] = st;
+    af_encode_results(total, st, chunk, out_stride, out_bit_off, out_nbits, status);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------
 void aec_split_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st) {
-    const SclGrid g = {(u32)((a.n_chunks + AS_LANES - 1) / AS_LANES), AS_THREADS};
-    if (m->dev.k == 1)
-        scl_launch_encode(aec_split_encode_kernel<true>, g, st, aec_fast_dev(m), a);
-    else
-        scl_launch_encode(aec_split_encode_kernel<false>, g, st, aec_fast_dev(m), a);
+    AEC_LAUNCH_ORDER1(m, scl_launch_encode, aec_split_encode_kernel, aec_grid_groups(a.n_chunks, AS_LANES, AS_THREADS), st, aec_fast_dev(m), a);
 }

@@ -12,7 +12,7 @@
 // Arithmetic as in scl_aec_fast.hip (scl_aec_math.h): (rng*c)//T in exact binary64 with ONE reciprocal of T per
 // launch, closed-form renormalisation, literal loops of the reference on its strict-comparison corners.
 #include "scl_aec_internal.h"
-#include "scl_aec_math.h"
+#include "scl_aec_frame.h"
 #include "scl_ans_fast_io.h"
 
 #define AS_THREADS 256
@@ -55,12 +55,6 @@ __device__ __forceinline__ void as_setup_table16(char *lds, const AecStaticDev &
 typedef AnsFwdWriter<AS_THREADS> AsOut;
 typedef AnsBitReader<AS_THREADS, true> AsIn;
 
-// one step of the literal loops, and the termination: `bit`, then `pending` copies of its inverse
-__device__ __forceinline__ void as_emit(AsOut &wr, char *lds, u32 bit, u32 pending) {
-    wr.put(lds, bit, 1);
-    wr.put_run(lds, bit ^ 1u, pending);
-}
-
 // one symbol of the encoder: shrink_range, then the renormalisation loops (:126-150)
 template <bool POW2>
 __device__ __forceinline__ void as_encode_symbol(u32 &low, u32 &hm, u32 &pending, u64 c, u64 d, u32 t, double xT,
@@ -74,21 +68,11 @@ __device__ __forceinline__ void as_encode_symbol(u32 &low, u32 &hm, u32 &pending
     const bool rare = edge | (k + pending > 32);                 // one condition, one branch
     if (__builtin_expect(rare, 0)) {
         af_renorm_literal_enc(low, hm, pending, [&](u32 bit) {
-            as_emit(wr, lds, bit, pending);
+            af_emit(wr, bit, pending, lds);
             wr.maybe_flush(lds);
         });
     } else {
-        // b0, then `pending` copies of !b0, then the other k - 1 common bits -- without a branch on k: for k = 0 the field is
-        // empty (v = 0, nb = 0) and the pending count just grows (as in scl_aec_iid.hip)
-        const bool any = k != 0;
-        const u32 km1 = (k - 1u) & 31u;
-        const u32 b0 = low >> 31;
-        const u32 rest = __builtin_amdgcn_ubfe(low, (32u - k) & 31u, km1);  // bits 30 .. 32-k of low
-        const u32 pat = (1u << pending) - (b0 ^ 1u);                       // pending <= 31 here
-        u32 fv = (pat << km1) | rest, fn = k + pending;
-        asm volatile("" : "+v"(fv), "+v"(fn));  // computed for every lane: the compiler would turn the selects into a branch
-        wr.put_field(lds, any ? fv : 0u, any ? fn : 0u);
-        pending = (any ? 0u : pending) + m;
+        af_put_common_flat(wr, low, k, m, pending, lds);
         low = nlow;
         hm = nhm;
     }
@@ -158,12 +142,9 @@ __global__ void __launch_bounds__(AS_THREADS, 4)
         for (u32 j = 0; i + j < n; ++j) w |= (u32)src[i + j] << (8 * j);
         code_word(w, n - i);
     }
-    af_terminate(low, pending, [&](u32 bit) { as_emit(wr, lds, bit, pending); });  // :153-159
-    const u64 total = wr.finish(lds);
-    out_bit_off[chunk] = chunk * out_stride * 8;
-    out_nbits[chunk] = (u32)total;
-    if (status)
-        status[chunk] = ((bad >= P.K) ? SCL_ST_SYMBOL : 0u) | af_header_status(n, P.size_bits);
+    af_terminate(low, pending, [&](u32 bit) { af_emit(wr, bit, pending, lds); });  // :153-159
+    af_encode_results(wr.finish(lds), ((bad >= P.K) ? SCL_ST_SYMBOL : 0u) | af_header_status(n, P.size_bits), chunk, out_stride,
+                      out_bit_off, out_nbits, status);
 }
 
 // LUT = true: total <= 4096, the decoder's search is one byte read by target slot; else a binary search on c
@@ -301,7 +282,7 @@ static AecStaticDev aec_static_dev(const scl_aec_model *m) {
 }
 
 void aec_static_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a, hipStream_t st, u32 *) {
-    const SclGrid g = {(u32)((a.n_chunks + AS_THREADS - 1) / AS_THREADS), AS_THREADS};
+    const SclGrid g = aec_grid(a.n_chunks, AS_THREADS);
     const AecStaticDev dev = aec_static_dev(m);
     if (dev.t != 0xFFFFFFFFu)
         scl_launch_encode(aec_static_encode_kernel<true>, g, st, dev, a);
@@ -310,7 +291,7 @@ void aec_static_encode_launch(const scl_aec_model *m, const SclEncodeArgs<u8> &a
 }
 
 void aec_static_decode_launch(const scl_aec_model *m, const SclDecodeArgs<u8> &a, hipStream_t st, u32 *) {
-    const SclGrid g = {(u32)((a.n_chunks + AS_THREADS - 1) / AS_THREADS), AS_THREADS};
+    const SclGrid g = aec_grid(a.n_chunks, AS_THREADS);
     const AecStaticDev dev = aec_static_dev(m);
     const bool pow2 = dev.t != 0xFFFFFFFFu;
 #define AS_LAUNCH_DEC(LUT, POW2) scl_launch_decode(aec_static_decode_kernel<LUT, POW2>, g, st, dev, a)

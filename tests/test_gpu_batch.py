@@ -292,6 +292,84 @@ def test_batch_aec_lds_table_kernels_short_chunks(dev):
             assert np.array_equal(got, rb), f"K={K} chunk {c}"
 
 
+# model name -> (kind, K, k); "<name>+lane": the same model with SCL_AEC_ENC=lane, so that aec_fast_encode_kernel runs
+LANE_FRAME_MODELS = {"order1_k16": ("orderk", 16, 1), "order2_k4": ("orderk", 4, 2), "iid_k11": ("iid", 11, 0),
+                     "iid_k100": ("iid", 100, 0), "order1_k256": ("orderk", 256, 1)}
+LANE_FRAME_CASES = list(LANE_FRAME_MODELS) + [m + "+lane" for m in ("order1_k16", "order2_k4", "iid_k11")]
+LANE_FRAME_EDGES = [0, 1, 2, 3, 4, 5, 15, 16, 17, 18, 63, 64, 65, 255, 256, 257, 1023, 1024]
+_lane_frame_reference = {}
+
+
+def _lane_frame_case(name):
+    """lengths, symbols and the oracle's streams and decodes of one model: computed once, shared by its cases, never changed"""
+    if name not in _lane_frame_reference:
+        kind, K, k = LANE_FRAME_MODELS[name]
+        o_kw = dict(f_init=np.ones(K)) if kind == "iid" else dict(k=k)
+        o_kind = orc.MODEL_IID if kind == "iid" else orc.MODEL_ORDERK
+        lens = np.array([1024] * 64 + [LANE_FRAME_EDGES[i % len(LANE_FRAME_EDGES)] for i in range(64)] + [1024] * 64
+                        + [1024] * 19, dtype=np.int32)
+        sym = np.random.default_rng(9000 + 31 * K + k).integers(0, K, (lens.size, 1040)).astype(np.uint8)
+        streams = [orc.aec_encode(sym[c, :lens[c]], o_kind, K, **o_kw) for c in range(lens.size)]
+        o_used = np.array([orc.aec_decode(rb, rn, o_kind, K, **o_kw)[1] for rb, rn in streams])  # empty chunks: header + 2
+        for a in (lens, sym, o_used):
+            a.setflags(write=False)
+        _lane_frame_reference[name] = (lens, sym, streams, o_used)
+    return _lane_frame_reference[name]
+
+
+@pytest.mark.parametrize("case", LANE_FRAME_CASES)
+def test_aec_lane_frames(case, dev, monkeypatch):
+    """What stands around the symbol step of the lane-per-chunk arithmetic-coder kernels (scl_aec_frame.h: header exit,
+    unchecked stretches with a wave-wide count, checked loop, peeled last symbol, epilogue; the encoders' word-ahead loop,
+    drain and termination; the wide / sparse kernels' symbol feed and output word), on every kernel family that uses it.
+    One launch of 64 x 3 + 19 chunks, cap 1040, uniform symbols: a wave of 64 equal chunks of 1024 (stretches with a
+    wave-uniform count); a wave whose lengths sit on every loop boundary (lanes drop out one by one, stretches entered off
+    a multiple of four); a wave of 64 equal chunks where one lane is given 10 bits (the header exit inside a full wave:
+    af_wave_min's partial-wave path, the other 63 lanes still run unchecked); a partial wave of 19."""
+    name, _, lane = case.partition("+")
+    if lane:
+        monkeypatch.setenv("SCL_AEC_ENC", "lane")
+    kind, K, k = LANE_FRAME_MODELS[name]
+    lens, sym, streams, o_used = _lane_frame_case(name)
+    n_chunks, cap, cut = lens.size, 1040, 128 + 37
+    # a stretch needs a wave-wide count of at least 16 symbols, i.e. at least 33 words left in every lane's stream
+    short = [c for c in range(n_chunks) if lens[c] == 1024 and not 64 <= c < 128 and streams[c][1] < 1280]
+    assert not short, f"streams too short for an unchecked stretch: chunks {short}"
+    model = (models.AecModel(1, [1] * K, K, 0, 1 << 30, 32, 32) if kind == "iid"
+             else models.AecModel(2, None, K, k, 1 << 30, 32, 32))
+    assert model.fast_path(cap), "this case must be served by the tuned kernels"
+    enc = model.encode_batch(torch.tensor(sym, device=dev), lens=torch.tensor(lens, device=dev))
+    torch.cuda.synchronize()
+    assert not enc.status.cpu().numpy().any()
+    data, offs, nbits = enc.data.cpu().numpy(), enc.bit_offset.cpu().numpy(), enc.nbits.cpu().numpy()
+    for c in sorted({0, 63, 127, 128, cut - 1, cut, cut + 1, 191, 192, n_chunks - 1} | set(range(64, 64 + len(LANE_FRAME_EDGES)))):
+        rb, rn = streams[c]
+        assert int(nbits[c]) == rn, f"chunk {c} (n={lens[c]}): {nbits[c]} bits vs oracle {rn}"
+        assert np.array_equal(_stream_bits(data, offs[c], rn), np.unpackbits(rb)[:rn]), f"chunk {c}"
+    avail = enc.nbits.clone()
+    avail[cut] = 10
+    got = []
+    for generic in (False, True):
+        out = model.alloc_decoded(n_chunks, cap, dev)
+        out[0].fill_(0xA5)
+        res = model.decode_batch(enc.data, enc.bit_offset, avail, cap, out=out, any_parameter_kernels=generic)
+        torch.cuda.synchronize()
+        got.append([out[0].cpu().numpy()] + [t.cpu().numpy() for t in res[1:]])
+    dec, dlens, used, status = got[0]
+    want_lens = lens.copy()
+    want_lens[cut] = 0
+    assert np.array_equal(dlens, want_lens)
+    assert status[cut] == backend_lib.ST_TRUNCATED and not np.delete(status, cut).any()
+    assert np.array_equal(np.delete(used, cut), np.delete(o_used, cut)), "consumed bits differ from the oracle's"
+    assert used[cut] == 0, "a stream shorter than its header consumes nothing"
+    for c in range(n_chunks):
+        assert np.array_equal(dec[c, :want_lens[c]], sym[c, :want_lens[c]]), f"chunk {c}"
+        assert (dec[c, (want_lens[c] + 3) & ~3:] == 0xA5).all(), f"chunk {c}: bytes beyond the chunk were written"
+        assert np.array_equal(got[1][0][c, :want_lens[c]], dec[c, :want_lens[c]]), f"chunk {c}: any-parameter symbols differ"
+    for what, a, b in zip(("lengths", "consumed bits", "status"), got[0][1:], got[1][1:]):
+        assert np.array_equal(a, b), f"tuned and any-parameter decoders differ in {what}"
+
+
 @pytest.mark.parametrize("K,T", [(2, 5), (17, 1000), (256, 4096), (100, 4097), (256, 65536), (3, 65536)])
 def test_batch_aec_static_model_kernels_vs_oracle(K, T, dev):
     """scl_aec_static.hip (FixedFreqModel: shared table in LDS, line-granular I/O): 300 ragged chunks incl. whole
