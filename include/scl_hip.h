@@ -534,7 +534,8 @@ int scl_lz77_wide_kernel_names(char *score, char *walk, char *resolve, uint64_t 
 /* ---- LZ77: the entropy stage, sequences and literals <-> block bits (scl_lz77_entropy.hip; added to ABI 8 as above) -------
  *   scl_lz77_entropy_encode_batch  <->  LZ77StreamsEncoder.encode_block   scl/compressors/lz77.py:301-361
  *   scl_lz77_entropy_decode_batch  <->  LZ77StreamsDecoder.decode_block   scl/compressors/lz77.py:364-428
- * One wavefront per stream.  A stream's bits are four fields in this order: literal counts, match lengths, match offsets,
+ * One wavefront per stream (ONE large stream on the whole GPU: scl_lz77_entropy_*_wide below, the same bits).  A stream's
+ * bits are four fields in this order: literal counts, match lengths, match offsets,
  * literals.  A sequence field is log-scale binned with o = binned_offset (0..32; the reference's default is 16): v < o is its
  * own bin, otherwise the bin is o + floor(log2(v - o + 1)) and the bits of v - o + 1 below its leading one follow as a
  * residual; the alphabet is 32 + o bins.  Each field is
@@ -611,6 +612,80 @@ int scl_lz77_entropy_kernel_names(char *enc, char *dec, uint64_t cap);
    significant bit first in the low len[i] bits, 0 / 0 for a symbol without a count.  SCL_E_PARAM: K outside 1..256, a count
    of 2^32 or more, no count at all, a codeword longer than 32 bits. */
 int scl_lz77_huffman_from_counts_host(const uint64_t *counts, uint32_t K, uint32_t *code, uint8_t *len);
+
+/* ---- LZ77: the entropy stage of ONE large stream across the whole GPU (scl_lz77_entropy_wide.hip; added to ABI 8 as above)
+ * scl_lz77_entropy_*_batch give every stream one wavefront -- and the decoder's walk one lane.  These two calls take ONE
+ * stream and use the whole chip; the bits, the rows, the literals, n_seq / n_lit / consumed and the status are what the
+ * batch calls give for a batch of that one stream (the layout and the status rules above), with two differences that the
+ * 32-bit words of the batch calls cannot express: d_nbits and `consumed` are 64-bit, and a stream of 2^32 bits or more is
+ * coded as long as every section fits its own 32-bit header (SCL_ST_CAPACITY otherwise, d_nbits = the length needed).
+ *   encode: the first n_seq entries of the three rows and n_lit literals from d_literals[0] on (host values: they size the
+ *           launches) -> d_out[0 .. out_cap_bytes), front to back.  Grid-wide histograms, ONE workgroup for the four trees
+ *           and the 64-bit position of every header and section, then every section emitted in tiles of 4096 values at its
+ *           own bit position.  All faults are decided before a bit is stored: a stream with a non-zero *d_status stores
+ *           NOTHING, no byte at or past d_out + out_cap_bytes is ever written, and *d_nbits is the length needed also for
+ *           SCL_ST_CAPACITY (0 for SCL_ST_SIZE / SCL_ST_SYMBOL).  Asynchronous on `stream`, no host read-back.
+ *   decode: the in_nbits bits from bit in_bit_offset of d_in (any bit alignment; d_in itself 4-byte aligned) -> the first
+ *           entries of the three rows (seq_cap each) and of d_literals (lit_cap bytes), and *d_result.  Field by field -- a
+ *           field's position is known only when the one before it is decoded: one workgroup reads the headers and counts
+ *           and builds the tree and a lookup table in scratch, the codewords are decoded by the self-synchronising scheme of
+ *           scl_prefix_decode_block (128 bits per thread, 256 threads per workgroup, passes relaunched until no workgroup's
+ *           exit moves; result.sync_passes = the passes, summed over the fields, in which a workgroup moved its start),
+ *           and the bins become values grid-wide after a 64-bit scan of the residual widths.  First fault wins, in field
+ *           order, with the batch decoder's status for the same damage.
+ *           SYNCHRONISING: the call reads device words between passes and between fields and returns when everything but
+ *           the last field's kernels has finished; per field it synchronises once for the headers and once per pass, at
+ *           most 1 + (workgroups of the field - 1) times, 4 + sum over the fields in all.
+ * No kernel waits on another workgroup (no flags, no look-back, no cooperative launch); nothing outside the output bytes,
+ * the input bytes d_in[0 .. in_size_bytes), the rows up to n_seq / seq_cap and the literal range is read or written on any
+ * input.  SCL_E_PARAM before any device call, the message prefixed with the entry point's name: a null pointer,
+ * binned_offset above 32, n_seq / n_lit / seq_cap / lit_cap of 2^32 or more, in_nbits of 2^46 or more, a stream that ends
+ * behind in_size_bytes, d_out / d_in not 4-byte or rows not 4-byte or d_scratch / d_nbits / d_result not 8-byte aligned,
+ * scratch smaller than scl_lz77_entropy_wide_scratch_bytes. */
+typedef struct scl_lz77_entropy_wide_encode_args {
+    const uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_seq] each */
+    uint64_t n_seq;
+    const uint8_t *d_literals;
+    uint64_t n_lit;
+    uint32_t binned_offset, reserved;
+    uint8_t *d_out;
+    uint64_t out_cap_bytes;
+    uint64_t *d_nbits;  /* one u64 */
+    uint32_t *d_status; /* one word */
+    void *d_scratch;
+    uint64_t scratch_bytes;
+} scl_lz77_entropy_wide_encode_args;
+
+typedef struct scl_lz77_entropy_wide_result {
+    uint64_t consumed;
+    uint32_t n_seq, n_lit, status, sync_passes;
+} scl_lz77_entropy_wide_result;
+
+typedef struct scl_lz77_entropy_wide_decode_args {
+    const uint8_t *d_in;
+    uint64_t in_size_bytes, in_bit_offset, in_nbits;
+    uint32_t binned_offset, reserved;
+    uint64_t seq_cap, lit_cap;
+    uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [seq_cap] each */
+    uint8_t *d_literals;                               /* lit_cap bytes */
+    scl_lz77_entropy_wide_result *d_result;
+    void *d_scratch;
+    uint64_t scratch_bytes;
+} scl_lz77_entropy_wide_decode_args;
+
+int scl_lz77_entropy_encode_wide(const scl_lz77_entropy_wide_encode_args *args, void *stream);
+int scl_lz77_entropy_decode_wide(const scl_lz77_entropy_wide_decode_args *args, void *stream);
+/* scratch for either call: encode of n_seq sequences and n_lit literals, decode with seq_cap = n_seq, lit_cap = n_lit and
+   in_nbits; monotone in every argument */
+uint64_t scl_lz77_entropy_wide_scratch_bytes(uint64_t n_seq, uint64_t n_lit, uint64_t in_nbits);
+/* The stream size from which both wide calls beat the one-wave kernels, counted in CODED VALUES, 3 * n_seq + n_lit: the
+   smallest measured stream from which both wide calls won at every larger measured stream on both sources (DESIGN.md
+   3.6.3).  Values, not block bytes: 16 MiB of equal bytes parse to 1 sequence and 6 literals, and on those 9 values one
+   wavefront is 0.03 ms ahead of the wide call's launches.  Below it scl_lz77_entropy_*_batch on a batch of one is the
+   faster route to the same bits; nothing in the library routes by it. */
+uint64_t scl_lz77_entropy_wide_threshold(void);
+/* the kernels that carry the emission, the decoder's synchronisation and the residuals, as scl_lz77_kernel_names */
+int scl_lz77_entropy_wide_kernel_names(char *emit, char *sync, char *resid, uint64_t cap);
 
 /* ---- stream compaction / framing ------------------------------------------------------------ */
 #define SCL_COMPACT_DENSE 0  /* stream c left-aligned at byte d_out_byte_offset[c], zero tail   */

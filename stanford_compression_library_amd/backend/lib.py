@@ -103,6 +103,28 @@ class Lz77EntropyDecodeArgs(C.Structure):
                 ("d_lit_cap", C.c_void_p), ("d_n_lit", C.c_void_p), ("d_consumed", C.c_void_p), ("d_status", C.c_void_p)]
 
 
+class Lz77EntropyWideEncodeArgs(C.Structure):
+    """scl_lz77_entropy_wide_encode_args"""
+    _fields_ = [("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p), ("n_seq", C.c_uint64),
+                ("d_literals", C.c_void_p), ("n_lit", C.c_uint64), ("binned_offset", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_out", C.c_void_p), ("out_cap_bytes", C.c_uint64), ("d_nbits", C.c_void_p), ("d_status", C.c_void_p),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
+
+
+class Lz77EntropyWideResult(C.Structure):
+    """scl_lz77_entropy_wide_result"""
+    _fields_ = [("consumed", C.c_uint64), ("n_seq", C.c_uint32), ("n_lit", C.c_uint32), ("status", C.c_uint32),
+                ("sync_passes", C.c_uint32)]
+
+
+class Lz77EntropyWideDecodeArgs(C.Structure):
+    """scl_lz77_entropy_wide_decode_args"""
+    _fields_ = [("d_in", C.c_void_p), ("in_size_bytes", C.c_uint64), ("in_bit_offset", C.c_uint64), ("in_nbits", C.c_uint64),
+                ("binned_offset", C.c_uint32), ("reserved", C.c_uint32), ("seq_cap", C.c_uint64), ("lit_cap", C.c_uint64),
+                ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p),
+                ("d_literals", C.c_void_p), ("d_result", C.c_void_p), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
+
+
 LZ77_INDEX, LZ77_PARSE = 1, 2
 LZ77_WIDE_INDEX, LZ77_WIDE_SCORE, LZ77_WIDE_WALK, LZ77_WIDE_EMIT = 1, 2, 4, 8
 
@@ -185,6 +207,12 @@ _SIGNATURES = {
     "scl_lz77_entropy_slot_bytes": (_u64, [_u64, _u64, _u32]),
     "scl_lz77_entropy_kernel_names": (_int, [C.c_char_p, C.c_char_p, _u64]),
     "scl_lz77_huffman_from_counts_host": (_int, [_u64p, _u32, _u32p, _u8p]),
+    # LZ77: the entropy stage of one large stream across the whole GPU (scl_lz77_entropy_wide.hip)
+    "scl_lz77_entropy_encode_wide": (_int, [C.POINTER(Lz77EntropyWideEncodeArgs), _vp]),
+    "scl_lz77_entropy_decode_wide": (_int, [C.POINTER(Lz77EntropyWideDecodeArgs), _vp]),
+    "scl_lz77_entropy_wide_scratch_bytes": (_u64, [_u64, _u64, _u64]),
+    "scl_lz77_entropy_wide_threshold": (_u64, []),
+    "scl_lz77_entropy_wide_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
     "scl_aec_model_create": (_int, [_int, _u32p, _u32, _u32, _u64, _u32, _u32, C.POINTER(_vp)]),
     "scl_aec_model_destroy": (None, [_vp]),
     "scl_aec_slot_bytes": (_u64, [_vp, _u64]),

@@ -9,7 +9,9 @@ Two call shapes, as in :mod:`.models`:
 * ``parse_wide`` / ``replay_wide`` -- that wide path on ONE stream resident in HBM: a :class:`ParsedBatch` of one stream;
 * ``parse_batch`` / ``replay_batch`` -- many independent streams resident in HBM, given as torch tensors;
   ``encode_batch`` / ``decode_batch`` turn their sequences and literals into block bits and back, ``compress_batch`` /
-  ``decompress_batch`` do both steps.  No call loops over streams on the host.
+  ``decompress_batch`` do both steps.  No call loops over streams on the host;
+* ``encode_wide`` / ``decode_wide`` -- that entropy stage for ONE stream on the whole GPU (csrc/scl_lz77_entropy_wide.hip),
+  the same bits; ``compress_wide`` / ``decompress_wide`` = ``parse_wide`` + ``encode_wide`` / ``decode_wide`` + ``replay_wide``.
 
 A batch is ``n_streams`` windows laid out one after another in one uint8 tensor; ``win_off`` (int64, ``n_streams + 1``
 entries) says where each starts.  uint32 / uint64 arrays of the C ABI travel as int32 / int64 tensors (the bit patterns).
@@ -410,6 +412,140 @@ def decompress_batch(bits, bit_offset, nbits, win, win_off, have, seq_cap: int,
     decoded = decode_batch(bits, bit_offset, nbits, seq_cap, lit_off, lit_cap, binned_offset, stream=stream)
     out_len, status = replay_batch(win, win_off, have, decoded.literal_count, decoded.match_length, decoded.match_offset,
                                    decoded.n_seq, decoded.literals, lit_off, decoded.n_lit, stream=stream)
+    return out_len, status | decoded.status, decoded.consumed
+
+
+# ---- the entropy stage of one large stream across the whole GPU (csrc/scl_lz77_entropy_wide.hip) ----------------------------
+def entropy_wide_threshold() -> int:
+    """coded values of a stream, ``3 * n_seq + n_lit``, from which ``encode_wide`` / ``decode_wide`` beat ``encode_batch`` /
+    ``decode_batch`` on a batch of one (measured: DESIGN.md 3.6.3); the bits are the same on both sides of it"""
+    return int(_lib.load().scl_lz77_entropy_wide_threshold())
+
+
+def entropy_wide_scratch_bytes(n_seq: int, n_lit: int, in_nbits: int = 0) -> int:
+    """scratch for ``encode_wide`` of ``n_seq`` sequences and ``n_lit`` literals, and for ``decode_wide`` of ``in_nbits``
+    bits with ``seq_cap = n_seq``, ``lit_cap = n_lit``"""
+    return int(_lib.load().scl_lz77_entropy_wide_scratch_bytes(int(n_seq), int(n_lit), int(in_nbits)))
+
+
+def entropy_wide_kernel_names():
+    """-> (emit, sync, resid) kernel names of the wide entropy stage as a kernel trace prints them"""
+    bufs = [C.create_string_buffer(128) for _ in range(3)]
+    _lib.check(_lib.load().scl_lz77_entropy_wide_kernel_names(*bufs, 128), "scl_lz77_entropy_wide_kernel_names")
+    return tuple(b.value.decode() for b in bufs)
+
+
+def encode_wide(parsed: ParsedBatch, binned_offset: int = DEFAULT_BINNED_OFFSET, out_stride: Optional[int] = None,
+                n_seq: Optional[int] = None, n_lit: Optional[int] = None, lit_off: Optional[int] = None, scratch=None,
+                stream=None, out: Optional[EncodedBatch] = None) -> EncodedBatch:
+    """``encode_batch`` for a ONE-stream :class:`ParsedBatch` (what ``parse_wide`` returns) on the whole GPU: the same bits,
+    ``nbits`` and ``status`` in an :class:`EncodedBatch` of one slot, so ``models.compact`` takes it unchanged.  ``n_seq`` /
+    ``n_lit`` / ``lit_off`` size the launches: they are read back once (one copy) unless all three are passed.
+    ``out_stride``: the slot's bytes, ANY positive count here (default: ``entropy_slot_bytes`` of the counts); nothing at or
+    past it is written.  ``result.nbits64`` is the length as int64 (``nbits`` is its low 32 bits); asynchronous otherwise.
+    ``scratch``: a uint8 tensor of at least ``entropy_wide_scratch_bytes(n_seq, n_lit)`` bytes to reuse across calls."""
+    import torch
+
+    L = _lib.load()
+    lc, ml, mo = parsed.literal_count, parsed.match_length, parsed.match_offset
+    assert lc.is_cuda and lc.dim() == 2 and lc.shape == ml.shape == mo.shape and lc.shape[0] == 1
+    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in (lc, ml, mo))
+    assert parsed.literals.dtype == torch.uint8 and parsed.literals.is_contiguous()
+    dev = lc.device
+    if n_seq is None or n_lit is None or lit_off is None:
+        words = torch.cat((parsed.n_seq.to(torch.int64).bitwise_and(0xFFFFFFFF),
+                           parsed.n_lit.to(torch.int64).bitwise_and(0xFFFFFFFF), parsed.lit_off.reshape(-1))).cpu().tolist()
+        n_seq = words[0] if n_seq is None else n_seq
+        n_lit = words[1] if n_lit is None else n_lit
+        lit_off = words[2] if lit_off is None else lit_off
+    n_seq, n_lit, lit_off = int(n_seq), int(n_lit), int(lit_off)
+    assert n_seq <= lc.shape[1] and lit_off + n_lit <= parsed.literals.numel()
+    if out is not None:
+        out_stride = out.out_stride
+    if out_stride is None:
+        out_stride = entropy_slot_bytes(n_seq, n_lit, binned_offset)
+    out_stride = int(out_stride)
+    if out is None:
+        out = EncodedBatch(torch.zeros(out_stride + 16, dtype=torch.uint8, device=dev),
+                           torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
+                           torch.zeros(1, dtype=torch.int32, device=dev), out_stride)
+    assert out.bits.dtype == torch.uint8 and out.bits.is_contiguous() and out.bits.numel() >= out_stride
+    assert out.nbits.numel() == 1 and out.status.numel() == 1 and out.bit_offset.numel() == 1
+    need = entropy_wide_scratch_bytes(n_seq, n_lit)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert scratch.numel() >= need
+    nbits64 = torch.zeros(1, dtype=torch.int64, device=dev)
+    a = _lib.Lz77EntropyWideEncodeArgs(lc.data_ptr(), ml.data_ptr(), mo.data_ptr(), n_seq,
+                                       parsed.literals.data_ptr() + lit_off, n_lit, int(binned_offset), 0,
+                                       out.bits.data_ptr(), out_stride, nbits64.data_ptr(), out.status.data_ptr(),
+                                       scratch.data_ptr(), int(scratch.numel()))
+    handle = _stream_handle(stream, dev)
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_entropy_encode_wide(C.byref(a), handle)
+    _lib.check(rc, "scl_lz77_entropy_encode_wide")
+    with torch.cuda.device(dev), torch.cuda.stream(None if stream is None else torch.cuda.ExternalStream(handle, device=dev)):
+        out.nbits.copy_(nbits64.to(torch.int32))  # the low 32 bits, as the batch call's words
+        out.bit_offset.zero_()
+    out.nbits64 = nbits64
+    out._inputs = (parsed, scratch)  # read asynchronously: they live as long as the result
+    return out
+
+
+def decode_wide(bits, bit_offset: int, nbits: int, seq_cap: int, lit_cap: int, binned_offset: int = DEFAULT_BINNED_OFFSET,
+                scratch=None, stream=None, out: Optional[DecodedBatch] = None) -> DecodedBatch:
+    """``decode_batch`` for ONE stream on the whole GPU: the ``nbits`` bits from absolute bit ``bit_offset`` of ``bits`` (host
+    integers, any bit alignment) -> a one-stream :class:`DecodedBatch` (literals from ``literals[0]`` on; ``consumed`` is
+    int64 here, and ``sync_passes`` counts the decoder's extra passes).  SYNCHRONISING on ``stream``: the field positions
+    are read back as the call goes.  ``scratch``: at least ``entropy_wide_scratch_bytes(seq_cap, lit_cap, nbits)`` bytes."""
+    import torch
+
+    L = _lib.load()
+    assert bits.is_cuda and bits.dtype == torch.uint8 and bits.is_contiguous()
+    dev, seq_cap, lit_cap = bits.device, int(seq_cap), int(lit_cap)
+    if out is None:
+        rows = lambda: torch.zeros((1, seq_cap), dtype=torch.int32, device=dev)  # noqa: E731
+        out = DecodedBatch(rows(), rows(), rows(), torch.zeros(max(lit_cap, 1), dtype=torch.uint8, device=dev), None, None,
+                           None, torch.zeros(1, dtype=torch.int64, device=dev), seq_cap, None)
+    assert out.seq_cap == seq_cap and out.literal_count.shape == (1, seq_cap) and out.literals.numel() >= lit_cap
+    need = entropy_wide_scratch_bytes(seq_cap, lit_cap, nbits)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert scratch.numel() >= need
+    result = torch.zeros(6, dtype=torch.int32, device=dev)  # scl_lz77_entropy_wide_result
+    a = _lib.Lz77EntropyWideDecodeArgs(bits.data_ptr(), int(bits.numel()), int(bit_offset), int(nbits), int(binned_offset), 0,
+                                       seq_cap, lit_cap, out.literal_count.data_ptr(), out.match_length.data_ptr(),
+                                       out.match_offset.data_ptr(), out.literals.data_ptr(), result.data_ptr(),
+                                       scratch.data_ptr(), int(scratch.numel()))
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_entropy_decode_wide(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_entropy_decode_wide")
+    out.consumed, out.n_seq, out.n_lit = result[0:2].view(torch.int64), result[2:3], result[3:4]
+    out.status, out.sync_passes = result[4:5], result[5:6]
+    out._inputs = (bits, scratch, result)
+    return out
+
+
+def compress_wide(win, start: int, min_match_length: int, max_matches: int, seq_cap: Optional[int] = None,
+                  binned_offset: int = DEFAULT_BINNED_OFFSET, out_stride: Optional[int] = None, scratch=None, stream=None,
+                  out: Optional[EncodedBatch] = None):
+    """``parse_wide`` + ``encode_wide``: ONE window whose block starts at ``start`` -> (:class:`EncodedBatch` of one slot,
+    :class:`ParsedBatch`), the bits of ``compress_batch`` for a batch of this one stream.  The counts are read back once
+    between the two steps (they size the encoder's launches).  ``scratch`` serves both steps, one after the other: at least
+    ``wide_scratch_bytes(win.numel())`` and ``entropy_wide_scratch_bytes`` of the counts."""
+    parsed = parse_wide(win, start, min_match_length, max_matches, seq_cap=seq_cap, scratch=scratch, stream=stream)
+    return encode_wide(parsed, binned_offset, out_stride, lit_off=int(start), scratch=scratch, stream=stream, out=out), parsed
+
+
+def decompress_wide(bits, bit_offset: int, nbits: int, win, have: int, seq_cap: int,
+                    binned_offset: int = DEFAULT_BINNED_OFFSET, scratch=None, stream=None):
+    """``decode_wide`` + ``replay_wide``: appends the block to ``win``, which holds ``have`` bytes already.  The room left in
+    the window bounds the literals.  -> (out_len, status, consumed): status = the decoder's | the replay's."""
+    lit_cap = max(int(win.numel()) - int(have), 0)
+    decoded = decode_wide(bits, bit_offset, nbits, seq_cap, lit_cap, binned_offset, scratch=scratch, stream=stream)
+    n_seq, n_lit = (int(x) & 0xFFFFFFFF for x in decoded._inputs[2][2:4].cpu().tolist())
+    out_len, status = replay_wide(win, have, decoded.literal_count, decoded.match_length, decoded.match_offset, n_seq,
+                                  decoded.literals, n_lit, stream=stream)
     return out_len, status | decoded.status, decoded.consumed
 
 

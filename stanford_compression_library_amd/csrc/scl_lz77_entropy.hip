@@ -11,15 +11,11 @@
 // header.  The encoder knows every size before it stores a bit (histograms -> trees -> sizes), so a stream that does not
 // fit stores nothing; the decoder walks field after field and stops at its first fault.  No workgroup waits on another,
 // every loop is bounded by the data, and nothing outside a stream's own slot / input bits / rows / literal range is touched.
-#include "scl_lz77_huffman.h"
-#include "scl_lz77_internal.h"
+#include "scl_lz77_entropy_internal.h"
 
 namespace {
 
 #define LZE_THREADS SCL_WAVE
-#define LZE_FIELD_K 64u     // room for a sequence field's alphabet: 32 bins + binned_offset <= 32
-#define LZE_LIT_BASE (3 * LZE_FIELD_K)
-#define LZE_SYMS (LZE_LIT_BASE + 256u)
 #define LZE_STAGE_WORDS 96u  // 64 codewords of at most 43 bits behind at most 31 pending bits: 87 words
 #define LZE_MAX_GRID (1u << 20)
 
@@ -30,31 +26,6 @@ __device__ __forceinline__ u64 lze_wave_sum(u64 v) {
         v += ((u64)hi << 32) | lo;
     }
     return v;
-}
-
-// log-scale binning (lz77.py:237-264): v < o is its own bin, else bin o + floor(log2(v - o + 1)) and `log` residual bits.
-// A bin past the alphabet (o = 0 and v = 2^32 - 1: the reference's "too large") comes back as it is: the caller refuses it.
-__device__ __forceinline__ u32 lze_bin(u32 v, u32 o, u32 *log, u32 *residual) {
-    if (v < o) {
-        *log = 0;
-        *residual = 0;
-        return v;
-    }
-    const u64 x = (u64)v - o + 1;
-    const u32 l = 63u - (u32)__builtin_clzll(x);
-    *log = l;
-    *residual = (u32)(x - (1ull << l));
-    return o + l;
-}
-
-// Elias-delta codeword of c (elias_delta_uint_coder.py): y = c + 1, n = bit length of y - 1, l = bit length of (n + 1) - 1:
-// l zeros, n + 1 in l + 1 bits, the n low bits of y.  At most 43 bits for c < 2^32.
-__device__ __forceinline__ u32 lze_elias_delta(u32 c, u64 *val) {
-    const u64 y = (u64)c + 1;
-    const u32 n = 63u - (u32)__builtin_clzll(y);
-    const u32 l = 31u - (u32)__builtin_clz(n + 1);
-    *val = ((u64)(n + 1) << n) | (y - (1ull << n));
-    return 2 * l + 1 + n;
 }
 
 // ---- the wave's bit appender -----------------------------------------------------------------------------------------
@@ -108,15 +79,6 @@ struct LzeWriter {
     __device__ __forceinline__ void finish() {  // the last partial word, zero bits behind the stream
         if ((pos & 31) && lz_lane() == 0) store_word(pos >> 5, stage[0]);
     }
-};
-
-struct LzeSmallTree {
-    double prob[2 * LZE_FIELD_K];
-    u16 heap[LZE_FIELD_K], parent[2 * LZE_FIELD_K], leaf_sym[LZE_FIELD_K];
-};
-struct LzeBigTree {
-    double prob[2 * LZ_HUFF_MAX_K];
-    u16 heap[LZ_HUFF_MAX_K], parent[2 * LZ_HUFF_MAX_K], kids[2 * LZ_HUFF_MAX_K], leaf_sym[LZ_HUFF_MAX_K];
 };
 
 // ---- encode ----------------------------------------------------------------------------------------------------------
@@ -263,54 +225,7 @@ __global__ __launch_bounds__(LZE_THREADS) void lz77_entropy_encode(
 }
 
 // ---- decode ----------------------------------------------------------------------------------------------------------
-// bits [p, p + w) of the input, w <= 32; reads only the bytes that hold them
-__device__ __forceinline__ u32 lze_read_bits(const u8 *in, u64 p, u32 w) {
-    if (w == 0) return 0;
-    const u64 first = p >> 3, last = (p + w - 1) >> 3;
-    u64 acc = 0;
-    for (u64 i = first; i <= last; ++i) acc = (acc << 8) | in[i];
-    const u32 have = (u32)(last - first + 1) * 8;
-    return (u32)((acc >> (have - (u32)(p & 7) - w)) & (w == 32 ? 0xFFFFFFFFull : (1ull << w) - 1));
-}
-
-// one lane's forward cursor over a section of `left` bits: never loads a byte that holds no bit of the section, and the
-// caller never takes more than `left`
-struct LzeCursor {
-    const u8 *in;
-    u64 next_byte, last_byte, buf, left;
-    u32 nbuf;
-
-    __device__ __forceinline__ void init(const u8 *in_, u64 p, u64 nbits) {
-        in = in_;
-        left = nbits;
-        buf = 0;
-        nbuf = 0;
-        next_byte = 1;
-        last_byte = 0;
-        if (nbits == 0) return;
-        next_byte = p >> 3;
-        last_byte = (p + nbits - 1) >> 3;
-        const u32 skip = (u32)(p & 7);
-        buf = (u64)in[next_byte++] << (56 + skip);
-        nbuf = 8 - skip;
-    }
-    __device__ __forceinline__ void refill() {
-        while (nbuf <= 56 && next_byte <= last_byte) {
-            buf |= (u64)in[next_byte++] << (56 - nbuf);
-            nbuf += 8;
-        }
-    }
-    __device__ __forceinline__ u32 get(u32 w) {  // w <= 32, w <= left
-        if (w == 0) return 0;
-        if (nbuf < w) refill();
-        const u32 v = (u32)(buf >> (64 - w));
-        buf <<= w;
-        nbuf -= w;
-        left -= w;
-        return v;
-    }
-};
-
+// (lze_read_bits and the one-lane cursor LzeCursor: scl_lz77_entropy_internal.h)
 __global__ __launch_bounds__(LZE_THREADS) void lz77_entropy_decode(
     const u8 *in, u64 in_size_bytes, const u64 *bit_off, const u32 *in_nbits, u64 n_streams, u32 seq_cap, u32 o,
     u32 *lit_count, u32 *match_len, u32 *match_off, u32 *n_seq_out, u8 *literals, u64 lit_bytes, const u64 *lit_off,

@@ -36,32 +36,16 @@
 // exits.  Both far below the 40 KiB that four workgroups per CU allow (160 KiB per CU).
 #include <string.h>
 
+#include "scl_bit_block.h"
 #include "scl_entry.h"
 #include "scl_prefix_internal.h"
 #include "scl_scan.h"
 
-#define PFB_THREADS 256
-#define PFB_PER_THREAD 16u
-#define PFB_TILE (PFB_THREADS * PFB_PER_THREAD)  // 4096 symbols: <= 131072 bits = 4096 words (+ 2 for the offset)
-#define PFB_TILE_WORDS (PFB_TILE * PF_MAX_LEN / 32u + 2u)
-#define PFB_SUB 128u                     // S: bits per decoder thread (>= 32: a codeword spans at most two)
-#define PFB_GROUP (PFB_THREADS * PFB_SUB)  // W: bits per decoder workgroup
-#define PFB_WIN_WORDS (PFB_GROUP / 32u + 4u)  // a walk ends before W + 64; + 31 bits of offset, + 1 word of lookahead
-#define PFB_SCAN_THREADS 1024
-#define PFB_NONE64 0xFFFFFFFFFFFFFFFFull
-
-// how a thread's walk over its subsequence ended
-#define PFB_END_EXIT 0u   // at a codeword boundary at or past the end of the subsequence (or at the end of the stream)
-#define PFB_END_TRUNC 1u  // in_nbits cuts the codeword that starts at `end`
-#define PFB_END_STATE 2u  // the codeword that starts at `end` walks into a missing child
-// one u32 per subsequence: start - i*S (0..31) | symbols << 6 (0..128) | how it ended << 15 | (end - i*S) << 17 (0..159)
-#define PFB_PACK(start_off, count, kind, end_off) ((start_off) | ((count) << 6) | ((kind) << 15) | ((end_off) << 17))
+static_assert(PFB_MAX_LEN == PF_MAX_LEN, "a tile's LDS words are sized by the longest codeword");
 
 // ---- encode ---------------------------------------------------------------------------------------------------------------
-struct PfbEncScratch {  // head of the encoder's scratch; u64 tile_bits[n_tiles] follows at byte 64
-    u32 fits;           // written by pfb_scan_tiles: the stream fits out_cap_bytes
-    u32 tail_word;      // the output word that out_cap_bytes cuts, in memory byte order
-};
+// (the shapes, PfbEncScratch -- the head of the encoder's scratch; u64 tile_bits[n_tiles] follows at byte 64 -- and the tile
+// emitter: scl_bit_block.h)
 
 // the {code, len} of the thread's PFB_PER_THREAD consecutive symbols (len 0 past the end of the block)
 template <typename SYM>
@@ -154,46 +138,14 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
     for (u32 i = tid; i < PFB_TILE_WORDS; i += PFB_THREADS) s_words[i] = 0;
     __syncthreads();
     uint2 e[PFB_PER_THREAD];
-    u32 bad = 0, tile_total;
+    u32 bad = 0;
     const u32 bits = pfb_load_codes<SYM>(P, s_enc, sym, n, (u64)blockIdx.x * PFB_TILE + tid * PFB_PER_THREAD, e, bad);
-    const u32 mine = scl_block_scan_excl<u32, PFB_THREADS, SclScanSum>(bits, s_wave, &tile_total);
-    const u64 base = tile_off[blockIdx.x];
-    const u32 r = (u32)(base & 31u);
-    // the thread's codewords are contiguous bits: whole words leave as they fill; the first and the last one are shared
-    // with the neighbouring threads, so every word is ORed in
-    u32 wi = (r + mine) >> 5, nacc = (r + mine) & 31u;
-    u64 acc = 0;
-#pragma unroll
-    for (u32 j = 0; j < PFB_PER_THREAD; ++j) {
-        if (e[j].y == 0) continue;
-        acc = (acc << e[j].y) | e[j].x;
-        nacc += e[j].y;
-        if (nacc >= 32) {
-            atomicOr(&s_words[wi++], (u32)(acc >> (nacc - 32)));
-            nacc -= 32;
-        }
-    }
-    if (nacc && bits) atomicOr(&s_words[wi], (u32)(acc << (32 - nacc)));
-    __syncthreads();
-    const u32 n_words = (r + tile_total + 31) >> 5;  // <= PFB_TILE_WORDS - 1
-    const u64 word0 = base >> 5;
-    for (u32 w = tid; w < n_words; w += PFB_THREADS) {
-        const u32 v = scl_bswap32(s_words[w]);
-        const u64 index = word0 + w;
-        u32 *dst = index == tail_index ? &head->tail_word : out32 + index;
-        if (w == 0 || w + 1 == n_words) {
-            if (v) atomicOr(dst, v);  // a word this tile may share with its neighbours
-        } else {
-            *dst = v;
-        }
-    }
+    pfb_emit_tile(e, bits, tile_off[blockIdx.x], s_words, s_wave, head, out32, tail_index);
 }
 
 __global__ void pfb_encode_tail_kernel(const PfbEncScratch *__restrict__ head, const u64 *__restrict__ nbits,
                                        u8 *__restrict__ out, u64 out_cap_bytes) {
-    if (!head->fits || ((*nbits + 31) >> 5) <= (out_cap_bytes >> 2)) return;  // nothing written, or not as far as that word
-    const u32 v = head->tail_word;
-    for (u64 b = out_cap_bytes & ~3ull; b < out_cap_bytes; ++b) out[b] = (u8)(v >> (8 * (b & 3)));
+    pfb_store_tail(head, *nbits, out, out_cap_bytes);
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------
@@ -212,31 +164,7 @@ struct PfbDecScratch {  // device pointers into the scratch
     u64 *group_end;     // [n_groups] PFB_NONE64, or (position of the codeword that ends the stream) << 2 | PFB_END_*
 };
 
-// the input a workgroup can reach, in LDS: big-endian words from the one that holds the workgroup's first bit, one pad word
-// per 32 (threads read S / 32 = 4 words apart: without it four lanes of every eight share a bank)
-#define PFB_WIN_AT(i) ((i) + ((i) >> 5))
-#define PFB_WIN_LDS (PFB_WIN_WORDS + PFB_WIN_WORDS / 32 + 1)
-
-__device__ __forceinline__ void pfb_load_window(u32 *s_win, const u8 *__restrict__ in, u64 in_size_bytes, u64 first_bit) {
-    const u64 word0 = first_bit >> 5;
-    for (u32 i = threadIdx.x; i < PFB_WIN_WORDS; i += PFB_THREADS) {
-        const u64 b = (word0 + i) * 4;
-        u32 v = 0;
-        if (b + 4 <= in_size_bytes) {
-            v = scl_bswap32(*reinterpret_cast<const u32 *>(in + b));
-        } else {
-            for (u32 k = 0; k < 4; ++k) v = (v << 8) | (b + k < in_size_bytes ? (u32)in[b + k] : 0u);
-        }
-        s_win[PFB_WIN_AT(i)] = v;
-    }
-}
-
-// the 32 bits from bit `pos` of the window (pos counts from the first bit of the window's first word), left-aligned
-__device__ __forceinline__ u32 pfb_peek(const u32 *s_win, u32 pos) {
-    const u32 i = pos >> 5, o = pos & 31u;
-    const u64 two = ((u64)s_win[PFB_WIN_AT(i)] << 32) | s_win[PFB_WIN_AT(i + 1)];
-    return (u32)((two << o) >> 32);
-}
+// (the input window a workgroup can reach, pfb_load_window / pfb_peek: scl_bit_block.h)
 
 // One codeword from the left-aligned `bits`, of which `rem` >= 1 belong to the stream.  Exactly what the one-lane
 // decoders of scl_prefix.hip decide: PFB_END_EXIT (a symbol of `len` bits), PFB_END_TRUNC, PFB_END_STATE.

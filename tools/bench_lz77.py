@@ -5,13 +5,18 @@ scaled to the batch.  Recorded, not gated: profiles/lz77_bench.txt.
 
     python tools/bench_lz77.py [--streams 4096] [--stream-kib 64] [--single-mib 16] [--steps 20] [--warmup 5]
                                [--single-steps N] [--single-warmup N] [--host-streams 64] [--out FILE]
-    python tools/bench_lz77.py --wide [--wide-kib 64,256,1024,4096,16384] [--out FILE]
+    python tools/bench_lz77.py --wide [--wide-kib 64,256,1024,4096,16384] [--wide-stages lz,entropy] [--out FILE]
 
 --wide times ONE stream on both paths in the same run -- the one-wave kernels (parse_batch / replay_batch of a batch of
 one) and the wide ones (parse_wide phase by phase, replay_wide) -- on the Markov source and on all-equal bytes, checks
 that both paths store the same sequences and literals and that the replay restores the input, and prints the ratios
 scl_lz77_wide_threshold() and the 10x gate at the largest size are read from.  The step count follows the time of a call:
-3 timed steps for a call of more than a second, up to 15 for short ones.
+3 timed steps for a call of more than a second, up to 15 for short ones.  The entropy stage of the same stream follows
+(--wide-stages picks either half): encode_batch / decode_batch of the one-stream batch beside encode_wide / decode_wide on
+the same ParsedBatch -- HIP events for the encoders, the wall clock around the call for the decoders (decode_wide
+synchronises) -- with the bits and the decoded rows compared at every size, a 10x gate of its own at the largest size, and
+the stream size -- in coded values, 3 n_seq + n_lit: what the stage's work depends on -- from which both wide calls win on
+both sources: scl_lz77_entropy_wide_threshold() is read from that line.
 
 Data: the first-order Markov source of bench_data.py over 16 symbols, one chain per stream (generated on the device).  The
 single stream is the first --single-mib MiB of the very same bytes, read as ONE window: its parse is one wavefront.
@@ -151,6 +156,99 @@ def timed_to_fit(fn):
     return statistics.median(ms), steps
 
 
+def timed_wall_to_fit(fn):
+    """timed_to_fit by the wall clock around fn, the device idle before and after: for calls that synchronise"""
+    def once():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    first = once()
+    steps = 3 if first > 1000 else 7 if first > 50 else 15
+    if first <= 1000:
+        once()
+    return statistics.median([once() for _ in range(steps)]), steps
+
+
+def wide_entropy_rows(source, win, dev):
+    """the entropy stage of one stream of win.numel() bytes on both paths -> (lines, dict of medians in ms)"""
+    n = int(win.numel())
+    name = f"{source} 1 x {n >> 10} KiB"
+    parsed = lz77.parse_wide(win, 0, L, M)
+    torch.cuda.synchronize()
+    n_seq, n_lit = int(parsed.n_seq[0]), int(parsed.n_lit[0])
+    stride = lz77.entropy_slot_bytes(n_seq, n_lit)
+    one = lz77.encode_batch(parsed, out_stride=stride)
+    scratch = torch.empty(lz77.entropy_wide_scratch_bytes(parsed.seq_cap, n, 8 * stride), dtype=torch.uint8, device=dev)
+    wide = lz77.encode_wide(parsed, out_stride=stride, n_seq=n_seq, n_lit=n_lit, lit_off=0, scratch=scratch)
+    torch.cuda.synchronize()
+    nbits = int(one.nbits[0]) & 0xFFFFFFFF
+    same_bits = bool(int(one.status[0]) == 0 and int(wide.status[0]) == 0 and int(wide.nbits64[0]) == nbits and
+                     torch.equal(one.bits[: (nbits + 7) // 8], wide.bits[: (nbits + 7) // 8]))
+    lit_cap = torch.full((1,), n, dtype=torch.int32, device=dev)
+    dec_one = lz77.decode_batch(one.bits, one.bit_offset, one.nbits, parsed.seq_cap, parsed.lit_off, lit_cap)
+    dec_wide = lz77.decode_wide(wide.bits, 0, nbits, parsed.seq_cap, n, scratch=scratch)
+    calls = (("one-wave encode", timed_to_fit, lambda: lz77.encode_batch(parsed, out=one)),
+             ("wide encode", timed_to_fit, lambda: lz77.encode_wide(parsed, n_seq=n_seq, n_lit=n_lit, lit_off=0, scratch=scratch,
+                                                                    out=wide)),
+             ("one-wave decode", timed_wall_to_fit, lambda: lz77.decode_batch(one.bits, one.bit_offset, one.nbits, parsed.seq_cap,
+                                                                              parsed.lit_off, lit_cap, out=dec_one)),
+             ("wide decode", timed_wall_to_fit, lambda: lz77.decode_wide(wide.bits, 0, nbits, parsed.seq_cap, n, scratch=scratch,
+                                                                         out=dec_wide)))
+    med, lines = {}, []
+    for what, timer, fn in calls:
+        med[what], steps = timer(fn)
+        lines.append(f"{name:26s} {what:16s}: median {med[what]:10.3f} ms over {steps:2d} steps  "
+                     f"{n / med[what] / 1e6:9.4f} GB/s of input")
+        print(lines[-1], flush=True)
+    torch.cuda.synchronize()
+    same_rows = bool(int(dec_one.status[0]) == 0 and int(dec_wide.status[0]) == 0 and int(dec_wide.n_seq[0]) == n_seq and
+                     int(dec_wide.n_lit[0]) == n_lit and int(dec_wide.consumed[0]) == nbits and
+                     int(dec_one.consumed[0]) & 0xFFFFFFFF == nbits and
+                     all(torch.equal(a[0, :n_seq], b[0, :n_seq]) and torch.equal(a[0, :n_seq], c[0, :n_seq])
+                         for a, b, c in ((dec_wide.literal_count, dec_one.literal_count, parsed.literal_count),
+                                         (dec_wide.match_length, dec_one.match_length, parsed.match_length),
+                                         (dec_wide.match_offset, dec_one.match_offset, parsed.match_offset))) and
+                     torch.equal(dec_wide.literals[:n_lit], dec_one.literals[:n_lit]) and
+                     torch.equal(dec_wide.literals[:n_lit], parsed.literals[:n_lit]))
+    lines.append(f"{name:26s} {n_seq} sequences, {n_lit} literals, {nbits} bits; one-wave / wide: encode "
+                 f"{med['one-wave encode'] / med['wide encode']:.2f}x, decode {med['one-wave decode'] / med['wide decode']:.2f}x; "
+                 f"sync_passes {int(dec_wide.sync_passes[0])}; identical bits: {'yes' if same_bits else 'NO'}, identical decoded "
+                 f"rows and literals (both paths, and the parse's): {'yes' if same_rows else 'NO'}")
+    print(lines[-1], flush=True)
+    med["values"] = 3 * n_seq + n_lit
+    return lines, med
+
+
+def run_wide_entropy(sizes_kib, sources, dev):
+    lines = [f"lz77 wide entropy bench: ONE stream, scl_lz77_entropy_*_batch on a batch of one vs scl_lz77_entropy_*_wide in the "
+             f"same run; binned_offset {lz77.DEFAULT_BINNED_OFFSET}, threshold {lz77.entropy_wide_threshold()} coded values; encoders: "
+             f"HIP events, decoders: wall clock around the call", f"kernels: {', '.join(lz77.entropy_kernel_names())} vs "
+             f"{', '.join(lz77.entropy_wide_kernel_names())}"]
+    print("\n".join(lines), flush=True)
+    ratios, values = {}, {}
+    for source, data in sources:
+        for kib in sizes_kib:
+            rows, med = wide_entropy_rows(source, data[: kib << 10].contiguous(), dev)
+            lines += rows
+            ratios[(source, kib)] = (med["one-wave encode"] / med["wide encode"], med["one-wave decode"] / med["wide decode"])
+            values[(source, kib)] = med["values"]
+    kib = max(sizes_kib)
+    e, d = ratios[("markov", kib)]
+    lines.append(f"entropy gate at {kib} KiB on the Markov source: wide encode {e:.1f}x, wide decode {d:.1f}x the one-wave kernels "
+                 f"(10x each is asked): {'met' if e >= 10 and d >= 10 else 'MISSED'}")
+    # by the size of the STREAM, 3 n_seq + n_lit coded values: the block's bytes do not say how much there is to code
+    ok = [v for v in values.values() if all(min(ratios[k]) > 1 for k in ratios if values[k] >= v)]
+    lost = [values[k] for k in ratios if min(ratios[k]) <= 1]
+    lines.append((f"both wide entropy calls are faster on every measured stream of at least {min(ok)} coded values (3 n_seq + "
+                  f"n_lit)" if ok else "the wide entropy calls are not both faster on the largest measured stream") +
+                 (f"; the largest measured stream on which one of them loses has {max(lost)}" if lost else "; none loses"))
+    print("\n".join(lines[-2:]), flush=True)
+    return lines
+
+
 def wide_shape_rows(source, win, dev):
     """one stream of win.numel() bytes on both paths -> (lines, dict of medians in ms)"""
     n = int(win.numel())
@@ -203,15 +301,24 @@ def wide_shape_rows(source, win, dev):
     return lines, med
 
 
-def run_wide(sizes_kib, dev):
+def run_wide(sizes_kib, dev, stages=("lz", "entropy")):
+    top = max(sizes_kib) << 10
+    markov = bench_data.markov1_chunks_device(16, max(top >> 16, 1), min(top, 1 << 16), 77, dev).reshape(-1)
+    sources = (("markov", markov), ("all-equal", torch.full((top,), 7, dtype=torch.uint8, device=dev)))
+    lines = []
+    if "lz" in stages:
+        lines += run_wide_lz(sizes_kib, sources, dev)
+    if "entropy" in stages:
+        lines += run_wide_entropy(sizes_kib, sources, dev)
+    return lines
+
+
+def run_wide_lz(sizes_kib, sources, dev):
     tile, cap = lz77.wide_shape()
     lines = [f"lz77 wide bench: ONE stream, one-wave kernels vs wide kernels in the same run; min_match_length {L}, "
              f"max_num_matches_considered {M}, tile {tile}, cap {cap}, threshold {lz77.wide_threshold()} bytes, HIP events, "
              f"{torch.cuda.get_device_name(0)}", f"kernels: {', '.join(lz77.wide_kernel_names())}"]
     print("\n".join(lines), flush=True)
-    top = max(sizes_kib) << 10
-    markov = bench_data.markov1_chunks_device(16, max(top >> 16, 1), min(top, 1 << 16), 77, dev).reshape(-1)
-    sources = (("markov", markov), ("all-equal", torch.full((top,), 7, dtype=torch.uint8, device=dev)))
     ratios = {}
     for source, data in sources:
         for kib in sizes_kib:
@@ -243,11 +350,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--wide", action="store_true")
     ap.add_argument("--wide-kib", default="64,256,1024,4096,16384")
+    ap.add_argument("--wide-stages", default="lz,entropy")
     args = ap.parse_args()
     lib.require_device()
     dev = torch.device("cuda:0")
     if args.wide:
-        text = "\n".join(run_wide([int(k) for k in args.wide_kib.split(",")], dev))
+        text = "\n".join(run_wide([int(k) for k in args.wide_kib.split(",")], dev, tuple(args.wide_stages.split(","))))
         if args.out:
             with open(args.out, "w") as f:
                 f.write(text + "\n")
