@@ -471,6 +471,80 @@ int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, const u
                          const uint32_t *h_match_len, const uint32_t *h_match_off, uint64_t n_seq,
                          const uint8_t *h_literals, uint64_t n_lit, uint64_t *out_len);
 
+/* ---- LZ77 with a sliding window: hash-bucket index, lazy parse, windowed replay (scl_lz77_sliding.hip; added to ABI 8) ----
+ *   scl_lz77_sliding_parse_batch   <->  LZ77SlidingWindowEncoder.lz77_parse_and_generate_sequences with a
+ *                                       HashBasedMatchFinder                     scl/compressors/lz77_sliding_window.py
+ *   scl_lz77_sliding_replay_batch  <->  LZ77SlidingWindowDecoder.execute_lz77_sequences
+ * The batch layout, the outputs and the statuses are those of scl_lz77_parse_batch / scl_lz77_replay_batch; the sequences
+ * go through the same entropy stage.  One wavefront per stream.
+ *   parse : hl = hash_length (1..8), m = hash_table_size (1 <= m < 2^32), C = max_chain_length (1..64), mml =
+ *           min_match_length (>= 1), W = window_size (0: no bound).  bucket(p) = the reference's hash(tuple(w[p..p+hl))) % m
+ *           (CPython's tuple hash: scl_lz77_sliding_bucket_host).  The candidates of p at horizon T are the C newest q < T
+ *           of p's bucket; those with p - q > W are skipped but counted.  A candidate is extended right (up to the end of
+ *           the window, over p if it comes to that) and then left while the bytes in front are equal, down to the start E
+ *           of the lookahead and to position max(0, E - W) + 1 of the source; the longest wins, the newest on ties.  From E
+ *           the first p whose best match has mml bytes or more is taken (T = p); if `lazy`, the positions behind it are
+ *           tried at the SAME horizon while each beats the best so far.  The sequence is (literals, length, offset), and
+ *           a lookahead without such a p gives literal-only sequences (k, 0, 0): DESIGN.md 3.6.4 has the rule in full.
+ *           A block yields at most block_len / mml + 2 sequences.  The index phase sorts all positions by (stream, bucket)
+ *           and marks those with a predecessor in their bucket within W.
+ *   replay: as scl_lz77_replay_batch, except that a sequence with match_length 0 copies nothing and its offset is not
+ *           looked at, and that an offset above min(W, bytes so far) is SCL_ST_STATE (W = 0: no bound).
+ * Both are asynchronous on `stream`.  SCL_E_PARAM before any device call: a null pointer, hl outside 1..8, m = 0 or
+ * m >= 2^32, C outside 1..64, mml = 0, total_bytes or n_streams >= 2^32, scratch misaligned (256 bytes) or smaller than
+ * scl_lz77_sliding_scratch_bytes. */
+typedef struct scl_lz77_sliding_parse_args {
+    const uint8_t *d_win;
+    const uint64_t *d_win_off; /* [n_streams + 1] */
+    const uint32_t *d_start;   /* [n_streams]     */
+    uint64_t n_streams;
+    uint64_t total_bytes;      /* bytes of d_win and of d_literals */
+    uint64_t hash_table_size;
+    uint32_t hash_length, max_chain_length;
+    uint32_t lazy, min_match_length;
+    uint32_t window_size, seq_cap;
+    uint32_t phases, reserved; /* phases: as scl_lz77_parse_args */
+    uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_streams * seq_cap] each */
+    uint8_t *d_literals;
+    uint32_t *d_n_seq, *d_n_lit, *d_status; /* [n_streams] each */
+    void *d_scratch;
+    uint64_t scratch_bytes;
+} scl_lz77_sliding_parse_args;
+
+typedef struct scl_lz77_sliding_replay_args {
+    uint8_t *d_win;
+    const uint64_t *d_win_off; /* [n_streams + 1]: the slots */
+    const uint32_t *d_have;    /* [n_streams]: bytes already in each slot */
+    uint64_t n_streams;
+    uint64_t total_bytes;      /* bytes of d_win */
+    uint32_t seq_cap, window_size;
+    const uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_streams * seq_cap] each */
+    const uint32_t *d_n_seq;
+    const uint8_t *d_literals;
+    uint64_t lit_bytes;
+    const uint64_t *d_lit_off; /* [n_streams] */
+    const uint32_t *d_n_lit;
+    uint32_t *d_out_len, *d_status;
+} scl_lz77_sliding_replay_args;
+
+uint64_t scl_lz77_sliding_scratch_bytes(uint64_t total_bytes, uint64_t n_streams);
+int scl_lz77_sliding_parse_batch(const scl_lz77_sliding_parse_args *args, void *stream);
+int scl_lz77_sliding_replay_batch(const scl_lz77_sliding_replay_args *args, void *stream);
+/* the kernels that carry the index (its scatter pass), the parse and the replay, as scl_lz77_kernel_names.  The scatter
+   kernel is one template on the digit source for both LZ77 coders: a trace prints the name followed by its argument. */
+int scl_lz77_sliding_kernel_names(char *index, char *parse, char *replay, uint64_t cap);
+/* bucket of the gram gram[0..hl): the function the kernels use, on the host.  0 for a null gram, hl outside 1..8 or m = 0 */
+uint32_t scl_lz77_sliding_bucket_host(const uint8_t *gram, uint32_t hl, uint32_t m);
+/* one stream in host memory, as scl_lz77_parse_host / scl_lz77_replay_host (always on one wavefront) */
+int scl_lz77_sliding_parse_host(const uint8_t *h_window, uint64_t n, uint64_t start, uint32_t hash_length,
+                                uint64_t hash_table_size, uint32_t max_chain_length, uint32_t lazy,
+                                uint32_t min_match_length, uint32_t window_size, uint32_t *h_lit_count,
+                                uint32_t *h_match_len, uint32_t *h_match_off, uint64_t seq_cap, uint64_t *n_seq,
+                                uint8_t *h_literals, uint64_t lit_cap, uint64_t *n_lit);
+int scl_lz77_sliding_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, uint32_t window_size,
+                                 const uint32_t *h_lit_count, const uint32_t *h_match_len, const uint32_t *h_match_off,
+                                 uint64_t n_seq, const uint8_t *h_literals, uint64_t n_lit, uint64_t *out_len);
+
 /* ---- LZ77: one large stream across the whole GPU (scl_lz77_wide.hip; added to ABI 8 as above) ---------------------------
  * scl_lz77_parse_batch / scl_lz77_replay_batch give every stream one wavefront: right for thousands of streams, serial
  * for one.  These two calls take ONE stream and use the whole chip; what they store is what the batch calls store for a

@@ -68,6 +68,26 @@ class Lz77ReplayArgs(C.Structure):
                 ("d_n_lit", C.c_void_p), ("d_out_len", C.c_void_p), ("d_status", C.c_void_p)]
 
 
+class Lz77SlidingParseArgs(C.Structure):
+    """scl_lz77_sliding_parse_args"""
+    _fields_ = [("d_win", C.c_void_p), ("d_win_off", C.c_void_p), ("d_start", C.c_void_p), ("n_streams", C.c_uint64),
+                ("total_bytes", C.c_uint64), ("hash_table_size", C.c_uint64), ("hash_length", C.c_uint32),
+                ("max_chain_length", C.c_uint32), ("lazy", C.c_uint32), ("min_match_length", C.c_uint32),
+                ("window_size", C.c_uint32), ("seq_cap", C.c_uint32), ("phases", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p),
+                ("d_literals", C.c_void_p), ("d_n_seq", C.c_void_p), ("d_n_lit", C.c_void_p), ("d_status", C.c_void_p),
+                ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
+
+
+class Lz77SlidingReplayArgs(C.Structure):
+    """scl_lz77_sliding_replay_args"""
+    _fields_ = [("d_win", C.c_void_p), ("d_win_off", C.c_void_p), ("d_have", C.c_void_p), ("n_streams", C.c_uint64),
+                ("total_bytes", C.c_uint64), ("seq_cap", C.c_uint32), ("window_size", C.c_uint32),
+                ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p), ("d_match_off", C.c_void_p),
+                ("d_n_seq", C.c_void_p), ("d_literals", C.c_void_p), ("lit_bytes", C.c_uint64), ("d_lit_off", C.c_void_p),
+                ("d_n_lit", C.c_void_p), ("d_out_len", C.c_void_p), ("d_status", C.c_void_p)]
+
+
 class Lz77WideParseArgs(C.Structure):
     """scl_lz77_wide_parse_args"""
     _fields_ = [("d_win", C.c_void_p), ("n", C.c_uint64), ("start", C.c_uint64), ("min_match_length", C.c_uint32),
@@ -193,6 +213,15 @@ _SIGNATURES = {
     "scl_lz77_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
     "scl_lz77_parse_host": (_int, [_u8p, _u64, _u64, _u32, _u32, _u32p, _u32p, _u32p, _u64, _u64p, _u8p, _u64, _u64p]),
     "scl_lz77_replay_host": (_int, [_u8p, _u64, _u64, _u32p, _u32p, _u32p, _u64, _u8p, _u64, _u64p]),
+    # LZ77 with a sliding window: hash-bucket index, lazy parse, windowed replay (scl_lz77_sliding.hip)
+    "scl_lz77_sliding_scratch_bytes": (_u64, [_u64, _u64]),
+    "scl_lz77_sliding_parse_batch": (_int, [C.POINTER(Lz77SlidingParseArgs), _vp]),
+    "scl_lz77_sliding_replay_batch": (_int, [C.POINTER(Lz77SlidingReplayArgs), _vp]),
+    "scl_lz77_sliding_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
+    "scl_lz77_sliding_bucket_host": (_u32, [_u8p, _u32, _u32]),
+    "scl_lz77_sliding_parse_host": (_int, [_u8p, _u64, _u64, _u32, _u64, _u32, _u32, _u32, _u32, _u32p, _u32p, _u32p, _u64,
+                                           _u64p, _u8p, _u64, _u64p]),
+    "scl_lz77_sliding_replay_host": (_int, [_u8p, _u64, _u64, _u32, _u32p, _u32p, _u32p, _u64, _u8p, _u64, _u64p]),
     # LZ77: one large stream across the whole GPU (scl_lz77_wide.hip)
     "scl_lz77_wide_scratch_bytes": (_u64, [_u64]),
     "scl_lz77_wide_replay_scratch_bytes": (_u64, [_u64, _u64]),

@@ -11,7 +11,11 @@ Two call shapes, as in :mod:`.models`:
   ``encode_batch`` / ``decode_batch`` turn their sequences and literals into block bits and back, ``compress_batch`` /
   ``decompress_batch`` do both steps.  No call loops over streams on the host;
 * ``encode_wide`` / ``decode_wide`` -- that entropy stage for ONE stream on the whole GPU (csrc/scl_lz77_entropy_wide.hip),
-  the same bits; ``compress_wide`` / ``decompress_wide`` = ``parse_wide`` + ``encode_wide`` / ``decode_wide`` + ``replay_wide``.
+  the same bits; ``compress_wide`` / ``decompress_wide`` = ``parse_wide`` + ``encode_wide`` / ``decode_wide`` + ``replay_wide``;
+* ``sliding_parse_host`` / ``sliding_replay_host`` / ``sliding_parse_batch`` / ``sliding_replay_batch`` /
+  ``sliding_compress_batch`` / ``sliding_decompress_batch`` -- the same shapes for the sliding-window coder
+  (csrc/scl_lz77_sliding.hip: hash-bucket index, lazy parse, windowed replay); its :class:`ParsedBatch` goes through the
+  same ``encode_batch``.
 
 A batch is ``n_streams`` windows laid out one after another in one uint8 tensor; ``win_off`` (int64, ``n_streams + 1``
 entries) says where each starts.  uint32 / uint64 arrays of the C ABI travel as int32 / int64 tensors (the bit patterns).
@@ -573,3 +577,193 @@ def kernel_names():
     bufs = [C.create_string_buffer(128) for _ in range(3)]
     _lib.check(_lib.load().scl_lz77_kernel_names(*bufs, 128), "scl_lz77_kernel_names")
     return tuple(b.value.decode() for b in bufs)
+
+
+# ---- sliding window: hash-bucket index, lazy parse, windowed replay (csrc/scl_lz77_sliding.hip) -------------------------------
+MAX_HASH_LENGTH = 8          # a gram is hashed from at most 8 bytes
+MAX_HASH_TABLE_SIZE = (1 << 32) - 1  # a bucket number is 32-bit
+MAX_CHAIN_LENGTH = 64        # one candidate per lane of a wavefront
+
+
+@dataclass(frozen=True)
+class SlidingParams:
+    """``HashBasedMatchFinder``'s five parameters and the coder's window size (0: no bound), with the reference's defaults"""
+
+    hash_length: int = 4
+    hash_table_size: int = 1000000
+    max_chain_length: int = 64
+    lazy: bool = True
+    min_match_length: int = 4
+    window_size: int = 1000000
+
+    def _c(self):
+        return (int(self.hash_length), int(self.hash_table_size), int(self.max_chain_length), int(bool(self.lazy)),
+                int(self.min_match_length), int(self.window_size))
+
+
+def sliding_seq_cap(block_len: int, min_match_length: int) -> int:
+    """sequences a block can produce at most: every match covers at least ``min_match_length`` bytes, and the end of a
+    block adds up to two literal-only sequences"""
+    return int(block_len) // max(int(min_match_length), 1) + 2
+
+
+def sliding_scratch_bytes(total_bytes: int, n_streams: int) -> int:
+    return int(_lib.load().scl_lz77_sliding_scratch_bytes(int(total_bytes), int(n_streams)))
+
+
+def sliding_kernel_names():
+    """-> (index, parse, replay) kernel names of the sliding-window coder as a kernel trace prints them"""
+    bufs = [C.create_string_buffer(128) for _ in range(3)]
+    _lib.check(_lib.load().scl_lz77_sliding_kernel_names(*bufs, 128), "scl_lz77_sliding_kernel_names")
+    return tuple(b.value.decode() for b in bufs)
+
+
+def sliding_bucket(gram, hash_table_size: int) -> int:
+    """the bucket of a gram of 1..8 bytes: ``hash(tuple(gram)) % hash_table_size`` of a 64-bit CPython, computed by the
+    function the kernels use.  Needs no device."""
+    gram = np.ascontiguousarray(gram, np.uint8)
+    if not 1 <= gram.size <= MAX_HASH_LENGTH or not 1 <= int(hash_table_size) <= MAX_HASH_TABLE_SIZE:
+        raise ValueError("a gram of 1..8 bytes and 1 <= hash_table_size < 2^32")
+    return int(_lib.load().scl_lz77_sliding_bucket_host(_lib.u8_ptr(gram), int(gram.size), int(hash_table_size)))
+
+
+def sliding_parse_host(window: np.ndarray, start: int, params: SlidingParams = SlidingParams()):
+    """``parse_host`` for the sliding-window coder (always one wavefront).  window: uint8 array = history + block, the block
+    starts at ``start``.  -> (literal_count, match_length, match_offset: uint32 arrays; literals: uint8 array)"""
+    L = _lib.load()
+    window = np.ascontiguousarray(window, np.uint8)
+    n, start = int(window.size), int(start)
+    cap = sliding_seq_cap(n - start, params.min_match_length)
+    seq = np.zeros((3, cap), np.uint32)
+    literals = np.zeros(max(n - start, 1), np.uint8)
+    n_seq, n_lit = C.c_uint64(0), C.c_uint64(0)
+    hl, m, chain, lazy, mml, W = params._c()
+    if not (0 <= hl < 1 << 32 and 0 <= m < 1 << 64 and 0 <= chain < 1 << 32 and 0 <= mml < 1 << 32 and 0 <= W < 1 << 32):
+        raise ValueError("the sliding-window parameters are unsigned 32-bit integers (hash_table_size: 64-bit)")
+    rc = L.scl_lz77_sliding_parse_host(_lib.u8_ptr(window), n, start, hl, m, chain, lazy, mml, W, _lib.u32_ptr(seq[0]),
+                                       _lib.u32_ptr(seq[1]), _lib.u32_ptr(seq[2]), cap, C.byref(n_seq),
+                                       _lib.u8_ptr(literals), n - start, C.byref(n_lit))
+    if rc != _lib.E_PARAM:  # a refused parameter is reported as such, device or not
+        _lib.require_device()
+    _lib.check(rc, "scl_lz77_sliding_parse_host")
+    k = n_seq.value
+    return seq[0, :k].copy(), seq[1, :k].copy(), seq[2, :k].copy(), literals[: n_lit.value].copy()
+
+
+def sliding_replay_host(history: np.ndarray, literal_count, match_length, match_offset, literals,
+                        window_size: int = 0) -> np.ndarray:
+    """``replay_host`` with the window's rules: a sequence with match length 0 copies nothing, and an offset beyond
+    ``min(window_size, bytes so far)`` raises ``SclHipError`` (``window_size`` 0: no bound)."""
+    L = _lib.load()
+    _lib.require_device()
+    lc, ml, mo = (np.ascontiguousarray(a, np.uint32) for a in (literal_count, match_length, match_offset))
+    literals = np.ascontiguousarray(literals, np.uint8)
+    history = np.asarray(history, np.uint8)
+    have = int(history.size)
+    grow = int(literals.size) + int(ml.astype(np.int64).sum())
+    if have + grow >= 1 << 32:
+        raise ValueError(f"a window of {have + grow} bytes: positions inside a stream are 32-bit")
+    buf = np.zeros(max(have + grow, 1), np.uint8)
+    buf[:have] = history
+    out_len = C.c_uint64(0)
+    rc = L.scl_lz77_sliding_replay_host(_lib.u8_ptr(buf), have, have + grow, int(window_size), _lib.u32_ptr(lc),
+                                        _lib.u32_ptr(ml), _lib.u32_ptr(mo), int(lc.size), _lib.u8_ptr(literals),
+                                        int(literals.size), C.byref(out_len))
+    _lib.check(rc, "scl_lz77_sliding_replay_host")
+    return buf[have: have + out_len.value]
+
+
+def sliding_parse_batch(win, win_off, start, params: SlidingParams = SlidingParams(), seq_cap: Optional[int] = None,
+                        scratch=None, stream=None, out: Optional[ParsedBatch] = None, phases: int = 0) -> ParsedBatch:
+    """``parse_batch`` for the sliding-window coder: the same layout and the same :class:`ParsedBatch` (``encode_batch``
+    takes it as it is).  ``seq_cap`` defaults to ``sliding_seq_cap`` of the longest block (one read-back of the block
+    lengths); ``scratch``: a uint8 tensor of at least ``sliding_scratch_bytes(win.numel(), n_streams)`` bytes."""
+    import torch
+
+    L = _lib.load()
+    assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous()
+    assert win_off.dtype == torch.int64 and start.dtype == torch.int32 and win_off.numel() == start.numel() + 1
+    dev, n_streams, total = win.device, int(start.numel()), int(win.numel())
+    if out is not None:
+        seq_cap = out.seq_cap
+    if seq_cap is None:
+        lens = win_off[1:] - win_off[:-1] - start.to(torch.int64).bitwise_and(0xFFFFFFFF)
+        seq_cap = sliding_seq_cap(max(int(lens.max().item()), 0) if n_streams else 0, params.min_match_length)
+    need = sliding_scratch_bytes(total, n_streams)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert scratch.numel() >= need
+    if out is None:
+        rows = lambda: torch.zeros((n_streams, seq_cap), dtype=torch.int32, device=dev)  # noqa: E731
+        words = lambda: torch.zeros(n_streams, dtype=torch.int32, device=dev)  # noqa: E731
+        out = ParsedBatch(rows(), rows(), rows(), torch.zeros(max(total, 1), dtype=torch.uint8, device=dev), words(),
+                          words(), words(), win_off[:-1] + start.to(torch.int64), int(seq_cap))
+    hl, m, chain, lazy, mml, W = params._c()
+    a = _lib.Lz77SlidingParseArgs(win.data_ptr(), win_off.data_ptr(), start.data_ptr(), n_streams, total, m, hl, chain, lazy,
+                                  mml, W, out.seq_cap, int(phases), 0, out.literal_count.data_ptr(),
+                                  out.match_length.data_ptr(), out.match_offset.data_ptr(), out.literals.data_ptr(),
+                                  out.n_seq.data_ptr(), out.n_lit.data_ptr(), out.status.data_ptr(), scratch.data_ptr(),
+                                  int(scratch.numel()))
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_sliding_parse_batch(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_sliding_parse_batch")
+    out._scratch = scratch  # the kernels read it asynchronously: it lives as long as the result
+    return out
+
+
+def sliding_replay_batch(win, win_off, have, literal_count, match_length, match_offset, n_seq, literals, lit_off, n_lit,
+                         window_size: int = 0, stream=None):
+    """``replay_batch`` with the window's rules (see :func:`sliding_replay_host`).  -> (out_len, status)"""
+    import torch
+
+    L = _lib.load()
+    assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous() and literals.dtype == torch.uint8
+    assert win_off.dtype == torch.int64 and lit_off.dtype == torch.int64
+    assert all(t.dtype == torch.int32 for t in (have, literal_count, match_length, match_offset, n_seq, n_lit))
+    dev, n_streams = win.device, int(have.numel())
+    assert win_off.numel() == n_streams + 1 and literal_count.dim() == 2 and literal_count.is_contiguous()
+    assert match_length.is_contiguous() and match_offset.is_contiguous()
+    assert match_length.shape == literal_count.shape == match_offset.shape and literal_count.shape[0] == n_streams
+    out_len = torch.zeros(n_streams, dtype=torch.int32, device=dev)
+    status = torch.zeros(n_streams, dtype=torch.int32, device=dev)
+    a = _lib.Lz77SlidingReplayArgs(win.data_ptr(), win_off.data_ptr(), have.data_ptr(), n_streams, int(win.numel()),
+                                   int(literal_count.shape[1]), int(window_size), literal_count.data_ptr(),
+                                   match_length.data_ptr(), match_offset.data_ptr(), n_seq.data_ptr(), literals.data_ptr(),
+                                   int(literals.numel()), lit_off.data_ptr(), n_lit.data_ptr(), out_len.data_ptr(),
+                                   status.data_ptr())
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_sliding_replay_batch(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_sliding_replay_batch")
+    return out_len, status
+
+
+def sliding_compress_batch(win, win_off, start, params: SlidingParams = SlidingParams(), seq_cap: Optional[int] = None,
+                           binned_offset: int = DEFAULT_BINNED_OFFSET, out_stride: Optional[int] = None, scratch=None,
+                           stream=None):
+    """``compress_batch`` for the sliding-window coder: parse + encode -> (:class:`EncodedBatch`, :class:`ParsedBatch`)"""
+    import torch
+
+    if seq_cap is None or out_stride is None:
+        lens = win_off[1:] - win_off[:-1] - start.to(torch.int64).bitwise_and(0xFFFFFFFF)
+        longest = max(int(lens.max().item()), 0) if start.numel() else 0
+        if seq_cap is None:
+            seq_cap = sliding_seq_cap(longest, params.min_match_length)
+        if out_stride is None:
+            out_stride = entropy_slot_bytes(seq_cap, longest, binned_offset)
+    parsed = sliding_parse_batch(win, win_off, start, params, seq_cap, scratch=scratch, stream=stream)
+    return encode_batch(parsed, binned_offset, out_stride, stream=stream), parsed
+
+
+def sliding_decompress_batch(bits, bit_offset, nbits, win, win_off, have, seq_cap: int, window_size: int = 0,
+                             binned_offset: int = DEFAULT_BINNED_OFFSET, stream=None):
+    """``decompress_batch`` for the sliding-window coder: decode + windowed replay -> (out_len, status, consumed)"""
+    import torch
+
+    room = (win_off[1:] - win_off[:-1] - have.to(torch.int64).bitwise_and(0xFFFFFFFF)).clamp(min=0, max=0xFFFFFFFF)
+    lit_off = torch.cumsum(room, 0) - room
+    lit_cap = torch.where(room >= 1 << 31, room - (1 << 32), room).to(torch.int32)
+    decoded = decode_batch(bits, bit_offset, nbits, seq_cap, lit_off, lit_cap, binned_offset, stream=stream)
+    out_len, status = sliding_replay_batch(win, win_off, have, decoded.literal_count, decoded.match_length,
+                                           decoded.match_offset, decoded.n_seq, decoded.literals, lit_off, decoded.n_lit,
+                                           window_size, stream=stream)
+    return out_len, status | decoded.status, decoded.consumed

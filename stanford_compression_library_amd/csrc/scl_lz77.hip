@@ -9,53 +9,15 @@
 //   bitmap: one bit per position: it has a candidate (an equal gram at q <= p - L) -- parallel over positions;
 //   parse : ONE WAVEFRONT PER STREAM walks the stream: skip to the next set bit (4096 positions per step), score the
 //           candidates 64 at a time (lane j = the j-th most recent), longest wins, lowest lane on ties.
-// One LARGE stream has kernels of its own, scl_lz77_wide.hip; the *_host calls below choose.  The device code both share is
-// in scl_lz77_internal.h.
+// One LARGE stream has kernels of its own, scl_lz77_wide.hip; the *_host calls below choose.  The device code they share --
+// and share with the sliding-window coder, scl_lz77_sliding.hip: the sort's histogram and scatter kernels, templates on
+// the digit source, and the replay's copy loop -- is in scl_lz77_internal.h; the scans of the sort are here, behind
+// lz77_scan_exclusive.
 // No workgroup waits on another (every dependency between workgroups is a kernel boundary), every loop is bounded by the
 // data, and reads and writes are checked against the buffers' sizes on any input.
 #include "scl_lz77_internal.h"
 
 namespace {
-
-// the stream that owns global position v: the last s with win_off[s] <= v if v < win_off[s + 1], else n_streams
-__device__ __forceinline__ u32 lz_stream_of(const u64 *win_off, u32 n_streams, u64 v) {
-    u32 lo = 0, hi = n_streams;  // invariant: the answer, if any, is in [lo, hi)
-    while (hi - lo > 1) {
-        const u32 mid = lo + (hi - lo) / 2;
-        if (win_off[mid] <= v)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    if (n_streams == 0 || win_off[lo] > v || v >= win_off[lo + 1]) return n_streams;
-    return lo;
-}
-
-// digit of position v in pass `pass`: passes 0..L-1 read gram byte `pass`, later ones a byte of the stream number
-__device__ __forceinline__ u32 lz_digit(const u8 *win, u64 N, const u64 *win_off, u32 n_streams, u32 L, u32 pass, u32 v) {
-    if (pass < L) {
-        const u64 g = (u64)v + pass;
-        return g < N ? win[g] : 0u;
-    }
-    return (lz_stream_of(win_off, n_streams, v) >> (8 * (pass - L))) & 255u;
-}
-
-// ---- index sort ------------------------------------------------------------------------------------------------------
-// in == nullptr: the identity permutation (the first pass)
-__global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_histogram(const u8 *win, u64 N, const u64 *win_off,
-                                                                       u32 n_streams, u32 L, u32 pass, const u32 *in,
-                                                                       u32 *hist, u64 n_tiles) {
-    __shared__ u32 cnt[256];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const u64 first = (u64)blockIdx.x * LZ_SORT_TILE + (u64)(threadIdx.x / SCL_WAVE) * (SCL_WAVE * LZ_SORT_ROUNDS) + lz_lane();
-    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
-        const u64 i = first + (u64)r * SCL_WAVE;
-        if (i < N) atomicAdd(&cnt[lz_digit(win, N, win_off, n_streams, L, pass, in ? in[i] : (u32)i)], 1u);
-    }
-    __syncthreads();
-    hist[(u64)threadIdx.x * n_tiles + blockIdx.x] = cnt[threadIdx.x];
-}
 
 // the scan of the tile histograms in three kernels: every block scans its 2048 entries, one workgroup scans the block
 // sums, every block adds its offset (the scans across a workgroup: scl_scan.h)
@@ -92,65 +54,6 @@ __global__ __launch_bounds__(LZ_SCAN_THREADS) void lz77_scan_add(V *hist, u64 n,
 #pragma unroll
     for (u32 j = 0; j < LZ_SCAN_PER_THREAD; ++j)
         if (at + j < n) hist[at + j] += add;
-}
-
-// ranked scatter: hist[digit * n_tiles + tile] = where this tile's first entry with that digit goes.  Inside the tile the
-// waves take their digits' places in wave order, and a wave ranks its 64 entries of a round by ballots: entry -> place
-// + (entries with the same digit in lower lanes).  rank_out != nullptr on the last pass: the inverse permutation.
-__global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_scatter(const u8 *win, u64 N, const u64 *win_off,
-                                                                     u32 n_streams, u32 L, u32 pass, const u32 *in,
-                                                                     u32 *out, u32 *rank_out, const u32 *hist,
-                                                                     u64 n_tiles) {
-    __shared__ u32 place[LZ_SORT_WAVES][256];
-    const u32 wave = threadIdx.x / SCL_WAVE, lane = lz_lane();
-    for (u32 w = 0; w < LZ_SORT_WAVES; ++w) place[w][threadIdx.x] = 0;
-    __syncthreads();
-    const u64 first = (u64)blockIdx.x * LZ_SORT_TILE + (u64)wave * (SCL_WAVE * LZ_SORT_ROUNDS) + lane;
-    u32 val[LZ_SORT_ROUNDS];
-    u32 dig[LZ_SORT_ROUNDS / 4] = {};  // four digits to a word
-#pragma unroll
-    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
-        const u64 i = first + (u64)r * SCL_WAVE;
-        val[r] = 0;
-        if (i < N) {
-            val[r] = in ? in[i] : (u32)i;
-            const u32 d = lz_digit(win, N, win_off, n_streams, L, pass, val[r]);
-            dig[r / 4] |= d << (8 * (r % 4));
-            atomicAdd(&place[wave][d], 1u);
-        }
-    }
-    __syncthreads();
-    {
-        u32 at = hist[(u64)threadIdx.x * n_tiles + blockIdx.x];
-        for (u32 w = 0; w < LZ_SORT_WAVES; ++w) {
-            const u32 c = place[w][threadIdx.x];
-            place[w][threadIdx.x] = at;
-            at += c;
-        }
-    }
-    __syncthreads();
-    volatile u32 *mine = place[wave];
-    const u64 below = (1ull << lane) - 1;
-#pragma unroll
-    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
-        const u64 i = first + (u64)r * SCL_WAVE;
-        const bool live = i < N;
-        const u32 d = (dig[r / 4] >> (8 * (r % 4))) & 255u;
-        u64 same = __ballot(live);
-#pragma unroll
-        for (u32 b = 0; b < 8; ++b) {
-            const u64 set = __ballot(live && ((d >> b) & 1u));
-            same &= ((d >> b) & 1u) ? set : ~set;
-        }
-        if (live) {
-            const u32 at = mine[d];
-            const u32 dest = at + (u32)__popcll(same & below);
-            if ((same >> lane) == 1ull) mine[d] = at + (u32)__popcll(same);  // the highest lane of the group moves the place
-            out[dest] = val[r];
-            if (rank_out) rank_out[val[r]] = dest;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
 }
 
 // ---- candidate bitmap ------------------------------------------------------------------------------------------------
@@ -246,10 +149,8 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_parse(const u8 *win, u
 }
 
 // ---- replay ----------------------------------------------------------------------------------------------------------
-// One wavefront per stream appends to the stream's window.  A match reads bytes this same wave stored while it executed
-// the sequences before: the release fence and the drain in front of every match copy order them (workgroup scope: the
-// wave's loads and stores go through the one L1 of its CU; no other wave touches the stream).  `win` is deliberately
-// neither const nor __restrict__: the reads must take the vector path, not the scalar cache.
+// One wavefront per stream appends to the stream's window: lz_replay_stream (scl_lz77_internal.h).  `win` is deliberately
+// neither const nor __restrict__, see there.
 __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_replay(u8 *win, u64 N, const u64 *win_off, const u32 *have_in,
                                                                  u32 n_streams, u32 seq_cap, const u32 *lit_count,
                                                                  const u32 *match_len, const u32 *match_off,
@@ -267,67 +168,14 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_replay(u8 *win, u64 N,
         l_at > lit_bytes || n_lit > lit_bytes - l_at) {
         status = SCL_ST_SIZE;
     } else {
-        const u32 cap = (u32)(end - base);
-        u8 *out = win + base;
-        const u8 *lit = literals + l_at;
         const u32 *lc = lit_count + (u64)s * seq_cap, *ml = match_len + (u64)s * seq_cap,
                   *mo = match_off + (u64)s * seq_cap;
-        u32 lp = 0;
-        for (u32 k = 0; k < n_seq; ++k) {
-            const u32 run = lc[k], len = ml[k], off = mo[k];
-            if (run > n_lit - lp) {
-                status = SCL_ST_TRUNCATED;
-                break;
-            }
-            if (run > cap - d) {
-                status = SCL_ST_CAPACITY;
-                break;
-            }
-            for (u32 j = lane; j < run; j += SCL_WAVE) out[d + j] = lit[lp + j];
-            d += run;
-            lp += run;
-            if (off == 0 || off > d) {
-                status = SCL_ST_STATE;
-                break;
-            }
-            if (len > cap - d) {
-                status = SCL_ST_CAPACITY;
-                break;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            // out[d + j] = out[d - off + (j mod off)]: every source byte was there before this sequence began
-            const u8 *src = out + (d - off);
-            u32 from = lane % off;
-            const u32 step = SCL_WAVE % off;
-            for (u32 j = lane; j < len; j += SCL_WAVE) {
-                out[d + j] = src[from];
-                from += step;
-                if (from >= off) from -= off;
-            }
-            d += len;
-        }
-        if (status == 0) {
-            const u32 rest = n_lit - lp;
-            if (rest > cap - d) {
-                status = SCL_ST_CAPACITY;
-            } else {
-                for (u32 j = lane; j < rest; j += SCL_WAVE) out[d + j] = lit[lp + j];
-                d += rest;
-            }
-        }
+        status = lz_replay_stream<false>(win + base, (u32)(end - base), &d, lc, ml, mo, n_seq, literals + l_at, n_lit, 0);
     }
     if (lane == 0) {
         out_len[s] = d - have;
         status_out[s] = status;
     }
-}
-
-u32 lz_stream_passes(u64 n_streams) {  // bytes of a stream number; n_streams itself marks bytes that belong to no stream
-    u32 passes = 0;
-    while (n_streams >> (8 * passes)) ++passes;
-    return n_streams > 1 ? passes : 0;
 }
 
 }  // namespace
@@ -382,20 +230,9 @@ extern "C" int scl_lz77_parse_batch(const scl_lz77_parse_args *a, void *stream) 
     u32 *hist = (u32 *)(scr + lay.hist), *sums = (u32 *)(scr + lay.block_sums);
     const u32 phases = a->phases ? a->phases : 3u;
     const u32 passes = L + lz_stream_passes(a->n_streams);
-    // the passes ping-pong between the two buffers and end in order_a
-    u32 *out = (passes & 1) ? order_a : order_b;
     if ((phases & SCL_LZ77_INDEX) && N) {
-        const u32 *in = nullptr;
-        for (u32 pass = 0; pass < passes; ++pass) {
-            hipLaunchKernelGGL(lz77_sort_histogram, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, a->d_win, N,
-                               a->d_win_off, n_streams, L, pass, in, hist, lay.n_tiles);
-            lz77_scan_exclusive(hist, lay.n_hist, sums, st);
-            hipLaunchKernelGGL(lz77_sort_scatter, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, a->d_win, N,
-                               a->d_win_off, n_streams, L, pass, in, out, pass + 1 == passes ? rank : nullptr, hist,
-                               lay.n_tiles);
-            in = out;
-            out = out == order_a ? order_b : order_a;
-        }
+        lz77_sort_positions(LzGramDigit{a->d_win, N, a->d_win_off, n_streams, L}, N, passes, lay, order_a, order_b, rank,
+                            hist, sums, st);
         hipLaunchKernelGGL(lz77_candidate_bitmap, dim3((u32)((N + 255) / 256)), dim3(256), 0, st, a->d_win, N,
                            a->d_win_off, n_streams, L, order_a, rank, bitmap);
     }

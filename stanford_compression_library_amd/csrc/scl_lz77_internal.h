@@ -1,14 +1,16 @@
 // scl_lz77_internal.h -- shapes, scratch layout and shared device code of the LZ77 kernels (scl_lz77.hip: batches, one
-// wavefront per stream; scl_lz77_wide.hip: one stream across the whole GPU).  Internal to csrc/.
+// wavefront per stream; scl_lz77_wide.hip: one stream across the whole GPU; scl_lz77_sliding.hip: the sliding-window coder,
+// one wavefront per stream).  Internal to csrc/.
 #pragma once
 
 #include "scl_common.h"
 #include "scl_scan.h"
 
 // ---- the index sort: a stable LSD radix sort of the POSITIONS, 8-bit digits ------------------------------------------
-// Nothing but the permutation moves: the digit of position v in gram pass d is the byte win[v + d] (0 past the buffer),
-// in stream pass k byte k of v's stream number.  A tile is 4 waves x 16 rounds x 64 positions; a wave owns 1024
-// consecutive entries, so tile order, wave order, round order and lane order together are the input order (stability).
+// Nothing but the permutation moves: the digit of position v in pass d comes from a digit source (LzGramDigit below: in
+// gram pass d the byte win[v + d], 0 past the buffer, in stream pass k byte k of v's stream number).  A tile is 4 waves x
+// 16 rounds x 64 positions; a wave owns 1024 consecutive entries, so tile order, wave order, round order and lane order
+// together are the input order (stability).
 #define LZ_SORT_THREADS 256
 #define LZ_SORT_ROUNDS 16
 #define LZ_SORT_WAVES (LZ_SORT_THREADS / SCL_WAVE)
@@ -180,5 +182,195 @@ __device__ __forceinline__ u32 lz_score(const u8 *win, u64 base, u64 gp, u32 lim
     }
     *best_q_out = best_q;
     return best_len;
+}
+
+// ---- the index sort's kernels, shared by the greedy index (scl_lz77.hip) and the hash-bucket index (scl_lz77_sliding.hip)
+// the stream that owns global position v: the last s with win_off[s] <= v if v < win_off[s + 1], else n_streams
+__device__ __forceinline__ u32 lz_stream_of(const u64 *win_off, u32 n_streams, u64 v) {
+    u32 lo = 0, hi = n_streams;  // invariant: the answer, if any, is in [lo, hi)
+    while (hi - lo > 1) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if (win_off[mid] <= v)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    if (n_streams == 0 || win_off[lo] > v || v >= win_off[lo + 1]) return n_streams;
+    return lo;
+}
+
+// The digit source of the greedy index: passes 0..L-1 read gram byte `pass` of position v, later ones a byte of the
+// stream number.  A digit source is a small struct passed by value with `u32 operator()(u32 pass, u32 v) const`.
+struct LzGramDigit {
+    const u8 *win;
+    u64 N;
+    const u64 *win_off;
+    u32 n_streams, L;
+    __device__ __forceinline__ u32 operator()(u32 pass, u32 v) const {
+        if (pass < L) {
+            const u64 g = (u64)v + pass;
+            return g < N ? win[g] : 0u;
+        }
+        return (lz_stream_of(win_off, n_streams, v) >> (8 * (pass - L))) & 255u;
+    }
+};
+
+// in == nullptr: the identity permutation (the first pass)
+template <class Digit>
+__global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_histogram(Digit digit, u64 N, u32 pass, const u32 *in,
+                                                                       u32 *hist, u64 n_tiles) {
+    __shared__ u32 cnt[256];
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const u64 first = (u64)blockIdx.x * LZ_SORT_TILE + (u64)(threadIdx.x / SCL_WAVE) * (SCL_WAVE * LZ_SORT_ROUNDS) + lz_lane();
+    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
+        const u64 i = first + (u64)r * SCL_WAVE;
+        if (i < N) atomicAdd(&cnt[digit(pass, in ? in[i] : (u32)i)], 1u);
+    }
+    __syncthreads();
+    hist[(u64)threadIdx.x * n_tiles + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// ranked scatter: hist[digit * n_tiles + tile] = where this tile's first entry with that digit goes.  Inside the tile the
+// waves take their digits' places in wave order, and a wave ranks its 64 entries of a round by ballots: entry -> place
+// + (entries with the same digit in lower lanes).  rank_out != nullptr on the last pass: the inverse permutation.
+template <class Digit>
+__global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_scatter(Digit digit, u64 N, u32 pass, const u32 *in, u32 *out,
+                                                                     u32 *rank_out, const u32 *hist, u64 n_tiles) {
+    __shared__ u32 place[LZ_SORT_WAVES][256];
+    const u32 wave = threadIdx.x / SCL_WAVE, lane = lz_lane();
+    for (u32 w = 0; w < LZ_SORT_WAVES; ++w) place[w][threadIdx.x] = 0;
+    __syncthreads();
+    const u64 first = (u64)blockIdx.x * LZ_SORT_TILE + (u64)wave * (SCL_WAVE * LZ_SORT_ROUNDS) + lane;
+    u32 val[LZ_SORT_ROUNDS];
+    u32 dig[LZ_SORT_ROUNDS / 4] = {};  // four digits to a word
+#pragma unroll
+    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
+        const u64 i = first + (u64)r * SCL_WAVE;
+        val[r] = 0;
+        if (i < N) {
+            val[r] = in ? in[i] : (u32)i;
+            const u32 d = digit(pass, val[r]);
+            dig[r / 4] |= d << (8 * (r % 4));
+            atomicAdd(&place[wave][d], 1u);
+        }
+    }
+    __syncthreads();
+    {
+        u32 at = hist[(u64)threadIdx.x * n_tiles + blockIdx.x];
+        for (u32 w = 0; w < LZ_SORT_WAVES; ++w) {
+            const u32 c = place[w][threadIdx.x];
+            place[w][threadIdx.x] = at;
+            at += c;
+        }
+    }
+    __syncthreads();
+    volatile u32 *mine = place[wave];
+    const u64 below = (1ull << lane) - 1;
+#pragma unroll
+    for (u32 r = 0; r < LZ_SORT_ROUNDS; ++r) {
+        const u64 i = first + (u64)r * SCL_WAVE;
+        const bool live = i < N;
+        const u32 d = (dig[r / 4] >> (8 * (r % 4))) & 255u;
+        u64 same = __ballot(live);
+#pragma unroll
+        for (u32 b = 0; b < 8; ++b) {
+            const u64 set = __ballot(live && ((d >> b) & 1u));
+            same &= ((d >> b) & 1u) ? set : ~set;
+        }
+        if (live) {
+            const u32 at = mine[d];
+            const u32 dest = at + (u32)__popcll(same & below);
+            if ((same >> lane) == 1ull) mine[d] = at + (u32)__popcll(same);  // the highest lane of the group moves the place
+            out[dest] = val[r];
+            if (rank_out) rank_out[val[r]] = dest;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// The stable LSD sort of the N positions over `passes` digits of `digit`, on `st`: order_a / order_b ping-pong and the
+// result ends in order_a, its inverse in rank.  passes >= 1.
+template <class Digit>
+static inline void lz77_sort_positions(Digit digit, u64 N, u32 passes, const Lz77Scratch &lay, u32 *order_a, u32 *order_b,
+                                       u32 *rank, u32 *hist, u32 *sums, hipStream_t st) {
+    u32 *out = (passes & 1) ? order_a : order_b;
+    const u32 *in = nullptr;
+    for (u32 pass = 0; pass < passes; ++pass) {
+        hipLaunchKernelGGL(lz77_sort_histogram<Digit>, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, digit, N, pass,
+                           in, hist, lay.n_tiles);
+        lz77_scan_exclusive(hist, lay.n_hist, sums, st);
+        hipLaunchKernelGGL(lz77_sort_scatter<Digit>, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, digit, N, pass, in,
+                           out, pass + 1 == passes ? rank : nullptr, hist, lay.n_tiles);
+        in = out;
+        out = out == order_a ? order_b : order_a;
+    }
+}
+
+static inline u32 lz_stream_passes(u64 n_streams) {  // bytes of a stream number; n_streams itself marks bytes that belong to no stream
+    u32 passes = 0;
+    while (n_streams >> (8 * passes)) ++passes;
+    return n_streams > 1 ? passes : 0;
+}
+
+// ---- replay: one wavefront appends one stream's sequences to its slot --------------------------------------------------
+// A match reads bytes this same wave stored while it executed the sequences before: the release fence and the drain in
+// front of every match copy order them (workgroup scope: the wave's loads and stores go through the one L1 of its CU; no
+// other wave touches the stream).  `out` is deliberately neither const nor __restrict__: the reads must take the vector
+// path, not the scalar cache.  out holds d bytes of cap already.  WINDOWED (the sliding-window coder): a sequence with
+// match length 0 copies nothing and its offset is not looked at, and an offset above `window` (0: no bound) is
+// SCL_ST_STATE.  -> the status; *d_io = the bytes in the slot afterwards.
+template <bool WINDOWED>
+__device__ __forceinline__ u32 lz_replay_stream(u8 *out, u32 cap, u32 *d_io, const u32 *lc, const u32 *ml, const u32 *mo,
+                                                u32 n_seq, const u8 *lit, u32 n_lit, u32 window) {
+    const u32 lane = lz_lane();
+    u32 status = 0, d = *d_io, lp = 0;
+    for (u32 k = 0; k < n_seq; ++k) {
+        const u32 run = lc[k], len = ml[k], off = mo[k];
+        if (run > n_lit - lp) {
+            status = SCL_ST_TRUNCATED;
+            break;
+        }
+        if (run > cap - d) {
+            status = SCL_ST_CAPACITY;
+            break;
+        }
+        for (u32 j = lane; j < run; j += SCL_WAVE) out[d + j] = lit[lp + j];
+        d += run;
+        lp += run;
+        if (WINDOWED && len == 0) continue;
+        if (off == 0 || off > d || (WINDOWED && window && off > window)) {
+            status = SCL_ST_STATE;
+            break;
+        }
+        if (len > cap - d) {
+            status = SCL_ST_CAPACITY;
+            break;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        // out[d + j] = out[d - off + (j mod off)]: every source byte was there before this sequence began
+        const u8 *src = out + (d - off);
+        u32 from = lane % off;
+        const u32 step = SCL_WAVE % off;
+        for (u32 j = lane; j < len; j += SCL_WAVE) {
+            out[d + j] = src[from];
+            from += step;
+            if (from >= off) from -= off;
+        }
+        d += len;
+    }
+    if (status == 0) {
+        const u32 rest = n_lit - lp;
+        if (rest > cap - d) {
+            status = SCL_ST_CAPACITY;
+        } else {
+            for (u32 j = lane; j < rest; j += SCL_WAVE) out[d + j] = lit[lp + j];
+            d += rest;
+        }
+    }
+    *d_io = d;
+    return status;
 }
 #endif  // __HIPCC__

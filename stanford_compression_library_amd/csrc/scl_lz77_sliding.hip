@@ -1,0 +1,483 @@
+// scl_lz77_sliding.hip -- sliding-window LZ77 for gfx950: hash-bucket index, lazy parse, windowed replay.
+//
+//   scl_lz77_sliding_parse_batch   <->  LZ77SlidingWindowEncoder.lz77_parse_and_generate_sequences + HashBasedMatchFinder
+//   scl_lz77_sliding_replay_batch  <->  LZ77SlidingWindowDecoder.execute_lz77_sequences
+//                                                                          scl/compressors/lz77_sliding_window.py
+//
+// The batch layout is scl_lz77.hip's.  The parse call runs
+//   keys  : key[v] = bucket of the hl-gram at v (LZ_NO_KEY where v has no whole gram inside its stream);
+//   index : the stable radix sort of scl_lz77_internal.h by (stream, key) -> order[] and rank[]: the positions of one
+//           bucket of one stream sit together, oldest first (the reference's hash_table chains, never trimmed: a chain
+//           capped at C entries is the C newest of them);
+//   bitmap: one bit per position: the newest older position of its bucket lies within W.  Every candidate at every
+//           horizon is such a position, so a clear bit means "no match here" for the walk that looks for the first match;
+//   parse : ONE WAVEFRONT PER STREAM; at p, lane k < C takes the k-th newest bucket-mate below the horizon, extends right
+//           and left, and a wave maximum over (length, 63 - lane) picks the longest, the newest on ties.
+// No workgroup waits on another, every loop is bounded by the data, and reads and writes are checked against the buffers'
+// sizes on any input.
+#include "scl_lz77_internal.h"
+
+#define LZ_NO_KEY 0xFFFFFFFFu  // m < 2^32, so no bucket has this number
+
+// CPython's hash(tuple(bytes)) % m (Objects/tupleobject.c, 64-bit build; the hash of a small int is the int itself)
+__host__ __device__ static inline u32 lz_sliding_bucket(const u8 *gram, u32 hl, u64 m) {
+    u64 acc = 0x27D4EB2F165667C5ull;
+    for (u32 j = 0; j < hl; ++j) {
+        acc += (u64)gram[j] * 0xC2B2AE3D27D4EB4Full;
+        acc = (acc << 31) | (acc >> 33);
+        acc *= 0x9E3779B185EBCA87ull;
+    }
+    acc += (u64)hl ^ (0x27D4EB2F165667C5ull ^ 3527539ull);
+    if (acc == ~0ull) acc = 1546275796ull;
+    const i64 r = (i64)acc % (i64)m;  // Python's %: the non-negative remainder
+    return (u32)(r < 0 ? r + (i64)m : r);
+}
+
+namespace {
+
+__global__ __launch_bounds__(256) void lz77_sliding_keys(const u8 *win, u64 N, const u64 *win_off, u32 n_streams, u32 hl,
+                                                         u64 m, u32 *key) {
+    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= N) return;
+    u32 k = LZ_NO_KEY;
+    const u32 s = lz_stream_of(win_off, n_streams, g);
+    if (s < n_streams) {
+        u64 end = win_off[s + 1];
+        if (end > N) end = N;
+        if (g + hl <= end) k = lz_sliding_bucket(win + g, hl, m);
+    }
+    key[g] = k;
+}
+
+// digit source of the bucket index: passes 0..key_passes-1 read a byte of the key, later ones a byte of the stream number
+struct LzKeyDigit {
+    const u32 *key;
+    const u64 *win_off;
+    u32 n_streams, key_passes;
+    __device__ __forceinline__ u32 operator()(u32 pass, u32 v) const {
+        if (pass < key_passes) return (key[v] >> (8 * pass)) & 255u;
+        return (lz_stream_of(win_off, n_streams, v) >> (8 * (pass - key_passes))) & 255u;
+    }
+};
+
+// bit g: the entry in front of rank[g] is an older position of g's stream and bucket, at most W back
+__global__ __launch_bounds__(256) void lz77_sliding_bitmap(u64 N, const u64 *win_off, u32 n_streams, u32 W, const u32 *order,
+                                                           const u32 *rank, const u32 *key, u64 *bitmap) {
+    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bit = false;
+    if (g < N) {
+        const u32 k = key[g], i = rank[g];
+        if (k != LZ_NO_KEY && i > 0 && i < N) {
+            const u32 s = lz_stream_of(win_off, n_streams, g);
+            const u64 c = order[i - 1];
+            bit = s < n_streams && c >= win_off[s] && c < g && g - c <= W && key[c] == k;
+        }
+    }
+    const u64 word = __ballot(bit);
+    if (lz_lane() == 0 && (g >> 6) < (N + 63) / 64) bitmap[g >> 6] = word;
+}
+
+// The best match for position p of the stream at `base` (n bytes) at horizon T <= p, the lookahead starting at E <= T; all
+// arguments are wave-uniform and p + hl <= n.  The entries in front of rank[p] are p's older bucket-mates, newest first;
+// those at or past T come first and are skipped (at most p - T), then lane k < C takes the k-th.  A candidate more than W
+// back is not scored but keeps its lane.  -> the length after both extensions (0: none), *lits_out = where the match
+// starts, counted from E, *off_out = its offset.
+__device__ __forceinline__ u32 lz_sliding_best(const u8 *win, u64 N, u64 base, u32 n, u32 E, u32 p, u32 T, u32 C, u32 W,
+                                               const u32 *order, const u32 *rank, const u32 *key, u32 *lits_out,
+                                               u32 *off_out) {
+    const u32 lane = lz_lane();
+    const u64 gp = base + p, gT = base + T;
+    const u32 i = rank[gp], kp = key[gp];
+    if (i >= N) return 0;  // not an index of this buffer: nothing to look at
+    u32 skip = 0;
+    if (T < p) {
+        while (true) {
+            const u64 back = (u64)skip + lane;
+            bool late = false;
+            if (back < i) {
+                const u32 c = order[i - 1 - back];
+                late = c >= gT && c < gp && key[c] == kp;
+            }
+            const u64 mask = __ballot(late);
+            if (mask != ~0ull) {
+                skip += (u32)__builtin_ctzll(~mask);
+                break;
+            }
+            skip += SCL_WAVE;
+        }
+    }
+    const u64 back = (u64)skip + lane;
+    u32 c = 0, start = p;
+    u64 score = 0;  // (length, 63 - lane): the maximum is the longest match, the newest on ties
+    bool ok = lane < C && back < i;
+    if (ok) {
+        c = order[i - 1 - back];
+        ok = c >= base && c < gT && key[c] == kp && gp - c <= W;
+    }
+    if (ok) {
+        const u8 *w = win + base;
+        u32 q = (u32)(c - base);
+        u32 len = lz_extend(win + c, win + gp, 0, n - p);
+        const u32 first = E > W ? E - W : 0;  // the oldest byte the coder's window still holds
+        while (start > E && q > first && w[start - 1] == w[q - 1]) {
+            --start;
+            --q;
+            ++len;
+        }
+        score = ((u64)len << 6) | (63u - lane);
+    }
+    for (u32 d = 32; d; d >>= 1) {
+        const u32 lo = __shfl_xor((u32)score, d), hi = __shfl_xor((u32)(score >> 32), d);
+        const u64 other = ((u64)hi << 32) | lo;
+        score = other > score ? other : score;
+    }
+    const u32 best_len = (u32)(score >> 6);
+    if (best_len == 0) return 0;
+    const u32 winner = 63u - (u32)(score & 63);
+    *lits_out = (u32)__builtin_amdgcn_readlane((int)(start - E), (int)winner);
+    *off_out = (u32)__builtin_amdgcn_readlane((int)(u32)(gp - c), (int)winner);
+    return best_len;
+}
+
+__global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_parse(const u8 *win, u64 N, const u64 *win_off,
+                                                                        const u32 *start, u32 n_streams, u32 hl, u32 C,
+                                                                        u32 lazy, u32 mml, u32 W, const u32 *order,
+                                                                        const u32 *rank, const u32 *key, const u64 *bitmap,
+                                                                        u32 seq_cap, u32 *lit_count, u32 *match_len,
+                                                                        u32 *match_off, u8 *literals, u32 *n_seq_out,
+                                                                        u32 *n_lit_out, u32 *status_out) {
+    const u32 s = blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE;
+    if (s >= n_streams) return;
+    const u32 lane = lz_lane();
+    const u64 base = win_off[s], end = win_off[s + 1];
+    const u32 st = start[s];
+    u32 n_seq = 0, n_lit = 0, status = 0;
+    if (base > end || end > N || end - base >= (1ull << 32) || st > end - base) {
+        status = SCL_ST_SIZE;
+    } else {
+        const u32 n = (u32)(end - base);
+        const u8 *w = win + base;
+        u8 *lit = literals + base + st;  // the block's own place in a buffer laid out like the windows: n - st bytes
+        u32 *out_lc = lit_count + (u64)s * seq_cap, *out_ml = match_len + (u64)s * seq_cap,
+            *out_mo = match_off + (u64)s * seq_cap;
+        u32 E = st;
+        while (E < n) {
+            if (n_seq >= seq_cap) {
+                status |= SCL_ST_CAPACITY;
+                break;
+            }
+            u32 lits = n - E, len = 0, off = 0;  // fewer than hl bytes left: all literals
+            if (n - E >= hl) {
+                const u32 stop = n - hl + 1;  // the positions [E, stop) have a whole gram
+                lits = stop - E;
+                u32 from = E;
+                while (true) {
+                    const u64 g = lz_next_bit(bitmap, base + from, base + stop);
+                    if (g >= base + stop) break;
+                    const u32 p = (u32)(g - base);
+                    u32 b_lits = 0, b_off = 0;
+                    const u32 b_len = lz_sliding_best(win, N, base, n, E, p, p, C, W, order, rank, key, &b_lits, &b_off);
+                    if (b_len >= mml) {
+                        len = b_len;
+                        lits = b_lits;
+                        off = b_off;
+                        if (lazy) {  // the positions behind p, at p's horizon, while each beats the best so far
+                            for (u32 pj = p + 1; pj < stop; ++pj) {
+                                const u32 l = lz_sliding_best(win, N, base, n, E, pj, p, C, W, order, rank, key, &b_lits, &b_off);
+                                if (l <= len) break;
+                                len = l;
+                                lits = b_lits;
+                                off = b_off;
+                            }
+                        }
+                        break;
+                    }
+                    from = p + 1;
+                }
+            }
+            for (u32 k = lane; k < lits; k += SCL_WAVE) lit[n_lit + k] = w[E + k];
+            if (lane == 0) {
+                out_lc[n_seq] = lits;
+                out_ml[n_seq] = len;
+                out_mo[n_seq] = off;
+            }
+            n_lit += lits;
+            n_seq += 1;
+            E += lits + len;
+        }
+    }
+    if (lane == 0) {
+        n_seq_out[s] = n_seq;
+        n_lit_out[s] = n_lit;
+        status_out[s] = status;
+    }
+}
+
+// lz77_replay of scl_lz77.hip with the window's two rules (lz_replay_stream<true>)
+__global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_replay(u8 *win, u64 N, const u64 *win_off,
+                                                                         const u32 *have_in, u32 n_streams, u32 seq_cap,
+                                                                         u32 window, const u32 *lit_count,
+                                                                         const u32 *match_len, const u32 *match_off,
+                                                                         const u32 *n_seq_in, const u8 *literals,
+                                                                         u64 lit_bytes, const u64 *lit_off,
+                                                                         const u32 *n_lit_in, u32 *out_len, u32 *status_out) {
+    const u32 s = blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE;
+    if (s >= n_streams) return;
+    const u32 lane = lz_lane();
+    const u64 base = win_off[s], end = win_off[s + 1];
+    const u32 have = have_in[s], n_seq = n_seq_in[s], n_lit = n_lit_in[s];
+    const u64 l_at = lit_off[s];
+    u32 status = 0, d = have;
+    if (base > end || end > N || end - base >= (1ull << 32) || have > end - base || n_seq > seq_cap ||
+        l_at > lit_bytes || n_lit > lit_bytes - l_at) {
+        status = SCL_ST_SIZE;
+    } else {
+        const u32 *lc = lit_count + (u64)s * seq_cap, *ml = match_len + (u64)s * seq_cap,
+                  *mo = match_off + (u64)s * seq_cap;
+        status = lz_replay_stream<true>(win + base, (u32)(end - base), &d, lc, ml, mo, n_seq, literals + l_at, n_lit, window);
+    }
+    if (lane == 0) {
+        out_len[s] = d - have;
+        status_out[s] = status;
+    }
+}
+
+struct SlidingScratch {
+    Lz77Scratch index;  // order_a, order_b, rank, bitmap, hist, block_sums as in the greedy index
+    u64 key, total;
+};
+
+SlidingScratch sliding_scratch_layout(u64 N) {
+    SlidingScratch s;
+    s.index = lz77_scratch_layout(N);
+    s.key = s.index.total;
+    s.total = s.key + scl_round_up(N * 4 ? N * 4 : 1, 256);
+    return s;
+}
+
+u32 key_passes(u64 m) {  // bytes of the largest bucket number, at least one pass
+    u32 passes = 1;
+    while (passes < 4 && ((m - 1) >> (8 * passes))) ++passes;
+    return passes;
+}
+
+int sliding_check_params(const char *what, u32 hl, u64 m, u32 C, u32 mml) {
+    SCL_REQUIRE(hl >= 1 && hl <= 8, "%s: hash_length %u: 1 <= hash_length <= 8", what, hl);
+    SCL_REQUIRE(m >= 1 && m < (1ull << 32), "%s: hash_table_size %llu: a bucket number is 32-bit, 1 <= hash_table_size < 2^32",
+                what, (unsigned long long)m);
+    SCL_REQUIRE(C >= 1 && C <= 64, "%s: max_chain_length %u: one candidate per lane, 1 <= max_chain_length <= 64", what, C);
+    SCL_REQUIRE(mml >= 1, "%s: min_match_length 0: a match has at least one byte", what);
+    return SCL_OK;
+}
+
+struct LzMeta {  // the small per-stream words of a batch of one, in one allocation
+    u64 win_off[2];
+    u64 lit_off;
+    u32 start, n_seq, n_lit, status, have, out_len;
+};
+
+}  // namespace
+
+extern "C" uint64_t scl_lz77_sliding_scratch_bytes(uint64_t total_bytes, uint64_t n_streams) {
+    (void)n_streams;
+    return sliding_scratch_layout(total_bytes).total;
+}
+
+extern "C" int scl_lz77_sliding_kernel_names(char *index, char *parse, char *replay, uint64_t cap) {
+    SCL_REQUIRE(cap >= 96, "lz77_sliding_kernel_names: cap must be at least 96");
+    if (index) snprintf(index, cap, "lz77_sort_scatter");
+    if (parse) snprintf(parse, cap, "lz77_sliding_parse");
+    if (replay) snprintf(replay, cap, "lz77_sliding_replay");
+    return SCL_OK;
+}
+
+extern "C" uint32_t scl_lz77_sliding_bucket_host(const uint8_t *gram, uint32_t hl, uint32_t m) {
+    if (!gram || hl < 1 || hl > 8 || m == 0) return 0;
+    return lz_sliding_bucket(gram, hl, m);
+}
+
+extern "C" int scl_lz77_sliding_parse_batch(const scl_lz77_sliding_parse_args *a, void *stream) {
+    const char *what = "lz77_sliding_parse_batch";
+    SCL_REQUIRE(a, "%s: null pointer argument", what);
+    SCL_REQUIRE(a->d_win_off && a->d_start && a->d_n_seq && a->d_n_lit && a->d_status && a->d_scratch &&
+                    (a->total_bytes == 0 || (a->d_win && a->d_literals)) &&
+                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
+                "%s: null pointer argument", what);
+    if (int rc = sliding_check_params(what, a->hash_length, a->hash_table_size, a->max_chain_length, a->min_match_length))
+        return rc;
+    SCL_REQUIRE(a->total_bytes < (1ull << 32) && a->n_streams < (1ull << 32),
+                "%s: a batch holds less than 2^32 bytes and 2^32 streams", what);
+    SCL_REQUIRE(a->phases <= 3, "%s: phases is a mask of SCL_LZ77_INDEX | SCL_LZ77_PARSE", what);
+    const SlidingScratch lay = sliding_scratch_layout(a->total_bytes);
+    SCL_REQUIRE(((uintptr_t)a->d_scratch & 255) == 0 && a->scratch_bytes >= lay.total,
+                "%s: d_scratch must be 256-byte aligned and hold scl_lz77_sliding_scratch_bytes = %llu bytes", what,
+                (unsigned long long)lay.total);
+    if (a->n_streams == 0) return SCL_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const u64 N = a->total_bytes;
+    const u32 n_streams = (u32)a->n_streams;
+    const u32 W = a->window_size ? a->window_size : 0xFFFFFFFFu;
+    u8 *scr = (u8 *)a->d_scratch;
+    u32 *order_a = (u32 *)(scr + lay.index.order_a), *order_b = (u32 *)(scr + lay.index.order_b);
+    u32 *rank = (u32 *)(scr + lay.index.rank), *key = (u32 *)(scr + lay.key);
+    u64 *bitmap = (u64 *)(scr + lay.index.bitmap);
+    u32 *hist = (u32 *)(scr + lay.index.hist), *sums = (u32 *)(scr + lay.index.block_sums);
+    const u32 phases = a->phases ? a->phases : 3u;
+    if ((phases & SCL_LZ77_INDEX) && N) {
+        const u32 blocks = (u32)((N + 255) / 256);
+        hipLaunchKernelGGL(lz77_sliding_keys, dim3(blocks), dim3(256), 0, st, a->d_win, N, a->d_win_off, n_streams,
+                           a->hash_length, a->hash_table_size, key);
+        const u32 kp = key_passes(a->hash_table_size);
+        lz77_sort_positions(LzKeyDigit{key, a->d_win_off, n_streams, kp}, N, kp + lz_stream_passes(a->n_streams), lay.index,
+                            order_a, order_b, rank, hist, sums, st);
+        hipLaunchKernelGGL(lz77_sliding_bitmap, dim3(blocks), dim3(256), 0, st, N, a->d_win_off, n_streams, W, order_a, rank,
+                           key, bitmap);
+    }
+    if (phases & SCL_LZ77_PARSE) {
+        const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
+        hipLaunchKernelGGL(lz77_sliding_parse, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, st, a->d_win, N, a->d_win_off,
+                           a->d_start, n_streams, a->hash_length, a->max_chain_length, a->lazy, a->min_match_length, W,
+                           order_a, rank, key, bitmap, a->seq_cap, a->d_lit_count, a->d_match_len, a->d_match_off,
+                           a->d_literals, a->d_n_seq, a->d_n_lit, a->d_status);
+    }
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+extern "C" int scl_lz77_sliding_replay_batch(const scl_lz77_sliding_replay_args *a, void *stream) {
+    const char *what = "lz77_sliding_replay_batch";
+    SCL_REQUIRE(a, "%s: null pointer argument", what);
+    SCL_REQUIRE(a->d_win_off && a->d_have && a->d_n_seq && a->d_lit_off && a->d_n_lit && a->d_out_len && a->d_status &&
+                    (a->total_bytes == 0 || a->d_win) && (a->lit_bytes == 0 || a->d_literals) &&
+                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
+                "%s: null pointer argument", what);
+    SCL_REQUIRE(a->n_streams < (1ull << 32), "%s: a batch holds less than 2^32 streams", what);
+    if (a->n_streams == 0) return SCL_OK;
+    const u32 n_streams = (u32)a->n_streams;
+    const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
+    hipLaunchKernelGGL(lz77_sliding_replay, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, (hipStream_t)stream, a->d_win,
+                       a->total_bytes, a->d_win_off, a->d_have, n_streams, a->seq_cap, a->window_size, a->d_lit_count,
+                       a->d_match_len, a->d_match_off, a->d_n_seq, a->d_literals, a->lit_bytes, a->d_lit_off, a->d_n_lit,
+                       a->d_out_len, a->d_status);
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+// ---- one stream in host memory -----------------------------------------------------------------------------------------
+extern "C" int scl_lz77_sliding_parse_host(const uint8_t *h_window, uint64_t n, uint64_t start, uint32_t hash_length,
+                                           uint64_t hash_table_size, uint32_t max_chain_length, uint32_t lazy,
+                                           uint32_t min_match_length, uint32_t window_size, uint32_t *h_lit_count,
+                                           uint32_t *h_match_len, uint32_t *h_match_off, uint64_t seq_cap, uint64_t *n_seq,
+                                           uint8_t *h_literals, uint64_t lit_cap, uint64_t *n_lit) {
+    const char *what = "lz77_sliding_parse_host";
+    SCL_REQUIRE(n_seq && n_lit && (h_window || n == 0) && (seq_cap == 0 || (h_lit_count && h_match_len && h_match_off)) &&
+                    (h_literals || lit_cap == 0),
+                "%s: null pointer argument", what);
+    if (int rc = sliding_check_params(what, hash_length, hash_table_size, max_chain_length, min_match_length)) return rc;
+    SCL_REQUIRE(n < (1ull << 32) && start <= n && seq_cap < (1ull << 32), "%s: start <= n < 2^32 and seq_cap < 2^32", what);
+    SCL_REQUIRE(lit_cap >= n - start, "%s: h_literals must hold the block (%llu bytes)", what,
+                (unsigned long long)(n - start));
+    const u64 scratch_bytes = scl_lz77_sliding_scratch_bytes(n, 1);
+    ScratchDev d_win, d_lit, d_seq, d_meta, d_scr;
+    int rc;
+    if ((rc = d_win.alloc(n)) || (rc = d_lit.alloc(n)) || (rc = d_seq.alloc(3 * seq_cap * 4)) ||
+        (rc = d_meta.alloc(sizeof(LzMeta))) || (rc = d_scr.alloc(scratch_bytes)))
+        return rc;
+    LzMeta meta = {};
+    meta.win_off[1] = n;
+    meta.start = (u32)start;
+    if (n) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, n, hipMemcpyHostToDevice));
+    SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
+    LzMeta *dm = (LzMeta *)d_meta.p;
+    scl_lz77_sliding_parse_args a = {};
+    a.d_win = (const u8 *)d_win.p;
+    a.d_win_off = dm->win_off;
+    a.d_start = &dm->start;
+    a.n_streams = 1;
+    a.total_bytes = n;
+    a.hash_length = hash_length;
+    a.hash_table_size = hash_table_size;
+    a.max_chain_length = max_chain_length;
+    a.lazy = lazy;
+    a.min_match_length = min_match_length;
+    a.window_size = window_size;
+    a.seq_cap = (u32)seq_cap;
+    a.d_lit_count = (u32 *)d_seq.p;
+    a.d_match_len = a.d_lit_count + seq_cap;
+    a.d_match_off = a.d_match_len + seq_cap;
+    a.d_literals = (u8 *)d_lit.p;
+    a.d_n_seq = &dm->n_seq;
+    a.d_n_lit = &dm->n_lit;
+    a.d_status = &dm->status;
+    a.d_scratch = d_scr.p;
+    a.scratch_bytes = scratch_bytes;
+    if ((rc = scl_lz77_sliding_parse_batch(&a, nullptr))) return rc;
+    SCL_HIP_TRY(hipDeviceSynchronize());
+    SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+    *n_seq = meta.n_seq;
+    *n_lit = meta.n_lit;
+    if (meta.status) return scl_status_to_error(meta.status, what);
+    if (meta.n_seq) {
+        SCL_HIP_TRY(hipMemcpy(h_lit_count, a.d_lit_count, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+        SCL_HIP_TRY(hipMemcpy(h_match_len, a.d_match_len, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+        SCL_HIP_TRY(hipMemcpy(h_match_off, a.d_match_off, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+    }
+    if (meta.n_lit) SCL_HIP_TRY(hipMemcpy(h_literals, a.d_literals + start, meta.n_lit, hipMemcpyDeviceToHost));
+    return SCL_OK;
+}
+
+extern "C" int scl_lz77_sliding_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, uint32_t window_size,
+                                            const uint32_t *h_lit_count, const uint32_t *h_match_len,
+                                            const uint32_t *h_match_off, uint64_t n_seq, const uint8_t *h_literals,
+                                            uint64_t n_lit, uint64_t *out_len) {
+    const char *what = "lz77_sliding_replay_host";
+    SCL_REQUIRE(out_len && (h_window || cap == 0) && (n_seq == 0 || (h_lit_count && h_match_len && h_match_off)) &&
+                    (h_literals || n_lit == 0),
+                "%s: null pointer argument", what);
+    SCL_REQUIRE(cap < (1ull << 32) && have <= cap && n_seq < (1ull << 32) && n_lit < (1ull << 32),
+                "%s: have <= cap < 2^32, n_seq and n_lit < 2^32", what);
+    ScratchDev d_win, d_lit, d_seq, d_meta;
+    int rc;
+    if ((rc = d_win.alloc(cap)) || (rc = d_lit.alloc(n_lit)) || (rc = d_seq.alloc(3 * n_seq * 4)) ||
+        (rc = d_meta.alloc(sizeof(LzMeta))))
+        return rc;
+    LzMeta meta = {};
+    meta.win_off[1] = cap;
+    meta.have = (u32)have;
+    meta.n_seq = (u32)n_seq;
+    meta.n_lit = (u32)n_lit;
+    u32 *d_lc = (u32 *)d_seq.p, *d_ml = d_lc + n_seq, *d_mo = d_ml + n_seq;
+    if (have) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, have, hipMemcpyHostToDevice));
+    if (n_lit) SCL_HIP_TRY(hipMemcpy(d_lit.p, h_literals, n_lit, hipMemcpyHostToDevice));
+    if (n_seq) {
+        SCL_HIP_TRY(hipMemcpy(d_lc, h_lit_count, n_seq * 4, hipMemcpyHostToDevice));
+        SCL_HIP_TRY(hipMemcpy(d_ml, h_match_len, n_seq * 4, hipMemcpyHostToDevice));
+        SCL_HIP_TRY(hipMemcpy(d_mo, h_match_off, n_seq * 4, hipMemcpyHostToDevice));
+    }
+    SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
+    LzMeta *dm = (LzMeta *)d_meta.p;
+    scl_lz77_sliding_replay_args a = {};
+    a.d_win = (u8 *)d_win.p;
+    a.d_win_off = dm->win_off;
+    a.d_have = &dm->have;
+    a.n_streams = 1;
+    a.total_bytes = cap;
+    a.seq_cap = (u32)n_seq;
+    a.window_size = window_size;
+    a.d_lit_count = d_lc;
+    a.d_match_len = d_ml;
+    a.d_match_off = d_mo;
+    a.d_n_seq = &dm->n_seq;
+    a.d_literals = (const u8 *)d_lit.p;
+    a.lit_bytes = n_lit;
+    a.d_lit_off = &dm->lit_off;
+    a.d_n_lit = &dm->n_lit;
+    a.d_out_len = &dm->out_len;
+    a.d_status = &dm->status;
+    if ((rc = scl_lz77_sliding_replay_batch(&a, nullptr))) return rc;
+    SCL_HIP_TRY(hipDeviceSynchronize());
+    SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+    *out_len = meta.out_len;
+    if (meta.out_len) SCL_HIP_TRY(hipMemcpy(h_window + have, (u8 *)d_win.p + have, meta.out_len, hipMemcpyDeviceToHost));
+    return scl_status_to_error(meta.status, what);
+}
