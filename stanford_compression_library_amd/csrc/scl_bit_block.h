@@ -1,7 +1,10 @@
 // scl_bit_block.h -- the pieces of "one block of variable-length codewords across the whole grid" that do not depend on
-// whose codewords they are: the shapes, the encoder's tile emitter and the decoder's input window.  ONE copy, used by
-// scl_prefix_block.hip (one prefix-free block, tables of a scl_prefix_model) and by scl_lz77_entropy_wide.hip (the four
-// fields of an LZ77 stream at any bit position, tables built on the device).  Internal to csrc/; DESIGN.md 3.5.1, 3.6.3.
+// whose codewords they are: the shapes, the encoder's tile emitter, the decoder's input window, the bodies of the
+// self-synchronising decoder (walk, sync, end-of-stream scan, write) over a codeword policy, and the host's pass loop.  ONE
+// copy, used by scl_prefix_block.hip (one prefix-free block, tables of a scl_prefix_model) and by scl_lz77_entropy_wide.hip
+// (the four fields of an LZ77 stream at any bit position, tables built on the device).  Each of the two keeps its codeword
+// policy, its __global__ kernels (thin: tables in LDS, one call) and its verdict on how a stream ended.  Internal to csrc/;
+// DESIGN.md 3.5.1, 3.6.3.
 #pragma once
 
 #include "scl_common.h"
@@ -28,6 +31,20 @@
 struct PfbEncScratch {  // head of the encoder's scratch
     u32 fits;           // the stream fits out_cap_bytes: set before a tile is emitted
     u32 tail_word;      // the output word that out_cap_bytes cuts, in memory byte order
+};
+
+struct PfbDecHead {   // head of the decoder's scratch (zeroed by the entry point); the host reads the two pass words
+    u32 start_pass;   // the last pass in which a workgroup moved its start
+    u32 exit_pass;    // the last pass in which a workgroup's last exit changed
+    u64 n_total;      // scan_groups: symbols of the stream (before the cap)
+    u64 last_group;   // scan_groups: the workgroup the stream ends in
+};
+
+struct PfbDecGroups {  // device pointers into the decoder's scratch
+    u32 *sub;          // [n_groups * 256] PFB_PACK
+    u64 *group_exit;   // [2][n_groups] relative to the stream, PFB_NONE64: the workgroup's last thread has no exit
+    u64 *group_count;  // [n_groups] symbols up to the workgroup's first cut; scan_groups: their exclusive scan
+    u64 *group_end;    // [n_groups] PFB_NONE64, or (position of the codeword that ends the stream) << 2 | PFB_END_*
 };
 
 #ifdef __HIPCC__
@@ -108,4 +125,205 @@ __device__ __forceinline__ u32 pfb_peek(const u32 *s_win, u32 pos) {
     const u64 two = ((u64)s_win[PFB_WIN_AT(i)] << 32) | s_win[PFB_WIN_AT(i + 1)];
     return (u32)((two << o) >> 32);
 }
+
+// ---- decode: the self-synchronising scheme (Weissenberger & Schmidt; scl_prefix_block.hip describes it) --------------------
+// The bodies of the sync, scan_groups and write kernels over a codeword policy CODE, which owns its tables:
+//   load()                          EVERY thread calls it, in front of the barrier behind pfb_load_window
+//   codeword(bits, rem, len, sym)   one codeword from the left-aligned `bits`, of which `rem` >= 1 belong to the stream:
+//                                   PFB_END_EXIT (symbol `sym` of `len` bits), or the PFB_END_* that ends the walk
+//   len_gcd()                       pass 0 starts thread i at i*S rounded up to it (1: at i*S)
+// The stream is `nbits` bits from bit `base_bit` of `in`.  Positions inside a kernel are relative to the workgroup's first
+// bit (32-bit): `avail` = bits of the stream from there on, clamped to W + 64, which no walk reaches; `shift` = bit of the
+// window's first word at which the workgroup starts.
+
+// Walks from `start` to the first boundary at or past `stop`; returns how the walk ended and where.
+template <class CODE>
+__device__ __forceinline__ u32 pfb_walk(const CODE &C, const u32 *s_win, u32 shift, u32 start, u32 stop, u32 avail, u32 &count,
+                                        u32 &end) {
+    u32 pos = start, n = 0, kind = PFB_END_EXIT;
+    while (pos < stop) {  // every turn moves pos forward by a codeword or leaves
+        u32 len, sym;
+        kind = C.codeword(pfb_peek(s_win, shift + pos), avail - pos, len, sym);
+        if (kind != PFB_END_EXIT) break;
+        pos += len;
+        ++n;
+    }
+    count = n;
+    end = pos;
+    return kind;
+}
+
+template <class CODE>
+__device__ __forceinline__ void pfb_sync_body(const CODE &C, const u8 *__restrict__ in, u64 in_size_bytes, u64 base_bit,
+                                              u64 nbits, u64 n_sub, u64 n_groups, PfbDecHead *head, const PfbDecGroups &sc,
+                                              u32 pass) {
+    __shared__ u32 s_win[PFB_WIN_LDS];
+    __shared__ u32 s_exit[PFB_THREADS];  // relative to the workgroup, 0xFFFFFFFF: no exit
+    __shared__ u64 s_wave[PFB_THREADS / 64];
+    __shared__ u32 s_first_cut;
+    __shared__ int s_rerun;
+    const u32 tid = threadIdx.x;
+    const u64 group = blockIdx.x;
+    const u64 group_bit = group * PFB_GROUP;  // relative to the stream
+    const u64 sub_index = group * PFB_THREADS + tid;
+    const bool active = sub_index < n_sub;
+    const u64 left64 = nbits - group_bit;
+    const u32 avail = (u32)(left64 < PFB_GROUP + 64u ? left64 : PFB_GROUP + 64u);
+    const u32 sub0 = tid * PFB_SUB;
+    const u32 stop = min(sub0 + PFB_SUB, avail);
+    const u64 *exit_in = sc.group_exit + ((pass + 1u) & 1u) * n_groups;
+    u64 *exit_out = sc.group_exit + (pass & 1u) * n_groups;
+
+    u32 start = 0, count = 0, kind = PFB_END_EXIT, end = 0;
+    u32 from_left = 0xFFFFFFFFu;  // thread 0: the exit of the workgroup on the left
+    if (pass == 0) {
+        if (active) {  // the guess: i*S rounded up to a multiple of the gcd of the code lengths (sub 0: bit 0, exact)
+            const u64 abs_bit = sub_index * PFB_SUB;
+            const u32 g = C.len_gcd();
+            start = min(sub0 + (u32)((g - (u32)(abs_bit % g)) % g), avail);
+        }
+    } else {
+        if (tid == 0) {
+            const u32 packed = sc.sub[sub_index];
+            const u64 ex = group ? exit_in[group - 1] : PFB_NONE64;
+            const bool moved = ex != PFB_NONE64 && (u32)(ex - group_bit) != (packed & 63u);
+            s_rerun = moved ? 1 : 0;
+            if (!moved) exit_out[group] = exit_in[group];
+            else from_left = (u32)(ex - group_bit);
+        }
+        __syncthreads();
+        if (!s_rerun) return;  // uniform: this workgroup stands as it is
+        if (active) {
+            const u32 packed = sc.sub[sub_index];
+            start = sub0 + (packed & 63u);
+            count = (packed >> 6) & 511u;
+            kind = (packed >> 15) & 3u;
+            end = sub0 + (packed >> 17);
+        }
+    }
+    C.load();
+    const u64 first_bit = base_bit + group_bit;
+    pfb_load_window(s_win, in, in_size_bytes, first_bit);
+    __syncthreads();
+    const u32 shift = (u32)(first_bit & 31u);
+    if (pass == 0 && active) kind = pfb_walk(C, s_win, shift, start, stop, avail, count, end);
+    s_exit[tid] = active && kind == PFB_END_EXIT ? end : 0xFFFFFFFFu;
+    __syncthreads();
+    // after round r threads 0..r are final: thread r's left neighbour was final when it read its exit
+    for (u32 round = 0; round < PFB_THREADS; ++round) {
+        const u32 left = tid ? s_exit[tid - 1] : from_left;
+        __syncthreads();  // every exit is read before any is written
+        const bool moved = active && left != 0xFFFFFFFFu && left != start;
+        if (moved) {
+            start = left;
+            kind = pfb_walk(C, s_win, shift, start, stop, avail, count, end);
+            s_exit[tid] = kind == PFB_END_EXIT ? end : 0xFFFFFFFFu;
+        }
+        if (!__syncthreads_or(moved ? 1 : 0)) break;
+    }
+    if (active) sc.sub[sub_index] = PFB_PACK(start - sub0, count, kind, end - sub0);
+    // what the workgroup contributes if the stream reaches it: the symbols up to its first cut, and the cut
+    if (tid == 0) s_first_cut = PFB_THREADS;
+    __syncthreads();
+    if (active && kind != PFB_END_EXIT) atomicMin(&s_first_cut, tid);
+    __syncthreads();
+    const u32 first_cut = s_first_cut;
+    u64 total;
+    (void)scl_block_scan_excl<u64, PFB_THREADS, SclScanSum>(active && tid <= first_cut ? (u64)count : 0ull, s_wave, &total);
+    if (tid == first_cut) sc.group_end[group] = ((group_bit + end) << 2) | kind;
+    if (tid == 0) {
+        sc.group_count[group] = total;
+        if (first_cut == PFB_THREADS) sc.group_end[group] = PFB_NONE64;
+    }
+    if (tid == PFB_THREADS - 1) {
+        const u64 ex = active && kind == PFB_END_EXIT ? group_bit + end : PFB_NONE64;
+        if (pass) {
+            head->start_pass = pass;  // this workgroup moved its start
+            if (ex != exit_in[group]) head->exit_pass = pass;
+        }
+        exit_out[group] = ex;
+    }
+}
+
+// ONE workgroup of PFB_SCAN_THREADS: the first workgroup whose walk ends the stream (the last one if none does) and, in
+// sc.group_count, the exclusive scan of the symbol counts up to it; returns that workgroup, *total = the symbols in front of
+// the end.  The verdict on sc.group_end[that workgroup] is the caller's.
+__device__ __forceinline__ u64 pfb_scan_to_end(const PfbDecGroups &sc, u64 n_groups, u64 *total) {
+    __shared__ u64 s_wave[PFB_SCAN_THREADS / 64];
+    __shared__ unsigned long long s_first;
+    if (threadIdx.x == 0) s_first = n_groups - 1;
+    __syncthreads();
+    u64 mine = PFB_NONE64;
+    for (u64 i = threadIdx.x; i < n_groups && mine == PFB_NONE64; i += PFB_SCAN_THREADS)
+        if (sc.group_end[i] != PFB_NONE64) mine = i;
+    if (mine != PFB_NONE64) atomicMin(&s_first, (unsigned long long)mine);
+    __syncthreads();
+    const u64 last_group = s_first;
+    *total = scl_block_scan_array<u64, PFB_SCAN_THREADS, SclScanSum>(sc.group_count, last_group + 1, s_wave);
+    return last_group;
+}
+
+// every thread decodes its final range once more and stores its symbols at its offset, up to out_cap of them.
+// consumed_at_cap (or null): with more than out_cap symbols in the stream, the bit behind symbol out_cap - 1 is stored there
+template <class CODE, typename SYM>
+__device__ __forceinline__ void pfb_write_body(const CODE &C, const u8 *__restrict__ in, u64 in_size_bytes, u64 base_bit,
+                                               u64 nbits, u64 n_sub, const PfbDecHead *head, const PfbDecGroups &sc,
+                                               SYM *__restrict__ out, u64 out_cap, u64 *consumed_at_cap) {
+    __shared__ u32 s_win[PFB_WIN_LDS];
+    __shared__ u64 s_wave[PFB_THREADS / 64];
+    __shared__ u32 s_first_cut;
+    const u32 tid = threadIdx.x;
+    const u64 group = blockIdx.x;
+    if (group > head->last_group) return;  // behind the end of the stream (uniform)
+    const u64 group_first = sc.group_count[group];
+    if (group_first >= out_cap) return;  // nothing of this workgroup is stored (uniform)
+    const u64 n_total = head->n_total;
+    const u64 group_bit = group * PFB_GROUP;
+    const u64 sub_index = group * PFB_THREADS + tid;
+    const bool active = sub_index < n_sub;
+    const u64 left64 = nbits - group_bit;
+    const u32 avail = (u32)(left64 < PFB_GROUP + 64u ? left64 : PFB_GROUP + 64u);
+    const u32 packed = active ? sc.sub[sub_index] : 0u;
+    const u32 kind = (packed >> 15) & 3u;
+    if (tid == 0) s_first_cut = PFB_THREADS;
+    C.load();
+    const u64 first_bit = base_bit + group_bit;
+    pfb_load_window(s_win, in, in_size_bytes, first_bit);
+    __syncthreads();
+    if (active && kind != PFB_END_EXIT) atomicMin(&s_first_cut, tid);
+    __syncthreads();
+    const u32 count = active && tid <= s_first_cut ? (packed >> 6) & 511u : 0u;
+    u64 total;
+    u64 index = group_first + scl_block_scan_excl<u64, PFB_THREADS, SclScanSum>((u64)count, s_wave, &total);
+    const u32 shift = (u32)(first_bit & 31u);
+    u32 pos = tid * PFB_SUB + (packed & 63u);
+    for (u32 k = 0; k < count && index < out_cap; ++k, ++index) {
+        u32 len, sym;
+        if (C.codeword(pfb_peek(s_win, shift + pos), avail - pos, len, sym) != PFB_END_EXIT)
+            break;  // (not reached: the same walk counted these symbols)
+        pos += len;
+        out[index] = (SYM)sym;
+        if (consumed_at_cap && index + 1 == out_cap && n_total > out_cap) *consumed_at_cap = group_bit + pos;
+    }
+}
 #endif  // __HIPCC__
+
+// ---- decode: the host's pass loop -------------------------------------------------------------------------------------------
+// launch(p) enqueues sync pass p on `st`.  Pass 0, then passes 1 .. n_groups - 1 at the most (workgroup w is final after pass
+// w), fewer when a pass changes no workgroup's exit: after each the host reads {start_pass, exit_pass} at d_pass_words.
+// *sync_passes grows by the passes in which a workgroup moved its start.
+template <class LAUNCH>
+static int pfb_run_sync_passes(LAUNCH launch, const void *d_pass_words, u64 n_groups, hipStream_t st, u32 *sync_passes) {
+    launch(0u);
+    SCL_HIP_TRY(hipGetLastError());
+    for (u64 pass = 1; pass < n_groups; ++pass) {
+        launch((u32)pass);
+        SCL_HIP_TRY(hipGetLastError());
+        u32 flags[2];
+        SCL_HIP_TRY(hipMemcpyAsync(flags, d_pass_words, 8, hipMemcpyDeviceToHost, st));
+        SCL_HIP_TRY(hipStreamSynchronize(st));
+        if (flags[0] == (u32)pass) ++*sync_passes;
+        if (flags[1] != (u32)pass) break;
+    }
+    return SCL_OK;
+}

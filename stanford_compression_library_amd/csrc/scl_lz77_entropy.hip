@@ -11,6 +11,8 @@
 // header.  The encoder knows every size before it stores a bit (histograms -> trees -> sizes), so a stream that does not
 // fit stores nothing; the decoder walks field after field and stops at its first fault.  No workgroup waits on another,
 // every loop is bounded by the data, and nothing outside a stream's own slot / input bits / rows / literal range is touched.
+// The step from histograms to code tables (lze_build_codes) and the counts parser (lze_parse_counts) are the ones the wide
+// stage uses: scl_lz77_entropy_internal.h.
 #include "scl_lz77_entropy_internal.h"
 
 namespace {
@@ -122,30 +124,8 @@ __global__ __launch_bounds__(LZE_THREADS) void lz77_entropy_encode(
             }
             for (u64 k = lane; k < n_lit; k += SCL_WAVE) atomicAdd(&hist[LZE_LIT_BASE + lit[k]], 1u);
             __syncthreads();
-            // the four trees, one lane each
-            if (lane < 4) {
-                LzHuffTree t;
-                if (lane < 3) {
-                    t = {small[lane].prob, small[lane].heap, small[lane].parent, nullptr, small[lane].leaf_sym};
-                } else {
-                    t = {big.prob, big.heap, big.parent, nullptr, big.leaf_sym};
-                }
-                n_leaves[lane] = lz_huffman_build(hist + lane * LZE_FIELD_K, lane < 3 ? A : 256u, t);
-            }
-            __syncthreads();
-            // the code tables
-            for (u32 f = 0; f < 4; ++f) {
-                const u16 *parent = f < 3 ? small[f].parent : big.parent;
-                const u16 *leaf_sym = f < 3 ? small[f].leaf_sym : big.leaf_sym;
-                for (u32 i = lane; i < n_leaves[f]; i += SCL_WAVE) {
-                    u32 c;
-                    const u32 len = lz_huffman_leaf_code(parent, i, &c);
-                    if (len > LZ_HUFF_MAX_CODE_BITS) atomicOr(&flags, SCL_ST_SIZE);
-                    code[f * LZE_FIELD_K + leaf_sym[i]] = c;
-                    clen[f * LZE_FIELD_K + leaf_sym[i]] = (u8)(len > 255 ? 255 : len);
-                }
-            }
-            __syncthreads();
+            // the four trees, one lane each, and the code tables
+            lze_build_codes<LZE_THREADS>(hist, A, lane, small, big, n_leaves, code, clen, &flags);
             status = flags;
             // sizes
             for (u32 f = 0; f < 4; ++f) {
@@ -262,45 +242,7 @@ __global__ __launch_bounds__(LZE_THREADS) void lz77_entropy_decode(
                 for (u32 j = lane; j < LZ_HUFF_MAX_K; j += SCL_WAVE) hist[j] = 0;
                 if (lane == 0) sh_status = sh_resid = 0;
                 __syncthreads();
-                if (lane == 0) {  // the counts: Elias-delta codewords until the section is used up, exactly
-                    LzeCursor cur;
-                    cur.init(in, at + pos, counts_size);
-                    u32 j = 0, st = 0;
-                    u64 total = 0;
-                    while (cur.left) {
-                        u32 l = 0;
-                        bool one = false;
-                        while (cur.left && l <= 5) {
-                            if (cur.get(1)) {
-                                one = true;
-                                break;
-                            }
-                            ++l;
-                        }
-                        // no 1 before the end, or n + 1 >= 64: a count of 2^32 or more, or a cut codeword
-                        if (!one || cur.left < l) {
-                            st = SCL_ST_STATE;
-                            break;
-                        }
-                        const u32 n = ((1u << l) | cur.get(l)) - 1;
-                        if (n > 32 || cur.left < n) {
-                            st = SCL_ST_STATE;
-                            break;
-                        }
-                        const u64 c = ((1ull << n) | cur.get(n)) - 1;
-                        if (c >> 32) {
-                            st = SCL_ST_STATE;
-                            break;
-                        }
-                        if (j < K) {  // counts past the alphabet are ignored, as the reference does
-                            hist[j] = (u32)c;
-                            total += c;
-                        }
-                        ++j;
-                    }
-                    if (st == 0 && (j < K || total == 0)) st = SCL_ST_STATE;
-                    sh_status = st;
-                }
+                if (lane == 0) sh_status = lze_parse_counts(in, at + pos, counts_size, K, hist);
                 __syncthreads();
                 status = sh_status;
                 if (status) break;

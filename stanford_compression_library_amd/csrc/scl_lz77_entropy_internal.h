@@ -1,5 +1,6 @@
 // scl_lz77_entropy_internal.h -- what the two entropy stages of LZ77 share: the field alphabets, the log-scale binning, the
-// Elias-delta codeword of a count, the tree storage and the one-lane bit readers.  scl_lz77_entropy.hip gives a stream one
+// Elias-delta codeword of a count, the tree storage, the one-lane bit readers, the encoders' step from histograms to code
+// tables (lze_build_codes) and the decoders' counts parser (lze_parse_counts).  scl_lz77_entropy.hip gives a stream one
 // wavefront, scl_lz77_entropy_wide.hip gives ONE stream the whole GPU; both code the same bits.
 // Internal to csrc/.
 #pragma once
@@ -93,5 +94,80 @@ struct LzeCursor {
         return v;
     }
 };
+
+// ---- the encoders: histograms -> trees -> code tables ----------------------------------------------------------------------
+// EVERY one of the workgroup's THREADS threads calls, `tid` its index, with hist[LZE_SYMS] complete behind a barrier.  Four
+// threads build the four trees (A = a sequence field's alphabet), then all fill code[] / clen[] of the symbols with a count
+// and raise SCL_ST_SIZE in *flags for a codeword above 32 bits.  Ends behind a barrier: the tables and *flags are readable.
+template <u32 THREADS>
+__device__ __forceinline__ void lze_build_codes(const u32 *hist, u32 A, u32 tid, LzeSmallTree *small /* [3] */, LzeBigTree &big,
+                                                u32 *n_leaves /* [4] */, u32 *code, u8 *clen, u32 *flags) {
+    if (tid < 4) {
+        LzHuffTree t;
+        if (tid < 3) {
+            t = {small[tid].prob, small[tid].heap, small[tid].parent, nullptr, small[tid].leaf_sym};
+        } else {
+            t = {big.prob, big.heap, big.parent, nullptr, big.leaf_sym};
+        }
+        n_leaves[tid] = lz_huffman_build(hist + tid * LZE_FIELD_K, tid < 3 ? A : 256u, t);
+    }
+    __syncthreads();
+    for (u32 f = 0; f < 4; ++f) {
+        const u16 *parent = f < 3 ? small[f].parent : big.parent;
+        const u16 *leaf_sym = f < 3 ? small[f].leaf_sym : big.leaf_sym;
+        for (u32 i = tid; i < n_leaves[f]; i += THREADS) {
+            u32 c;
+            const u32 len = lz_huffman_leaf_code(parent, i, &c);
+            if (len > LZ_HUFF_MAX_CODE_BITS) atomicOr(flags, (u32)SCL_ST_SIZE);
+            code[f * LZE_FIELD_K + leaf_sym[i]] = c;
+            clen[f * LZE_FIELD_K + leaf_sym[i]] = (u8)(len > 255 ? 255 : len);
+        }
+    }
+    __syncthreads();
+}
+
+// ---- the decoders: the counts of a field -----------------------------------------------------------------------------------
+// ONE lane: the `counts_size` bits from bit `p` of `in` are Elias-delta codewords until the section is used up, exactly;
+// the first K of them go to hist[] (zeroed by the caller; counts past the alphabet are ignored, as the reference does).
+// Returns 0 or SCL_ST_STATE.
+__device__ __forceinline__ u32 lze_parse_counts(const u8 *in, u64 p, u32 counts_size, u32 K, u32 *hist) {
+    LzeCursor cur;
+    cur.init(in, p, counts_size);
+    u32 j = 0, st = 0;
+    u64 total = 0;
+    while (cur.left) {
+        u32 l = 0;
+        bool one = false;
+        while (cur.left && l <= 5) {
+            if (cur.get(1)) {
+                one = true;
+                break;
+            }
+            ++l;
+        }
+        // no 1 before the end, or n + 1 >= 64: a count of 2^32 or more, or a cut codeword
+        if (!one || cur.left < l) {
+            st = SCL_ST_STATE;
+            break;
+        }
+        const u32 n = ((1u << l) | cur.get(l)) - 1;
+        if (n > 32 || cur.left < n) {
+            st = SCL_ST_STATE;
+            break;
+        }
+        const u64 c = ((1ull << n) | cur.get(n)) - 1;
+        if (c >> 32) {
+            st = SCL_ST_STATE;
+            break;
+        }
+        if (j < K) {
+            hist[j] = (u32)c;
+            total += c;
+        }
+        ++j;
+    }
+    if (st == 0 && (j < K || total == 0)) st = SCL_ST_STATE;
+    return st;
+}
 
 #endif  // __HIPCC__

@@ -21,11 +21,11 @@
 //          lzw_dec_head    ONE workgroup: the headers, the Elias-delta counts (one lane: at most 256 codewords), the tree, a
 //                          2^9 lookup table and the node array in scratch; every fault of the one-lane decoder in its order
 //          lzw_sync / lzw_scan_groups / lzw_write   the self-synchronising scheme of scl_prefix_block.hip (Weissenberger &
-//                          Schmidt), SPECIALISED here: pfb_sync / pfb_scan_groups / pfb_write take the tables of a
-//                          scl_prefix_model and report the one-lane prefix decoder's statuses; these take the device-built
-//                          tree at a bit base and report the LZ77 one-lane decoder's (a cut codeword and a missing child are
-//                          both SCL_ST_STATE, SCL_ST_CAPACITY is decided at a leaf).  The shapes, the packing of a
-//                          subsequence and the input window are the shared ones (scl_bit_block.h)
+//                          Schmidt) from the ONE copy of its bodies (pfb_sync_body, pfb_scan_to_end, pfb_write_body and the
+//                          host's pass loop, scl_bit_block.h).  Owned here: the codeword policy LzwCode over the device-built
+//                          tree (a cut codeword and a missing child both end a walk as PFB_END_STATE), the section's bit
+//                          base, and the LZ77 one-lane decoder's verdict in lzw_scan_groups (a cut is SCL_ST_STATE,
+//                          SCL_ST_CAPACITY is decided at the leaf behind the cap)
 //          lzw_resid_bits / lzw_resid_scan / lzw_resid   the bins become values: a 64-bit scan of the residual widths over
 //                          tiles of 4096 gives each value its bits; the one-lane decoder's step of 64 values decides where a
 //                          truncated section stops counting
@@ -113,28 +113,7 @@ __global__ void __launch_bounds__(PFB_THREADS) lzw_layout_kernel(LzwEncIn in, Lz
     }
     if (tid == 0) flags = sc.head->flags;
     __syncthreads();
-    if (tid < 4) {
-        LzHuffTree t;
-        if (tid < 3) {
-            t = {small[tid].prob, small[tid].heap, small[tid].parent, nullptr, small[tid].leaf_sym};
-        } else {
-            t = {big.prob, big.heap, big.parent, nullptr, big.leaf_sym};
-        }
-        n_leaves[tid] = lz_huffman_build(hist + tid * LZE_FIELD_K, tid < 3 ? A : 256u, t);
-    }
-    __syncthreads();
-    for (u32 f = 0; f < 4; ++f) {
-        const u16 *parent = f < 3 ? small[f].parent : big.parent;
-        const u16 *leaf_sym = f < 3 ? small[f].leaf_sym : big.leaf_sym;
-        for (u32 i = tid; i < n_leaves[f]; i += PFB_THREADS) {
-            u32 c;
-            const u32 len = lz_huffman_leaf_code(parent, i, &c);
-            if (len > LZ_HUFF_MAX_CODE_BITS) atomicOr(&flags, (u32)SCL_ST_SIZE);
-            code[f * LZE_FIELD_K + leaf_sym[i]] = c;
-            clen[f * LZE_FIELD_K + leaf_sym[i]] = (u8)(len > 255 ? 255 : len);
-        }
-    }
-    __syncthreads();
+    lze_build_codes<PFB_THREADS>(hist, A, tid, small, big, n_leaves, code, clen, &flags);
     u32 status = flags;
     u64 pos = 0;
     bool header_overflow = false;
@@ -299,10 +278,7 @@ __global__ void lzw_tail_kernel(const LzwEncHead *__restrict__ head, u8 *__restr
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------
 struct LzwDecState {   // head of the decoder's scratch (256 bytes, zeroed by the entry point); the host reads it per field
-    u32 start_pass;    // the last pass in which a workgroup moved its start   } the two words the host reads per pass
-    u32 exit_pass;     // the last pass in which a workgroup's last exit changed }
-    u64 n_total;       // lzw_scan_groups: symbols of the section (before the cap)
-    u64 last_group;    // lzw_scan_groups: the workgroup the section ends in
+    PfbDecHead sync;   // first: the host reads its two pass words from byte 0; n_total and last_group are of the section
     u64 pos;           // bits of the stream used so far: `consumed`
     u32 status, go;    // go: the field has a values section to decode (lzw_dec_head)
     u32 count[4];      // values decoded per field
@@ -321,10 +297,7 @@ struct LzwDecScratch {
     u16 *kids;         // [2 * LZ_HUFF_MAX_K]
     u16 *leaf_sym;     // [LZ_HUFF_MAX_K]
     u64 *resid_bits;   // [tiles(seq_cap)]
-    u32 *sub;          // [n_groups * 256] PFB_PACK
-    u64 *group_exit;   // [2][n_groups] relative to the section, PFB_NONE64: the workgroup's last thread has no exit
-    u64 *group_count;  // [n_groups] symbols up to the workgroup's first cut; lzw_scan_groups: their exclusive scan
-    u64 *group_end;    // [n_groups] PFB_NONE64, or (position of the codeword that ends the section) << 2 | PFB_END_STATE
+    PfbDecGroups g;    // positions relative to the section; a section ends with PFB_END_STATE only
 };
 
 struct LzwDecIn {
@@ -377,41 +350,7 @@ __global__ void __launch_bounds__(PFB_THREADS) lzw_dec_head_kernel(LzwDecIn a, L
                 st = SCL_ST_TRUNCATED;
                 break;
             }
-            LzeCursor cur;  // the counts: Elias-delta codewords until the section is used up, exactly
-            cur.init(a.in, at + pos, counts_size);
-            u32 j = 0;
-            u64 total = 0;
-            while (cur.left) {
-                u32 l = 0;
-                bool one = false;
-                while (cur.left && l <= 5) {
-                    if (cur.get(1)) {
-                        one = true;
-                        break;
-                    }
-                    ++l;
-                }
-                if (!one || cur.left < l) {
-                    st = SCL_ST_STATE;
-                    break;
-                }
-                const u32 n = ((1u << l) | cur.get(l)) - 1;
-                if (n > 32 || cur.left < n) {
-                    st = SCL_ST_STATE;
-                    break;
-                }
-                const u64 c = ((1ull << n) | cur.get(n)) - 1;
-                if (c >> 32) {
-                    st = SCL_ST_STATE;
-                    break;
-                }
-                if (j < K) {  // counts past the alphabet are ignored, as the reference does
-                    hist[j] = (u32)c;
-                    total += c;
-                }
-                ++j;
-            }
-            if (st == 0 && (j < K || total == 0)) st = SCL_ST_STATE;
+            st = lze_parse_counts(a.in, at + pos, counts_size, K, hist);
             if (st) break;
             pos += counts_size;
             if (pos + 32 > nbits) {
@@ -474,181 +413,75 @@ __global__ void __launch_bounds__(PFB_THREADS) lzw_dec_head_kernel(LzwDecIn a, L
         S->values_at = sh_pos;
         S->values_size = sh_values_size;
         S->m = m;
-        S->start_pass = S->exit_pass = 0;
+        S->sync.start_pass = S->sync.exit_pass = 0;
         S->resid_total = 0;
         S->resid_fail_at = PFB_NONE64;
         S->resid_fail_k = S->resid_overflow = LZW_NONE32;
     }
 }
 
-// the tree of the field in LDS
-struct LzwTables {
-    const u32 *lut;
-    const u16 *kids, *leaf_sym;
+// the codeword policy of pfb_sync_body / pfb_write_body: the tree of the field, from scratch into LDS
+struct LzwCode {
+    const LzwDecScratch &sc;  // lzw_dec_head's lut, kids and leaf_sym
+    u32 *s_lut;             // [LZW_LUT_SIZE]
+    u16 *s_kids, *s_leaf;   // [2 * LZ_HUFF_MAX_K], [LZ_HUFF_MAX_K]
     u32 m;
+
+    __device__ __forceinline__ void load() const {
+        for (u32 i = threadIdx.x; i < LZW_LUT_SIZE; i += PFB_THREADS) s_lut[i] = sc.lut[i];
+        for (u32 i = threadIdx.x; i < 2 * LZ_HUFF_MAX_K; i += PFB_THREADS) s_kids[i] = sc.kids[i];
+        for (u32 i = threadIdx.x; i < LZ_HUFF_MAX_K; i += PFB_THREADS) s_leaf[i] = sc.leaf_sym[i];
+    }
+    __device__ __forceinline__ u32 len_gcd() const { return 1u; }  // (no gcd is kept for a tree built on the device)
+    // PFB_END_EXIT: a symbol of `len` bits; PFB_END_STATE: what ends the one-lane walk -- a bit into the missing child, or the
+    // section cut the codeword.
+    __device__ __forceinline__ u32 codeword(u32 bits, u32 rem, u32 &len, u32 &sym) const {
+        const u32 e = s_lut[bits >> (32u - LZW_LUT_BITS)];
+        const u32 kind = e >> 30;
+        len = (e >> 16) & 63u;
+        sym = e & 0xFFFFu;
+        if (len > rem) return PFB_END_STATE;
+        if (kind == LZW_KIND_LEAF) return PFB_END_EXIT;
+        if (kind == LZW_KIND_NONE) return PFB_END_STATE;
+        u32 node = sym;
+        for (u32 d = LZW_LUT_BITS; d < LZ_HUFF_MAX_CODE_BITS; ++d) {
+            if (d == rem) return PFB_END_STATE;
+            const u32 next = s_kids[2 * (node - m) + ((bits >> (31u - d)) & 1u)];
+            if (next == LZ_HUFF_NONE) return PFB_END_STATE;
+            if (next < m) {
+                sym = s_leaf[next];
+                len = d + 1;
+                return PFB_END_EXIT;
+            }
+            node = next;
+        }
+        return PFB_END_STATE;  // (not reached: lzw_dec_head refused a code above 32 bits)
+    }
 };
 
-__device__ __forceinline__ void lzw_load_tables(const LzwDecScratch &sc, u32 *s_lut, u16 *s_kids, u16 *s_leaf) {
-    for (u32 i = threadIdx.x; i < LZW_LUT_SIZE; i += PFB_THREADS) s_lut[i] = sc.lut[i];
-    for (u32 i = threadIdx.x; i < 2 * LZ_HUFF_MAX_K; i += PFB_THREADS) s_kids[i] = sc.kids[i];
-    for (u32 i = threadIdx.x; i < LZ_HUFF_MAX_K; i += PFB_THREADS) s_leaf[i] = sc.leaf_sym[i];
-}
-
-// One codeword from the left-aligned `bits`, of which `rem` >= 1 belong to the section.  PFB_END_EXIT: a symbol of `len` bits;
-// PFB_END_STATE: what ends the one-lane walk -- a bit into the missing child, or the section cut the codeword.
-__device__ __forceinline__ u32 lzw_codeword(const LzwTables &T, u32 bits, u32 rem, u32 &len, u32 &sym) {
-    const u32 e = T.lut[bits >> (32u - LZW_LUT_BITS)];
-    const u32 kind = e >> 30;
-    len = (e >> 16) & 63u;
-    sym = e & 0xFFFFu;
-    if (len > rem) return PFB_END_STATE;
-    if (kind == LZW_KIND_LEAF) return PFB_END_EXIT;
-    if (kind == LZW_KIND_NONE) return PFB_END_STATE;
-    u32 node = sym;
-    for (u32 d = LZW_LUT_BITS; d < LZ_HUFF_MAX_CODE_BITS; ++d) {
-        if (d == rem) return PFB_END_STATE;
-        const u32 next = T.kids[2 * (node - T.m) + ((bits >> (31u - d)) & 1u)];
-        if (next == LZ_HUFF_NONE) return PFB_END_STATE;
-        if (next < T.m) {
-            sym = T.leaf_sym[next];
-            len = d + 1;
-            return PFB_END_EXIT;
-        }
-        node = next;
-    }
-    return PFB_END_STATE;  // (not reached: lzw_dec_head refused a code above 32 bits)
-}
-
-// Walks from `start` to the first boundary at or past `stop` (positions relative to the workgroup's first bit, as in
-// scl_prefix_block.hip); returns how the walk ended and where.
-__device__ __forceinline__ u32 lzw_walk(const LzwTables &T, const u32 *s_win, u32 shift, u32 start, u32 stop, u32 avail,
-                                        u32 &count, u32 &end) {
-    u32 pos = start, n = 0, kind = PFB_END_EXIT;
-    while (pos < stop) {  // every turn moves pos forward by a codeword or leaves
-        u32 len, sym;
-        kind = lzw_codeword(T, pfb_peek(s_win, shift + pos), avail - pos, len, sym);
-        if (kind != PFB_END_EXIT) break;
-        pos += len;
-        ++n;
-    }
-    count = n;
-    end = pos;
-    return kind;
-}
-
-// pfb_sync_kernel over the field's section: `base_bit` = its first bit in the input, `nbits` = values_size
+// the field's section: `base_bit` = its first bit in the input, `nbits` = values_size
 __global__ void __launch_bounds__(PFB_THREADS, 4) lzw_sync_kernel(LzwDecIn a, u64 base_bit, u64 nbits, u64 n_sub, u64 n_groups,
                                                                   LzwDecScratch sc, u32 m, u32 pass) {
     __shared__ u32 s_lut[LZW_LUT_SIZE];
     __shared__ u16 s_kids[2 * LZ_HUFF_MAX_K], s_leaf[LZ_HUFF_MAX_K];
-    __shared__ u32 s_win[PFB_WIN_LDS];
-    __shared__ u32 s_exit[PFB_THREADS];  // relative to the workgroup, 0xFFFFFFFF: no exit
-    __shared__ u64 s_wave[PFB_THREADS / 64];
-    __shared__ u32 s_first_cut;
-    __shared__ int s_rerun;
-    const LzwTables T = {s_lut, s_kids, s_leaf, m};
-    const u32 tid = threadIdx.x;
-    const u64 group = blockIdx.x;
-    const u64 group_bit = group * PFB_GROUP;  // relative to the section
-    const u64 sub_index = group * PFB_THREADS + tid;
-    const bool active = sub_index < n_sub;
-    const u64 left64 = nbits - group_bit;
-    const u32 avail = (u32)(left64 < PFB_GROUP + 64u ? left64 : PFB_GROUP + 64u);
-    const u32 sub0 = tid * PFB_SUB;
-    const u32 stop = min(sub0 + PFB_SUB, avail);
-    const u64 *exit_in = sc.group_exit + ((pass + 1u) & 1u) * n_groups;
-    u64 *exit_out = sc.group_exit + (pass & 1u) * n_groups;
-
-    u32 start = 0, count = 0, kind = PFB_END_EXIT, end = 0;
-    u32 from_left = 0xFFFFFFFFu;  // thread 0: the exit of the workgroup on the left
-    if (pass == 0) {
-        if (active) start = min(sub0, avail);  // the guess (sub 0: bit 0, exact)
-    } else {
-        if (tid == 0) {
-            const u32 packed = sc.sub[sub_index];
-            const u64 ex = group ? exit_in[group - 1] : PFB_NONE64;
-            const bool moved = ex != PFB_NONE64 && (u32)(ex - group_bit) != (packed & 63u);
-            s_rerun = moved ? 1 : 0;
-            if (!moved) exit_out[group] = exit_in[group];
-            else from_left = (u32)(ex - group_bit);
-        }
-        __syncthreads();
-        if (!s_rerun) return;  // uniform: this workgroup stands as it is
-        if (active) {
-            const u32 packed = sc.sub[sub_index];
-            start = sub0 + (packed & 63u);
-            count = (packed >> 6) & 511u;
-            kind = (packed >> 15) & 3u;
-            end = sub0 + (packed >> 17);
-        }
-    }
-    lzw_load_tables(sc, s_lut, s_kids, s_leaf);
-    const u64 first_bit = base_bit + group_bit;
-    pfb_load_window(s_win, a.in, a.in_size_bytes, first_bit);
-    __syncthreads();
-    const u32 shift = (u32)(first_bit & 31u);
-    if (pass == 0 && active) kind = lzw_walk(T, s_win, shift, start, stop, avail, count, end);
-    s_exit[tid] = active && kind == PFB_END_EXIT ? end : 0xFFFFFFFFu;
-    __syncthreads();
-    // after round r threads 0..r are final: thread r's left neighbour was final when it read its exit
-    for (u32 round = 0; round < PFB_THREADS; ++round) {
-        const u32 left = tid ? s_exit[tid - 1] : from_left;
-        __syncthreads();  // every exit is read before any is written
-        const bool moved = active && left != 0xFFFFFFFFu && left != start;
-        if (moved) {
-            start = left;
-            kind = lzw_walk(T, s_win, shift, start, stop, avail, count, end);
-            s_exit[tid] = kind == PFB_END_EXIT ? end : 0xFFFFFFFFu;
-        }
-        if (!__syncthreads_or(moved ? 1 : 0)) break;
-    }
-    if (active) sc.sub[sub_index] = PFB_PACK(start - sub0, count, kind, end - sub0);
-    // what the workgroup contributes if the section reaches it: the symbols up to its first cut, and the cut
-    if (tid == 0) s_first_cut = PFB_THREADS;
-    __syncthreads();
-    if (active && kind != PFB_END_EXIT) atomicMin(&s_first_cut, tid);
-    __syncthreads();
-    const u32 first_cut = s_first_cut;
-    u64 total;
-    (void)scl_block_scan_excl<u64, PFB_THREADS, SclScanSum>(active && tid <= first_cut ? (u64)count : 0ull, s_wave, &total);
-    if (tid == first_cut) sc.group_end[group] = ((group_bit + end) << 2) | kind;
-    if (tid == 0) {
-        sc.group_count[group] = total;
-        if (first_cut == PFB_THREADS) sc.group_end[group] = PFB_NONE64;
-    }
-    if (tid == PFB_THREADS - 1) {
-        const u64 ex = active && kind == PFB_END_EXIT ? group_bit + end : PFB_NONE64;
-        if (pass) {
-            sc.state->start_pass = pass;  // this workgroup moved its start
-            if (ex != exit_in[group]) sc.state->exit_pass = pass;
-        }
-        exit_out[group] = ex;
-    }
+    pfb_sync_body(LzwCode{sc, s_lut, s_kids, s_leaf, m}, a.in, a.in_size_bytes, base_bit, nbits, n_sub, n_groups, &sc.state->sync,
+                  sc.g, pass);
 }
 
 // ONE workgroup: where the section ends, the symbol offsets of the workgroups up to there, the field's count and status as
 // the one-lane walk decides them: more symbols than `cap` is SCL_ST_CAPACITY at the leaf behind the cap, before any later
 // fault; otherwise a cut is SCL_ST_STATE
 __global__ void __launch_bounds__(PFB_SCAN_THREADS) lzw_scan_groups_kernel(LzwDecScratch sc, u64 n_groups, u64 cap, u32 f) {
-    __shared__ u64 s_wave[PFB_SCAN_THREADS / 64];
-    __shared__ unsigned long long s_first;
-    if (threadIdx.x == 0) s_first = n_groups - 1;
-    __syncthreads();
-    u64 mine = PFB_NONE64;
-    for (u64 i = threadIdx.x; i < n_groups && mine == PFB_NONE64; i += PFB_SCAN_THREADS)
-        if (sc.group_end[i] != PFB_NONE64) mine = i;
-    if (mine != PFB_NONE64) atomicMin(&s_first, (unsigned long long)mine);
-    __syncthreads();
-    const u64 last_group = s_first;
-    const u64 total = scl_block_scan_array<u64, PFB_SCAN_THREADS, SclScanSum>(sc.group_count, last_group + 1, s_wave);
+    u64 total;
+    const u64 last_group = pfb_scan_to_end(sc.g, n_groups, &total);
     if (threadIdx.x == 0) {
         LzwDecState *S = sc.state;
-        const u64 cut = sc.group_end[last_group];
+        const u64 cut = sc.g.group_end[last_group];
         u32 status = 0;
         if (total > cap) status = SCL_ST_CAPACITY;
         else if (cut != PFB_NONE64) status = SCL_ST_STATE;
-        S->n_total = total;
-        S->last_group = last_group;
+        S->sync.n_total = total;
+        S->sync.last_group = last_group;
         S->count[f] = (u32)(total < cap ? total : cap);
         S->status = status;
         if (status == 0) {
@@ -663,41 +496,8 @@ __global__ void __launch_bounds__(PFB_THREADS, 4) lzw_write_kernel(LzwDecIn a, u
                                                                    LzwDecScratch sc, u32 m, SYM *__restrict__ out, u64 cap) {
     __shared__ u32 s_lut[LZW_LUT_SIZE];
     __shared__ u16 s_kids[2 * LZ_HUFF_MAX_K], s_leaf[LZ_HUFF_MAX_K];
-    __shared__ u32 s_win[PFB_WIN_LDS];
-    __shared__ u64 s_wave[PFB_THREADS / 64];
-    __shared__ u32 s_first_cut;
-    const LzwTables T = {s_lut, s_kids, s_leaf, m};
-    const u32 tid = threadIdx.x;
-    const u64 group = blockIdx.x;
-    if (group > sc.state->last_group) return;  // behind the end of the section (uniform)
-    const u64 group_first = sc.group_count[group];
-    if (group_first >= cap) return;  // nothing of this workgroup is stored (uniform)
-    const u64 group_bit = group * PFB_GROUP;
-    const u64 sub_index = group * PFB_THREADS + tid;
-    const bool active = sub_index < n_sub;
-    const u64 left64 = nbits - group_bit;
-    const u32 avail = (u32)(left64 < PFB_GROUP + 64u ? left64 : PFB_GROUP + 64u);
-    const u32 packed = active ? sc.sub[sub_index] : 0u;
-    const u32 kind = (packed >> 15) & 3u;
-    if (tid == 0) s_first_cut = PFB_THREADS;
-    lzw_load_tables(sc, s_lut, s_kids, s_leaf);
-    const u64 first_bit = base_bit + group_bit;
-    pfb_load_window(s_win, a.in, a.in_size_bytes, first_bit);
-    __syncthreads();
-    if (active && kind != PFB_END_EXIT) atomicMin(&s_first_cut, tid);
-    __syncthreads();
-    const u32 count = active && tid <= s_first_cut ? (packed >> 6) & 511u : 0u;
-    u64 total;
-    u64 index = group_first + scl_block_scan_excl<u64, PFB_THREADS, SclScanSum>((u64)count, s_wave, &total);
-    const u32 shift = (u32)(first_bit & 31u);
-    u32 pos = tid * PFB_SUB + (packed & 63u);
-    for (u32 k = 0; k < count && index < cap; ++k, ++index) {
-        u32 len, sym;
-        if (lzw_codeword(T, pfb_peek(s_win, shift + pos), avail - pos, len, sym) != PFB_END_EXIT)
-            break;  // (not reached: the same walk counted these symbols)
-        pos += len;
-        out[index] = (SYM)sym;
-    }
+    pfb_write_body(LzwCode{sc, s_lut, s_kids, s_leaf, m}, a.in, a.in_size_bytes, base_bit, nbits, n_sub, &sc.state->sync, sc.g, out,
+                   cap, (u64 *)nullptr);
 }
 
 // the residual width of the thread's PFB_PER_THREAD consecutive bins of tile `tile` (0 past the field's count)
@@ -823,6 +623,7 @@ LzwDecLayout lzw_dec_layout(u64 seq_cap, u64 in_nbits) {
 }
 
 static_assert(sizeof(LzwEncHead) <= 256 && sizeof(LzwDecState) <= 256, "the heads are one carved part each");
+static_assert(offsetof(LzwDecState, sync) == 0, "the host reads the two pass words from byte 0 of the scratch");
 
 }  // namespace
 
@@ -912,9 +713,9 @@ extern "C" int scl_lz77_entropy_decode_wide(const scl_lz77_entropy_wide_decode_a
                 (unsigned long long)a->scratch_bytes, (unsigned long long)l.total);
     hipStream_t st = (hipStream_t)stream;
     u8 *p = (u8 *)a->d_scratch;
-    const LzwDecScratch sc = {(LzwDecState *)(p + l.state), (u32 *)(p + l.lut),         (u16 *)(p + l.kids),
-                              (u16 *)(p + l.leaf_sym),      (u64 *)(p + l.resid_bits),  (u32 *)(p + l.sub),
-                              (u64 *)(p + l.group_exit),    (u64 *)(p + l.group_count), (u64 *)(p + l.group_end)};
+    const LzwDecScratch sc = {(LzwDecState *)(p + l.state), (u32 *)(p + l.lut), (u16 *)(p + l.kids), (u16 *)(p + l.leaf_sym),
+                              (u64 *)(p + l.resid_bits),
+                              {(u32 *)(p + l.sub), (u64 *)(p + l.group_exit), (u64 *)(p + l.group_count), (u64 *)(p + l.group_end)}};
     const LzwDecIn in = {a->d_in, a->in_size_bytes, a->in_bit_offset, a->in_nbits, a->binned_offset};
     SCL_HIP_TRY(hipMemsetAsync(sc.state, 0, sizeof(LzwDecState), st));
     u32 sync_passes = 0;
@@ -930,18 +731,10 @@ extern "C" int scl_lz77_entropy_decode_wide(const scl_lz77_entropy_wide_decode_a
         const u64 n_sub = (nbits + PFB_SUB - 1) / PFB_SUB, n_groups = lzw_groups(nbits);
         const u64 cap = f < 3 ? a->seq_cap : a->lit_cap;
         const dim3 grid((u32)n_groups), block(PFB_THREADS);
-        hipLaunchKernelGGL(lzw_sync_kernel, grid, block, 0, st, in, base_bit, nbits, n_sub, n_groups, sc, h.m, 0u);
-        SCL_HIP_TRY(hipGetLastError());
-        // workgroup w is final after pass w: passes 1 .. n_groups - 1 at the most, fewer when a pass changes no exit
-        for (u64 pass = 1; pass < n_groups; ++pass) {
-            hipLaunchKernelGGL(lzw_sync_kernel, grid, block, 0, st, in, base_bit, nbits, n_sub, n_groups, sc, h.m, (u32)pass);
-            SCL_HIP_TRY(hipGetLastError());
-            u32 flags[2];  // {start_pass, exit_pass}
-            SCL_HIP_TRY(hipMemcpyAsync(flags, sc.state, 8, hipMemcpyDeviceToHost, st));
-            SCL_HIP_TRY(hipStreamSynchronize(st));
-            if (flags[0] == (u32)pass) ++sync_passes;
-            if (flags[1] != (u32)pass) break;
-        }
+        const auto sync = [&](u32 pass) {
+            hipLaunchKernelGGL(lzw_sync_kernel, grid, block, 0, st, in, base_bit, nbits, n_sub, n_groups, sc, h.m, pass);
+        };
+        if (int rc = pfb_run_sync_passes(sync, sc.state, n_groups, st, &sync_passes)) return rc;
         hipLaunchKernelGGL(lzw_scan_groups_kernel, dim3(1), dim3(PFB_SCAN_THREADS), 0, st, sc, n_groups, cap, f);
         if (f < 3) {
             u32 *row = f == 0 ? a->d_lit_count : f == 1 ? a->d_match_len : a->d_match_off;

@@ -28,6 +28,9 @@
 //          pfb_scan_groups  ONE workgroup: first workgroup whose walk ends the stream (cut codeword / missing child),
 //                           exclusive 64-bit scan of the symbol counts up to it, the result triple
 //          pfb_write        every thread decodes its final range once more and stores its symbols at its offset
+//          The scheme's code stands ONCE, in scl_bit_block.h (pfb_sync_body, pfb_scan_to_end, pfb_write_body, the host's
+//          pass loop), shared with scl_lz77_entropy_wide.hip.  Owned here: the codeword policy PfbCode<FAST> over the tables
+//          of a scl_prefix_model, the three kernels as thin wrappers, and the verdict of pfb_scan_groups.
 // No kernel waits on another workgroup: no flag is spun on, no look-back, no cooperative launch -- a grid that is not
 // resident all at once finishes like any other.  Every loop is bounded by the data: symbols in a tile, bits left in a
 // subsequence, 256 rounds, a walk of at most 32 bits.
@@ -149,94 +152,70 @@ __global__ void pfb_encode_tail_kernel(const PfbEncScratch *__restrict__ head, c
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------
-struct PfbDecHead {      // head of the decoder's scratch (64 bytes)
-    u32 start_pass;      // the last pass in which a workgroup moved its start
-    u32 exit_pass;       // the last pass in which a workgroup's last exit changed
-    u64 n_total;         // pfb_scan_groups: symbols of the stream (before out_cap)
-    u64 last_group;      // pfb_scan_groups: the workgroup the stream ends in
-};
-
+// (PfbDecHead -- the head of the decoder's scratch, 64 bytes --, the input window and the bodies of the three kernels over a
+// codeword policy: scl_bit_block.h.  Here: the policy over the tables of a scl_prefix_model, and the verdict)
 struct PfbDecScratch {  // device pointers into the scratch
     PfbDecHead *head;
-    u32 *sub;           // [n_groups * 256] PFB_PACK
-    u64 *group_exit;    // [2][n_groups] relative to the stream, PFB_NONE64: the workgroup's last thread has no exit
-    u64 *group_count;   // [n_groups] symbols up to the workgroup's first cut; pfb_scan_groups: their exclusive scan
-    u64 *group_end;     // [n_groups] PFB_NONE64, or (position of the codeword that ends the stream) << 2 | PFB_END_*
+    PfbDecGroups g;
 };
 
-// (the input window a workgroup can reach, pfb_load_window / pfb_peek: scl_bit_block.h)
-
-// One codeword from the left-aligned `bits`, of which `rem` >= 1 belong to the stream.  Exactly what the one-lane
-// decoders of scl_prefix.hip decide: PFB_END_EXIT (a symbol of `len` bits), PFB_END_TRUNC, PFB_END_STATE.
+// FAST: the 11-bit table and the deep nodes in LDS (byte alphabets); otherwise the node array where it is
 template <bool FAST>
-__device__ __forceinline__ u32 pfb_codeword(const PrefixDev &P, const u16 *s_lut, const u32 *s_deep, u32 bits, u32 rem,
-                                            u32 &len, u32 &sym) {
-    if constexpr (FAST) {
-        const u32 T = P.lut_bits;
-        const u32 e = s_lut[bits >> (32u - T)];
-        const u32 kind = (e >> 4) & 3u;
-        len = e & 15u;
-        sym = e >> 6;
-        if (len > rem) return PFB_END_TRUNC;
-        if (kind == PF_KIND_SYM) return PFB_END_EXIT;
-        if (kind == PF_KIND_NONE) return PFB_END_STATE;
-        u32 node = sym;
-        for (u32 d = T; d < PF_MAX_LEN; ++d) {
-            if (d == rem) return PFB_END_TRUNC;
-            const u32 next = (s_deep[node] >> (16u * ((bits >> (31u - d)) & 1u))) & 0xFFFFu;
-            if (next == PF16_NONE) return PFB_END_STATE;
-            if (next & PF16_LEAF) {
-                sym = next & 0xFFu;
-                len = d + 1;
-                return PFB_END_EXIT;
-            }
-            node = next;
+struct PfbCode {
+    const PrefixDev &P;
+    u16 *s_lut;   // [1 << PF_LUT_BITS]
+    u32 *s_deep;  // [PF_DEEP_NODES]
+
+    __device__ __forceinline__ void load() const {
+        if constexpr (FAST) {
+            for (u32 i = threadIdx.x; i < (1u << P.lut_bits); i += PFB_THREADS) s_lut[i] = P.d_lut[i];
+            for (u32 i = threadIdx.x; i < P.n_deep; i += PFB_THREADS) s_deep[i] = P.d_deep[i];
         }
-        return PFB_END_STATE;  // (not reached: the tree is at most 32 deep)
-    } else {
-        u32 node = 0;
-        for (u32 d = 0; d < PF_MAX_LEN; ++d) {
-            if (d == rem) return PFB_END_TRUNC;
-            const uint2 ch = P.d_nodes[node];
-            const u32 next = ((bits >> (31u - d)) & 1u) ? ch.y : ch.x;
-            if (next == PF_NONE) return PFB_END_STATE;
-            if (next & PF_LEAF) {
-                sym = next & 0xFFFFu;
-                len = d + 1;
-                return PFB_END_EXIT;
+    }
+    __device__ __forceinline__ u32 len_gcd() const { return P.len_gcd; }
+    // Exactly what the one-lane decoders of scl_prefix.hip decide: PFB_END_EXIT, PFB_END_TRUNC (the stream cuts the
+    // codeword), PFB_END_STATE (a missing child).
+    __device__ __forceinline__ u32 codeword(u32 bits, u32 rem, u32 &len, u32 &sym) const {
+        if constexpr (FAST) {
+            const u32 T = P.lut_bits;
+            const u32 e = s_lut[bits >> (32u - T)];
+            const u32 kind = (e >> 4) & 3u;
+            len = e & 15u;
+            sym = e >> 6;
+            if (len > rem) return PFB_END_TRUNC;
+            if (kind == PF_KIND_SYM) return PFB_END_EXIT;
+            if (kind == PF_KIND_NONE) return PFB_END_STATE;
+            u32 node = sym;
+            for (u32 d = T; d < PF_MAX_LEN; ++d) {
+                if (d == rem) return PFB_END_TRUNC;
+                const u32 next = (s_deep[node] >> (16u * ((bits >> (31u - d)) & 1u))) & 0xFFFFu;
+                if (next == PF16_NONE) return PFB_END_STATE;
+                if (next & PF16_LEAF) {
+                    sym = next & 0xFFu;
+                    len = d + 1;
+                    return PFB_END_EXIT;
+                }
+                node = next;
             }
-            node = next;
+            return PFB_END_STATE;  // (not reached: the tree is at most 32 deep)
+        } else {
+            u32 node = 0;
+            for (u32 d = 0; d < PF_MAX_LEN; ++d) {
+                if (d == rem) return PFB_END_TRUNC;
+                const uint2 ch = P.d_nodes[node];
+                const u32 next = ((bits >> (31u - d)) & 1u) ? ch.y : ch.x;
+                if (next == PF_NONE) return PFB_END_STATE;
+                if (next & PF_LEAF) {
+                    sym = next & 0xFFFFu;
+                    len = d + 1;
+                    return PFB_END_EXIT;
+                }
+                node = next;
+            }
+            return rem > PF_MAX_LEN ? PFB_END_STATE : PFB_END_TRUNC;  // (not reached)
         }
-        return rem > PF_MAX_LEN ? PFB_END_STATE : PFB_END_TRUNC;  // (not reached)
     }
-}
-
-template <bool FAST>
-__device__ __forceinline__ void pfb_load_tables(const PrefixDev &P, u16 *s_lut, u32 *s_deep) {
-    if constexpr (FAST) {
-        for (u32 i = threadIdx.x; i < (1u << P.lut_bits); i += PFB_THREADS) s_lut[i] = P.d_lut[i];
-        for (u32 i = threadIdx.x; i < P.n_deep; i += PFB_THREADS) s_deep[i] = P.d_deep[i];
-    }
-}
-
-// Positions below are relative to the workgroup's first bit (32-bit): `avail` = bits of the stream from there on, clamped
-// to W + 64, which no walk reaches; `shift` = bit of the window's first word at which the workgroup starts.
-// Walks from `start` to the first boundary at or past `stop`; returns how the walk ended and where.
-template <bool FAST>
-__device__ __forceinline__ u32 pfb_walk(const PrefixDev &P, const u16 *s_lut, const u32 *s_deep, const u32 *s_win, u32 shift,
-                                        u32 start, u32 stop, u32 avail, u32 &count, u32 &end) {
-    u32 pos = start, n = 0, kind = PFB_END_EXIT;
-    while (pos < stop) {  // every turn moves pos forward by a codeword or leaves
-        u32 len, sym;
-        kind = pfb_codeword<FAST>(P, s_lut, s_deep, pfb_peek(s_win, shift + pos), avail - pos, len, sym);
-        if (kind != PFB_END_EXIT) break;
-        pos += len;
-        ++n;
-    }
-    count = n;
-    end = pos;
-    return kind;
-}
+};
 
 template <bool FAST>
 __global__ void __launch_bounds__(PFB_THREADS, 4)
@@ -244,111 +223,18 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
                     u64 n_groups, PfbDecScratch sc, u32 pass) {
     __shared__ u16 s_lut[FAST ? (1u << PF_LUT_BITS) : 1];
     __shared__ u32 s_deep[FAST ? PF_DEEP_NODES : 1];
-    __shared__ u32 s_win[PFB_WIN_LDS];
-    __shared__ u32 s_exit[PFB_THREADS];  // relative to the workgroup, 0xFFFFFFFF: no exit
-    __shared__ u64 s_wave[PFB_THREADS / 64];
-    __shared__ u32 s_first_cut;
-    __shared__ int s_rerun;
-    const u32 tid = threadIdx.x;
-    const u64 group = blockIdx.x;
-    const u64 group_bit = group * PFB_GROUP;  // relative to the stream
-    const u64 sub_index = group * PFB_THREADS + tid;
-    const bool active = sub_index < n_sub;
-    const u64 left64 = in_nbits - group_bit;
-    const u32 avail = (u32)(left64 < PFB_GROUP + 64u ? left64 : PFB_GROUP + 64u);
-    const u32 sub0 = tid * PFB_SUB;
-    const u32 stop = min(sub0 + PFB_SUB, avail);
-    const u64 *exit_in = sc.group_exit + ((pass + 1u) & 1u) * n_groups;
-    u64 *exit_out = sc.group_exit + (pass & 1u) * n_groups;
-
-    u32 start = 0, count = 0, kind = PFB_END_EXIT, end = 0;
-    u32 from_left = 0xFFFFFFFFu;  // thread 0: the exit of the workgroup on the left
-    if (pass == 0) {
-        if (active) {  // the guess: i*S rounded up to a multiple of the gcd of the code lengths (sub 0: bit 0, exact)
-            const u64 abs_bit = sub_index * PFB_SUB;
-            const u32 g = P.len_gcd;
-            start = min(sub0 + (u32)((g - (u32)(abs_bit % g)) % g), avail);
-        }
-    } else {
-        if (tid == 0) {
-            const u32 packed = sc.sub[sub_index];
-            const u64 ex = group ? exit_in[group - 1] : PFB_NONE64;
-            const bool moved = ex != PFB_NONE64 && (u32)(ex - group_bit) != (packed & 63u);
-            s_rerun = moved ? 1 : 0;
-            if (!moved) exit_out[group] = exit_in[group];
-            else from_left = (u32)(ex - group_bit);
-        }
-        __syncthreads();
-        if (!s_rerun) return;  // uniform: this workgroup stands as it is
-        if (active) {
-            const u32 packed = sc.sub[sub_index];
-            start = sub0 + (packed & 63u);
-            count = (packed >> 6) & 511u;
-            kind = (packed >> 15) & 3u;
-            end = sub0 + (packed >> 17);
-        }
-    }
-    pfb_load_tables<FAST>(P, s_lut, s_deep);
-    const u64 first_bit = in_bit_offset + group_bit;
-    pfb_load_window(s_win, in, in_size_bytes, first_bit);
-    __syncthreads();
-    const u32 shift = (u32)(first_bit & 31u);
-    if (pass == 0 && active) kind = pfb_walk<FAST>(P, s_lut, s_deep, s_win, shift, start, stop, avail, count, end);
-    s_exit[tid] = active && kind == PFB_END_EXIT ? end : 0xFFFFFFFFu;
-    __syncthreads();
-    // after round r threads 0..r are final: thread r's left neighbour was final when it read its exit
-    for (u32 round = 0; round < PFB_THREADS; ++round) {
-        const u32 left = tid ? s_exit[tid - 1] : from_left;
-        __syncthreads();  // every exit is read before any is written
-        const bool moved = active && left != 0xFFFFFFFFu && left != start;
-        if (moved) {
-            start = left;
-            kind = pfb_walk<FAST>(P, s_lut, s_deep, s_win, shift, start, stop, avail, count, end);
-            s_exit[tid] = kind == PFB_END_EXIT ? end : 0xFFFFFFFFu;
-        }
-        if (!__syncthreads_or(moved ? 1 : 0)) break;
-    }
-    if (active) sc.sub[sub_index] = PFB_PACK(start - sub0, count, kind, end - sub0);
-    // what the workgroup contributes if the stream reaches it: the symbols up to its first cut, and the cut
-    if (tid == 0) s_first_cut = PFB_THREADS;
-    __syncthreads();
-    if (active && kind != PFB_END_EXIT) atomicMin(&s_first_cut, tid);
-    __syncthreads();
-    const u32 first_cut = s_first_cut;
-    u64 total;
-    (void)scl_block_scan_excl<u64, PFB_THREADS, SclScanSum>(active && tid <= first_cut ? (u64)count : 0ull, s_wave, &total);
-    if (tid == first_cut) sc.group_end[group] = ((group_bit + end) << 2) | kind;
-    if (tid == 0) {
-        sc.group_count[group] = total;
-        if (first_cut == PFB_THREADS) sc.group_end[group] = PFB_NONE64;
-    }
-    if (tid == PFB_THREADS - 1) {
-        const u64 ex = active && kind == PFB_END_EXIT ? group_bit + end : PFB_NONE64;
-        if (pass) {
-            sc.head->start_pass = pass;  // this workgroup moved its start
-            if (ex != exit_in[group]) sc.head->exit_pass = pass;
-        }
-        exit_out[group] = ex;
-    }
+    pfb_sync_body(PfbCode<FAST>{P, s_lut, s_deep}, in, in_size_bytes, in_bit_offset, in_nbits, n_sub, n_groups, sc.head, sc.g,
+                  pass);
 }
 
 // ONE workgroup: where the stream ends, the symbol offsets of the workgroups up to there, the result
 __global__ void __launch_bounds__(PFB_SCAN_THREADS)
     pfb_scan_groups_kernel(PfbDecScratch sc, u64 n_groups, u64 in_nbits, u64 out_cap, u32 sync_passes,
                            scl_prefix_block_result *__restrict__ result) {
-    __shared__ u64 s_wave[PFB_SCAN_THREADS / 64];
-    __shared__ unsigned long long s_first;
-    if (threadIdx.x == 0) s_first = n_groups - 1;
-    __syncthreads();
-    u64 mine = PFB_NONE64;
-    for (u64 i = threadIdx.x; i < n_groups && mine == PFB_NONE64; i += PFB_SCAN_THREADS)
-        if (sc.group_end[i] != PFB_NONE64) mine = i;
-    if (mine != PFB_NONE64) atomicMin(&s_first, (unsigned long long)mine);
-    __syncthreads();
-    const u64 last_group = s_first;
-    const u64 total = scl_block_scan_array<u64, PFB_SCAN_THREADS, SclScanSum>(sc.group_count, last_group + 1, s_wave);
+    u64 total;
+    const u64 last_group = pfb_scan_to_end(sc.g, n_groups, &total);
     if (threadIdx.x == 0) {
-        const u64 cut = sc.group_end[last_group];
+        const u64 cut = sc.g.group_end[last_group];
         const u64 end = cut == PFB_NONE64 ? in_nbits : cut >> 2;
         u32 status = cut == PFB_NONE64 ? 0u : ((cut & 3u) == PFB_END_TRUNC ? SCL_ST_TRUNCATED : SCL_ST_STATE);
         u64 consumed = end;
@@ -371,43 +257,10 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
                      PfbDecScratch sc, SYM *__restrict__ out, u64 out_cap, scl_prefix_block_result *__restrict__ result) {
     __shared__ u16 s_lut[FAST ? (1u << PF_LUT_BITS) : 1];
     __shared__ u32 s_deep[FAST ? PF_DEEP_NODES : 1];
-    __shared__ u32 s_win[PFB_WIN_LDS];
-    __shared__ u64 s_wave[PFB_THREADS / 64];
-    __shared__ u32 s_first_cut;
-    const u32 tid = threadIdx.x;
-    const u64 group = blockIdx.x;
-    if (group > sc.head->last_group) return;  // behind the end of the stream (uniform)
-    const u64 group_first = sc.group_count[group];
-    if (group_first >= out_cap) return;  // nothing of this workgroup is stored (uniform)
-    const u64 n_total = sc.head->n_total;
-    const u64 group_bit = group * PFB_GROUP;
-    const u64 sub_index = group * PFB_THREADS + tid;
-    const bool active = sub_index < n_sub;
-    const u64 left64 = in_nbits - group_bit;
-    const u32 avail = (u32)(left64 < PFB_GROUP + 64u ? left64 : PFB_GROUP + 64u);
-    const u32 packed = active ? sc.sub[sub_index] : 0u;
-    const u32 kind = (packed >> 15) & 3u;
-    if (tid == 0) s_first_cut = PFB_THREADS;
-    pfb_load_tables<FAST>(P, s_lut, s_deep);
-    const u64 first_bit = in_bit_offset + group_bit;
-    pfb_load_window(s_win, in, in_size_bytes, first_bit);
-    __syncthreads();
-    if (active && kind != PFB_END_EXIT) atomicMin(&s_first_cut, tid);
-    __syncthreads();
-    const u32 count = active && tid <= s_first_cut ? (packed >> 6) & 511u : 0u;
-    u64 total;
-    u64 index = group_first + scl_block_scan_excl<u64, PFB_THREADS, SclScanSum>((u64)count, s_wave, &total);
-    const u32 shift = (u32)(first_bit & 31u);
-    u32 pos = tid * PFB_SUB + (packed & 63u);
-    for (u32 k = 0; k < count && index < out_cap; ++k, ++index) {
-        u32 len, sym;
-        if (pfb_codeword<FAST>(P, s_lut, s_deep, pfb_peek(s_win, shift + pos), avail - pos, len, sym) != PFB_END_EXIT)
-            break;  // (not reached: the same walk counted these symbols)
-        pos += len;
-        out[index] = (SYM)sym;
-        if (index + 1 == out_cap && n_total > out_cap) result->consumed = group_bit + pos;
-    }
+    pfb_write_body(PfbCode<FAST>{P, s_lut, s_deep}, in, in_size_bytes, in_bit_offset, in_nbits, n_sub, sc.head, sc.g, out, out_cap,
+                   &result->consumed);
 }
+
 
 // ---- host API -------------------------------------------------------------------------------------------------------------
 extern "C" int scl_prefix_block_info_get(const scl_prefix_model *m, scl_prefix_block_info *info) {
@@ -477,27 +330,18 @@ static int pfb_decode_run(const scl_prefix_model *m, const u8 *d_in, u64 in_size
     PfbDecScratch sc;
     u8 *p = (u8 *)d_scratch;
     sc.head = (PfbDecHead *)p;
-    sc.group_exit = (u64 *)(p + 64);
-    sc.group_count = sc.group_exit + 2 * n_groups;
-    sc.group_end = sc.group_count + n_groups;
-    sc.sub = (u32 *)(sc.group_end + n_groups);
+    sc.g.group_exit = (u64 *)(p + 64);
+    sc.g.group_count = sc.g.group_exit + 2 * n_groups;
+    sc.g.group_end = sc.g.group_count + n_groups;
+    sc.g.sub = (u32 *)(sc.g.group_end + n_groups);
     SCL_HIP_TRY(hipMemsetAsync(sc.head, 0, 64, st));
     const dim3 grid((u32)n_groups), block(PFB_THREADS);
-    hipLaunchKernelGGL(pfb_sync_kernel<FAST>, grid, block, 0, st, m->dev, d_in, in_size_bytes, in_bit_offset, in_nbits, n_sub,
-                       n_groups, sc, 0u);
-    SCL_HIP_TRY(hipGetLastError());
-    // workgroup w is final after pass w: passes 1 .. n_groups - 1 at the most, fewer when a pass changes no exit
     u32 sync_passes = 0;
-    for (u64 pass = 1; pass < n_groups; ++pass) {
-        hipLaunchKernelGGL(pfb_sync_kernel<FAST>, grid, block, 0, st, m->dev, d_in, in_size_bytes, in_bit_offset, in_nbits,
-                           n_sub, n_groups, sc, (u32)pass);
-        SCL_HIP_TRY(hipGetLastError());
-        u32 flags[2];  // {start_pass, exit_pass}
-        SCL_HIP_TRY(hipMemcpyAsync(flags, sc.head, 8, hipMemcpyDeviceToHost, st));
-        SCL_HIP_TRY(hipStreamSynchronize(st));
-        if (flags[0] == (u32)pass) ++sync_passes;
-        if (flags[1] != (u32)pass) break;
-    }
+    const auto sync = [&](u32 pass) {
+        hipLaunchKernelGGL(pfb_sync_kernel<FAST>, grid, block, 0, st, m->dev, d_in, in_size_bytes, in_bit_offset, in_nbits, n_sub,
+                           n_groups, sc, pass);
+    };
+    if (int rc = pfb_run_sync_passes(sync, sc.head, n_groups, st, &sync_passes)) return rc;
     hipLaunchKernelGGL(pfb_scan_groups_kernel, dim3(1), dim3(PFB_SCAN_THREADS), 0, st, sc, n_groups, in_nbits, out_cap,
                        sync_passes, d_result);
     hipLaunchKernelGGL((pfb_write_kernel<SYM, FAST>), grid, block, 0, st, m->dev, d_in, in_size_bytes, in_bit_offset, in_nbits,
