@@ -394,6 +394,61 @@ int scl_prefix_encode_block_host_u16(const scl_prefix_model *m, const uint16_t *
 int scl_prefix_decode_block_host_u16(const scl_prefix_model *m, const uint8_t *h_in, uint64_t in_nbits,
                                      uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed);
 
+/* ---- integer codes, ONE block coded by the whole grid (scl_uint_block.hip; added to ABI 8 as above) ----------------------
+ * The reference's three prefix codes over unbounded non-negative integers -- GolombUintEncoder(M) (golomb_coder.py),
+ * UniversalUintEncoder (universal_uint_coder.py), EliasDeltaUintEncoder (elias_delta_uint_coder.py) -- over uint32 values,
+ * with the kernels of the prefix-free block above: the codeword is computed from the value instead of read from a table
+ * (csrc/scl_uint_code.h), everything else is the same code.  The stream is the codewords back to back.
+ * A codeword travels in one 32-bit word.  Longer ones are not coded: universal x >= 2^16, Elias-delta x >= 2^24 - 1,
+ * Golomb x / M + 1 + b (+ 1) > 32 with b = floor(log2 M).
+ *   encode: as scl_prefix_encode_block.  *d_status: SCL_ST_SIZE = a value whose codeword is longer than 32 bits (*d_nbits = 0),
+ *           SCL_ST_CAPACITY = (nbits + 7) / 8 > out_cap_bytes (*d_nbits = the length needed).  With either, no codeword is
+ *           stored (the call still zeroes d_out up to min(out_cap_bytes, 4 * n)).
+ *   decode: as scl_prefix_decode_block, d_result likewise.  status: SCL_ST_TRUNCATED = in_nbits ends inside a codeword (in
+ *           its unary part, length field, remainder or Golomb's extra bit); SCL_ST_SIZE = a prefix that announces a
+ *           codeword of more than 32 bits; SCL_ST_CAPACITY = bits are left after out_cap values.  consumed = the bits of the
+ *           whole codewords in front, whose values are delivered.
+ * SCL_E_PARAM (message = the entry point's name + ':'), before any device call: a null pointer, an unknown kind, a Golomb
+ * code with M = 0 or M >= 2^31 (M is not looked at for the other kinds), misaligned d_out / d_in (4 bytes), d_val / d_out_val
+ * (4 bytes), d_scratch / d_nbits / d_result (8 bytes), scratch_bytes below scl_uint_block_scratch_bytes, n >= 2^32 values,
+ * in_nbits >= 2^46, a stream that ends behind in_size_bytes. */
+#define SCL_UINT_GOLOMB 0u
+#define SCL_UINT_UNIVERSAL 1u
+#define SCL_UINT_ELIAS_DELTA 2u
+
+typedef struct scl_uint_code {
+    uint32_t kind; /* SCL_UINT_*               */
+    uint32_t M;    /* Golomb's parameter        */
+} scl_uint_code;
+
+typedef struct scl_uint_block_result {
+    uint64_t n_out, consumed;
+    uint32_t status, sync_passes;
+} scl_uint_block_result;
+
+/* device scratch that serves an encode of n_values and a decode of in_nbits */
+uint64_t scl_uint_block_scratch_bytes(uint64_t n_values, uint64_t in_nbits);
+int scl_uint_encode_block(const scl_uint_code *code, const uint32_t *d_val, uint64_t n, uint8_t *d_out,
+                          uint64_t out_cap_bytes, uint64_t *d_nbits, uint32_t *d_status, void *d_scratch,
+                          uint64_t scratch_bytes, void *stream);
+int scl_uint_decode_block(const scl_uint_code *code, const uint8_t *d_in, uint64_t in_size_bytes, uint64_t in_bit_offset,
+                          uint64_t in_nbits, uint32_t *d_out_val, uint64_t out_cap, scl_uint_block_result *d_result,
+                          void *d_scratch, uint64_t scratch_bytes, void *stream);
+/* one block in host memory: allocate, copy, run, synchronise.  *status = the block's status word: with SCL_ST_SIZE a caller
+   codes the block elsewhere, so a non-zero status is reported, not turned into SCL_E_CHUNK.  encode: h_out receives the
+   stream only for status 0 (SCL_E_PARAM if it needs more than out_cap_bytes); decode: the n_out values in front of the
+   fault are delivered with any status. */
+int scl_uint_encode_block_host(const scl_uint_code *code, const uint32_t *h_val, uint64_t n, uint8_t *h_out,
+                               uint64_t out_cap_bytes, uint64_t *nbits, uint32_t *status);
+int scl_uint_decode_block_host(const scl_uint_code *code, const uint8_t *h_in, uint64_t in_nbits, uint32_t *h_out_val,
+                               uint64_t out_cap, uint64_t *n_out, uint64_t *consumed, uint32_t *status);
+/* The code rule itself, on the host, no device: what the kernels compute per value (the same function compiled for both).
+   scl_uint_codeword_host: *bits = the codeword right-aligned, *len = its length, 0 for one longer than 32 bits.
+   scl_uint_decode_one_host: one codeword from the 32 left-aligned bits of `bits32`, of which `rem` >= 1 belong to the stream
+   -> 0 (*x in *len bits), SCL_ST_TRUNCATED or SCL_ST_SIZE.  Both: SCL_E_PARAM for a refused code, a null pointer or rem = 0. */
+int scl_uint_codeword_host(const scl_uint_code *code, uint32_t x, uint32_t *bits, uint32_t *len);
+int scl_uint_decode_one_host(const scl_uint_code *code, uint32_t bits32, uint32_t rem, uint32_t *len, uint32_t *x);
+
 /* ---- LZ77: match index, greedy parse and sequence replay (scl_lz77.hip; added to ABI 8 as above) -----------------------
  * The LZ layer of the reference's LZ77 coder, for a batch of independent streams, one wavefront per stream:
  *   scl_lz77_parse_batch   <->  LZ77Encoder.lz77_parse_and_generate_sequences   scl/compressors/lz77.py:525-603

@@ -20,6 +20,7 @@ E_PARAM, E_ALLOC, E_HIP, E_NODEVICE, E_CHUNK = -2, -7, -8, -9, -10
 ST_CAPACITY, ST_SYMBOL, ST_TRUNCATED, ST_STATE, ST_TOTAL, ST_SIZE = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 MODEL_FIXED, MODEL_IID, MODEL_ORDERK = 0, 1, 2
 COMPACT_DENSE, COMPACT_FRAMED = 0, 1
+UINT_GOLOMB, UINT_UNIVERSAL, UINT_ELIAS_DELTA = 0, 1, 2
 
 
 class SclHipError(RuntimeError):
@@ -48,6 +49,11 @@ class PrefixBlockInfo(C.Structure):
 
 class PrefixBlockResult(C.Structure):
     _fields_ = [("n_out", C.c_uint64), ("consumed", C.c_uint64), ("status", C.c_uint32), ("sync_passes", C.c_uint32)]
+
+
+class UintCodeStruct(C.Structure):
+    """scl_uint_code"""
+    _fields_ = [("kind", C.c_uint32), ("M", C.c_uint32)]
 
 
 class Lz77ParseArgs(C.Structure):
@@ -206,6 +212,14 @@ _SIGNATURES = {
     "scl_prefix_decode_block": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
     "scl_prefix_encode_block_host": (_int, _ENC_HOST),
     "scl_prefix_decode_block_host": (_int, _DEC_HOST),
+    # integer codes (Golomb, universal, Elias-delta): one block coded by the whole grid (scl_uint_block.hip)
+    "scl_uint_block_scratch_bytes": (_u64, [_u64, _u64]),
+    "scl_uint_encode_block": (_int, [C.POINTER(UintCodeStruct), _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "scl_uint_decode_block": (_int, [C.POINTER(UintCodeStruct), _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "scl_uint_encode_block_host": (_int, [C.POINTER(UintCodeStruct), _u32p, _u64, _u8p, _u64, _u64p, _u32p]),
+    "scl_uint_decode_block_host": (_int, [C.POINTER(UintCodeStruct), _u8p, _u64, _u32p, _u64, _u64p, _u64p, _u32p]),
+    "scl_uint_codeword_host": (_int, [C.POINTER(UintCodeStruct), _u32, _u32p, _u32p]),
+    "scl_uint_decode_one_host": (_int, [C.POINTER(UintCodeStruct), _u32, _u32, _u32p, _u32p]),
     # LZ77: match index, greedy parse, sequence replay (scl_lz77.hip)
     "scl_lz77_scratch_bytes": (_u64, [_u64, _u64]),
     "scl_lz77_parse_batch": (_int, [C.POINTER(Lz77ParseArgs), _vp]),

@@ -579,6 +579,128 @@ class PrefixModel(_DeviceModel):
         return out[:n_out], n_out, consumed, tail & 0xFFFFFFFF, (tail >> 32) & 0xFFFFFFFF
 
 
+class UintCode:
+    """one of the three integer codes (``"golomb"`` with its ``M``, ``"universal"``, ``"elias_delta"``) over uint32 values, a
+    block at a time across the whole grid (csrc/scl_uint_block.hip).  There is no table and no device handle: the code is the
+    pair ``{kind, M}``.  A codeword longer than 32 bits is not coded: ``ST_SIZE`` in the status, for the caller to act on."""
+
+    KINDS = {"golomb": _lib.UINT_GOLOMB, "universal": _lib.UINT_UNIVERSAL, "elias_delta": _lib.UINT_ELIAS_DELTA}
+
+    def __init__(self, kind, M: Optional[int] = None):
+        self._L = _lib.load()
+        self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind)
+        golomb = self.kind == _lib.UINT_GOLOMB
+        assert (M is not None) == golomb, "M belongs to the Golomb code, and to it alone"
+        self.M = int(M) if golomb else 1
+        if not 0 <= self.M < (1 << 32):
+            raise _lib.SclHipError(_lib.E_PARAM, "UintCode", f"Golomb parameter M = {M}: 1 <= M < 2^31")
+        self._c = _lib.UintCodeStruct(self.kind, self.M)
+        self.codeword(0)  # an unknown kind or a refused M raises here
+        # the shortest codeword: what bounds the values of a stream
+        self.min_len = {_lib.UINT_GOLOMB: self.M.bit_length(), _lib.UINT_UNIVERSAL: 2}.get(self.kind, 1)
+
+    # -- the rule, on the host -----------------------------------------------------------------------------------------
+    def codeword(self, x: int):
+        """-> (bits, length) of the codeword of ``x`` < 2^32; length 0: longer than 32 bits"""
+        bits, length = C.c_uint32(0), C.c_uint32(0)
+        _lib.check(self._L.scl_uint_codeword_host(C.byref(self._c), int(x), C.byref(bits), C.byref(length)),
+                   "scl_uint_codeword_host")
+        return int(bits.value), int(length.value)
+
+    def decode_one(self, bits32: int, rem: int):
+        """one codeword from 32 left-aligned bits of which ``rem`` belong to the stream -> (status, length, value)"""
+        length, x = C.c_uint32(0), C.c_uint32(0)
+        rc = self._L.scl_uint_decode_one_host(C.byref(self._c), int(bits32), int(rem), C.byref(length), C.byref(x))
+        if rc < 0:
+            _lib.check(rc, "scl_uint_decode_one_host")
+        return rc, int(length.value), int(x.value)
+
+    # -- one block, host memory ----------------------------------------------------------------------------------------
+    def encode_host(self, values: np.ndarray):
+        """uint32 array -> (packed MSB-first bytes, nbits, status); with ``ST_SIZE`` in the status nothing was coded"""
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        cap = 4 * values.size + 16
+        out = np.zeros(cap, dtype=np.uint8)
+        nbits, status = C.c_uint64(0), C.c_uint32(0)
+        rc = self._L.scl_uint_encode_block_host(C.byref(self._c), _lib.u32_ptr(values), values.size, _lib.u8_ptr(out), cap,
+                                                C.byref(nbits), C.byref(status))
+        _lib.check(rc, "scl_uint_encode_block_host")
+        return out[: (nbits.value + 7) // 8], int(nbits.value), int(status.value)
+
+    def decode_host(self, packed: np.ndarray, nbits: int, out_cap: Optional[int] = None):
+        """(packed bytes, EXACT stream bits) -> (uint32 values, num_bits_consumed, status).  The output holds ``nbits //
+        min_len`` values, which bounds any stream of this code; the values in front of a fault are delivered."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        cap = int(nbits) // self.min_len if out_cap is None else int(out_cap)
+        if packed.size == 0:
+            packed = np.zeros(1, dtype=np.uint8)
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        n_out, used, status = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        rc = self._L.scl_uint_decode_block_host(C.byref(self._c), _lib.u8_ptr(packed), int(nbits), _lib.u32_ptr(out), cap,
+                                                C.byref(n_out), C.byref(used), C.byref(status))
+        _lib.check(rc, "scl_uint_decode_block_host")
+        return out[: n_out.value], int(used.value), int(status.value)
+
+    # -- one block, device memory (torch tensors) ----------------------------------------------------------------------
+    def _block_scratch(self, n_values: int, nbits: int, device):
+        import torch
+
+        nbytes = int(self._L.scl_uint_block_scratch_bytes(int(n_values), int(nbits)))
+        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+    def encode_block_into(self, values, out, out_cap_bytes: Optional[int] = None, scratch=None):
+        """1-D uint32 / int32 tensor -> its stream at the front of the uint8 tensor ``out``, asynchronously on the current
+        stream.  -> int64 tensor ``[nbits, status]`` on the device.  ``scratch``: a uint8 tensor to use, else one is made."""
+        import torch
+
+        assert values.is_cuda and values.dtype in (torch.uint32, torch.int32) and values.dim() == 1 and values.is_contiguous()
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+        cap = out.numel() if out_cap_bytes is None else int(out_cap_bytes)
+        assert cap <= out.numel()
+        dev = values.device
+        st = torch.cuda.current_stream(dev).cuda_stream
+        meta = torch.zeros(2, dtype=torch.int64, device=dev)
+        if scratch is None:
+            scratch, _ = self._block_scratch(values.numel(), 0, dev)
+        with torch.cuda.device(dev):
+            rc = self._L.scl_uint_encode_block(C.byref(self._c), values.data_ptr(), values.numel(), out.data_ptr(), cap,
+                                               meta.data_ptr(), meta.data_ptr() + 8, scratch.data_ptr(), scratch.numel(), st)
+        _lib.check(rc, "scl_uint_encode_block")
+        return meta
+
+    def encode_block_device(self, values):
+        """1-D uint32 / int32 tensor on the device -> (uint8 tensor holding the stream, nbits, status).  Waits for the result."""
+        import torch
+
+        out = torch.empty(4 * values.numel() + 16, dtype=torch.uint8, device=values.device)
+        nbits, status = (int(v) for v in self.encode_block_into(values, out).cpu())
+        return out[: (nbits + 7) // 8], nbits, status & 0xFFFFFFFF
+
+    def decode_block_device(self, data, nbits: int, bit_offset: int = 0, out_cap: Optional[int] = None, out=None,
+                            scratch=None):
+        """the ``nbits`` bits from bit ``bit_offset`` of the uint8 device tensor ``data`` -> (values, n_out, consumed, status,
+        sync_passes).  ``out_cap`` defaults to ``nbits // min_len``; ``out`` is an optional int32 / uint32 tensor of at least
+        ``out_cap`` elements.  The call synchronises the current stream: the library reads a device flag between passes."""
+        import torch
+
+        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
+        dev = data.device
+        cap = int(nbits) // self.min_len if out_cap is None else int(out_cap)
+        if out is None:
+            out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        assert out.is_cuda and out.dtype in (torch.uint32, torch.int32) and out.is_contiguous() and out.numel() >= cap
+        st = torch.cuda.current_stream(dev).cuda_stream
+        result = torch.zeros(3, dtype=torch.int64, device=dev)
+        if scratch is None:
+            scratch, _ = self._block_scratch(0, nbits, dev)
+        with torch.cuda.device(dev):
+            rc = self._L.scl_uint_decode_block(C.byref(self._c), data.data_ptr(), data.numel(), int(bit_offset), int(nbits),
+                                               out.data_ptr(), cap, result.data_ptr(), scratch.data_ptr(), scratch.numel(), st)
+        _lib.check(rc, "scl_uint_decode_block")
+        n_out, consumed, tail = (int(v) for v in result.cpu())
+        return out[:n_out], n_out, consumed, tail & 0xFFFFFFFF, (tail >> 32) & 0xFFFFFFFF
+
+
 class AecModel(_DeviceModel):
     _prefix = "aec"
     _needs_scratch = True

@@ -3,8 +3,11 @@
 Drop-in for reference scl/compressors/elias_delta_uint_coder.py: ``EliasDeltaUintEncoder`` (:37-64),
 ``EliasDeltaUintDecoder`` (:67-115).  x >= 0 is coded through y = x + 1: with n = bit length of y minus one and l = bit
 length of (n + 1) minus one, the codeword is l zeros, n + 1 in l + 1 bits, and the n bits of y below its leading one.
-LZ77 codes its symbol counts with it (a few hundred values per block), so this is host code: whole blocks are laid out
-with array operations, one pass per bit of the longest codeword.
+LZ77 codes its symbol counts with it (a few hundred values per block), so small blocks are host code: whole blocks are laid
+out with array operations, one pass per bit of the longest codeword.  From ``UINT_BLOCK_MIN`` values (on decode: bits) on a
+block goes to the gfx950 kernels (csrc/scl_uint_block.hip, routed by compressors/_uint_block.py), which write and read the
+same bits; a block with a codeword above 32 bits (x >= 2^24 - 1) comes back to the host.  Such a block needs the device:
+without one the call raises ``SclHipError``, it does not fall back.
 """
 from __future__ import annotations
 
@@ -43,6 +46,18 @@ def bit_length(v: np.ndarray) -> np.ndarray:
     return b + 1
 
 
+def _device(coder, size: int):
+    """(the router, the device's code of this coder object) for a block of ``size`` values / bits, (None, None) below the
+    threshold -- imported late: _uint_block lays its bits with this module"""
+    from . import _uint_block
+
+    if size < _uint_block.UINT_BLOCK_MIN:
+        return None, None
+    if getattr(coder, "_code", None) is None:
+        coder._code = _uint_block.UintCode("elias_delta")
+    return _uint_block, coder._code
+
+
 class EliasDeltaUintEncoder(DataEncoder):
     def encode_symbol(self, x: int) -> BitArray:
         assert isinstance(x, int)
@@ -55,6 +70,11 @@ class EliasDeltaUintEncoder(DataEncoder):
         data = data_block.data_list
         if len(data) == 0:
             return BitArray("")
+        route, code = _device(self, len(data))
+        if route is not None:
+            bits = route.device_encode(code, data)
+            if bits is not None:
+                return bits
         assert all(isinstance(x, (int, np.integer)) and x >= 0 for x in data)
         if max(data) >= _VECTOR_LIMIT:
             out = BitArray("")
@@ -82,6 +102,11 @@ class EliasDeltaUintDecoder(DataDecoder):
 
     def decode_block(self, bitarray: BitArray) -> Tuple[DataBlock, int]:
         """every bit of ``bitarray`` is decoded (reference :98-115)"""
+        route, code = _device(self, len(bitarray))
+        if route is not None:
+            got = route.device_decode(code, bitarray)
+            if got is not None:
+                return got
         bits = bitarray._b
         total = int(bits.size)
         ones = np.flatnonzero(bits)

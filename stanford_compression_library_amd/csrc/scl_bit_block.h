@@ -47,6 +47,30 @@ struct PfbDecGroups {  // device pointers into the decoder's scratch
     u64 *group_end;    // [n_groups] PFB_NONE64, or (position of the codeword that ends the stream) << 2 | PFB_END_*
 };
 
+// ---- the scratch of a coder of one block of n values / of a stream of nbits bits (host) -----------------------------------
+// encoder: PfbEncScratch, then u64 tile_bits[tiles] at byte 64; decoder: PfbDecHead, then the arrays of PfbDecGroups at byte 64
+struct PfbDecScratch {  // device pointers into the decoder's scratch
+    PfbDecHead *head;
+    PfbDecGroups g;
+};
+
+static inline u64 pfb_tiles(u64 n) { return (n + PFB_TILE - 1) / PFB_TILE; }
+static inline u64 pfb_subs(u64 nbits) { return (nbits + PFB_SUB - 1) / PFB_SUB; }
+static inline u64 pfb_groups(u64 nbits) { return (pfb_subs(nbits) + PFB_THREADS - 1) / PFB_THREADS; }
+static inline u64 pfb_enc_scratch(u64 n) { return 64 + pfb_tiles(n) * 8; }
+static inline u64 pfb_dec_scratch(u64 nbits) { return 64 + pfb_groups(nbits) * (PFB_THREADS * 4 + 4 * 8); }
+
+static inline PfbDecScratch pfb_dec_carve(void *d_scratch, u64 n_groups) {
+    PfbDecScratch sc;
+    u8 *p = (u8 *)d_scratch;
+    sc.head = (PfbDecHead *)p;
+    sc.g.group_exit = (u64 *)(p + 64);
+    sc.g.group_count = sc.g.group_exit + 2 * n_groups;
+    sc.g.group_end = sc.g.group_count + n_groups;
+    sc.g.sub = (u32 *)(sc.g.group_end + n_groups);
+    return sc;
+}
+
 #ifdef __HIPCC__
 // ---- encode: one tile of PFB_TILE values -----------------------------------------------------------------------------------
 // EVERY thread of the workgroup calls.  e[j] = {bits, length} of the thread's PFB_PER_THREAD consecutive values (length 0:

@@ -154,10 +154,6 @@ __global__ void pfb_encode_tail_kernel(const PfbEncScratch *__restrict__ head, c
 // ---- decode ---------------------------------------------------------------------------------------------------------------
 // (PfbDecHead -- the head of the decoder's scratch, 64 bytes --, the input window and the bodies of the three kernels over a
 // codeword policy: scl_bit_block.h.  Here: the policy over the tables of a scl_prefix_model, and the verdict)
-struct PfbDecScratch {  // device pointers into the scratch
-    PfbDecHead *head;
-    PfbDecGroups g;
-};
 
 // FAST: the 11-bit table and the deep nodes in LDS (byte alphabets); otherwise the node array where it is
 template <bool FAST>
@@ -271,15 +267,7 @@ extern "C" int scl_prefix_block_info_get(const scl_prefix_model *m, scl_prefix_b
     return SCL_OK;
 }
 
-static u64 pfb_tiles(u64 n) { return (n + PFB_TILE - 1) / PFB_TILE; }
-static u64 pfb_subs(u64 nbits) { return (nbits + PFB_SUB - 1) / PFB_SUB; }
-static u64 pfb_groups(u64 nbits) { return (pfb_subs(nbits) + PFB_THREADS - 1) / PFB_THREADS; }
-static u64 pfb_enc_scratch(u64 n) { return 64 + pfb_tiles(n) * 8; }
-static u64 pfb_dec_scratch(u64 nbits) {
-    const u64 g = pfb_groups(nbits);
-    return 64 + g * (PFB_THREADS * 4 + 4 * 8);
-}
-
+// (the sizes and the layout of the scratch: pfb_enc_scratch, pfb_dec_scratch, pfb_dec_carve of scl_bit_block.h)
 extern "C" uint64_t scl_prefix_block_scratch_bytes(const scl_prefix_model *m, uint64_t n_symbols, uint64_t in_nbits) {
     if (!m) return 0;
     const u64 e = pfb_enc_scratch(n_symbols), d = pfb_dec_scratch(in_nbits);
@@ -327,13 +315,7 @@ template <class SYM, bool FAST>
 static int pfb_decode_run(const scl_prefix_model *m, const u8 *d_in, u64 in_size_bytes, u64 in_bit_offset, u64 in_nbits,
                           SYM *d_out_sym, u64 out_cap, scl_prefix_block_result *d_result, void *d_scratch, hipStream_t st) {
     const u64 n_sub = pfb_subs(in_nbits), n_groups = pfb_groups(in_nbits);
-    PfbDecScratch sc;
-    u8 *p = (u8 *)d_scratch;
-    sc.head = (PfbDecHead *)p;
-    sc.g.group_exit = (u64 *)(p + 64);
-    sc.g.group_count = sc.g.group_exit + 2 * n_groups;
-    sc.g.group_end = sc.g.group_count + n_groups;
-    sc.g.sub = (u32 *)(sc.g.group_end + n_groups);
+    const PfbDecScratch sc = pfb_dec_carve(d_scratch, n_groups);
     SCL_HIP_TRY(hipMemsetAsync(sc.head, 0, 64, st));
     const dim3 grid((u32)n_groups), block(PFB_THREADS);
     u32 sync_passes = 0;
