@@ -449,6 +449,46 @@ int scl_uint_decode_block_host(const scl_uint_code *code, const uint8_t *h_in, u
 int scl_uint_codeword_host(const scl_uint_code *code, uint32_t x, uint32_t *bits, uint32_t *len);
 int scl_uint_decode_one_host(const scl_uint_code *code, uint32_t bits32, uint32_t rem, uint32_t *len, uint32_t *x);
 
+/* ---- integer codes, batched: one wavefront lane per chunk (scl_uint.hip; added to ABI 8 as above) -----------------------
+ * The same three codes with the call shape of scl_prefix_encode_batch / scl_prefix_decode_batch, a scl_uint_code in place of
+ * the model: rows of uint32 values (strides in ELEMENTS), one independent stream per chunk, stream layout, bit_offset, nbits
+ * and slots as there.  EVERY uint32 value has a codeword here: a lane writes it as a run of ones and at most two fields of
+ * at most 32 bits (universal and Elias-delta codewords reach 64 bits, a Golomb codeword x / M + 32).
+ *   scl_uint_slot_bytes: n_values codewords of max_value (no shorter value has a longer one: the lengths never decrease in
+ *           x), plus the writer's last word, rounded up to 128; 0 for a refused code.
+ *   encode: d_status[c]: SCL_ST_CAPACITY alone = the stream needs more than out_stride bytes in whole words; nbits[c] is then
+ *           (as always) the length needed, counted in 64 bits and saturating at 2^32 - 1, and what the slot holds is
+ *           unspecified.  Nothing is stored at or past a slot's end; zero bits follow a stream up to its last stored word.
+ *   decode: d_out_lens, d_consumed and the whole codewords in front of a fault as scl_prefix_decode_batch.  d_status[c], in
+ *           the order a sequential reader meets them (csrc/scl_uint_code.h): SCL_ST_TRUNCATED = in_nbits
+ *           ends inside a codeword; SCL_ST_SIZE = the codeword announces a value of 2^32 and more (Golomb: ones up to a
+ *           quotient q with M * q >= 2^32, or M * q + r >= 2^32; universal: 32 ones; Elias-delta: six zeros, n > 32, or
+ *           n = 32 with low bits); SCL_ST_CAPACITY = bits are left after out_cap values.
+ *   Two kernel pairs that write and read the same bits: the tuned pair runs when value rows and output rows start on 16-byte
+ *   boundaries (pointer and stride), d_in does, in_size_bytes is a multiple of 16 and the calling thread has not called
+ *   scl_set_any_parameter_kernels(1); other rows run the any-parameter pair as they are (no row is re-laid).
+ *   scl_uint_kernel_names names the pair of a batch of such aligned rows, as rocprofv3 prints it.
+ * SCL_E_PARAM (message = the entry point's name + ':'), before any device call: a null pointer (d_lens and d_status may be
+ * null), an unknown kind, a Golomb code with M = 0 or M >= 2^31, an out_stride that is not a positive multiple of 16 below
+ * 512 MiB, d_out not 16-byte aligned, d_in / d_val / d_out_val not 4-byte aligned. */
+uint64_t scl_uint_slot_bytes(const scl_uint_code *code, uint64_t n_values, uint32_t max_value);
+int scl_uint_encode_batch(const scl_uint_code *code, const uint32_t *d_val, uint64_t val_stride, const uint32_t *d_lens,
+                          uint32_t chunk_len, uint64_t n_chunks, uint8_t *d_out, uint64_t out_stride,
+                          uint64_t *d_out_bit_offset, uint32_t *d_out_nbits, uint32_t *d_status, void *stream);
+int scl_uint_decode_batch(const scl_uint_code *code, const uint8_t *d_in, uint64_t in_size_bytes,
+                          const uint64_t *d_bit_offset, const uint32_t *d_in_nbits, uint64_t n_chunks, uint32_t *d_out_val,
+                          uint64_t out_stride, uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed,
+                          uint32_t *d_status, void *stream);
+int scl_uint_kernel_names(const scl_uint_code *code, uint64_t n_chunks, char *enc, char *dec, uint64_t cap);
+/* The rule of these kernels on the host, no device (the same functions compiled for both).
+   scl_uint_fields_host: the codeword of x = *run ones, then the widths[0] low bits of fields[0], then the widths[1] low bits
+   of fields[1] (a width is at most 32; 0: no such field).
+   scl_uint_decode_wide_one_host: one codeword read from bit bit_pos of the buf_bytes bytes at buf (zeros behind them), of
+   which `rem` >= 1 bits belong to the stream -> 0 (*x in *len bits), SCL_ST_TRUNCATED or SCL_ST_SIZE. */
+int scl_uint_fields_host(const scl_uint_code *code, uint32_t x, uint32_t *run, uint32_t *fields, uint32_t *widths);
+int scl_uint_decode_wide_one_host(const scl_uint_code *code, const uint8_t *buf, uint64_t buf_bytes, uint64_t bit_pos,
+                                  uint32_t rem, uint32_t *len, uint32_t *x);
+
 /* ---- LZ77: match index, greedy parse and sequence replay (scl_lz77.hip; added to ABI 8 as above) -----------------------
  * The LZ layer of the reference's LZ77 coder, for a batch of independent streams, one wavefront per stream:
  *   scl_lz77_parse_batch   <->  LZ77Encoder.lz77_parse_and_generate_sequences   scl/compressors/lz77.py:525-603

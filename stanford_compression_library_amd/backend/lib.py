@@ -220,6 +220,14 @@ _SIGNATURES = {
     "scl_uint_decode_block_host": (_int, [C.POINTER(UintCodeStruct), _u8p, _u64, _u32p, _u64, _u64p, _u64p, _u32p]),
     "scl_uint_codeword_host": (_int, [C.POINTER(UintCodeStruct), _u32, _u32p, _u32p]),
     "scl_uint_decode_one_host": (_int, [C.POINTER(UintCodeStruct), _u32, _u32, _u32p, _u32p]),
+    # ... and batched, one lane per chunk (scl_uint.hip): the prefix batch's call shape over uint32 rows
+    "scl_uint_slot_bytes": (_u64, [C.POINTER(UintCodeStruct), _u64, _u32]),
+    "scl_uint_encode_batch": (_int, [C.POINTER(UintCodeStruct), _vp, _u64, _vp, _u32, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "scl_uint_decode_batch": (_int, [C.POINTER(UintCodeStruct), _vp, _u64, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _vp,
+                                     _vp]),
+    "scl_uint_kernel_names": (_int, [C.POINTER(UintCodeStruct), _u64, C.c_char_p, C.c_char_p, _u64]),
+    "scl_uint_fields_host": (_int, [C.POINTER(UintCodeStruct), _u32, _u32p, _u32p, _u32p]),
+    "scl_uint_decode_wide_one_host": (_int, [C.POINTER(UintCodeStruct), _u8p, _u64, _u64, _u32, _u32p, _u32p]),
     # LZ77: match index, greedy parse, sequence replay (scl_lz77.hip)
     "scl_lz77_scratch_bytes": (_u64, [_u64, _u64]),
     "scl_lz77_parse_batch": (_int, [C.POINTER(Lz77ParseArgs), _vp]),

@@ -581,8 +581,10 @@ class PrefixModel(_DeviceModel):
 
 class UintCode:
     """one of the three integer codes (``"golomb"`` with its ``M``, ``"universal"``, ``"elias_delta"``) over uint32 values, a
-    block at a time across the whole grid (csrc/scl_uint_block.hip).  There is no table and no device handle: the code is the
-    pair ``{kind, M}``.  A codeword longer than 32 bits is not coded: ``ST_SIZE`` in the status, for the caller to act on."""
+    block at a time across the whole grid (csrc/scl_uint_block.hip) or many chunks at a time, one lane each
+    (csrc/scl_uint.hip).  There is no table and no device handle: the code is the pair ``{kind, M}``.  The block calls do not
+    code a codeword longer than 32 bits: ``ST_SIZE`` in the status, for the caller to act on; the batch calls carry every
+    uint32 value."""
 
     KINDS = {"golomb": _lib.UINT_GOLOMB, "universal": _lib.UINT_UNIVERSAL, "elias_delta": _lib.UINT_ELIAS_DELTA}
 
@@ -699,6 +701,125 @@ class UintCode:
         _lib.check(rc, "scl_uint_decode_block")
         n_out, consumed, tail = (int(v) for v in result.cpu())
         return out[:n_out], n_out, consumed, tail & 0xFFFFFFFF, (tail >> 32) & 0xFFFFFFFF
+
+    # -- the rule without the 32-bit limit, on the host ----------------------------------------------------------------
+    def fields(self, x: int):
+        """the codeword of any ``x`` < 2^32 in the pieces a lane puts -> (run, ((field, width), (field, width))): ``run``
+        ones, then the ``width`` low bits of each field (a width of 0: no such field)"""
+        run, f, w = C.c_uint32(0), (C.c_uint32 * 2)(), (C.c_uint32 * 2)()
+        _lib.check(self._L.scl_uint_fields_host(C.byref(self._c), int(x), C.byref(run), f, w), "scl_uint_fields_host")
+        return int(run.value), ((int(f[0]), int(w[0])), (int(f[1]), int(w[1])))
+
+    def decode_wide_one(self, buf: np.ndarray, bit_pos: int, rem: int):
+        """one codeword read sequentially from bit ``bit_pos`` of the packed bytes ``buf``, of which ``rem`` bits belong to the
+        stream -> (status, length, value)"""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        length, x = C.c_uint32(0), C.c_uint32(0)
+        rc = self._L.scl_uint_decode_wide_one_host(C.byref(self._c), _lib.u8_ptr(buf), buf.size, int(bit_pos), int(rem),
+                                                   C.byref(length), C.byref(x))
+        if rc < 0:
+            _lib.check(rc, "scl_uint_decode_wide_one_host")
+        return rc, int(length.value), int(x.value)
+
+    # -- N chunks, device memory (torch tensors): one lane per chunk (csrc/scl_uint.hip) ---------------------------------
+    # Names and returns are _DeviceModel's, so that compact() / compact_into() take the EncodedBatch unchanged; values are
+    # int32 / uint32 rows and every uint32 value has a codeword (no ST_SIZE on encode).
+    def slot_bytes(self, n_values: int, max_value: int = 0xFFFFFFFF) -> int:
+        """bytes that hold any ``n_values`` values up to ``max_value`` (the codeword lengths never decrease in the value)"""
+        return int(self._L.scl_uint_slot_bytes(C.byref(self._c), int(n_values), int(max_value)))
+
+    def alloc_encoded(self, n_chunks: int, chunk_len: int, device, out_stride: Optional[int] = None,
+                      max_value: int = 0xFFFFFFFF) -> EncodedBatch:
+        import torch
+
+        stride = int(out_stride or self.slot_bytes(chunk_len, max_value))
+        return EncodedBatch(torch.empty(n_chunks * stride + 16, dtype=torch.uint8, device=device), stride,
+                            torch.empty(n_chunks, dtype=torch.int64, device=device),
+                            torch.empty(n_chunks, dtype=torch.int32, device=device),
+                            torch.empty(n_chunks, dtype=torch.int32, device=device), n_chunks)
+
+    @staticmethod
+    def _is_values(t) -> bool:
+        import torch
+
+        return t.is_cuda and t.dtype in (torch.uint32, torch.int32) and t.dim() == 2 and t.stride(1) == 1
+
+    def encode_batch(self, values, lens=None, out_stride: Optional[int] = None, stream=None,
+                     out: Optional[EncodedBatch] = None, any_parameter_kernels: bool = False) -> EncodedBatch:
+        """values: int32 / uint32 CUDA tensor [n_chunks, chunk_len] (row-contiguous).  lens: optional int32 [n_chunks].
+        ``out_stride`` defaults to the slot of ``chunk_len`` values of 2^32 - 1 -- pass the batch's own bound
+        (:meth:`slot_bytes` with its largest value); a chunk whose slot is too small comes back with ``ST_CAPACITY`` and the
+        length it needs in ``nbits``."""
+        import torch
+
+        assert self._is_values(values)
+        n_chunks, chunk_len = values.shape
+        dev = values.device
+        if out is None:
+            out = self.alloc_encoded(n_chunks, chunk_len, dev, out_stride)
+        assert out.n_chunks == n_chunks and out.layout == "linear"
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev), _any_parameter(any_parameter_kernels):
+            rc = self._L.scl_uint_encode_batch(C.byref(self._c), values.data_ptr(), values.stride(0),
+                                               lens.data_ptr() if lens is not None else None, chunk_len, n_chunks,
+                                               out.data.data_ptr(), out.stride, out.bit_offset.data_ptr(),
+                                               out.nbits.data_ptr(), out.status.data_ptr(), st)
+        _lib.check(rc, "scl_uint_encode_batch")
+        return out
+
+    def alloc_decoded(self, n_chunks: int, chunk_cap: int, device):
+        import torch
+
+        out_stride = (int(chunk_cap) + 3) // 4 * 4
+        return (torch.empty((n_chunks, out_stride), dtype=torch.int32, device=device),
+                torch.empty(n_chunks, dtype=torch.int32, device=device),
+                torch.empty(n_chunks, dtype=torch.int32, device=device),
+                torch.empty(n_chunks, dtype=torch.int32, device=device))
+
+    def decode_encoded(self, enc: EncodedBatch, chunk_cap: int, stream=None, out=None, any_parameter_kernels: bool = False):
+        return self.decode_batch(enc.data, enc.bit_offset, enc.nbits, chunk_cap, stream=stream, out=out,
+                                 any_parameter_kernels=any_parameter_kernels)
+
+    def decode_batch(self, data, bit_offset, nbits, chunk_cap: int, stream=None, out=None,
+                     any_parameter_kernels: bool = False):
+        """-> (values int32 [n_chunks, chunk_cap], lens int32, consumed int32, status int32) on the device; the values are
+        uint32 bit patterns.  ``out`` reuses buffers from :meth:`alloc_decoded`."""
+        import torch
+
+        assert data.is_cuda and data.dtype == torch.uint8
+        n_chunks = int(bit_offset.numel())
+        dev = data.device
+        val, lens, used, status = out if out is not None else self.alloc_decoded(n_chunks, chunk_cap, dev)
+        assert self._is_values(val) and val.shape[1] >= chunk_cap
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev), _any_parameter(any_parameter_kernels):
+            rc = self._L.scl_uint_decode_batch(C.byref(self._c), data.data_ptr(), data.numel(), bit_offset.data_ptr(),
+                                               nbits.data_ptr(), n_chunks, val.data_ptr(), val.stride(0), int(chunk_cap),
+                                               lens.data_ptr(), used.data_ptr(), status.data_ptr(), st)
+        _lib.check(rc, "scl_uint_decode_batch")
+        return val[:, :chunk_cap], lens, used, status
+
+    @staticmethod
+    def rows_take_tuned(t) -> bool:
+        """do the rows of this 2-D tensor (or the start and size of this 1-D stream buffer) meet what the tuned kernels ask of
+        them: 16-byte aligned starts, strides and sizes (include/scl_hip.h)"""
+        step = t.stride(0) if t.dim() == 2 else t.numel()
+        return (t.data_ptr() | (step * t.element_size())) % 16 == 0
+
+    def kernel_names(self, n_chunks: int, values=None, data=None, any_parameter_kernels: bool = False):
+        """(encode kernel, decode kernel) of a batch, as rocprofv3 prints them.  ``values`` / ``data``: the value (or output)
+        rows and the stream buffer of the call that is meant -- rows the tuned kernels do not take run the any-parameter
+        pair."""
+        names = []
+        for side, tensors in ((0, (values,)), (1, (values, data))):
+            generic = any_parameter_kernels or any(t is not None and not self.rows_take_tuned(t) for t in tensors)
+            bufs = [None, None]
+            bufs[side] = C.create_string_buffer(160)
+            with _any_parameter(generic):
+                _lib.check(self._L.scl_uint_kernel_names(C.byref(self._c), int(n_chunks), bufs[0], bufs[1], 160),
+                           "scl_uint_kernel_names")
+            names.append(bufs[side].value.decode())
+        return tuple(names)
 
 
 class AecModel(_DeviceModel):

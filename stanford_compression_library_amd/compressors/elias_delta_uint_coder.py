@@ -8,6 +8,9 @@ out with array operations, one pass per bit of the longest codeword.  From ``UIN
 block goes to the gfx950 kernels (csrc/scl_uint_block.hip, routed by compressors/_uint_block.py), which write and read the
 same bits; a block with a codeword above 32 bits (x >= 2^24 - 1) comes back to the host.  Such a block needs the device:
 without one the call raises ``SclHipError``, it does not fall back.
+
+``encode_blocks`` / ``decode_blocks`` code many blocks at a time, one wavefront lane per block (csrc/scl_uint.hip, every
+uint32 value): ``_uint_block.UintBatchMixin``.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import numpy as np
 from ..core.data_block import DataBlock
 from ..core.data_encoder_decoder import DataDecoder, DataEncoder
 from ..utils.bitarray_utils import BitArray, bitarray_to_uint, uint_to_bitarray
+from . import _uint_block
 
 __all__ = ["EliasDeltaUintEncoder", "EliasDeltaUintDecoder"]
 
@@ -48,17 +52,22 @@ def bit_length(v: np.ndarray) -> np.ndarray:
 
 def _device(coder, size: int):
     """(the router, the device's code of this coder object) for a block of ``size`` values / bits, (None, None) below the
-    threshold -- imported late: _uint_block lays its bits with this module"""
-    from . import _uint_block
-
+    threshold"""
     if size < _uint_block.UINT_BLOCK_MIN:
         return None, None
-    if getattr(coder, "_code", None) is None:
-        coder._code = _uint_block.UintCode("elias_delta")
-    return _uint_block, coder._code
+    return _uint_block, coder._uint_code()
 
 
-class EliasDeltaUintEncoder(DataEncoder):
+class _EliasDeltaDevice(_uint_block.UintBatchMixin):
+    _code = None
+
+    def _uint_code(self):
+        if self._code is None:
+            self._code = _uint_block.UintCode("elias_delta")
+        return self._code
+
+
+class EliasDeltaUintEncoder(_EliasDeltaDevice, DataEncoder):
     def encode_symbol(self, x: int) -> BitArray:
         assert isinstance(x, int)
         assert x >= 0
@@ -89,7 +98,7 @@ class EliasDeltaUintEncoder(DataEncoder):
         return BitArray._wrap(scatter_codewords(value, 2 * l + 1 + n))
 
 
-class EliasDeltaUintDecoder(DataDecoder):
+class EliasDeltaUintDecoder(_EliasDeltaDevice, DataDecoder):
     def decode_symbol(self, encoded_bitarray: BitArray) -> Tuple[int, int]:
         used = 0
         while encoded_bitarray[used] != 1:

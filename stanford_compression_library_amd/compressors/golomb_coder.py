@@ -8,6 +8,9 @@ else r + cutoff in b + 1 bits.
 ``encode_block`` / ``decode_block`` run on the device (csrc/scl_uint_block.hip) from ``UINT_BLOCK_MIN`` values / bits on and
 on the host below it, for codewords above 32 bits and for values of 2^32 and more: compressors/_uint_block.py.  The stream
 is the block's codewords back to back either way; ``decode_block`` reads every bit it is given.
+
+``encode_blocks`` / ``decode_blocks`` code many blocks at a time, one wavefront lane per block (csrc/scl_uint.hip, every
+uint32 value): ``_uint_block.UintBatchMixin``.
 """
 from __future__ import annotations
 
@@ -35,7 +38,7 @@ class GolombCodeParams:
         self.rice_code = self.cutoff == self.M
 
 
-class _GolombDevice:
+class _GolombDevice(_uint_block.UintBatchMixin):
     _code = None
 
     def _uint_code(self) -> UintCode:
@@ -46,6 +49,9 @@ class _GolombDevice:
 
     def _on_device(self) -> bool:
         return self.params.M < (1 << 31)
+
+    def _batch_code(self):
+        return self._uint_code() if self._on_device() else None
 
 
 class GolombUintEncoder(_GolombDevice, PrefixFreeEncoder):

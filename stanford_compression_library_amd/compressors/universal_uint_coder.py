@@ -7,6 +7,9 @@ Drop-in for reference scl/compressors/universal_uint_coder.py: ``UniversalUintEn
 
 ``encode_block`` / ``decode_block`` run on the device (csrc/scl_uint_block.hip) from ``UINT_BLOCK_MIN`` values / bits on and
 on the host below it and for values of 2^16 and more (codewords above 32 bits): compressors/_uint_block.py.
+
+``encode_blocks`` / ``decode_blocks`` code many blocks at a time, one wavefront lane per block (csrc/scl_uint.hip, every
+uint32 value): ``_uint_block.UintBatchMixin``.
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ from .elias_delta_uint_coder import bit_length
 __all__ = ["UniversalUintEncoder", "UniversalUintDecoder"]
 
 
-class _UniversalDevice:
+class _UniversalDevice(_uint_block.UintBatchMixin):
     _code = None
 
     def _uint_code(self) -> UintCode:

@@ -150,16 +150,6 @@ __global__ void __launch_bounds__(PFB_THREADS, 4)
 }
 
 // ---- host API -------------------------------------------------------------------------------------------------------------
-// the public {kind, M} checked and turned into the kernels' rule
-static int ub_rule(const char *what, const scl_uint_code *code, SclUintRule *rule) {
-    SCL_REQUIRE(code, "%s: null pointer argument", what);
-    SCL_REQUIRE(code->kind <= SCL_UINT_ELIAS_DELTA, "%s: unknown code kind %u", what, code->kind);
-    SCL_REQUIRE(code->kind != SCL_UINT_GOLOMB || (code->M >= 1 && code->M < (1u << 31)),
-                "%s: Golomb parameter M = %u: 1 <= M < 2^31", what, code->M);
-    *rule = scl_uint_rule_make(code->kind, code->M);
-    return SCL_OK;
-}
-
 extern "C" uint64_t scl_uint_block_scratch_bytes(uint64_t n_values, uint64_t in_nbits) {
     const u64 e = pfb_enc_scratch(n_values), d = pfb_dec_scratch(in_nbits);
     return scl_round_up(e > d ? e : d, 256);
@@ -167,7 +157,7 @@ extern "C" uint64_t scl_uint_block_scratch_bytes(uint64_t n_values, uint64_t in_
 
 extern "C" int scl_uint_codeword_host(const scl_uint_code *code, uint32_t x, uint32_t *bits, uint32_t *len) {
     SclUintRule C;
-    if (int rc = ub_rule("uint_codeword_host", code, &C)) return rc;
+    if (int rc = scl_uint_rule_checked("uint_codeword_host", code, &C)) return rc;
     SCL_REQUIRE(bits && len, "uint_codeword_host: null pointer argument");
     const SclUintWord w = scl_uint_codeword(C, x);
     *bits = w.bits;
@@ -177,7 +167,7 @@ extern "C" int scl_uint_codeword_host(const scl_uint_code *code, uint32_t x, uin
 
 extern "C" int scl_uint_decode_one_host(const scl_uint_code *code, uint32_t bits32, uint32_t rem, uint32_t *len, uint32_t *x) {
     SclUintRule C;
-    if (int rc = ub_rule("uint_decode_one_host", code, &C)) return rc;
+    if (int rc = scl_uint_rule_checked("uint_decode_one_host", code, &C)) return rc;
     SCL_REQUIRE(len && x, "uint_decode_one_host: null pointer argument");
     SCL_REQUIRE(rem >= 1, "uint_decode_one_host: rem = 0: at least one bit belongs to the stream");
     *len = *x = 0;
@@ -188,7 +178,7 @@ extern "C" int scl_uint_decode_one_host(const scl_uint_code *code, uint32_t bits
 static int ub_encode(const char *what, const scl_uint_code *code, const u32 *d_val, u64 n, u8 *d_out, u64 out_cap_bytes,
                      u64 *d_nbits, u32 *d_status, void *d_scratch, u64 scratch_bytes, hipStream_t st) {
     SclUintRule C;
-    if (int rc = ub_rule(what, code, &C)) return rc;
+    if (int rc = scl_uint_rule_checked(what, code, &C)) return rc;
     SCL_REQUIRE(d_out && d_nbits && d_status && d_scratch && (d_val || n == 0), "%s: null pointer argument", what);
     SCL_REQUIRE(n < (1ull << 32), "%s: %llu values: a block holds fewer than 2^32", what, (unsigned long long)n);
     SCL_REQUIRE(((uintptr_t)d_out & 3) == 0 && ((uintptr_t)d_scratch & 7) == 0 && ((uintptr_t)d_nbits & 7) == 0 &&
@@ -224,7 +214,7 @@ static int ub_decode(const char *what, const scl_uint_code *code, const u8 *d_in
                      u64 in_nbits, u32 *d_out_val, u64 out_cap, scl_uint_block_result *d_result, void *d_scratch,
                      u64 scratch_bytes, hipStream_t st) {
     SclUintRule C;
-    if (int rc = ub_rule(what, code, &C)) return rc;
+    if (int rc = scl_uint_rule_checked(what, code, &C)) return rc;
     SCL_REQUIRE(d_in && d_result && d_scratch && (d_out_val || out_cap == 0), "%s: null pointer argument", what);
     SCL_REQUIRE(in_nbits < (1ull << 46) && in_bit_offset < (1ull << 62), "%s: stream of %llu bits: 2^46 and more are not coded",
                 what, (unsigned long long)in_nbits);
@@ -275,7 +265,7 @@ extern "C" int scl_uint_encode_block_host(const scl_uint_code *code, const uint3
                                           uint64_t out_cap_bytes, uint64_t *nbits, uint32_t *status) {
     const char *what = "uint_encode_block_host";
     SclUintRule C;
-    if (int rc = ub_rule(what, code, &C)) return rc;
+    if (int rc = scl_uint_rule_checked(what, code, &C)) return rc;
     SCL_REQUIRE(h_out && nbits && status && (h_val || n == 0), "%s: null pointer argument", what);
     SCL_REQUIRE(n < (1ull << 32), "%s: %llu values: a block holds fewer than 2^32", what, (unsigned long long)n);
     const u64 reach = n * (PFB_MAX_LEN / 8);
@@ -306,7 +296,7 @@ extern "C" int scl_uint_decode_block_host(const scl_uint_code *code, const uint8
                                           uint32_t *status) {
     const char *what = "uint_decode_block_host";
     SclUintRule C;
-    if (int rc = ub_rule(what, code, &C)) return rc;
+    if (int rc = scl_uint_rule_checked(what, code, &C)) return rc;
     SCL_REQUIRE(h_in && n_out && consumed && status && (h_out_val || out_cap == 0), "%s: null pointer argument", what);
     SCL_REQUIRE(in_nbits < (1ull << 46), "%s: stream of %llu bits: 2^46 and more are not coded", what,
                 (unsigned long long)in_nbits);

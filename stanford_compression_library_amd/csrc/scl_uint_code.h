@@ -9,7 +9,8 @@
 //                the n bits of y below its leading one
 // A codeword travels in one 32-bit word (PFB_MAX_LEN): universal x < 2^16, Elias-delta x <= 2^24 - 2, Golomb
 // x / M + 1 + b (+ 1) <= 32; longer ones are refused (length 0 / PFB_END_STATE), never split.  Used by scl_uint_block.hip;
-// DESIGN.md 3.5.2.
+// DESIGN.md 3.5.2.  The lane-per-stream kernels of scl_uint.hip carry every 32-bit value: their form of the rule (the
+// codeword in pieces, one codeword read sequentially) is at the end of this header; DESIGN.md 3.5.3.
 #pragma once
 
 #include "scl_bit_block.h"
@@ -34,6 +35,16 @@ static inline SclUintRule scl_uint_rule_make(u32 kind, u32 M) {
     c.cutoff = (2u << c.b) - c.M;
     if (c.cutoff != c.M) c.recip = ~0ull / c.M + 1;  // M >= 3 divides no power of two: floor((2^64 - 1) / M) + 1 = ceil
     return c;
+}
+
+// the public {kind, M} checked and turned into the kernels' rule; `what` names the entry point in the error text
+static inline int scl_uint_rule_checked(const char *what, const scl_uint_code *code, SclUintRule *rule) {
+    SCL_REQUIRE(code, "%s: null pointer argument", what);
+    SCL_REQUIRE(code->kind <= SCL_UINT_ELIAS_DELTA, "%s: unknown code kind %u", what, code->kind);
+    SCL_REQUIRE(code->kind != SCL_UINT_GOLOMB || (code->M >= 1 && code->M < (1u << 31)),
+                "%s: Golomb parameter M = %u: 1 <= M < 2^31", what, code->M);
+    *rule = scl_uint_rule_make(code->kind, code->M);
+    return SCL_OK;
 }
 
 __host__ __device__ __forceinline__ u32 scl_uint_clz(u32 v) { return v ? (u32)__builtin_clz(v) : 32u; }
@@ -112,4 +123,129 @@ __host__ __device__ __forceinline__ u32 scl_uint_decode(const SclUintRule &c, u3
     x = c.M * q + r;  // below 2^32: q <= 31 - b and M < 2^(b+1)
     len = need;
     return PFB_END_EXIT;
+}
+
+// ---- the rule without the 32-bit limit (scl_uint.hip: one lane per stream) ------------------------------
+// The codeword of ANY 32-bit x in pieces a sequential writer can put: `run` ones, then two fields of at most 32 bits each
+// (a field of 0 bits is empty).
+//   Golomb       run = q, f0 = the zero and the remainder: 1 + b (+ 1) <= 32 bits (b <= 30); no second field
+//   universal    no run; f0 = L - 1 ones and the zero, L <= 32 bits; f1 = x in L bits
+//   Elias-delta  no run; f0 = n + 1 in 2l + 1 <= 11 bits (the l zeros are its high bits); f1 = the low n <= 32 bits of
+//                y = x + 1 (y = 2^32 for x = 2^32 - 1: n = 32, f1 = 0, 43 bits in all)
+// Golomb's run is as long as x / M; the other two codes stop at 64 bits.
+struct SclUintFields {
+    u32 run;
+    u32 f0, n0;
+    u32 f1, n1;
+};
+
+__host__ __device__ __forceinline__ u64 scl_uint_fields_len(const SclUintFields &f) { return (u64)f.run + f.n0 + f.n1; }
+
+__host__ __device__ __forceinline__ SclUintFields scl_uint_fields(const SclUintRule &c, u32 x) {
+    SclUintFields f = {0u, 0u, 0u, 0u, 0u};
+    if (c.kind == SCL_UINT_GOLOMB) {
+        const u32 q = scl_uint_div(c, x), r = x - q * c.M;
+        const bool longer = c.cutoff != c.M && r >= c.cutoff;
+        f.run = q;
+        f.f0 = longer ? r + c.cutoff : r;  // below 2^(b+1): the zero in front of it is the field's own top bit
+        f.n0 = 1u + c.b + (longer ? 1u : 0u);
+    } else if (c.kind == SCL_UINT_UNIVERSAL) {
+        const u32 L = x ? 32u - scl_uint_clz(x) : 1u;
+        f.f0 = ((1u << (L - 1u)) - 1u) << 1;
+        f.n0 = L;
+        f.f1 = x;
+        f.n1 = L;
+    } else {
+        const u64 y = (u64)x + 1u;
+        const u32 n = (y >> 32) ? 32u : 31u - scl_uint_clz((u32)y), l = 31u - scl_uint_clz(n + 1u);
+        f.f0 = n + 1u;
+        f.n0 = 2u * l + 1u;
+        f.f1 = (u32)(y - (1ull << n));
+        f.n1 = n;
+    }
+    return f;
+}
+
+// One codeword read sequentially from a bit source of which `rem` >= 1 bits belong to the stream.  SRC supplies
+//   u32 look()      the next 32 bits, left-aligned (what lies behind the stream is not looked at)
+//   void skip(n)    consume n <= 32 bits
+//   void relief()   every codeword passes one, and at most two words are consumed between two (a ring reader refills there)
+// Returns 0 with `x` in `len` bits, or the verdict in the order a sequential reader meets it:
+//   Golomb       the ones read inside the stream reach a quotient q with M * q >= 2^32 -> SCL_ST_SIZE (this, not the stream,
+//                bounds the loop); the stream ends before the zero -> SCL_ST_TRUNCATED; the b remainder bits or the extra bit
+//                of a long remainder are missing -> SCL_ST_TRUNCATED; M * q + r >= 2^32 -> SCL_ST_SIZE
+//   universal    the 32nd one inside the stream -> SCL_ST_SIZE; the run reaches the end -> SCL_ST_TRUNCATED; 2L > rem ->
+//                SCL_ST_TRUNCATED
+//   Elias-delta  the 6th zero inside the stream -> SCL_ST_SIZE; the zeros reach the end, or 2l + 1 > rem -> SCL_ST_TRUNCATED;
+//                n > 32 -> SCL_ST_SIZE; 2l + 1 + n > rem -> SCL_ST_TRUNCATED; n = 32 with a low field != 0 -> SCL_ST_SIZE
+// After a verdict the source stands somewhere inside the codeword: the caller reads no further.
+template <class SRC>
+__host__ __device__ __forceinline__ u32 scl_uint_decode_wide(const SclUintRule &c, SRC &src, u32 rem, u32 &len, u32 &x) {
+    if (c.kind == SCL_UINT_GOLOMB) {
+        const u64 qlim = ((1ull << 32) + c.M - 1u) / c.M;  // the first quotient whose M * q leaves 32 bits
+        u64 q = 0;
+        u32 left = rem, k;
+        for (;;) {  // the ones, up to a word at a time
+            const u32 avail = left < 32u ? left : 32u;
+            k = scl_uint_clz(~src.look());
+            k = k < avail ? k : avail;
+            if (q + k >= qlim) return SCL_ST_SIZE;
+            q += k;
+            left -= k;
+            if (k < avail) break;  // the zero is in sight: k < 32 ones and the zero are still in front of the source
+            if (left == 0) return SCL_ST_TRUNCATED;
+            src.skip(32u);  // k == avail == 32
+            src.relief();
+        }
+        src.skip(k + 1u);
+        left -= 1u;
+        src.relief();
+        if (c.b > left) return SCL_ST_TRUNCATED;
+        u32 r = c.b ? src.look() >> (32u - c.b) : 0u;
+        src.skip(c.b);
+        left -= c.b;
+        if (c.cutoff != c.M && r >= c.cutoff) {
+            if (left == 0) return SCL_ST_TRUNCATED;
+            r = 2u * r + (src.look() >> 31) - c.cutoff;
+            src.skip(1u);
+            left -= 1u;
+        }
+        const u64 v = (u64)c.M * q + r;  // q < qlim: M * q is below 2^32, the remainder may carry it over
+        if (v >> 32) return SCL_ST_SIZE;
+        x = (u32)v;
+        len = rem - left;
+        return 0u;
+    }
+    if (c.kind == SCL_UINT_UNIVERSAL) {
+        const u32 avail = rem < 32u ? rem : 32u;
+        u32 k = scl_uint_clz(~src.look());
+        k = k < avail ? k : avail;
+        if (k >= 32u) return SCL_ST_SIZE;
+        if (k == rem) return SCL_ST_TRUNCATED;
+        const u32 L = k + 1u;
+        if (2u * L > rem) return SCL_ST_TRUNCATED;
+        src.skip(L);
+        src.relief();
+        x = src.look() >> (32u - L);
+        src.skip(L);
+        len = 2u * L;
+        return 0u;
+    }
+    const u32 avail = rem < 32u ? rem : 32u;
+    const u32 bits = src.look();
+    u32 l = scl_uint_clz(bits);
+    l = l < avail ? l : avail;
+    if (l >= 6u) return SCL_ST_SIZE;
+    if (l == rem || 2u * l + 1u > rem) return SCL_ST_TRUNCATED;
+    const u32 n = ((bits << l) >> (31u - l)) - 1u;  // l + 1 bits from the first one on: n + 1 >= 2^l
+    if (n > 32u) return SCL_ST_SIZE;
+    if (2u * l + 1u + n > rem) return SCL_ST_TRUNCATED;
+    src.skip(2u * l + 1u);
+    src.relief();
+    const u32 low = n ? src.look() >> (32u - n) : 0u;
+    if (n == 32u && low != 0u) return SCL_ST_SIZE;
+    src.skip(n);
+    x = n == 32u ? 0xFFFFFFFFu : ((1u << n) | low) - 1u;
+    len = 2u * l + 1u + n;
+    return 0u;
 }
