@@ -10,6 +10,7 @@ Everything raises ``SclHipError`` when the HIP library or a device is missing: n
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import threading
 import os
 from dataclasses import dataclass
@@ -441,6 +442,52 @@ class RangeModel(_DeviceModel):
         return bool(self._L.scl_range_fast_path(self._h))
 
 
+# -- one block in device memory: what PrefixModel and UintCode do around their entry points ------------------------------------
+def _encode_block_into(entry, name, values, dtypes, out, out_cap_bytes, stream, scratch_for):
+    """``entry(values, n, out, cap, nbits, status, scratch, scratch_bytes, stream)`` is the C entry point behind its model or
+    rule; ``scratch_for(device, stream)`` -> the uint8 scratch tensor.  -> int64 tensor ``[nbits, status]`` on the device."""
+    import torch
+
+    assert values.is_cuda and values.dtype in dtypes and values.dim() == 1 and values.is_contiguous()
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+    cap = out.numel() if out_cap_bytes is None else int(out_cap_bytes)
+    assert cap <= out.numel()
+    dev = values.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    meta = torch.zeros(2, dtype=torch.int64, device=dev)
+    scratch = scratch_for(dev, st)
+    with torch.cuda.device(dev):
+        rc = entry(values.data_ptr(), values.numel(), out.data_ptr(), cap, meta.data_ptr(), meta.data_ptr() + 8,
+                   scratch.data_ptr(), scratch.numel(), st)
+    _lib.check(rc, name)
+    return meta
+
+
+def _decode_block_device(entry, name, data, nbits, bit_offset, out_cap, out, dtypes, min_len, stream, scratch_for):
+    """``entry(data, size, bit_offset, nbits, out, cap, result, scratch, scratch_bytes, stream)`` is the C entry point behind
+    its model or rule.  -> (values, n_out, consumed, status, sync_passes); the library has synchronised the stream, a
+    ``stream`` that is not torch's current one is synchronised here."""
+    import torch
+
+    assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
+    dev = data.device
+    cap = int(nbits) // min_len if out_cap is None else int(out_cap)
+    if out is None:
+        out = torch.empty(max(cap, 1), dtype=dtypes[0], device=dev)
+    assert out.is_cuda and out.dtype in dtypes and out.is_contiguous() and out.numel() >= cap
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    result = torch.zeros(3, dtype=torch.int64, device=dev)
+    scratch = scratch_for(dev, st)
+    with torch.cuda.device(dev):
+        rc = entry(data.data_ptr(), data.numel(), int(bit_offset), int(nbits), out.data_ptr(), cap, result.data_ptr(),
+                   scratch.data_ptr(), scratch.numel(), st)
+    _lib.check(rc, name)
+    if stream is not None:
+        torch.cuda.ExternalStream(int(st), device=dev).synchronize()
+    n_out, consumed, tail = (int(v) for v in result.cpu())
+    return out[:n_out], n_out, consumed, tail & 0xFFFFFFFF, (tail >> 32) & 0xFFFFFFFF
+
+
 class PrefixModel(_DeviceModel):
     """any prefix-free code table on the device: symbol i is coded with the ``lengths[i]`` low bits of ``codes[i]``, most
     significant first (1..32 bits).  Linear slots only.  The streams carry no size header (``size_bits`` = 0)."""
@@ -524,21 +571,9 @@ class PrefixModel(_DeviceModel):
         """1-D symbol tensor -> its stream at the front of the uint8 tensor ``out`` (zeroed by the call), asynchronously.
         -> int64 tensor ``[nbits, status]`` on the device; status ``ST_CAPACITY``: ``out_cap_bytes`` (default: all of
         ``out``) is too small and nothing was written."""
-        import torch
-
-        assert sym.is_cuda and sym.dtype in self._torch_sym_dtypes() and sym.dim() == 1 and sym.is_contiguous()
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
-        cap = out.numel() if out_cap_bytes is None else int(out_cap_bytes)
-        assert cap <= out.numel()
-        dev = sym.device
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        meta = torch.zeros(2, dtype=torch.int64, device=dev)
-        scratch, nbytes = self._block_scratch(sym.numel(), 0, dev, st)
-        with torch.cuda.device(dev):
-            rc = self._sym_fn("encode_block")(self._h, sym.data_ptr(), sym.numel(), out.data_ptr(), cap, meta.data_ptr(),
-                                              meta.data_ptr() + 8, scratch.data_ptr(), nbytes, st)
-        _lib.check(rc, "scl_prefix_encode_block")
-        return meta
+        return _encode_block_into(functools.partial(self._sym_fn("encode_block"), self._h), "scl_prefix_encode_block", sym,
+                                  self._torch_sym_dtypes(), out, out_cap_bytes, stream,
+                                  lambda dev, st: self._block_scratch(sym.numel(), 0, dev, st)[0])
 
     def encode_block_device(self, sym):
         """1-D symbol tensor on the device -> (uint8 tensor holding the stream, nbits).  Waits for the result (``nbits`` is
@@ -558,25 +593,9 @@ class PrefixModel(_DeviceModel):
         correction passes that moved a start).  ``out_cap`` defaults to ``nbits // min_len``, which holds any stream;
         ``out`` is an optional symbol tensor of at least ``out_cap`` elements.  The call synchronises the stream: the
         library reads a device flag between its passes."""
-        import torch
-
-        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
-        dev = data.device
-        cap = int(nbits) // self.min_len if out_cap is None else int(out_cap)
-        if out is None:
-            out = torch.empty(max(cap, 1), dtype=self._torch_sym_dtypes()[0], device=dev)
-        assert out.is_cuda and out.dtype in self._torch_sym_dtypes() and out.is_contiguous() and out.numel() >= cap
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        result = torch.zeros(3, dtype=torch.int64, device=dev)
-        scratch, nbytes = self._block_scratch(0, nbits, dev, st)
-        with torch.cuda.device(dev):
-            rc = self._sym_fn("decode_block")(self._h, data.data_ptr(), data.numel(), int(bit_offset), int(nbits),
-                                              out.data_ptr(), cap, result.data_ptr(), scratch.data_ptr(), nbytes, st)
-        _lib.check(rc, "scl_prefix_decode_block")
-        if stream is not None:
-            torch.cuda.ExternalStream(int(st), device=dev).synchronize()
-        n_out, consumed, tail = (int(v) for v in result.cpu())
-        return out[:n_out], n_out, consumed, tail & 0xFFFFFFFF, (tail >> 32) & 0xFFFFFFFF
+        return _decode_block_device(functools.partial(self._sym_fn("decode_block"), self._h), "scl_prefix_decode_block", data,
+                                    nbits, bit_offset, out_cap, out, self._torch_sym_dtypes(), self.min_len, stream,
+                                    lambda dev, st: self._block_scratch(0, nbits, dev, st)[0])
 
 
 class UintCode:
@@ -655,20 +674,9 @@ class UintCode:
         stream.  -> int64 tensor ``[nbits, status]`` on the device.  ``scratch``: a uint8 tensor to use, else one is made."""
         import torch
 
-        assert values.is_cuda and values.dtype in (torch.uint32, torch.int32) and values.dim() == 1 and values.is_contiguous()
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
-        cap = out.numel() if out_cap_bytes is None else int(out_cap_bytes)
-        assert cap <= out.numel()
-        dev = values.device
-        st = torch.cuda.current_stream(dev).cuda_stream
-        meta = torch.zeros(2, dtype=torch.int64, device=dev)
-        if scratch is None:
-            scratch, _ = self._block_scratch(values.numel(), 0, dev)
-        with torch.cuda.device(dev):
-            rc = self._L.scl_uint_encode_block(C.byref(self._c), values.data_ptr(), values.numel(), out.data_ptr(), cap,
-                                               meta.data_ptr(), meta.data_ptr() + 8, scratch.data_ptr(), scratch.numel(), st)
-        _lib.check(rc, "scl_uint_encode_block")
-        return meta
+        return _encode_block_into(functools.partial(self._L.scl_uint_encode_block, C.byref(self._c)), "scl_uint_encode_block",
+                                  values, (torch.int32, torch.uint32), out, out_cap_bytes, None,
+                                  lambda dev, st: scratch if scratch is not None else self._block_scratch(values.numel(), 0, dev)[0])
 
     def encode_block_device(self, values):
         """1-D uint32 / int32 tensor on the device -> (uint8 tensor holding the stream, nbits, status).  Waits for the result."""
@@ -685,22 +693,9 @@ class UintCode:
         ``out_cap`` elements.  The call synchronises the current stream: the library reads a device flag between passes."""
         import torch
 
-        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()
-        dev = data.device
-        cap = int(nbits) // self.min_len if out_cap is None else int(out_cap)
-        if out is None:
-            out = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        assert out.is_cuda and out.dtype in (torch.uint32, torch.int32) and out.is_contiguous() and out.numel() >= cap
-        st = torch.cuda.current_stream(dev).cuda_stream
-        result = torch.zeros(3, dtype=torch.int64, device=dev)
-        if scratch is None:
-            scratch, _ = self._block_scratch(0, nbits, dev)
-        with torch.cuda.device(dev):
-            rc = self._L.scl_uint_decode_block(C.byref(self._c), data.data_ptr(), data.numel(), int(bit_offset), int(nbits),
-                                               out.data_ptr(), cap, result.data_ptr(), scratch.data_ptr(), scratch.numel(), st)
-        _lib.check(rc, "scl_uint_decode_block")
-        n_out, consumed, tail = (int(v) for v in result.cpu())
-        return out[:n_out], n_out, consumed, tail & 0xFFFFFFFF, (tail >> 32) & 0xFFFFFFFF
+        return _decode_block_device(functools.partial(self._L.scl_uint_decode_block, C.byref(self._c)), "scl_uint_decode_block",
+                                    data, nbits, bit_offset, out_cap, out, (torch.int32, torch.uint32), self.min_len, None,
+                                    lambda dev, st: scratch if scratch is not None else self._block_scratch(0, nbits, dev)[0])
 
     # -- the rule without the 32-bit limit, on the host ----------------------------------------------------------------
     def fields(self, x: int):

@@ -1,10 +1,12 @@
 // scl_bit_block.h -- the pieces of "one block of variable-length codewords across the whole grid" that do not depend on
-// whose codewords they are: the shapes, the encoder's tile emitter, the decoder's input window, the bodies of the
-// self-synchronising decoder (walk, sync, end-of-stream scan, write) over a codeword policy, and the host's pass loop.  ONE
-// copy, used by scl_prefix_block.hip (one prefix-free block, tables of a scl_prefix_model) and by scl_lz77_entropy_wide.hip
-// (the four fields of an LZ77 stream at any bit position, tables built on the device).  Each of the two keeps its codeword
-// policy, its __global__ kernels (thin: tables in LDS, one call) and its verdict on how a stream ended.  Internal to csrc/;
-// DESIGN.md 3.5.1, 3.6.3.
+// whose codewords they are: the shapes; the encoder (the bodies of the tile-bits and tile-emit kernels over a value policy, the
+// scan of the tile sums, the tail kernel); the decoder (its input window, the bodies of the self-synchronising scheme -- walk,
+// sync, end-of-stream scan, write -- over a codeword policy, the verdict kernel); the host side (the launchers with the entry
+// points' checks, the pass loop of a section, the staging of one block in host memory).  ONE copy, used by
+// scl_prefix_block.hip (tables of a scl_prefix_model), scl_uint_block.hip (Golomb, universal, Elias-delta: a rule, no table)
+// and scl_lz77_entropy_wide.hip (the four fields of an LZ77 stream at any bit position, tables built on the device, its own
+// seven-section scan and verdict).  Each keeps its two policies and its __global__ kernels over them (thin: tables in LDS, one
+// call).  Internal to csrc/; DESIGN.md 3.5.1, 3.5.2, 3.6.3.
 #pragma once
 
 #include "scl_common.h"
@@ -53,6 +55,14 @@ struct PfbDecScratch {  // device pointers into the decoder's scratch
     PfbDecHead *head;
     PfbDecGroups g;
 };
+
+struct PfbDecResult {  // what a block decoder reports: the layout of scl_prefix_block_result and scl_uint_block_result
+    u64 n_out, consumed;
+    u32 status, sync_passes;
+};
+#define PFB_RESULT_IS(T)                                                                                                   \
+    static_assert(sizeof(T) == 24 && offsetof(T, consumed) == 8 && offsetof(T, status) == 16 && offsetof(T, sync_passes) == 20, \
+                  #T " is PfbDecResult under another name")
 
 static inline u64 pfb_tiles(u64 n) { return (n + PFB_TILE - 1) / PFB_TILE; }
 static inline u64 pfb_subs(u64 nbits) { return (nbits + PFB_SUB - 1) / PFB_SUB; }
@@ -115,10 +125,68 @@ __device__ __forceinline__ void pfb_emit_tile(const uint2 (&e)[PFB_PER_THREAD], 
     }
 }
 
+// ---- encode: the bodies of the tile kernels over a value policy ENC, which owns its input and its tables -------------------
+//   kTables, load()        EVERY thread calls load(), in front of a barrier: it fills the policy's LDS tables (kTables: it
+//                          has some; without, tile-bits needs no barrier)
+//   codes(block, e, bad)   the {bits, length} of the thread's PFB_PER_THREAD consecutive values of tile `block` (the contract of
+//                          pfb_emit_tile) -> the sum of the lengths; bad = 1 on a value of the block that has no codeword
+//   kFault                 the status bit that tile-bits raises for such a value (0: none, the caller finds them elsewhere)
+//   tile_base(block)       the bit of the stream at which tile `block` starts (tile-emit; called behind codes(block, ...))
+// One workgroup per tile.  tile-bits: tile_bits[tile] = the bits of the tile, *status |= kFault.
+template <class ENC>
+__device__ __forceinline__ void pfb_tile_bits_body(ENC E, u64 *__restrict__ tile_bits, u32 *__restrict__ status) {
+    __shared__ u32 s_wave[PFB_THREADS / 64];
+    E.load();
+    if constexpr (ENC::kTables) __syncthreads();
+    uint2 e[PFB_PER_THREAD];
+    u32 bad = 0, total;
+    const u32 bits = E.codes(blockIdx.x, e, bad);
+    (void)scl_block_scan_excl<u32, PFB_THREADS, SclScanSum>(bits, s_wave, &total);
+    const int any_bad = ENC::kFault ? __syncthreads_or((int)bad) : 0;
+    if (threadIdx.x == 0) {
+        tile_bits[blockIdx.x] = total;
+        if (any_bad) atomicOr(status, (u32)ENC::kFault);
+    }
+}
+
+// tile-emit: the tile's codewords go to the output at tile_base (pfb_emit_tile).  A stream that does not fit, or that a fault
+// stopped, stores nothing (uniform: the whole grid leaves).
+template <class ENC>
+__device__ __forceinline__ void pfb_encode_tile_body(ENC E, PfbEncScratch *__restrict__ head, u32 *__restrict__ out32,
+                                                     u64 tail_index) {
+    __shared__ u32 s_wave[PFB_THREADS / 64];
+    __shared__ u32 s_words[PFB_TILE_WORDS];
+    if (!head->fits) return;
+    E.load();
+    for (u32 i = threadIdx.x; i < PFB_TILE_WORDS; i += PFB_THREADS) s_words[i] = 0;
+    __syncthreads();
+    uint2 e[PFB_PER_THREAD];
+    u32 bad = 0;
+    const u32 bits = E.codes(blockIdx.x, e, bad);
+    pfb_emit_tile(e, bits, E.tile_base(blockIdx.x), s_words, s_wave, head, out32, tail_index);
+}
+
+// ONE workgroup: the tile sums become the tile offsets (exclusive 64-bit scan), and the verdict.  STOP: the status bits (of
+// tile-bits, the kernel in front) that stop the coding: such a stream has no length and stores nothing.
+template <u32 STOP>
+__global__ void __launch_bounds__(PFB_SCAN_THREADS)
+    pfb_scan_tiles_kernel(u64 *__restrict__ tile_bits, u64 n_tiles, u64 out_cap_bytes, PfbEncScratch *__restrict__ head,
+                          u64 *__restrict__ nbits, u32 *__restrict__ status) {
+    __shared__ u64 s_wave[PFB_SCAN_THREADS / 64];
+    const u64 total = scl_block_scan_array<u64, PFB_SCAN_THREADS, SclScanSum>(tile_bits, n_tiles, s_wave);
+    if (threadIdx.x == 0) {
+        const bool coded = (*status & STOP) == 0;
+        const bool fits = coded && (total + 7) / 8 <= out_cap_bytes;
+        head->fits = fits ? 1u : 0u;
+        *nbits = coded ? total : 0ull;
+        if (coded && !fits) atomicOr(status, (u32)SCL_ST_CAPACITY);
+    }
+}
+
 // out_cap_bytes % 4 != 0: the bytes of the last, partial word come from head->tail_word (one thread)
-__device__ __forceinline__ void pfb_store_tail(const PfbEncScratch *__restrict__ head, u64 nbits, u8 *__restrict__ out,
-                                               u64 out_cap_bytes) {
-    if (!head->fits || ((nbits + 31) >> 5) <= (out_cap_bytes >> 2)) return;  // nothing written, or not as far as that word
+static __global__ void pfb_encode_tail_kernel(const PfbEncScratch *__restrict__ head, const u64 *__restrict__ nbits,
+                                              u8 *__restrict__ out, u64 out_cap_bytes) {
+    if (!head->fits || ((*nbits + 31) >> 5) <= (out_cap_bytes >> 2)) return;  // nothing written, or not as far as that word
     const u32 v = head->tail_word;
     for (u64 b = out_cap_bytes & ~3ull; b < out_cap_bytes; ++b) out[b] = (u8)(v >> (8 * (b & 3)));
 }
@@ -287,6 +355,32 @@ __device__ __forceinline__ u64 pfb_scan_to_end(const PfbDecGroups &sc, u64 n_gro
     return last_group;
 }
 
+// ONE workgroup: where the stream ends, the symbol offsets of the workgroups up to there, the result as the one-lane decoder
+// reports it.  A codeword that in_nbits cuts is SCL_ST_TRUNCATED; CUT: the status of any other end of a walk.
+template <u32 CUT>
+__global__ void __launch_bounds__(PFB_SCAN_THREADS)
+    pfb_scan_groups_kernel(PfbDecScratch sc, u64 n_groups, u64 in_nbits, u64 out_cap, u32 sync_passes,
+                           PfbDecResult *__restrict__ result) {
+    u64 total;
+    const u64 last_group = pfb_scan_to_end(sc.g, n_groups, &total);
+    if (threadIdx.x == 0) {
+        const u64 cut = sc.g.group_end[last_group];
+        const u64 end = cut == PFB_NONE64 ? in_nbits : cut >> 2;
+        u32 status = cut == PFB_NONE64 ? 0u : ((cut & 3u) == PFB_END_TRUNC ? SCL_ST_TRUNCATED : CUT);
+        u64 consumed = end;
+        // the one-lane decoder looks at out_cap before every codeword: bits left after out_cap symbols are
+        // SCL_ST_CAPACITY whatever they hold.  total > out_cap: the write kernel stores `consumed` (0 for out_cap = 0)
+        if (total > out_cap || (total == out_cap && end < in_nbits)) status = SCL_ST_CAPACITY;
+        if (total > out_cap) consumed = 0;
+        sc.head->n_total = total;
+        sc.head->last_group = last_group;
+        result->n_out = total < out_cap ? total : out_cap;
+        result->consumed = consumed;
+        result->status = status;
+        result->sync_passes = sync_passes;
+    }
+}
+
 // every thread decodes its final range once more and stores its symbols at its offset, up to out_cap of them.
 // consumed_at_cap (or null): with more than out_cap symbols in the stream, the bit behind symbol out_cap - 1 is stored there
 template <class CODE, typename SYM>
@@ -332,16 +426,20 @@ __device__ __forceinline__ void pfb_write_body(const CODE &C, const u8 *__restri
 }
 #endif  // __HIPCC__
 
-// ---- decode: the host's pass loop -------------------------------------------------------------------------------------------
-// launch(p) enqueues sync pass p on `st`.  Pass 0, then passes 1 .. n_groups - 1 at the most (workgroup w is final after pass
-// w), fewer when a pass changes no workgroup's exit: after each the host reads {start_pass, exit_pass} at d_pass_words.
-// *sync_passes grows by the passes in which a workgroup moved its start.
-template <class LAUNCH>
-static int pfb_run_sync_passes(LAUNCH launch, const void *d_pass_words, u64 n_groups, hipStream_t st, u32 *sync_passes) {
-    launch(0u);
+// ---- decode: one section of `nbits` >= 1 bits, the host's pass loop ---------------------------------------------------------
+// sync(grid, n_sub, n_groups, p) enqueues sync pass p on `st`.  Pass 0, then passes 1 .. n_groups - 1 at the most (workgroup w
+// is final after pass w), fewer when a pass changes no workgroup's exit: after each the host reads {start_pass, exit_pass} at
+// d_pass_words.  *sync_passes grows by the passes in which a workgroup moved its start.  Then scan(n_groups, *sync_passes) and
+// write(grid, n_sub) enqueue the caller's scan_groups and write kernels.
+template <class SYNC, class SCAN, class WRITE>
+static int pfb_decode_section(u64 nbits, const void *d_pass_words, hipStream_t st, u32 *sync_passes, SYNC sync, SCAN scan,
+                              WRITE write) {
+    const u64 n_sub = pfb_subs(nbits), n_groups = pfb_groups(nbits);
+    const dim3 grid((u32)n_groups);
+    sync(grid, n_sub, n_groups, 0u);
     SCL_HIP_TRY(hipGetLastError());
     for (u64 pass = 1; pass < n_groups; ++pass) {
-        launch((u32)pass);
+        sync(grid, n_sub, n_groups, (u32)pass);
         SCL_HIP_TRY(hipGetLastError());
         u32 flags[2];
         SCL_HIP_TRY(hipMemcpyAsync(flags, d_pass_words, 8, hipMemcpyDeviceToHost, st));
@@ -349,5 +447,156 @@ static int pfb_run_sync_passes(LAUNCH launch, const void *d_pass_words, u64 n_gr
         if (flags[0] == (u32)pass) ++*sync_passes;
         if (flags[1] != (u32)pass) break;
     }
+    scan(n_groups, *sync_passes);
+    write(grid, n_sub);
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+// ---- the entry points of a coder of one block (prefix-free codes, integer codes) --------------------------------------------
+struct PfbWords {  // what the two coders' messages name differently
+    const char *values, *scratch_fn;         // what a block holds ("symbols"); the function that sizes the scratch
+    const char *enc_aligned, *dec_aligned;  // the alignment rule of the encode call, of the decode call
+};
+// what an encode / a decode call takes behind its model or rule, under the names of include/scl_hip.h
+struct PfbEncodeArgs {
+    const void *d_val;
+    u64 n;
+    u8 *d_out;
+    u64 out_cap_bytes, *d_nbits;
+    u32 *d_status;
+    void *d_scratch;
+    u64 scratch_bytes;
+};
+struct PfbDecodeArgs {
+    const u8 *d_in;
+    u64 in_size_bytes, in_bit_offset, in_nbits;
+    void *d_out;
+    u64 out_cap;
+    PfbDecResult *d_result;
+    void *d_scratch;
+    u64 scratch_bytes;
+};
+
+#ifdef __HIPCC__
+// Encode: the caller has checked its model or rule, and that its own pointers (values, status) are `aligned`.  `reach`: the
+// bytes of the longest stream of a.n values (the tiles OR their shared words in, so the output is zeroed that far).
+// tile_bits(grid, tile_bits, status) and emit(grid, tile_off, head, out32, tail_index) enqueue the caller's two tile kernels.
+template <u32 STOP, class BITS, class EMIT>
+static int pfb_encode_launch(const char *what, const PfbWords &w, const PfbEncodeArgs &a, bool aligned, u64 reach, hipStream_t st,
+                             BITS tile_bits_launch, EMIT emit_launch) {
+    SCL_REQUIRE(a.d_out && a.d_nbits && a.d_status && a.d_scratch && (a.d_val || a.n == 0), "%s: null pointer argument", what);
+    SCL_REQUIRE(a.n < (1ull << 32), "%s: %llu %s: a block holds fewer than 2^32", what, (unsigned long long)a.n, w.values);
+    SCL_REQUIRE(((uintptr_t)a.d_out & 3) == 0 && ((uintptr_t)a.d_scratch & 7) == 0 && ((uintptr_t)a.d_nbits & 7) == 0 && aligned,
+                "%s: %s", what, w.enc_aligned);
+    SCL_REQUIRE(a.scratch_bytes >= pfb_enc_scratch(a.n), "%s: scratch of %llu bytes, %s asks for %llu", what,
+                (unsigned long long)a.scratch_bytes, w.scratch_fn, (unsigned long long)pfb_enc_scratch(a.n));
+    SCL_HIP_TRY(hipMemsetAsync(a.d_nbits, 0, 8, st));
+    SCL_HIP_TRY(hipMemsetAsync(a.d_status, 0, 4, st));
+    if (a.n == 0) return SCL_OK;
+    PfbEncScratch *head = (PfbEncScratch *)a.d_scratch;
+    u64 *tile_bits = (u64 *)((u8 *)a.d_scratch + 64);
+    const dim3 grid((u32)pfb_tiles(a.n));
+    const u64 zeroed = reach < a.out_cap_bytes ? reach : a.out_cap_bytes;
+    if (zeroed) SCL_HIP_TRY(hipMemsetAsync(a.d_out, 0, zeroed, st));
+    SCL_HIP_TRY(hipMemsetAsync(head, 0, 64, st));
+    tile_bits_launch(grid, tile_bits, a.d_status);
+    hipLaunchKernelGGL(pfb_scan_tiles_kernel<STOP>, dim3(1), dim3(PFB_SCAN_THREADS), 0, st, tile_bits, pfb_tiles(a.n),
+                       a.out_cap_bytes, head, a.d_nbits, a.d_status);
+    const u64 tail_index = (a.out_cap_bytes & 3) ? a.out_cap_bytes >> 2 : PFB_NONE64;
+    emit_launch(grid, (const u64 *)tile_bits, head, (u32 *)a.d_out, tail_index);
+    if (a.out_cap_bytes & 3)
+        hipLaunchKernelGGL(pfb_encode_tail_kernel, dim3(1), dim3(1), 0, st, (const PfbEncScratch *)head, (const u64 *)a.d_nbits,
+                           a.d_out, a.out_cap_bytes);
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
+}
+
+// Decode: as encode.  sync(grid, n_sub, n_groups, sc, pass) and write(grid, n_sub, sc) enqueue the caller's two kernels.
+template <u32 CUT, class SYNC, class WRITE>
+static int pfb_decode_launch(const char *what, const PfbWords &w, const PfbDecodeArgs &a, bool aligned, hipStream_t st,
+                             SYNC sync_launch, WRITE write_launch) {
+    SCL_REQUIRE(a.d_in && a.d_result && a.d_scratch && (a.d_out || a.out_cap == 0), "%s: null pointer argument", what);
+    SCL_REQUIRE(a.in_nbits < (1ull << 46) && a.in_bit_offset < (1ull << 62), "%s: stream of %llu bits: 2^46 and more are not coded",
+                what, (unsigned long long)a.in_nbits);
+    SCL_REQUIRE(((uintptr_t)a.d_in & 3) == 0 && ((uintptr_t)a.d_scratch & 7) == 0 && ((uintptr_t)a.d_result & 7) == 0 && aligned,
+                "%s: %s", what, w.dec_aligned);
+    SCL_REQUIRE(a.scratch_bytes >= pfb_dec_scratch(a.in_nbits), "%s: scratch of %llu bytes, %s asks for %llu", what,
+                (unsigned long long)a.scratch_bytes, w.scratch_fn, (unsigned long long)pfb_dec_scratch(a.in_nbits));
+    SCL_REQUIRE((a.in_bit_offset + a.in_nbits + 7) / 8 <= a.in_size_bytes, "%s: the stream ends behind in_size_bytes", what);
+    if (a.in_nbits == 0) {  // an empty stream: nothing decoded, nothing is launched
+        SCL_HIP_TRY(hipMemsetAsync(a.d_result, 0, sizeof(PfbDecResult), st));
+        return SCL_OK;
+    }
+    const PfbDecScratch sc = pfb_dec_carve(a.d_scratch, pfb_groups(a.in_nbits));
+    SCL_HIP_TRY(hipMemsetAsync(sc.head, 0, 64, st));
+    u32 sync_passes = 0;
+    return pfb_decode_section(
+        a.in_nbits, sc.head, st, &sync_passes,
+        [&](dim3 grid, u64 n_sub, u64 n_groups, u32 pass) { sync_launch(grid, n_sub, n_groups, sc, pass); },
+        [&](u64 n_groups, u32 passes) {
+            hipLaunchKernelGGL(pfb_scan_groups_kernel<CUT>, dim3(1), dim3(PFB_SCAN_THREADS), 0, st, sc, n_groups, a.in_nbits,
+                               a.out_cap, passes, a.d_result);
+        },
+        [&](dim3 grid, u64 n_sub) { write_launch(grid, n_sub, sc); });
+}
+#endif  // __HIPCC__
+
+// ---- one block in host memory: four device buffers, copy in, run, wait, read the result, copy out ---------------------------
+// run(const PfbEncodeArgs &) is the coder's encode call on the null stream (its checks included).  -> *nbits, *status; the
+// stream's bytes reach h_out with status 0 only.
+template <class RUN>
+static int pfb_encode_staged(const char *what, const PfbWords &w, const void *h_val, u64 n, u64 val_bytes, u64 reach, u8 *h_out,
+                             u64 out_cap_bytes, u64 *nbits, u32 *status, RUN run) {
+    SCL_REQUIRE(n < (1ull << 32), "%s: %llu %s: a block holds fewer than 2^32", what, (unsigned long long)n, w.values);
+    const u64 cap = reach < out_cap_bytes ? reach : out_cap_bytes;  // no stream of n values is longer than `reach`
+    const u64 scratch_bytes = pfb_enc_scratch(n);
+    ScratchDev d_val, d_out, d_meta, d_scr;
+    int rc;
+    if ((rc = d_val.alloc(n * val_bytes)) || (rc = d_out.alloc(cap)) || (rc = d_meta.alloc(16)) || (rc = d_scr.alloc(scratch_bytes)))
+        return rc;
+    if (n) SCL_HIP_TRY(hipMemcpy(d_val.p, h_val, n * val_bytes, hipMemcpyHostToDevice));
+    rc = run(PfbEncodeArgs{d_val.p, n, (u8 *)d_out.p, cap, (u64 *)d_meta.p, (u32 *)d_meta.p + 2, d_scr.p, scratch_bytes});
+    if (rc) return rc;
+    SCL_HIP_TRY(hipDeviceSynchronize());
+    u64 meta[2];
+    SCL_HIP_TRY(hipMemcpy(meta, d_meta.p, 16, hipMemcpyDeviceToHost));
+    const u64 bytes = (meta[0] + 7) / 8;
+    SCL_REQUIRE(bytes <= out_cap_bytes, "%s: output needs %llu bytes, capacity %llu", what, (unsigned long long)bytes,
+                (unsigned long long)out_cap_bytes);
+    *nbits = meta[0];
+    *status = (u32)meta[1];
+    if (*status == 0 && bytes) SCL_HIP_TRY(hipMemcpy(h_out, d_out.p, bytes, hipMemcpyDeviceToHost));
+    return SCL_OK;
+}
+
+// run(const PfbDecodeArgs &) is the coder's decode call on the null stream.  The device copy is padded to the words a window
+// load reaches, EVERY byte behind the stream zero (no policy trusts a bit past in_nbits -- each tests `len > rem` / `d == rem`
+// first -- but what it looks at is defined).  -> *n_out, *consumed, *status; the values reach h_out with status 0, and in front
+// of a fault if `partial`.
+template <class RUN>
+static int pfb_decode_staged(const char *what, const u8 *h_in, u64 in_nbits, void *h_out, u64 val_bytes, u64 out_cap, bool partial,
+                             u64 *n_out, u64 *consumed, u32 *status, RUN run) {
+    SCL_REQUIRE(in_nbits < (1ull << 46), "%s: stream of %llu bits: 2^46 and more are not coded", what,
+                (unsigned long long)in_nbits);
+    const u64 in_bytes = (in_nbits + 7) / 8, in_size = scl_round_up(in_bytes, 4) + 4;
+    const u64 scratch_bytes = pfb_dec_scratch(in_nbits);
+    ScratchDev d_in, d_out, d_res, d_scr;
+    int rc;
+    if ((rc = d_in.alloc(in_size)) || (rc = d_out.alloc(out_cap * val_bytes)) || (rc = d_res.alloc(sizeof(PfbDecResult))) ||
+        (rc = d_scr.alloc(scratch_bytes)))
+        return rc;
+    SCL_HIP_TRY(hipMemset((u8 *)d_in.p + in_bytes, 0, in_size - in_bytes));
+    if (in_bytes) SCL_HIP_TRY(hipMemcpy(d_in.p, h_in, in_bytes, hipMemcpyHostToDevice));
+    rc = run(PfbDecodeArgs{(const u8 *)d_in.p, in_size, 0, in_nbits, d_out.p, out_cap, (PfbDecResult *)d_res.p, d_scr.p,
+                           scratch_bytes});
+    if (rc) return rc;
+    SCL_HIP_TRY(hipDeviceSynchronize());
+    PfbDecResult res;
+    SCL_HIP_TRY(hipMemcpy(&res, d_res.p, sizeof(res), hipMemcpyDeviceToHost));
+    *n_out = res.n_out;
+    *consumed = res.consumed;
+    *status = res.status;
+    if (res.n_out && (res.status == 0 || partial)) SCL_HIP_TRY(hipMemcpy(h_out, d_out.p, res.n_out * val_bytes, hipMemcpyDeviceToHost));
     return SCL_OK;
 }

@@ -13,19 +13,20 @@
 //          lzw_heads       one workgroup per field: the two headers and the Elias-delta counts, ORed in at any bit position
 //          lzw_tile_bits / lzw_scan_tiles / lzw_emit   as pfb_tile_bits / pfb_scan_tiles / pfb_encode_tile of
 //                          scl_prefix_block.hip over the seven sections at once -- the codewords of four fields, the residuals
-//                          of three -- with the tile emitter they share (pfb_emit_tile, scl_bit_block.h) from a section base
-//                          at any bit; a codeword tile takes {code, len} of bin(v), a residual tile (residual(v), log(v))
-//          lzw_tail        out_cap_bytes % 4 != 0: the bytes of the last, partial word
+//                          of three: a codeword tile takes {code, len} of bin(v), a residual tile (residual(v), log(v)), from
+//                          a section base at any bit.  lzw_tile_bits and lzw_emit are the ONE copy of those bodies
+//                          (pfb_tile_bits_body, pfb_encode_tile_body, scl_bit_block.h) over the value policy LzwEnc; the
+//                          last, partial word of out_cap_bytes % 4 != 0 is that header's pfb_encode_tail_kernel
 // decode   field by field (a field starts where the one before it ended, and the residuals' length is known only from the
 //          decoded bins); the host reads one small struct per field and two words per pass:
 //          lzw_dec_head    ONE workgroup: the headers, the Elias-delta counts (one lane: at most 256 codewords), the tree, a
 //                          2^9 lookup table and the node array in scratch; every fault of the one-lane decoder in its order
 //          lzw_sync / lzw_scan_groups / lzw_write   the self-synchronising scheme of scl_prefix_block.hip (Weissenberger &
 //                          Schmidt) from the ONE copy of its bodies (pfb_sync_body, pfb_scan_to_end, pfb_write_body and the
-//                          host's pass loop, scl_bit_block.h).  Owned here: the codeword policy LzwCode over the device-built
-//                          tree (a cut codeword and a missing child both end a walk as PFB_END_STATE), the section's bit
-//                          base, and the LZ77 one-lane decoder's verdict in lzw_scan_groups (a cut is SCL_ST_STATE,
-//                          SCL_ST_CAPACITY is decided at the leaf behind the cap)
+//                          host's pass loop pfb_decode_section, scl_bit_block.h).  Owned here: the codeword policy LzwCode over
+//                          the device-built tree (a cut codeword and a missing child both end a walk as PFB_END_STATE), the
+//                          section's bit base, and the LZ77 one-lane decoder's verdict in lzw_scan_groups (a cut is
+//                          SCL_ST_STATE, SCL_ST_CAPACITY is decided at the leaf behind the cap)
 //          lzw_resid_bits / lzw_resid_scan / lzw_resid   the bins become values: a 64-bit scan of the residual widths over
 //                          tiles of 4096 gives each value its bits; the one-lane decoder's step of 64 values decides where a
 //                          truncated section stops counting
@@ -201,50 +202,58 @@ __global__ void __launch_bounds__(PFB_THREADS) lzw_heads_kernel(LzwEncIn in, Lzw
     }
 }
 
-// the {bits, length} of the thread's PFB_PER_THREAD consecutive values of tile `block` of the seven sections
-__device__ __forceinline__ u32 lzw_load_tile(const LzwEncIn &in, const uint2 *s_enc, u32 block, u32 seq_tiles, u32 *section,
-                                             uint2 (&e)[PFB_PER_THREAD]) {
-    const u32 s = block < 6 * seq_tiles ? block / seq_tiles : 6u;
-    const u32 tile = s < 6 ? block - s * seq_tiles : block - 6 * seq_tiles;
-    const u64 first = (u64)tile * PFB_TILE + threadIdx.x * PFB_PER_THREAD;
-    *section = s;
-    u32 bits = 0;
-    if (s < 6) {
-        const u32 f = s >> 1;
-        const u32 *row = lzw_row(in, f);
-#pragma unroll
-        for (u32 j = 0; j < PFB_PER_THREAD; ++j) {
-            uint2 c = make_uint2(0u, 0u);
-            if (first + j < in.n_seq) {
-                u32 log, res;
-                const u32 b = lze_bin(row[first + j], in.o, &log, &res);
-                c = (s & 1u) ? make_uint2(res, log) : s_enc[f * LZE_FIELD_K + b];
-            }
-            e[j] = c;
-            bits += c.y;
-        }
-    } else {
-#pragma unroll
-        for (u32 j = 0; j < PFB_PER_THREAD; ++j) {
-            const uint2 c = first + j < in.n_lit ? s_enc[LZE_LIT_BASE + in.lit[first + j]] : make_uint2(0u, 0u);
-            e[j] = c;
-            bits += c.y;
-        }
+// the value policy of pfb_tile_bits_body / pfb_encode_tile_body: the code tables of lzw_layout, from scratch into LDS.  No
+// fault is raised here: lzw_hist found the values without a bin.
+struct LzwEnc {
+    const LzwEncIn &in;
+    const LzwEncScratch &sc;
+    u32 seq_tiles;
+    uint2 *s_enc;  // [LZE_SYMS]
+    u32 section;   // of the tile that codes() loaded
+    static constexpr bool kTables = true;
+    static constexpr u32 kFault = 0;
+
+    __device__ __forceinline__ void load() const {
+        for (u32 j = threadIdx.x; j < LZE_SYMS; j += PFB_THREADS) s_enc[j] = sc.enc[j];
     }
-    return bits;
-}
+    __device__ __forceinline__ u64 tile_base(u32 block) const { return sc.head->section_at[section] + sc.tile_bits[block]; }
+    // the {bits, length} of the thread's PFB_PER_THREAD consecutive values of tile `block` of the seven sections
+    __device__ __forceinline__ u32 codes(u32 block, uint2 (&e)[PFB_PER_THREAD], u32 &) {
+        const u32 s = block < 6 * seq_tiles ? block / seq_tiles : 6u;
+        const u32 tile = s < 6 ? block - s * seq_tiles : block - 6 * seq_tiles;
+        const u64 first = (u64)tile * PFB_TILE + threadIdx.x * PFB_PER_THREAD;
+        section = s;
+        u32 bits = 0;
+        if (s < 6) {
+            const u32 f = s >> 1;
+            const u32 *row = lzw_row(in, f);
+#pragma unroll
+            for (u32 j = 0; j < PFB_PER_THREAD; ++j) {
+                uint2 c = make_uint2(0u, 0u);
+                if (first + j < in.n_seq) {
+                    u32 log, res;
+                    const u32 b = lze_bin(row[first + j], in.o, &log, &res);
+                    c = (s & 1u) ? make_uint2(res, log) : s_enc[f * LZE_FIELD_K + b];
+                }
+                e[j] = c;
+                bits += c.y;
+            }
+        } else {
+#pragma unroll
+            for (u32 j = 0; j < PFB_PER_THREAD; ++j) {
+                const uint2 c = first + j < in.n_lit ? s_enc[LZE_LIT_BASE + in.lit[first + j]] : make_uint2(0u, 0u);
+                e[j] = c;
+                bits += c.y;
+            }
+        }
+        return bits;
+    }
+};
 
 __global__ void __launch_bounds__(PFB_THREADS, 4) lzw_tile_bits_kernel(LzwEncIn in, LzwEncScratch sc, u32 seq_tiles) {
     __shared__ uint2 s_enc[LZE_SYMS];
-    __shared__ u32 s_wave[PFB_THREADS / 64];
     if (!sc.head->tile.fits) return;  // (uniform: the whole grid leaves)
-    for (u32 j = threadIdx.x; j < LZE_SYMS; j += PFB_THREADS) s_enc[j] = sc.enc[j];
-    __syncthreads();
-    uint2 e[PFB_PER_THREAD];
-    u32 section, total;
-    const u32 bits = lzw_load_tile(in, s_enc, blockIdx.x, seq_tiles, &section, e);
-    (void)scl_block_scan_excl<u32, PFB_THREADS, SclScanSum>(bits, s_wave, &total);
-    if (threadIdx.x == 0) sc.tile_bits[blockIdx.x] = total;
+    pfb_tile_bits_body(LzwEnc{in, sc, seq_tiles, s_enc, 0u}, sc.tile_bits, (u32 *)nullptr);
 }
 
 // ONE workgroup: the tile sums of every section become the tile offsets inside it
@@ -259,21 +268,7 @@ __global__ void __launch_bounds__(PFB_SCAN_THREADS) lzw_scan_tiles_kernel(LzwEnc
 __global__ void __launch_bounds__(PFB_THREADS, 4) lzw_emit_kernel(LzwEncIn in, LzwEncScratch sc, u32 seq_tiles,
                                                                   u32 *__restrict__ out32, u64 tail_index) {
     __shared__ uint2 s_enc[LZE_SYMS];
-    __shared__ u32 s_wave[PFB_THREADS / 64];
-    __shared__ u32 s_words[PFB_TILE_WORDS];
-    if (!sc.head->tile.fits) return;  // a faulted stream stores nothing (uniform: the whole grid leaves)
-    for (u32 j = threadIdx.x; j < LZE_SYMS; j += PFB_THREADS) s_enc[j] = sc.enc[j];
-    for (u32 i = threadIdx.x; i < PFB_TILE_WORDS; i += PFB_THREADS) s_words[i] = 0;
-    __syncthreads();
-    uint2 e[PFB_PER_THREAD];
-    u32 section;
-    const u32 bits = lzw_load_tile(in, s_enc, blockIdx.x, seq_tiles, &section, e);
-    const u64 base = sc.head->section_at[section] + sc.tile_bits[blockIdx.x];
-    pfb_emit_tile(e, bits, base, s_words, s_wave, &sc.head->tile, out32, tail_index);
-}
-
-__global__ void lzw_tail_kernel(const LzwEncHead *__restrict__ head, u8 *__restrict__ out, u64 out_cap_bytes) {
-    pfb_store_tail(&head->tile, head->total_bits, out, out_cap_bytes);
+    pfb_encode_tile_body(LzwEnc{in, sc, seq_tiles, s_enc, 0u}, &sc.head->tile, out32, tail_index);
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------
@@ -585,9 +580,6 @@ __global__ void lzw_finish_kernel(LzwDecScratch sc, u32 sync_passes, scl_lz77_en
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-u64 lzw_tiles(u64 n) { return (n + PFB_TILE - 1) / PFB_TILE; }
-u64 lzw_groups(u64 nbits) { return ((nbits + PFB_SUB - 1) / PFB_SUB + PFB_THREADS - 1) / PFB_THREADS; }
-
 struct LzwEncLayout {
     u64 head, hist, enc, tile_bits, total;
 };
@@ -597,7 +589,7 @@ LzwEncLayout lzw_enc_layout(u64 n_seq, u64 n_lit) {
     l.head = c.take(sizeof(LzwEncHead));
     l.hist = c.take(LZE_SYMS * 4);
     l.enc = c.take(LZE_SYMS * 8);
-    l.tile_bits = c.take((6 * lzw_tiles(n_seq) + lzw_tiles(n_lit)) * 8);
+    l.tile_bits = c.take((6 * pfb_tiles(n_seq) + pfb_tiles(n_lit)) * 8);
     l.total = c.at;
     return l;
 }
@@ -606,14 +598,14 @@ struct LzwDecLayout {
     u64 state, lut, kids, leaf_sym, resid_bits, group_exit, group_count, group_end, sub, total;
 };
 LzwDecLayout lzw_dec_layout(u64 seq_cap, u64 in_nbits) {
-    const u64 g = lzw_groups(in_nbits);
+    const u64 g = pfb_groups(in_nbits);
     LzwDecLayout l;
     SclCarver c;
     l.state = c.take(sizeof(LzwDecState));
     l.lut = c.take(LZW_LUT_SIZE * 4);
     l.kids = c.take(2 * LZ_HUFF_MAX_K * 2);
     l.leaf_sym = c.take(LZ_HUFF_MAX_K * 2);
-    l.resid_bits = c.take(lzw_tiles(seq_cap) * 8);
+    l.resid_bits = c.take(pfb_tiles(seq_cap) * 8);
     l.group_exit = c.take(2 * g * 8);
     l.group_count = c.take(g * 8);
     l.group_end = c.take(g * 8);
@@ -667,7 +659,7 @@ extern "C" int scl_lz77_entropy_encode_wide(const scl_lz77_entropy_wide_encode_a
     const LzwEncIn in = {{a->d_lit_count, a->d_match_len, a->d_match_off}, a->d_literals, (u32)a->n_seq, (u32)a->n_lit,
                          a->binned_offset};
     SCL_HIP_TRY(hipMemsetAsync(p, 0, l.enc, st));  // the head and the histograms
-    const u64 seq_tiles = lzw_tiles(a->n_seq), lit_tiles = lzw_tiles(a->n_lit), n_tiles = 6 * seq_tiles + lit_tiles;
+    const u64 seq_tiles = pfb_tiles(a->n_seq), lit_tiles = pfb_tiles(a->n_lit), n_tiles = 6 * seq_tiles + lit_tiles;
     const u64 most = seq_tiles > lit_tiles ? seq_tiles : lit_tiles;
     const u32 hist_grid = (u32)(most * PFB_PER_THREAD < LZW_HIST_MAX_GRID ? (most ? most * PFB_PER_THREAD : 1) : LZW_HIST_MAX_GRID);
     hipLaunchKernelGGL(lzw_hist_kernel, dim3(hist_grid), dim3(PFB_THREADS), 0, st, in, sc);
@@ -687,7 +679,8 @@ extern "C" int scl_lz77_entropy_encode_wide(const scl_lz77_entropy_wide_encode_a
                                tail_index);
         }
         if (a->out_cap_bytes & 3)
-            hipLaunchKernelGGL(lzw_tail_kernel, dim3(1), dim3(1), 0, st, (const LzwEncHead *)sc.head, a->d_out, a->out_cap_bytes);
+            hipLaunchKernelGGL(pfb_encode_tail_kernel, dim3(1), dim3(1), 0, st, (const PfbEncScratch *)&sc.head->tile,
+                               (const u64 *)&sc.head->total_bits, a->d_out, a->out_cap_bytes);
     }
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
@@ -728,26 +721,26 @@ extern "C" int scl_lz77_entropy_decode_wide(const scl_lz77_entropy_wide_decode_a
         if (h.status) break;
         if (!h.go) continue;
         const u64 nbits = h.values_size, base_bit = a->in_bit_offset + h.values_at;
-        const u64 n_sub = (nbits + PFB_SUB - 1) / PFB_SUB, n_groups = lzw_groups(nbits);
         const u64 cap = f < 3 ? a->seq_cap : a->lit_cap;
-        const dim3 grid((u32)n_groups), block(PFB_THREADS);
-        const auto sync = [&](u32 pass) {
+        u32 *row = f == 0 ? a->d_lit_count : f == 1 ? a->d_match_len : a->d_match_off;
+        const dim3 block(PFB_THREADS);
+        const auto sync = [&](dim3 grid, u64 n_sub, u64 n_groups, u32 pass) {
             hipLaunchKernelGGL(lzw_sync_kernel, grid, block, 0, st, in, base_bit, nbits, n_sub, n_groups, sc, h.m, pass);
         };
-        if (int rc = pfb_run_sync_passes(sync, sc.state, n_groups, st, &sync_passes)) return rc;
-        hipLaunchKernelGGL(lzw_scan_groups_kernel, dim3(1), dim3(PFB_SCAN_THREADS), 0, st, sc, n_groups, cap, f);
-        if (f < 3) {
-            u32 *row = f == 0 ? a->d_lit_count : f == 1 ? a->d_match_len : a->d_match_off;
-            hipLaunchKernelGGL(lzw_write_kernel<u32>, grid, block, 0, st, in, base_bit, nbits, n_sub, sc, h.m, row, cap);
-            // a codeword has at least one bit: the section holds at most `nbits` values
-            const u64 n_tiles = lzw_tiles(cap < nbits ? cap : nbits);
-            if (n_tiles) {
-                hipLaunchKernelGGL(lzw_resid_bits_kernel, dim3((u32)n_tiles), block, 0, st, sc, (const u32 *)row, a->binned_offset, f);
-                hipLaunchKernelGGL(lzw_resid_scan_kernel, dim3(1), dim3(PFB_SCAN_THREADS), 0, st, sc, n_tiles);
-                hipLaunchKernelGGL(lzw_resid_kernel, dim3((u32)n_tiles), block, 0, st, in, sc, row, f);
-            }
-        } else {
-            hipLaunchKernelGGL(lzw_write_kernel<u8>, grid, block, 0, st, in, base_bit, nbits, n_sub, sc, h.m, a->d_literals, cap);
+        const auto scan = [&](u64 n_groups, u32) {
+            hipLaunchKernelGGL(lzw_scan_groups_kernel, dim3(1), dim3(PFB_SCAN_THREADS), 0, st, sc, n_groups, cap, f);
+        };
+        const auto write = [&](dim3 grid, u64 n_sub) {
+            if (f < 3) hipLaunchKernelGGL(lzw_write_kernel<u32>, grid, block, 0, st, in, base_bit, nbits, n_sub, sc, h.m, row, cap);
+            else hipLaunchKernelGGL(lzw_write_kernel<u8>, grid, block, 0, st, in, base_bit, nbits, n_sub, sc, h.m, a->d_literals, cap);
+        };
+        if (int rc = pfb_decode_section(nbits, sc.state, st, &sync_passes, sync, scan, write)) return rc;
+        // the bins become values.  A codeword has at least one bit: the section holds at most `nbits` values
+        const u64 n_tiles = f < 3 ? pfb_tiles(cap < nbits ? cap : nbits) : 0;
+        if (n_tiles) {
+            hipLaunchKernelGGL(lzw_resid_bits_kernel, dim3((u32)n_tiles), block, 0, st, sc, (const u32 *)row, a->binned_offset, f);
+            hipLaunchKernelGGL(lzw_resid_scan_kernel, dim3(1), dim3(PFB_SCAN_THREADS), 0, st, sc, n_tiles);
+            hipLaunchKernelGGL(lzw_resid_kernel, dim3((u32)n_tiles), block, 0, st, in, sc, row, f);
         }
         SCL_HIP_TRY(hipGetLastError());
     }

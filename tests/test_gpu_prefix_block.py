@@ -8,7 +8,7 @@ encoder tile."""
 import numpy as np
 import pytest
 
-from prefix_helpers import code_bits, encode_numpy, goldens, make_dist, stream_bits, table_case
+from prefix_helpers import code_bits, deep_chains, encode_numpy, goldens, make_dist, stream_bits, table_case
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -68,6 +68,9 @@ def table(name):
             case = table_case("random17")
             keep = [s for s in range(case.K) if s not in (2, 9, 16)]
             _tables[name] = Table(name, case.arr("code")[keep], case.arr("len")[keep], case.arr("probs")[keep])
+        elif name == "deep512":  # the incomplete 256-symbol table of test_gpu_prefix_limits.py, lengths 2 .. 32
+            code, length = deep_chains(512)
+            _tables[name] = Table(name, code, length, 2.0 ** -length.astype(np.float64))
         elif name == "fixed3":  # 8 symbols, all 3 bits: every guess is exact
             _tables[name] = Table(name, np.arange(8), np.full(8, 3), np.ones(8))
         elif name == "never":  # {0: "0", 1: "11", 2: "101", 3: "100"}
@@ -268,6 +271,69 @@ def test_encode_capacity_one_byte_short(name):
     assert (nbits, status & 0xFFFFFFFF) == (want_bits, ST_CAPACITY)  # the length it needs is still reported
 
 
+@pytest.mark.parametrize("name", ["random17", "random300"])
+def test_encode_symbol_outside_the_alphabet_and_capacity_at_once(name):
+    """both faults are reported, with the length needed, and no codeword is stored: the output holds the zeros the call lays
+    down (as far as the longest stream of n symbols reaches, the cap at the most) and the filler behind them"""
+    dev = device()
+    t = table(name)
+    rng = np.random.default_rng(12)
+    sym = t.draw(rng, 2 * t.tile + 9)
+    bad = sym.copy()
+    bad[2 * t.tile + 5] = t.K
+    sym[2 * t.tile + 5] = 0  # what the stream codes there
+    _, want_bits = encode_numpy(t.bits_of, sym)
+    cap = (want_bits + 7) // 8 - 1
+    zeroed = min(((len(sym) * t.max_len + 7) // 8 + 3) // 4 * 4, cap)
+    arena = Arena(cap + 8 + 4 * GUARD, dev)
+    out = arena.take(cap + 8, align=4)
+    meta = t.model.encode_block_into(sym_tensor(t, bad, dev), out, out_cap_bytes=cap)
+    torch.cuda.synchronize()
+    arena.check(f"{name}/symbol+capacity")
+    nbits, status = (int(v) for v in meta.cpu())
+    assert (nbits, status & 0xFFFFFFFF) == (want_bits, ST_SYMBOL | ST_CAPACITY)
+    raw = out.cpu().numpy()
+    assert not raw[:zeroed].any() and (raw[zeroed:] == FILL).all()
+
+
+def trimmed_to_byte_residues(ends, least):
+    """-> {r: n} for r = 1, 2, 3: the largest n > ``least`` whose first n codewords end in a stream of r mod 4 bytes"""
+    nbytes = (np.asarray(ends, np.int64) + 7) // 8
+    found = {}
+    for r in (1, 2, 3):
+        hits = np.nonzero(nbytes[least:] % 4 == r)[0]
+        assert hits.size, f"no prefix of {r} mod 4 bytes"
+        found[r] = least + int(hits[-1]) + 1
+    return found
+
+
+@pytest.mark.parametrize("name", ["random17", "random300"])
+def test_exact_fit_through_the_tail_word(name):
+    """out_cap_bytes = the stream's bytes, 1, 2 and 3 mod 4: the last word reaches the output through the tail kernel, byte
+    by byte, and the byte behind the cap stays; the decoder then reads the same bytes with in_size_bytes cutting its last
+    word (the byte-wise tail of its window)"""
+    dev = device()
+    t = table(name)
+    rng = np.random.default_rng(13)
+    sym = t.draw(rng, 2 * t.tile + 40)
+    for r, n in trimmed_to_byte_residues(np.cumsum(t.len[sym]), 2 * t.tile).items():
+        want, want_bits = encode_numpy(t.bits_of, sym[:n])
+        cap = (want_bits + 7) // 8
+        assert cap % 4 == r and want.size == cap
+        arena = Arena(cap + 4 * GUARD, dev)
+        out = arena.take(cap, align=4)  # the guard starts at the byte behind the cap
+        out.fill_(0x3C)
+        meta = t.model.encode_block_into(sym_tensor(t, sym[:n], dev), out, out_cap_bytes=cap)
+        torch.cuda.synchronize()
+        arena.check(f"{name}/fit{r}")
+        nbits, status = (int(v) for v in meta.cpu())
+        assert (nbits, status & 0xFFFFFFFF) == (want_bits, 0)
+        assert np.array_equal(out.cpu().numpy(), want)
+        assert out.numel() == cap
+        got = block_decode(t, out, 0, want_bits, n, f"{name}/fit{r}/decode")
+        assert got[1:4] == (n, want_bits, 0) and np.array_equal(got[0], sym[:n])
+
+
 # ---- 3. decode equals the one-lane decoder --------------------------------------------------------------------------------------
 def decode_targets(t):
     return [1, t.W - 1, t.W, t.W + 1, 3 * t.W + 77]
@@ -443,6 +509,48 @@ def test_damaged_streams_equal_the_one_lane_decoder(name):
         assert ST_STATE in statuses  # a complete tree has no missing child
     if t.max_len > 1:
         assert ST_TRUNCATED in statuses
+
+
+def test_host_decode_of_a_stream_that_ends_one_bit_into_a_word():
+    """decode_block_host stages the stream in a padded device buffer; a stream of 1 mod 32 bits leaves three bytes between
+    its end and the next word that the decoder's window loads.  Whatever they hold, the symbols, `consumed` and the error
+    are those of the one-lane scl_prefix_decode_host -- as coded, and cut inside the last codeword.  An incomplete table:
+    bits behind the stream could lead into a missing child."""
+    import ctypes as C
+
+    from stanford_compression_library_amd.backend import lib as _lib
+    from stanford_compression_library_amd.backend.models import PrefixModel
+
+    t = table("deep512")
+    assert sum(2.0 ** -t.len.astype(np.float64)) < 1  # incomplete
+    rng = np.random.default_rng(14)
+    sym = t.draw(rng, 2 * PrefixModel.BLOCK_PARALLEL_MIN)
+    ends = np.cumsum(t.len[sym])
+    n = int(np.nonzero((ends % 32 == 1) & (t.len[sym] >= 2))[0][-1]) + 1  # the longest prefix of 1 mod 32 bits
+    sym, ends = sym[:n], ends[:n]
+    packed, nbits = encode_numpy(t.bits_of, sym)
+    assert nbits % 32 == 1 and nbits - int(t.len[sym[-1]]) >= PrefixModel.BLOCK_PARALLEL_MIN * t.min_len
+
+    def call(name, nb):
+        out = np.zeros(nb // t.min_len, t.model.sym_dtype)
+        n_out, used = C.c_uint64(0), C.c_uint64(0)
+        rc = t.model._sym_fn(name)(t.model._h, _lib.u8_ptr(packed), nb, t.model._host_ptr(out), out.size, C.byref(n_out),
+                                   C.byref(used))
+        return rc, int(n_out.value), int(used.value), out[:n_out.value if rc == 0 else 0].astype(np.int64)
+
+    for nb, want in ((nbits, (0, n, nbits)), (nbits - 1, (_lib.E_CHUNK, n - 1, int(ends[-2])))):
+        block, lane = call("decode_block_host", nb), call("decode_host", nb)
+        assert block[:3] == lane[:3] == want, (nb, block[:3], lane[:3], want)
+        assert np.array_equal(block[3], lane[3]) and (block[0] or np.array_equal(block[3], sym))
+        host, used = None, None
+        try:
+            host, used = t.model.decode_host(packed, nb)  # the path the classes take: the block call at this size
+        except _lib.SclHipError as e:
+            assert e.code == want[0] and "TRUNCATED" in str(e)
+        if want[0] == 0:
+            assert used == nbits and np.array_equal(host, sym)
+        else:
+            assert host is None
 
 
 # ---- 6. 64-bit addressing ---------------------------------------------------------------------------------------------------------

@@ -372,6 +372,48 @@ def test_encode_refuses_without_storing(kind, M):
     assert block_encode(code, bad, nbytes + 64, f"{kind}{M}/size2")[1:] == (0, ST_SIZE)
 
 
+@pytest.mark.parametrize("kind,M", CODES, ids=CODE_IDS)
+def test_encode_size_and_capacity_at_once(kind, M):
+    """a value without a codeword of 32 bits in the last tile and five bytes of room: SIZE stops the coding, so nbits is 0
+    and the capacity is never looked at -- not CAPACITY, not both"""
+    code = UintCode(kind, M)
+    b, cutoff = golomb_params(M) if kind == "golomb" else (0, 0)
+    bad = draw(kind, M, 2 * TILE + 100, 4)
+    bad[-3] = {"universal": 1 << 16, "elias_delta": (1 << 24) - 1}.get(kind, (32 - b) * (M or 1))
+    raw, nbits, status = block_encode(code, bad, 5, f"{kind}{M}/size+capacity")
+    assert (nbits, status) == (0, ST_SIZE)
+    assert not raw[:5].any() and (raw[5:] == FILL).all()
+
+
+@pytest.mark.parametrize("kind,M", CODES, ids=CODE_IDS)
+def test_exact_fit_through_the_tail_word(kind, M):
+    """out_cap_bytes = the stream's bytes, 1, 2 and 3 mod 4: the last word reaches the output through the tail kernel, byte
+    by byte, and the byte behind the cap stays; the decoder then reads the same bytes with in_size_bytes cutting its last
+    word (the byte-wise tail of its window)"""
+    code = UintCode(kind, M)
+    dev = device()
+    values = draw(kind, M, 2 * TILE + 60, 8)
+    bits, ends = encode_bits(kind, M, values)
+    nbytes = (ends + 7) // 8
+    for r in (1, 2, 3):
+        hits = np.nonzero(nbytes[2 * TILE:] % 4 == r)[0]
+        assert hits.size, f"no prefix of {r} mod 4 bytes"
+        n = 2 * TILE + int(hits[-1]) + 1
+        nbits = int(ends[n - 1])
+        cap = (nbits + 7) // 8
+        assert cap % 4 == r
+        arena = Arena(cap + 4 * GUARD, dev)
+        out = arena.take(cap, align=4)  # the guard starts at the byte behind the cap
+        meta = code.encode_block_into(value_tensor(values[:n], dev), out, out_cap_bytes=cap)
+        torch.cuda.synchronize()
+        arena.check(f"{kind}{M}/fit{r}")
+        assert tuple(int(v) for v in meta.cpu()) == (nbits, 0)
+        assert np.array_equal(out.cpu().numpy(), pack(bits[:nbits]))
+        assert out.numel() == cap
+        got = block_decode(code, out, 0, nbits, n, f"{kind}{M}/fit{r}/decode")
+        assert got[1:4] == (n, nbits, 0) and np.array_equal(got[0], values[:n].astype(np.uint32))
+
+
 # ---- 6. scratch reused from a larger block ---------------------------------------------------------------------------------------
 def test_scratch_reused_from_a_larger_block():
     dev = device()
