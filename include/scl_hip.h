@@ -489,6 +489,70 @@ int scl_uint_fields_host(const scl_uint_code *code, uint32_t x, uint32_t *run, u
 int scl_uint_decode_wide_one_host(const scl_uint_code *code, const uint8_t *buf, uint64_t buf_bytes, uint64_t bit_pos,
                                   uint32_t rem, uint32_t *len, uint32_t *x);
 
+/* ---- fixed-width codes, batched: a stream across as many workgroups as it has tiles (scl_fixed.hip; added to ABI 8 as above)
+ * The data section of the reference's FixedBitwidthEncoder.encode_block (fixed_bitwidth_compressor.py): symbol index i of a
+ * stream of width w is the w bits [i * w, (i + 1) * w) of the stream, most significant first, stream bit b = bit 7 - b % 8 of
+ * byte b / 8; the unused bits of the last stored word are 0.  No table, no model, no scan: a ragged batch of streams, each with
+ * its own length n[c] < 2^32 (d_lens, or chunk_len for all), width h_widths[c] in 1..32 and alphabet size h_K[c] with
+ * 1 <= K <= 2^w.  h_widths and h_K are HOST arrays of n_chunks entries, uploaded by the call.  32 symbols are w words for
+ * every w, so a workgroup's tile of SCL_FIXED_TILE symbols is a whole number of stream words: the grid is (tiles of the
+ * longest stream) x (streams), workgroups past a stream's end leave at once, and one large stream fills the GPU by the same
+ * call.  Rows are uint8, uint16 (_u16) or uint32 (_u32) indices, strides in ELEMENTS; rows are read and written in 16-byte
+ * pieces, so row starts (pointer, stride * element size) are multiples of 16 bytes, as are slots.
+ *   scl_fixed_slot_bytes(n, w): the stream's whole words, rounded up to 16; 0 for w outside 1..32 or a stream of 2^32 bits
+ *           and more.
+ *   encode: stream c from bit 0 of slot c (bit_offset[c] = 8 * c * out_stride), nbits[c] = n * w (saturating at 2^32 - 1).
+ *           d_status[c]: SCL_ST_SYMBOL = an index >= K (coded as index 0); SCL_ST_CAPACITY = the stream's words need more than
+ *           out_stride bytes: nothing is stored, nbits[c] still reports n * w.  Nothing is stored at or past a slot's end
+ *           or past the stream's last word.
+ *   decode: stream c = the d_in_nbits[c] bits from ANY bit d_bit_offset[c] of d_in, d_lens[c] (or out_cap for all) symbols
+ *           asked for.  d_out_lens[c] = the whole symbols delivered, d_consumed[c] = their bits.  d_status[c]:
+ *           SCL_ST_TRUNCATED = n * w > in_nbits (or the bits reach past in_size_bytes): the whole symbols in front are
+ *           delivered; SCL_ST_SYMBOL = a decoded index >= K, stored as 0; SCL_ST_CAPACITY = n > out_cap: nothing is stored
+ *           past out_cap.  No byte at or past in_size_bytes is read.
+ *   d_status may not be null here: the call zeroes it and the kernels raise faults on it with atomics.
+ *   scl_fixed_kernel_names(sym_bytes, ...): the pair for rows of 1, 2 or 4 byte symbols, as rocprofv3 prints it.
+ * SCL_E_PARAM (message = the entry point's name + ':'), before any device call: a null pointer (d_lens may be null), a
+ * width outside 1..32, K = 0 or K > 2^w, a width above 8 / 16 through the uint8 / uint16 entry, a row or slot stride that is
+ * not a multiple of 16 bytes (out_stride positive, below 512 MiB) or a row stride below chunk_len / out_cap, d_sym / d_out / d_in / d_out_sym not 16-byte aligned,
+ * more than 2^31 - 1 workgroups. */
+#define SCL_FIXED_TILE 8192u /* symbols per workgroup: 256 lanes x 32 symbols */
+uint64_t scl_fixed_slot_bytes(uint64_t n_symbols, uint32_t width);
+int scl_fixed_encode_batch(const uint8_t *d_sym, uint64_t sym_stride, const uint32_t *d_lens, uint32_t chunk_len,
+                           const uint32_t *h_widths, const uint64_t *h_K, uint64_t n_chunks, uint8_t *d_out,
+                           uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits, uint32_t *d_status,
+                           void *stream);
+int scl_fixed_encode_batch_u16(const uint16_t *d_sym, uint64_t sym_stride, const uint32_t *d_lens, uint32_t chunk_len,
+                               const uint32_t *h_widths, const uint64_t *h_K, uint64_t n_chunks, uint8_t *d_out,
+                               uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits, uint32_t *d_status,
+                               void *stream);
+int scl_fixed_encode_batch_u32(const uint32_t *d_sym, uint64_t sym_stride, const uint32_t *d_lens, uint32_t chunk_len,
+                               const uint32_t *h_widths, const uint64_t *h_K, uint64_t n_chunks, uint8_t *d_out,
+                               uint64_t out_stride, uint64_t *d_out_bit_offset, uint32_t *d_out_nbits, uint32_t *d_status,
+                               void *stream);
+int scl_fixed_decode_batch(const uint8_t *d_in, uint64_t in_size_bytes, const uint64_t *d_bit_offset,
+                           const uint32_t *d_in_nbits, const uint32_t *d_lens, const uint32_t *h_widths, const uint64_t *h_K,
+                           uint64_t n_chunks, uint8_t *d_out_sym, uint64_t out_stride, uint32_t out_cap,
+                           uint32_t *d_out_lens, uint32_t *d_consumed, uint32_t *d_status, void *stream);
+int scl_fixed_decode_batch_u16(const uint8_t *d_in, uint64_t in_size_bytes, const uint64_t *d_bit_offset,
+                               const uint32_t *d_in_nbits, const uint32_t *d_lens, const uint32_t *h_widths,
+                               const uint64_t *h_K, uint64_t n_chunks, uint16_t *d_out_sym, uint64_t out_stride,
+                               uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed, uint32_t *d_status, void *stream);
+int scl_fixed_decode_batch_u32(const uint8_t *d_in, uint64_t in_size_bytes, const uint64_t *d_bit_offset,
+                               const uint32_t *d_in_nbits, const uint32_t *d_lens, const uint32_t *h_widths,
+                               const uint64_t *h_K, uint64_t n_chunks, uint32_t *d_out_sym, uint64_t out_stride,
+                               uint32_t out_cap, uint32_t *d_out_lens, uint32_t *d_consumed, uint32_t *d_status, void *stream);
+int scl_fixed_kernel_names(uint32_t sym_bytes, uint64_t n_chunks, char *enc, char *dec, uint64_t cap);
+/* one stream in host memory (uint32 indices): allocate, copy, run, synchronise.  *status = the stream's status word, reported
+   rather than turned into SCL_E_CHUNK.  encode: h_out receives the (nbits + 7) / 8 stream bytes for a status without
+   SCL_ST_CAPACITY (SCL_E_PARAM if out_cap_bytes is below them).  decode: the stream is the in_nbits bits from bit
+   in_bit_offset of h_in; h_out_idx receives the *n_out <= out_cap whole symbols in front of a fault. */
+int scl_fixed_encode_host(const uint32_t *h_idx, uint64_t n, uint32_t width, uint64_t K, uint8_t *h_out,
+                          uint64_t out_cap_bytes, uint64_t *nbits, uint32_t *status);
+int scl_fixed_decode_host(const uint8_t *h_in, uint64_t in_bit_offset, uint64_t in_nbits, uint64_t n, uint32_t width,
+                          uint64_t K, uint32_t *h_out_idx, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed,
+                          uint32_t *status);
+
 /* ---- LZ77: match index, greedy parse and sequence replay (scl_lz77.hip; added to ABI 8 as above) -----------------------
  * The LZ layer of the reference's LZ77 coder, for a batch of independent streams, one wavefront per stream:
  *   scl_lz77_parse_batch   <->  LZ77Encoder.lz77_parse_and_generate_sequences   scl/compressors/lz77.py:525-603

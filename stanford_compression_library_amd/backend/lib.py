@@ -21,6 +21,7 @@ ST_CAPACITY, ST_SYMBOL, ST_TRUNCATED, ST_STATE, ST_TOTAL, ST_SIZE = 0x1, 0x2, 0x
 MODEL_FIXED, MODEL_IID, MODEL_ORDERK = 0, 1, 2
 COMPACT_DENSE, COMPACT_FRAMED = 0, 1
 UINT_GOLOMB, UINT_UNIVERSAL, UINT_ELIAS_DELTA = 0, 1, 2
+FIXED_TILE = 8192  # SCL_FIXED_TILE: symbols a workgroup of the fixed-width kernels codes
 
 
 class SclHipError(RuntimeError):
@@ -228,6 +229,16 @@ _SIGNATURES = {
     "scl_uint_kernel_names": (_int, [C.POINTER(UintCodeStruct), _u64, C.c_char_p, C.c_char_p, _u64]),
     "scl_uint_fields_host": (_int, [C.POINTER(UintCodeStruct), _u32, _u32p, _u32p, _u32p]),
     "scl_uint_decode_wide_one_host": (_int, [C.POINTER(UintCodeStruct), _u8p, _u64, _u64, _u32, _u32p, _u32p]),
+    # fixed-width codes, batched (scl_fixed.hip): widths and alphabet sizes are host arrays
+    "scl_fixed_slot_bytes": (_u64, [_u64, _u32]),
+    **{f"scl_fixed_encode_batch{s}": (_int, [_vp, _u64, _vp, _u32, _u32p, _u64p, _u64, _vp, _u64, _vp, _vp, _vp, _vp])
+       for s in ("", "_u16", "_u32")},
+    **{f"scl_fixed_decode_batch{s}": (_int, [_vp, _u64, _vp, _vp, _vp, _u32p, _u64p, _u64, _vp, _u64, _u32, _vp, _vp, _vp,
+                                             _vp])
+       for s in ("", "_u16", "_u32")},
+    "scl_fixed_kernel_names": (_int, [_u32, _u64, C.c_char_p, C.c_char_p, _u64]),
+    "scl_fixed_encode_host": (_int, [_u32p, _u64, _u32, _u64, _u8p, _u64, _u64p, _u32p]),
+    "scl_fixed_decode_host": (_int, [_u8p, _u64, _u64, _u64, _u32, _u64, _u32p, _u64, _u64p, _u64p, _u32p]),
     # LZ77: match index, greedy parse, sequence replay (scl_lz77.hip)
     "scl_lz77_scratch_bytes": (_u64, [_u64, _u64]),
     "scl_lz77_parse_batch": (_int, [C.POINTER(Lz77ParseArgs), _vp]),
@@ -403,3 +414,7 @@ def u8_ptr(a: np.ndarray):
 
 def u32_ptr(a: np.ndarray):
     return a.ctypes.data_as(_u32p)
+
+
+def u64_ptr(a: np.ndarray):
+    return a.ctypes.data_as(_u64p)

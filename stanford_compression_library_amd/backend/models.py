@@ -817,6 +817,143 @@ class UintCode:
         return tuple(names)
 
 
+class FixedWidthCode:
+    """fixed-width codes of symbol indices: index ``i`` of a stream of width ``w`` is the stream's bits ``[i * w, (i + 1) * w)``
+    (csrc/scl_fixed.hip).  There is no table and no device handle, not even a parameter: every stream of a batch brings its own
+    width (1..32) and alphabet size ``K`` (1..2^w).  A stream is coded by as many workgroups as it has tiles of ``TILE``
+    symbols, so one call serves many small streams and one large one alike.  Rows are uint8, uint16 / int16 or uint32 / int32
+    indices; a width above 8 or 16 needs the wider rows."""
+
+    TILE = _lib.FIXED_TILE
+
+    def __init__(self):
+        self._L = _lib.load()
+
+    @staticmethod
+    def _suffix(t) -> str:
+        return {1: "", 2: "_u16", 4: "_u32"}[t.element_size()]
+
+    @staticmethod
+    def _is_rows(t) -> bool:
+        import torch
+
+        return (t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and
+                t.dtype in (torch.uint8, torch.int16, torch.uint16, torch.int32, torch.uint32))
+
+    @staticmethod
+    def _host_params(widths, K, n_chunks: int):
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(widths, dtype=np.uint32), (n_chunks,)))
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(K, dtype=np.uint64), (n_chunks,)))
+        return w, k
+
+    def slot_bytes(self, n_symbols: int, width: int) -> int:
+        """bytes of the slot of ``n_symbols`` indices of ``width`` bits: the stream's whole words, in pieces of 16 (0: refused)"""
+        return int(self._L.scl_fixed_slot_bytes(int(n_symbols), int(width)))
+
+    def alloc_encoded(self, n_chunks: int, chunk_len: int, device, out_stride: Optional[int] = None,
+                      width: int = 32) -> EncodedBatch:
+        import torch
+
+        stride = int(out_stride or self.slot_bytes(chunk_len, width))
+        return EncodedBatch(torch.empty(n_chunks * stride + 16, dtype=torch.uint8, device=device), stride,
+                            torch.empty(n_chunks, dtype=torch.int64, device=device),
+                            torch.empty(n_chunks, dtype=torch.int32, device=device),
+                            torch.empty(n_chunks, dtype=torch.int32, device=device), n_chunks)
+
+    def encode_batch(self, sym, lens, widths, K, out_stride: Optional[int] = None, stream=None,
+                     out: Optional[EncodedBatch] = None) -> EncodedBatch:
+        """sym: index rows [n_chunks, chunk_len] on the device (row starts on 16-byte boundaries).  lens: optional int32
+        [n_chunks] on the device.  widths, K: per stream, HOST arrays (or one number for all).  ``out_stride`` defaults to the
+        slot of ``chunk_len`` indices of the widest stream."""
+        import torch
+
+        assert self._is_rows(sym)
+        n_chunks, chunk_len = sym.shape
+        w, k = self._host_params(widths, K, n_chunks)
+        dev = sym.device
+        if out is None:
+            out = self.alloc_encoded(n_chunks, chunk_len, dev, out_stride, int(w.max()) if n_chunks else 1)
+        assert out.n_chunks == n_chunks and out.layout == "linear"
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        fn = getattr(self._L, "scl_fixed_encode_batch" + self._suffix(sym))
+        with torch.cuda.device(dev):
+            rc = fn(sym.data_ptr(), sym.stride(0), lens.data_ptr() if lens is not None else None, chunk_len,
+                    _lib.u32_ptr(w), _lib.u64_ptr(k), n_chunks, out.data.data_ptr(), out.stride, out.bit_offset.data_ptr(),
+                    out.nbits.data_ptr(), out.status.data_ptr(), st)
+        _lib.check(rc, "scl_fixed_encode_batch" + self._suffix(sym))
+        return out
+
+    def alloc_decoded(self, n_chunks: int, chunk_cap: int, device, dtype=None):
+        import torch
+
+        dtype = dtype or torch.int32
+        per16 = 16 // torch.empty(0, dtype=dtype).element_size()
+        out_stride = max((int(chunk_cap) + per16 - 1) // per16 * per16, per16)
+        return (torch.empty((n_chunks, out_stride), dtype=dtype, device=device),
+                torch.empty(n_chunks, dtype=torch.int32, device=device),
+                torch.empty(n_chunks, dtype=torch.int32, device=device),
+                torch.empty(n_chunks, dtype=torch.int32, device=device))
+
+    def decode_encoded(self, enc: EncodedBatch, lens, widths, K, chunk_cap: int, stream=None, out=None, dtype=None):
+        return self.decode_batch(enc.data, enc.bit_offset, enc.nbits, lens, widths, K, chunk_cap, stream=stream, out=out,
+                                 dtype=dtype)
+
+    def decode_batch(self, data, bit_offset, nbits, lens, widths, K, chunk_cap: int, stream=None, out=None, dtype=None):
+        """stream c = the ``nbits[c]`` bits from ANY bit ``bit_offset[c]`` of the uint8 device tensor ``data``; ``lens[c]`` (or
+        ``chunk_cap`` for all) indices are asked of it -> (indices [n_chunks, chunk_cap], lens int32, consumed int32, status
+        int32) on the device.  ``out`` reuses buffers from :meth:`alloc_decoded`, ``dtype`` chooses the rows of new ones."""
+        import torch
+
+        assert data.is_cuda and data.dtype == torch.uint8
+        n_chunks = int(bit_offset.numel())
+        w, k = self._host_params(widths, K, n_chunks)
+        dev = data.device
+        val, got, used, status = out if out is not None else self.alloc_decoded(n_chunks, chunk_cap, dev, dtype)
+        assert self._is_rows(val) and val.shape[1] >= chunk_cap
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        fn = getattr(self._L, "scl_fixed_decode_batch" + self._suffix(val))
+        with torch.cuda.device(dev):
+            rc = fn(data.data_ptr(), data.numel(), bit_offset.data_ptr(), nbits.data_ptr(),
+                    lens.data_ptr() if lens is not None else None, _lib.u32_ptr(w), _lib.u64_ptr(k), n_chunks,
+                    val.data_ptr(), val.stride(0), int(chunk_cap), got.data_ptr(), used.data_ptr(), status.data_ptr(), st)
+        _lib.check(rc, "scl_fixed_decode_batch" + self._suffix(val))
+        return val[:, :chunk_cap], got, used, status
+
+    # -- one stream, host memory -----------------------------------------------------------------------------------------
+    def encode_host(self, idx: np.ndarray, width: int, K: int):
+        """uint32 indices -> (packed MSB-first bytes, nbits, status)"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        cap = (idx.size * int(width) + 7) // 8 + 16
+        out = np.zeros(cap, dtype=np.uint8)
+        nbits, status = C.c_uint64(0), C.c_uint32(0)
+        rc = self._L.scl_fixed_encode_host(_lib.u32_ptr(idx), idx.size, int(width), int(K), _lib.u8_ptr(out), cap,
+                                           C.byref(nbits), C.byref(status))
+        _lib.check(rc, "scl_fixed_encode_host")
+        return out[: (nbits.value + 7) // 8], int(nbits.value), int(status.value)
+
+    def decode_host(self, packed: np.ndarray, bit_offset: int, nbits: int, n: int, width: int, K: int,
+                    out_cap: Optional[int] = None):
+        """``n`` indices from the ``nbits`` bits at bit ``bit_offset`` of the packed bytes -> (uint32 indices, consumed, status);
+        the whole indices in front of a fault are delivered"""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        if packed.size == 0:
+            packed = np.zeros(1, dtype=np.uint8)
+        assert int(bit_offset) + int(nbits) <= 8 * packed.size, "the stream's bits lie inside the packed bytes"
+        cap = int(n) if out_cap is None else int(out_cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        n_out, used, status = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        rc = self._L.scl_fixed_decode_host(_lib.u8_ptr(packed), int(bit_offset), int(nbits), int(n), int(width), int(K),
+                                           _lib.u32_ptr(out), cap, C.byref(n_out), C.byref(used), C.byref(status))
+        _lib.check(rc, "scl_fixed_decode_host")
+        return out[: n_out.value], int(used.value), int(status.value)
+
+    def kernel_names(self, n_chunks: int, sym_bytes: int = 1):
+        """(encode kernel, decode kernel) for rows of ``sym_bytes`` wide indices, as rocprofv3 prints them"""
+        enc, dec = C.create_string_buffer(160), C.create_string_buffer(160)
+        _lib.check(self._L.scl_fixed_kernel_names(int(sym_bytes), int(n_chunks), enc, dec, 160), "scl_fixed_kernel_names")
+        return enc.value.decode(), dec.value.decode()
+
+
 class AecModel(_DeviceModel):
     _prefix = "aec"
     _needs_scratch = True

@@ -24,6 +24,8 @@ __all__ = [
     "uint_to_bitarray",
     "bitarray_to_uint",
     "get_random_bitarray",
+    "float_to_bitarrays",
+    "bitarrays_to_float",
 ]
 
 
@@ -204,3 +206,18 @@ def bitarray_to_uint(bit_array: BitArray) -> int:
 def get_random_bitarray(size) -> BitArray:
     """``size`` random bits (reference scl/utils/bitarray_utils.py:41-42; unseeded there too)."""
     return BitArray._wrap(np.random.randint(0, 2, int(size)).astype(np.uint8))
+
+
+def float_to_bitarrays(x: float, max_precision: int):
+    """``x`` >= 0 -> (bits of its integer part, the first ``max_precision`` bits of its fraction), the fraction truncated:
+    ``int(frac * 2**max_precision)`` in double, the reference's arithmetic (scl/utils/bitarray_utils.py:45-68) -- Shannon and
+    Shannon-Fano-Elias codewords are these bits, so the rounding of that product is part of the code"""
+    whole = int(x)
+    frac = x - whole
+    scaled = int(frac * np.power(2, max_precision))
+    return uint_to_bitarray(whole), uint_to_bitarray(scaled, bit_width=max_precision)
+
+
+def bitarrays_to_float(uint_x_bitarray: BitArray, frac_x_bitarray: BitArray) -> float:
+    """the inverse of :func:`float_to_bitarrays` (reference scl/utils/bitarray_utils.py:71-88)"""
+    return bitarray_to_uint(uint_x_bitarray) + bitarray_to_uint(frac_x_bitarray) / np.power(2, len(frac_x_bitarray))
