@@ -1,12 +1,17 @@
 """Sliding-window LZ77 without a GPU: the bucket function, the restated rule against the reference's goldens, the wrong
-variants the goldens tell apart, the window class, the parameters the C ABI refuses, and a user's own match finder."""
+variants the goldens tell apart, the window class, the parameters the C ABI refuses, a user's own match finder, and the
+restated bucket index with the properties of the inputs that test_gpu_lz77_sliding_limits.py relies on."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from lz77_helpers import use_host_prefix_coder
-from lz77_sliding_helpers import (VARIANTS, bucket, case_params, golden_blocks, goldens, parse_restated, replay_restated)
+from lz77_helpers import edge_batch, ragged_batch, tiled_batch, use_host_prefix_coder
+from lz77_sliding_helpers import (LONG_LEAD, LONG_N, LONG_PARAMS, LONG_STEP, NO_KEY, ONE_STREAM_HL, ONE_STREAM_SEED, VARIANTS,
+                                  assert_index_equal, bits_of, bucket, buckets_restated, case_params, class_block,
+                                  golden_blocks, goldens, key_passes, long_batch, long_gaps, long_reference, long_stream,
+                                  parse_restated, replay_restated, sliding_index_restated, sliding_index_shape, sort_passes,
+                                  stream_passes)
 from stanford_compression_library_amd.backend import lib as backend_lib
 from stanford_compression_library_amd.backend import lz77 as dev
 from stanford_compression_library_amd.compressors.lz77 import LZ77StreamsDecoder
@@ -187,3 +192,150 @@ def test_a_users_match_finder_runs_the_host_loop_and_round_trips(monkeypatch):
         assert status == 0 and np.array_equal(back, data)
         history = np.concatenate([history, data])[-32:]
         assert enc.window.get_window_as_list() == history.tolist()
+
+
+# ---- the restated index and the inputs of test_gpu_lz77_sliding_limits.py -----------------------------------------------------
+BUCKET_SIZES = (1, 255, 256, 257, 65535, 65536, 65537, 1 << 24, (1 << 24) + 1, 1 << 31, (1 << 31) + 1, (1 << 32) - 1)
+
+
+def test_restated_sliding_scratch_layout_equals_the_library():
+    """pins the offsets the white-box index test reads at to sliding_scratch_layout"""
+    for N in (0, 1, 63, 64, 65, 40001, len(tiled_batch()["buf"])):
+        sh = sliding_index_shape(N)
+        assert sh.total == dev.sliding_scratch_bytes(N, 3), N
+        assert sh.key == dev.scratch_bytes(N, 3) and sh.key % 256 == 0 and sh.total - sh.key >= max(4 * N, 1)
+
+
+@pytest.mark.parametrize("hl", [1, 4, 8])
+def test_vectorised_buckets_equal_the_definition_the_interpreter_and_the_library(hl):
+    rng = np.random.default_rng(10 + hl)
+    n = 150
+    buf = rng.integers(0, 256, n + hl - 1).astype(np.uint8)
+    buf[40: 40 + 2 * hl], buf[70: 70 + 2 * hl] = 0, 255  # grams of one byte repeated
+    signed = [hash(tuple(buf[p: p + hl].tolist())) for p in range(n)]
+    assert min(signed) < 0 < max(signed)  # hashes that are negative as signed 64-bit numbers: the remainder is not C's
+    for m in BUCKET_SIZES:
+        got = buckets_restated(buf, hl, m)
+        assert got.shape == (n,) and got.dtype == np.int64
+        for p in range(n):
+            gram = buf[p: p + hl]
+            assert got[p] == signed[p] % m == bucket(gram.tolist(), m) == dev.sliding_bucket(gram, m), (p, m)
+    assert buckets_restated(buf[: hl - 1], hl, 7).size == 0
+
+
+def test_pass_counts_of_the_index_cases():
+    """key_passes and lz_stream_passes restated, at their edges; the white-box cases reach every total from 1 to 7, both
+    parities of the ping-pong, and all four key pass counts"""
+    assert [key_passes(m) for m in (1, 256, 257, 65536, 65537, 1 << 24, (1 << 24) + 1, (1 << 32) - 1)] == [1, 1, 2, 2, 3, 3, 4, 4]
+    assert [stream_passes(n) for n in (0, 1, 2, 255, 256, 257, 65535, 65536, 70000)] == [0, 0, 1, 1, 2, 2, 2, 3, 3]
+    from lz77_sliding_helpers import INDEX_CASES, index_batch
+
+    sizes = {name: len(index_batch(name)["windows"]) for name in {c[0] for c in INDEX_CASES}}
+    assert sizes == {"ragged": 130, "one": 1, "edge257": 257, "tiled": 70000}
+    for name, hl, m, W, passes in INDEX_CASES:
+        assert sort_passes(m, sizes[name]) == passes, (name, m)
+    assert {c[4] for c in INDEX_CASES} == {1, 2, 3, 4, 5, 6, 7}
+    assert {key_passes(c[2]) for c in INDEX_CASES} == {1, 2, 3, 4}
+    assert {m for _, _, m, _, _ in INDEX_CASES} >= {256, 257, 65536, 65537, 1 << 24, (1 << 24) + 1, (1 << 32) - 1}
+
+
+def test_index_comparison_names_the_stage_that_is_wrong():
+    """assert_index_equal against arrays with two entries exchanged (or one bit flipped), on either side: the message names
+    keys, sort, inverse or bitmap, and bitmap bits at and above N do not count"""
+    b = edge_batch(9)
+    N = len(b["buf"])
+    want = sliding_index_restated(b["buf"], b["win_off"], 3, 257, 60)
+    assert N % 64 and (want[0] == NO_KEY).any() and bits_of(want[3], N).any()
+    assert_index_equal(want, want, N)
+    for stage, word in enumerate(("keys", "sort", "inverse", "bitmap")):
+        wrong = [a.copy() for a in want]
+        if stage < 3:
+            i, j = 45, 60
+            assert wrong[stage][i] != wrong[stage][j]
+            wrong[stage][[i, j]] = wrong[stage][[j, i]]
+        else:
+            wrong[3][1] ^= np.uint64(1 << 7)
+        for got, expected in ((tuple(wrong), want), (want, tuple(wrong))):
+            with pytest.raises(AssertionError, match=f": {word}"):
+                assert_index_equal(got, expected, N, "case")
+    above = [a.copy() for a in want]
+    above[3][-1] |= np.uint64(1 << 63)
+    assert_index_equal(tuple(above), want, N)
+
+
+def test_one_stream_batch_puts_no_key_next_to_bucket_255():
+    """At m = 256 the sort reads one byte of the key and there is no stream-number pass: the lead, the tail and the last
+    hl - 1 positions of the stream (NO_KEY, low byte 0xFF) sort among the positions of bucket 255"""
+    b = edge_batch(1, ONE_STREAM_SEED)
+    N, (base, end) = len(b["buf"]), b["win_off"].tolist()
+    assert base == 40 and N == end + 40 and sort_passes(256, 1) == 1
+    key, order, rank, bitmap = sliding_index_restated(b["buf"], b["win_off"], ONE_STREAM_HL, 256, 60)
+    assert (key[:base] == NO_KEY).all() and (key[end - ONE_STREAM_HL + 1:] == NO_KEY).all()
+    assert (key[base: end - ONE_STREAM_HL + 1] != NO_KEY).all() and (key == 255).sum() >= 2
+    sorted_keys = key[order]
+    last = np.flatnonzero((sorted_keys & 255) == 255)
+    assert last.size == (key == 255).sum() + (key == NO_KEY).sum() and last[-1] == N - 1
+    mates = sorted_keys[last]
+    assert ((mates[1:] == 255) & (mates[:-1] == NO_KEY)).any() and ((mates[1:] == NO_KEY) & (mates[:-1] == 255)).any()
+    # the oldest position of bucket 255 has a lead byte in front of it in order[]: only the re-checks keep its bit clear
+    oldest = int(np.flatnonzero(key == 255)[0])
+    assert order[rank[oldest] - 1] < base and not bits_of(bitmap, N)[oldest]
+    # with all four key passes NO_KEY sorts behind every bucket, 0xFFFFFFFE included
+    big = sliding_index_restated(b["buf"], b["win_off"], ONE_STREAM_HL, (1 << 32) - 1, 60)
+    assert (big[0][big[1]][-int((big[0] == NO_KEY).sum()):] == NO_KEY).all()
+
+
+def test_tiled_and_ragged_batches_have_the_shapes_the_gpu_tests_name():
+    t = tiled_batch()
+    sh = sliding_index_shape(len(t["buf"]))
+    assert len(t["windows"]) >= 65536 and sh.n_scan_blocks > 256 and (t["ids"][1:] == t["ids"][:-1]).any()
+    r = ragged_batch()
+    assert len(r["windows"]) == 130 and any(r["start"]) and any(len(w) == 0 for w in r["windows"])
+    # m = 1: every position of a stream that has a gram is in the one bucket
+    key = sliding_index_restated(r["buf"], r["win_off"], 4, 1, 16)[0]
+    assert set(key.tolist()) == {0, NO_KEY}
+
+
+@pytest.mark.parametrize("between", [False, True])
+def test_long_stream_has_the_gaps_the_gpu_tests_walk(between):
+    """W = 0, m = 2^32 - 1: three literal runs of at least 3 * 4096 bytes, no bitmap bit inside them, a match behind each;
+    runs that start off a word boundary, and one whose match is the last position of the search range, in a word that the
+    `to & 63` mask cuts (neither nothing nor all but one bit)"""
+    p = LONG_PARAMS[0]
+    hl, m, C, W, lazy, mml = p
+    assert (m, W) == ((1 << 32) - 1, 0) and len(long_stream()) == LONG_N
+    gaps = long_gaps(long_reference(p)[0])
+    assert len(gaps) == 3 and all(run >= 3 * LONG_STEP for _, run in gaps)
+    b = long_batch(between)
+    s = 1 if between else 0
+    base = int(b["win_off"][s])
+    assert base == (1 + LONG_LEAD if between else 1) and base % 2 == 1 and np.array_equal(b["windows"][s], long_stream())
+    bits = bits_of(sliding_index_restated(b["buf"], b["win_off"], hl, m, W)[3], len(b["buf"]))
+    to = base + LONG_N - hl + 1  # the end of every search of this stream
+    behind = []
+    for at, run in gaps:
+        assert not bits[base + at: base + at + run].any()
+        nxt = base + at + run + int(np.argmax(bits[base + at + run: to]))
+        assert bits[nxt]
+        behind.append(nxt)
+    assert all((base + at) % 64 for at, _ in gaps)
+    assert (to & 63) not in (0, 63) and behind[-1] == to - 1 and behind[0] >> 6 != (to - 1) >> 6
+
+
+def test_long_stream_has_repeats_on_both_sides_of_the_window_and_colliding_buckets():
+    free, bound, colliding = (long_reference(p)[0] for p in LONG_PARAMS)
+    assert LONG_PARAMS[1][3] == 1000 and 1001 in free[:, 2] and free[:, 2].max() > 3 * LONG_STEP
+    taken = bound[bound[:, 1] > 0]
+    assert len(taken) >= 4 and taken[:, 2].max() == 1000 and len(taken) < (free[:, 1] > 0).sum()
+    assert len(long_gaps(bound)) >= 2
+    hl, m, C, W, lazy, mml = LONG_PARAMS[2]
+    b = long_batch(False)
+    bits = bits_of(sliding_index_restated(b["buf"], b["win_off"], hl, m, W)[3], len(b["buf"]))
+    assert m == 65536 and W < LONG_N and bits.sum() > 100 * (colliding[:, 1] > 0).sum() > 0
+
+
+def test_class_block_has_matches_inside_the_window_only():
+    history, block = class_block()
+    assert len(history) > 1000 and len(block) == 100000
+    seq, _ = parse_restated(np.concatenate([history[-1000:], block]), 1000, (4, 1000000, 64, 1, 4, 1000))
+    assert (seq[:, 1] > 0).sum() > 1000 and seq[:, 2].max() <= 1000 and seq[:, 2].max() > 900
