@@ -40,28 +40,37 @@ def default_seq_cap(block_len: int, min_match_length: int) -> int:
 
 
 # ---- one stream, host memory ---------------------------------------------------------------------------------------------
-def parse_host(window: np.ndarray, start: int, min_match_length: int, max_matches: int):
-    """window: uint8 array = history + block, the block starts at ``start``.
-    -> (literal_count, match_length, match_offset: uint32 arrays; literals: uint8 array)"""
+def _parse_host(entry: str, window, start: int, seq_cap, extra, device_first: bool):
+    """One host parse through the C call ``entry``, whose own parameters ``extra`` stand between ``start`` and the rows;
+    ``seq_cap(block_len)`` sizes the rows.  ``device_first``: ask for a device before anything else, else only once the
+    call has not refused a parameter (that is reported as such, device or not)."""
     L = _lib.load()
-    _lib.require_device()
+    if device_first:
+        _lib.require_device()
     window = np.ascontiguousarray(window, np.uint8)
     n, start = int(window.size), int(start)
-    cap = default_seq_cap(n - start, min_match_length)
+    cap = seq_cap(n - start)
     seq = np.zeros((3, cap), np.uint32)
     literals = np.zeros(max(n - start, 1), np.uint8)
     n_seq, n_lit = C.c_uint64(0), C.c_uint64(0)
-    rc = L.scl_lz77_parse_host(_lib.u8_ptr(window), n, start, int(min_match_length), int(max_matches), _lib.u32_ptr(seq[0]),
-                               _lib.u32_ptr(seq[1]), _lib.u32_ptr(seq[2]), cap, C.byref(n_seq), _lib.u8_ptr(literals),
-                               n - start, C.byref(n_lit))
-    _lib.check(rc, "scl_lz77_parse_host")
+    rc = getattr(L, entry)(_lib.u8_ptr(window), n, start, *extra, _lib.u32_ptr(seq[0]), _lib.u32_ptr(seq[1]),
+                           _lib.u32_ptr(seq[2]), cap, C.byref(n_seq), _lib.u8_ptr(literals), n - start, C.byref(n_lit))
+    if not device_first and rc != _lib.E_PARAM:
+        _lib.require_device()
+    _lib.check(rc, entry)
     k = n_seq.value
     return seq[0, :k].copy(), seq[1, :k].copy(), seq[2, :k].copy(), literals[: n_lit.value].copy()
 
 
-def replay_host(history: np.ndarray, literal_count, match_length, match_offset, literals) -> np.ndarray:
-    """-> the bytes the sequences and literals append to ``history`` (uint8 array).  A damaged sequence raises
-    ``SclHipError`` (SCL_E_CHUNK) naming the status."""
+def parse_host(window: np.ndarray, start: int, min_match_length: int, max_matches: int):
+    """window: uint8 array = history + block, the block starts at ``start``.
+    -> (literal_count, match_length, match_offset: uint32 arrays; literals: uint8 array)"""
+    return _parse_host("scl_lz77_parse_host", window, start, lambda block: default_seq_cap(block, min_match_length),
+                       (int(min_match_length), int(max_matches)), device_first=True)
+
+
+def _replay_host(entry: str, history, literal_count, match_length, match_offset, literals, extra):
+    """One host replay through the C call ``entry``, whose own parameters ``extra`` stand between the capacity and the rows"""
     L = _lib.load()
     _lib.require_device()
     lc, ml, mo = (np.ascontiguousarray(a, np.uint32) for a in (literal_count, match_length, match_offset))
@@ -74,10 +83,16 @@ def replay_host(history: np.ndarray, literal_count, match_length, match_offset, 
     buf = np.zeros(max(have + grow, 1), np.uint8)
     buf[:have] = history
     out_len = C.c_uint64(0)
-    rc = L.scl_lz77_replay_host(_lib.u8_ptr(buf), have, have + grow, _lib.u32_ptr(lc), _lib.u32_ptr(ml), _lib.u32_ptr(mo),
-                                int(lc.size), _lib.u8_ptr(literals), int(literals.size), C.byref(out_len))
-    _lib.check(rc, "scl_lz77_replay_host")
+    rc = getattr(L, entry)(_lib.u8_ptr(buf), have, have + grow, *extra, _lib.u32_ptr(lc), _lib.u32_ptr(ml),
+                           _lib.u32_ptr(mo), int(lc.size), _lib.u8_ptr(literals), int(literals.size), C.byref(out_len))
+    _lib.check(rc, entry)
     return buf[have: have + out_len.value]
+
+
+def replay_host(history: np.ndarray, literal_count, match_length, match_offset, literals) -> np.ndarray:
+    """-> the bytes the sequences and literals append to ``history`` (uint8 array).  A damaged sequence raises
+    ``SclHipError`` (SCL_E_CHUNK) naming the status."""
+    return _replay_host("scl_lz77_replay_host", history, literal_count, match_length, match_offset, literals, ())
 
 
 # ---- batches, device memory (torch tensors) --------------------------------------------------------------------------------
@@ -107,44 +122,79 @@ def _stream_handle(stream, device):
     return stream if stream is not None else torch.cuda.current_stream(device).cuda_stream
 
 
-def parse_batch(win, win_off, start, min_match_length: int, max_matches: int, seq_cap: int, scratch=None, stream=None,
-                out: Optional[ParsedBatch] = None, phases: int = 0) -> ParsedBatch:
-    """win: uint8 CUDA tensor (the windows back to back); win_off: int64 [n_streams + 1]; start: int32 [n_streams].
-    ``seq_cap``: entries per row (``default_seq_cap`` of the longest block always suffices).  ``scratch``: a uint8 tensor of
-    ``scratch_bytes(win.numel(), n_streams)`` bytes to reuse across calls; ``phases``: 0 = index and parse,
-    ``lib.LZ77_INDEX`` / ``lib.LZ77_PARSE`` = one of them on the same scratch."""
+def _kernel_names(entry: str, count: int = 3):
+    """the ``count`` kernel names the C call ``entry`` writes, as a kernel trace prints them"""
+    bufs = [C.create_string_buffer(128) for _ in range(count)]
+    _lib.check(getattr(_lib.load(), entry)(*bufs, 128), entry)
+    return tuple(b.value.decode() for b in bufs)
+
+
+def _new_parsed(n_streams: int, seq_cap: int, lit_bytes: int, lit_off, dev) -> ParsedBatch:
+    """a fresh, zeroed :class:`ParsedBatch` of ``n_streams`` rows with ``lit_bytes`` bytes for the literals"""
+    import torch
+
+    rows = lambda: torch.zeros((n_streams, seq_cap), dtype=torch.int32, device=dev)  # noqa: E731
+    words = lambda: torch.zeros(n_streams, dtype=torch.int32, device=dev)  # noqa: E731
+    return ParsedBatch(rows(), rows(), rows(), torch.zeros(max(lit_bytes, 1), dtype=torch.uint8, device=dev), words(),
+                       words(), words(), lit_off, int(seq_cap))
+
+
+def _longest_block(win_off, start) -> int:
+    """the longest block of a batch: one read-back (uint32 values travel as int32 bit patterns)"""
+    import torch
+
+    lens = win_off[1:] - win_off[:-1] - start.to(torch.int64).bitwise_and(0xFFFFFFFF)
+    return max(int(lens.max().item()), 0) if start.numel() else 0
+
+
+def _parse_batch(entry: str, need_bytes, fill, win, win_off, start, seq_cap, scratch, stream, out):
+    """The parse of a batch through the C call ``entry``: ``need_bytes(total, n_streams)`` sizes the scratch,
+    ``fill(out, scratch, n_streams, total)`` makes the argument struct, and a ``seq_cap`` given as a function is called
+    with the longest block when neither ``out`` nor the caller brings a number"""
     import torch
 
     L = _lib.load()
     assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous()
     assert win_off.dtype == torch.int64 and start.dtype == torch.int32 and win_off.numel() == start.numel() + 1
     dev, n_streams, total = win.device, int(start.numel()), int(win.numel())
-    need = scratch_bytes(total, n_streams)
+    if out is not None:
+        seq_cap = out.seq_cap
+    if callable(seq_cap):
+        seq_cap = seq_cap(_longest_block(win_off, start))
+    need = need_bytes(total, n_streams)
     if scratch is None:
         scratch = torch.empty(need, dtype=torch.uint8, device=dev)
     assert scratch.numel() >= need
     if out is None:
-        rows = lambda: torch.zeros((n_streams, seq_cap), dtype=torch.int32, device=dev)  # noqa: E731
-        words = lambda: torch.zeros(n_streams, dtype=torch.int32, device=dev)  # noqa: E731
-        out = ParsedBatch(rows(), rows(), rows(), torch.zeros(max(total, 1), dtype=torch.uint8, device=dev), words(),
-                          words(), words(), win_off[:-1] + start.to(torch.int64), int(seq_cap))
-    a = _lib.Lz77ParseArgs(win.data_ptr(), win_off.data_ptr(), start.data_ptr(), n_streams, total, int(min_match_length),
-                           int(max_matches), out.seq_cap, int(phases), out.literal_count.data_ptr(),
-                           out.match_length.data_ptr(), out.match_offset.data_ptr(), out.literals.data_ptr(),
-                           out.n_seq.data_ptr(), out.n_lit.data_ptr(), out.status.data_ptr(), scratch.data_ptr(),
-                           int(scratch.numel()))
+        out = _new_parsed(n_streams, seq_cap, total, win_off[:-1] + start.to(torch.int64), dev)
+    a = fill(out, scratch, n_streams, total)
     with torch.cuda.device(dev):
-        rc = L.scl_lz77_parse_batch(C.byref(a), _stream_handle(stream, dev))
-    _lib.check(rc, "scl_lz77_parse_batch")
+        rc = getattr(L, entry)(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, entry)
     out._scratch = scratch  # the kernels read it asynchronously: it lives as long as the result
     return out
 
 
-def replay_batch(win, win_off, have, literal_count, match_length, match_offset, n_seq, literals, lit_off, n_lit,
-                 stream=None):
-    """Appends to the windows in place.  win: uint8 CUDA tensor of slots, slot s = [win_off[s], win_off[s + 1]) holding
-    ``have[s]`` bytes already; sequence rows as :class:`ParsedBatch`; stream s's ``n_lit[s]`` literals start at
-    ``literals[lit_off[s]]``.  -> (out_len, status): int32 [n_streams] each."""
+def parse_batch(win, win_off, start, min_match_length: int, max_matches: int, seq_cap: int, scratch=None, stream=None,
+                out: Optional[ParsedBatch] = None, phases: int = 0) -> ParsedBatch:
+    """win: uint8 CUDA tensor (the windows back to back); win_off: int64 [n_streams + 1]; start: int32 [n_streams].
+    ``seq_cap``: entries per row (``default_seq_cap`` of the longest block always suffices).  ``scratch``: a uint8 tensor of
+    ``scratch_bytes(win.numel(), n_streams)`` bytes to reuse across calls; ``phases``: 0 = index and parse,
+    ``lib.LZ77_INDEX`` / ``lib.LZ77_PARSE`` = one of them on the same scratch."""
+    def fill(out, scratch, n_streams, total):
+        return _lib.Lz77ParseArgs(win.data_ptr(), win_off.data_ptr(), start.data_ptr(), n_streams, total,
+                                  int(min_match_length), int(max_matches), out.seq_cap, int(phases),
+                                  out.literal_count.data_ptr(), out.match_length.data_ptr(), out.match_offset.data_ptr(),
+                                  out.literals.data_ptr(), out.n_seq.data_ptr(), out.n_lit.data_ptr(),
+                                  out.status.data_ptr(), scratch.data_ptr(), int(scratch.numel()))
+
+    return _parse_batch("scl_lz77_parse_batch", scratch_bytes, fill, win, win_off, start, seq_cap, scratch, stream, out)
+
+
+def _replay_batch(entry: str, args, window: int, win, win_off, have, literal_count, match_length, match_offset, n_seq,
+                  literals, lit_off, n_lit, stream):
+    """The replay of a batch through the C call ``entry``; ``args`` is its argument struct, whose seventh field takes
+    ``window``: the sliding-window coder's ``window_size``, 0 for the greedy one's ``reserved``"""
     import torch
 
     L = _lib.load()
@@ -157,14 +207,23 @@ def replay_batch(win, win_off, have, literal_count, match_length, match_offset, 
     assert match_length.shape == literal_count.shape == match_offset.shape and literal_count.shape[0] == n_streams
     out_len = torch.zeros(n_streams, dtype=torch.int32, device=dev)
     status = torch.zeros(n_streams, dtype=torch.int32, device=dev)
-    a = _lib.Lz77ReplayArgs(win.data_ptr(), win_off.data_ptr(), have.data_ptr(), n_streams, int(win.numel()),
-                            int(literal_count.shape[1]), 0, literal_count.data_ptr(), match_length.data_ptr(),
-                            match_offset.data_ptr(), n_seq.data_ptr(), literals.data_ptr(), int(literals.numel()),
-                            lit_off.data_ptr(), n_lit.data_ptr(), out_len.data_ptr(), status.data_ptr())
+    a = args(win.data_ptr(), win_off.data_ptr(), have.data_ptr(), n_streams, int(win.numel()), int(literal_count.shape[1]),
+             int(window), literal_count.data_ptr(), match_length.data_ptr(), match_offset.data_ptr(), n_seq.data_ptr(),
+             literals.data_ptr(), int(literals.numel()), lit_off.data_ptr(), n_lit.data_ptr(), out_len.data_ptr(),
+             status.data_ptr())
     with torch.cuda.device(dev):
-        rc = L.scl_lz77_replay_batch(C.byref(a), _stream_handle(stream, dev))
-    _lib.check(rc, "scl_lz77_replay_batch")
+        rc = getattr(L, entry)(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, entry)
     return out_len, status
+
+
+def replay_batch(win, win_off, have, literal_count, match_length, match_offset, n_seq, literals, lit_off, n_lit,
+                 stream=None):
+    """Appends to the windows in place.  win: uint8 CUDA tensor of slots, slot s = [win_off[s], win_off[s + 1]) holding
+    ``have[s]`` bytes already; sequence rows as :class:`ParsedBatch`; stream s's ``n_lit[s]`` literals start at
+    ``literals[lit_off[s]]``.  -> (out_len, status): int32 [n_streams] each."""
+    return _replay_batch("scl_lz77_replay_batch", _lib.Lz77ReplayArgs, 0, win, win_off, have, literal_count, match_length,
+                         match_offset, n_seq, literals, lit_off, n_lit, stream)
 
 
 # ---- one large stream across the whole GPU (csrc/scl_lz77_wide.hip) ------------------------------------------------------------
@@ -190,9 +249,7 @@ def wide_replay_scratch_bytes(n_seq: int, grow_bytes: int) -> int:
 
 def wide_kernel_names():
     """-> (score, walk, resolve) kernel names as a kernel trace prints them"""
-    bufs = [C.create_string_buffer(128) for _ in range(3)]
-    _lib.check(_lib.load().scl_lz77_wide_kernel_names(*bufs, 128), "scl_lz77_wide_kernel_names")
-    return tuple(b.value.decode() for b in bufs)
+    return _kernel_names("scl_lz77_wide_kernel_names")
 
 
 def parse_wide(win, start: int, min_match_length: int, max_matches: int, seq_cap: Optional[int] = None, scratch=None,
@@ -216,11 +273,8 @@ def parse_wide(win, start: int, min_match_length: int, max_matches: int, seq_cap
     if scratch is None:
         scratch = torch.empty(need, dtype=torch.uint8, device=dev)
     assert scratch.numel() >= need
-    rows = lambda: torch.zeros((1, seq_cap), dtype=torch.int32, device=dev)  # noqa: E731
-    words = lambda: torch.zeros(1, dtype=torch.int32, device=dev)  # noqa: E731
     if out is None:
-        out = ParsedBatch(rows(), rows(), rows(), torch.zeros(max(n, 1), dtype=torch.uint8, device=dev), words(), words(),
-                          words(), torch.full((1,), start, dtype=torch.int64, device=dev), int(seq_cap))
+        out = _new_parsed(1, seq_cap, n, torch.full((1,), start, dtype=torch.int64, device=dev), dev)
     assert out.literal_count.shape == (1, out.seq_cap) and out.literals.numel() >= n
     a = _lib.Lz77WideParseArgs(win.data_ptr(), n, start, int(min_match_length), int(max_matches), out.seq_cap, int(phases),
                                out.literal_count.data_ptr(), out.match_length.data_ptr(), out.match_offset.data_ptr(),
@@ -388,17 +442,36 @@ def compress_batch(win, win_off, start, min_match_length: int, max_matches: int,
     literals as bytes -- so the defaults cost ONE read-back, of the block lengths, before anything is launched; parse and
     encode then follow each other on ``stream`` without the host in between.  That stride is the worst case (about 3.5
     bytes per input byte at ``min_match_length`` 6); pass a smaller one where the data allows it."""
-    import torch
-
-    if seq_cap is None or out_stride is None:
-        lens = win_off[1:] - win_off[:-1] - start.to(torch.int64).bitwise_and(0xFFFFFFFF)
-        longest = max(int(lens.max().item()), 0) if start.numel() else 0
-        if seq_cap is None:
-            seq_cap = default_seq_cap(longest, min_match_length)
-        if out_stride is None:
-            out_stride = entropy_slot_bytes(seq_cap, longest, binned_offset)
+    seq_cap, out_stride = _default_caps(win_off, start, seq_cap, out_stride, binned_offset,
+                                        lambda longest: default_seq_cap(longest, min_match_length))
     parsed = parse_batch(win, win_off, start, min_match_length, max_matches, seq_cap, scratch=scratch, stream=stream)
     return encode_batch(parsed, binned_offset, out_stride, stream=stream), parsed
+
+
+def _default_caps(win_off, start, seq_cap, out_stride, binned_offset, seq_cap_of):
+    """``seq_cap`` and ``out_stride`` of a compress call with the missing ones filled in from the longest block"""
+    if seq_cap is None or out_stride is None:
+        longest = _longest_block(win_off, start)
+        if seq_cap is None:
+            seq_cap = seq_cap_of(longest)
+        if out_stride is None:
+            out_stride = entropy_slot_bytes(seq_cap, longest, binned_offset)
+    return seq_cap, out_stride
+
+
+def _decompress_batch(replay, bits, bit_offset, nbits, win, win_off, have, seq_cap, binned_offset, stream):
+    """decode + ``replay`` (``replay_batch`` or ``sliding_replay_batch`` with its window), the literals of stream s in the
+    room its slot has left"""
+    import torch
+
+    # (uint32 values travel as int32 bit patterns: masked on the way in, wrapped on the way out)
+    room = (win_off[1:] - win_off[:-1] - have.to(torch.int64).bitwise_and(0xFFFFFFFF)).clamp(min=0, max=0xFFFFFFFF)
+    lit_off = torch.cumsum(room, 0) - room
+    lit_cap = torch.where(room >= 1 << 31, room - (1 << 32), room).to(torch.int32)
+    decoded = decode_batch(bits, bit_offset, nbits, seq_cap, lit_off, lit_cap, binned_offset, stream=stream)
+    out_len, status = replay(win, win_off, have, decoded.literal_count, decoded.match_length, decoded.match_offset,
+                             decoded.n_seq, decoded.literals, lit_off, decoded.n_lit, stream=stream)
+    return out_len, status | decoded.status, decoded.consumed
 
 
 def decompress_batch(bits, bit_offset, nbits, win, win_off, have, seq_cap: int,
@@ -407,16 +480,7 @@ def decompress_batch(bits, bit_offset, nbits, win, win_off, have, seq_cap: int,
     holds ``have[s]`` bytes already (see :func:`replay_batch`).  A block has at most as many literals as bytes, so the
     room left in the slot bounds them.  -> (out_len, status, consumed): int32 [n_streams] each; status = the decoder's
     | the replay's (a stream the decoder faulted on replays what was decoded before the fault)."""
-    import torch
-
-    # (uint32 values travel as int32 bit patterns: masked on the way in, wrapped on the way out)
-    room = (win_off[1:] - win_off[:-1] - have.to(torch.int64).bitwise_and(0xFFFFFFFF)).clamp(min=0, max=0xFFFFFFFF)
-    lit_off = torch.cumsum(room, 0) - room
-    lit_cap = torch.where(room >= 1 << 31, room - (1 << 32), room).to(torch.int32)
-    decoded = decode_batch(bits, bit_offset, nbits, seq_cap, lit_off, lit_cap, binned_offset, stream=stream)
-    out_len, status = replay_batch(win, win_off, have, decoded.literal_count, decoded.match_length, decoded.match_offset,
-                                   decoded.n_seq, decoded.literals, lit_off, decoded.n_lit, stream=stream)
-    return out_len, status | decoded.status, decoded.consumed
+    return _decompress_batch(replay_batch, bits, bit_offset, nbits, win, win_off, have, seq_cap, binned_offset, stream)
 
 
 # ---- the entropy stage of one large stream across the whole GPU (csrc/scl_lz77_entropy_wide.hip) ----------------------------
@@ -434,9 +498,7 @@ def entropy_wide_scratch_bytes(n_seq: int, n_lit: int, in_nbits: int = 0) -> int
 
 def entropy_wide_kernel_names():
     """-> (emit, sync, resid) kernel names of the wide entropy stage as a kernel trace prints them"""
-    bufs = [C.create_string_buffer(128) for _ in range(3)]
-    _lib.check(_lib.load().scl_lz77_entropy_wide_kernel_names(*bufs, 128), "scl_lz77_entropy_wide_kernel_names")
-    return tuple(b.value.decode() for b in bufs)
+    return _kernel_names("scl_lz77_entropy_wide_kernel_names")
 
 
 def encode_wide(parsed: ParsedBatch, binned_offset: int = DEFAULT_BINNED_OFFSET, out_stride: Optional[int] = None,
@@ -555,9 +617,7 @@ def decompress_wide(bits, bit_offset: int, nbits: int, win, have: int, seq_cap: 
 
 def entropy_kernel_names():
     """-> (encode, decode) kernel names of the entropy stage as a kernel trace prints them"""
-    bufs = [C.create_string_buffer(128) for _ in range(2)]
-    _lib.check(_lib.load().scl_lz77_entropy_kernel_names(*bufs, 128), "scl_lz77_entropy_kernel_names")
-    return tuple(b.value.decode() for b in bufs)
+    return _kernel_names("scl_lz77_entropy_kernel_names", 2)
 
 
 def huffman_from_counts(counts):
@@ -574,9 +634,7 @@ def huffman_from_counts(counts):
 
 def kernel_names():
     """-> (index, parse, replay) kernel names as a kernel trace prints them"""
-    bufs = [C.create_string_buffer(128) for _ in range(3)]
-    _lib.check(_lib.load().scl_lz77_kernel_names(*bufs, 128), "scl_lz77_kernel_names")
-    return tuple(b.value.decode() for b in bufs)
+    return _kernel_names("scl_lz77_kernel_names")
 
 
 # ---- sliding window: hash-bucket index, lazy parse, windowed replay (csrc/scl_lz77_sliding.hip) -------------------------------
@@ -613,9 +671,7 @@ def sliding_scratch_bytes(total_bytes: int, n_streams: int) -> int:
 
 def sliding_kernel_names():
     """-> (index, parse, replay) kernel names of the sliding-window coder as a kernel trace prints them"""
-    bufs = [C.create_string_buffer(128) for _ in range(3)]
-    _lib.check(_lib.load().scl_lz77_sliding_kernel_names(*bufs, 128), "scl_lz77_sliding_kernel_names")
-    return tuple(b.value.decode() for b in bufs)
+    return _kernel_names("scl_lz77_sliding_kernel_names")
 
 
 def sliding_bucket(gram, hash_table_size: int) -> int:
@@ -630,47 +686,20 @@ def sliding_bucket(gram, hash_table_size: int) -> int:
 def sliding_parse_host(window: np.ndarray, start: int, params: SlidingParams = SlidingParams()):
     """``parse_host`` for the sliding-window coder (always one wavefront).  window: uint8 array = history + block, the block
     starts at ``start``.  -> (literal_count, match_length, match_offset: uint32 arrays; literals: uint8 array)"""
-    L = _lib.load()
-    window = np.ascontiguousarray(window, np.uint8)
-    n, start = int(window.size), int(start)
-    cap = sliding_seq_cap(n - start, params.min_match_length)
-    seq = np.zeros((3, cap), np.uint32)
-    literals = np.zeros(max(n - start, 1), np.uint8)
-    n_seq, n_lit = C.c_uint64(0), C.c_uint64(0)
+    _lib.load()
     hl, m, chain, lazy, mml, W = params._c()
     if not (0 <= hl < 1 << 32 and 0 <= m < 1 << 64 and 0 <= chain < 1 << 32 and 0 <= mml < 1 << 32 and 0 <= W < 1 << 32):
         raise ValueError("the sliding-window parameters are unsigned 32-bit integers (hash_table_size: 64-bit)")
-    rc = L.scl_lz77_sliding_parse_host(_lib.u8_ptr(window), n, start, hl, m, chain, lazy, mml, W, _lib.u32_ptr(seq[0]),
-                                       _lib.u32_ptr(seq[1]), _lib.u32_ptr(seq[2]), cap, C.byref(n_seq),
-                                       _lib.u8_ptr(literals), n - start, C.byref(n_lit))
-    if rc != _lib.E_PARAM:  # a refused parameter is reported as such, device or not
-        _lib.require_device()
-    _lib.check(rc, "scl_lz77_sliding_parse_host")
-    k = n_seq.value
-    return seq[0, :k].copy(), seq[1, :k].copy(), seq[2, :k].copy(), literals[: n_lit.value].copy()
+    return _parse_host("scl_lz77_sliding_parse_host", window, start, lambda block: sliding_seq_cap(block, mml),
+                       (hl, m, chain, lazy, mml, W), device_first=False)
 
 
 def sliding_replay_host(history: np.ndarray, literal_count, match_length, match_offset, literals,
                         window_size: int = 0) -> np.ndarray:
     """``replay_host`` with the window's rules: a sequence with match length 0 copies nothing, and an offset beyond
     ``min(window_size, bytes so far)`` raises ``SclHipError`` (``window_size`` 0: no bound)."""
-    L = _lib.load()
-    _lib.require_device()
-    lc, ml, mo = (np.ascontiguousarray(a, np.uint32) for a in (literal_count, match_length, match_offset))
-    literals = np.ascontiguousarray(literals, np.uint8)
-    history = np.asarray(history, np.uint8)
-    have = int(history.size)
-    grow = int(literals.size) + int(ml.astype(np.int64).sum())
-    if have + grow >= 1 << 32:
-        raise ValueError(f"a window of {have + grow} bytes: positions inside a stream are 32-bit")
-    buf = np.zeros(max(have + grow, 1), np.uint8)
-    buf[:have] = history
-    out_len = C.c_uint64(0)
-    rc = L.scl_lz77_sliding_replay_host(_lib.u8_ptr(buf), have, have + grow, int(window_size), _lib.u32_ptr(lc),
-                                        _lib.u32_ptr(ml), _lib.u32_ptr(mo), int(lc.size), _lib.u8_ptr(literals),
-                                        int(literals.size), C.byref(out_len))
-    _lib.check(rc, "scl_lz77_sliding_replay_host")
-    return buf[have: have + out_len.value]
+    return _replay_host("scl_lz77_sliding_replay_host", history, literal_count, match_length, match_offset, literals,
+                        (int(window_size),))
 
 
 def sliding_parse_batch(win, win_off, start, params: SlidingParams = SlidingParams(), seq_cap: Optional[int] = None,
@@ -678,78 +707,33 @@ def sliding_parse_batch(win, win_off, start, params: SlidingParams = SlidingPara
     """``parse_batch`` for the sliding-window coder: the same layout and the same :class:`ParsedBatch` (``encode_batch``
     takes it as it is).  ``seq_cap`` defaults to ``sliding_seq_cap`` of the longest block (one read-back of the block
     lengths); ``scratch``: a uint8 tensor of at least ``sliding_scratch_bytes(win.numel(), n_streams)`` bytes."""
-    import torch
+    def fill(out, scratch, n_streams, total):
+        hl, m, chain, lazy, mml, W = params._c()
+        return _lib.Lz77SlidingParseArgs(win.data_ptr(), win_off.data_ptr(), start.data_ptr(), n_streams, total, m, hl,
+                                         chain, lazy, mml, W, out.seq_cap, int(phases), 0, out.literal_count.data_ptr(),
+                                         out.match_length.data_ptr(), out.match_offset.data_ptr(),
+                                         out.literals.data_ptr(), out.n_seq.data_ptr(), out.n_lit.data_ptr(),
+                                         out.status.data_ptr(), scratch.data_ptr(), int(scratch.numel()))
 
-    L = _lib.load()
-    assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous()
-    assert win_off.dtype == torch.int64 and start.dtype == torch.int32 and win_off.numel() == start.numel() + 1
-    dev, n_streams, total = win.device, int(start.numel()), int(win.numel())
-    if out is not None:
-        seq_cap = out.seq_cap
     if seq_cap is None:
-        lens = win_off[1:] - win_off[:-1] - start.to(torch.int64).bitwise_and(0xFFFFFFFF)
-        seq_cap = sliding_seq_cap(max(int(lens.max().item()), 0) if n_streams else 0, params.min_match_length)
-    need = sliding_scratch_bytes(total, n_streams)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    assert scratch.numel() >= need
-    if out is None:
-        rows = lambda: torch.zeros((n_streams, seq_cap), dtype=torch.int32, device=dev)  # noqa: E731
-        words = lambda: torch.zeros(n_streams, dtype=torch.int32, device=dev)  # noqa: E731
-        out = ParsedBatch(rows(), rows(), rows(), torch.zeros(max(total, 1), dtype=torch.uint8, device=dev), words(),
-                          words(), words(), win_off[:-1] + start.to(torch.int64), int(seq_cap))
-    hl, m, chain, lazy, mml, W = params._c()
-    a = _lib.Lz77SlidingParseArgs(win.data_ptr(), win_off.data_ptr(), start.data_ptr(), n_streams, total, m, hl, chain, lazy,
-                                  mml, W, out.seq_cap, int(phases), 0, out.literal_count.data_ptr(),
-                                  out.match_length.data_ptr(), out.match_offset.data_ptr(), out.literals.data_ptr(),
-                                  out.n_seq.data_ptr(), out.n_lit.data_ptr(), out.status.data_ptr(), scratch.data_ptr(),
-                                  int(scratch.numel()))
-    with torch.cuda.device(dev):
-        rc = L.scl_lz77_sliding_parse_batch(C.byref(a), _stream_handle(stream, dev))
-    _lib.check(rc, "scl_lz77_sliding_parse_batch")
-    out._scratch = scratch  # the kernels read it asynchronously: it lives as long as the result
-    return out
+        seq_cap = lambda longest: sliding_seq_cap(longest, params.min_match_length)  # noqa: E731
+    return _parse_batch("scl_lz77_sliding_parse_batch", sliding_scratch_bytes, fill, win, win_off, start, seq_cap, scratch,
+                        stream, out)
 
 
 def sliding_replay_batch(win, win_off, have, literal_count, match_length, match_offset, n_seq, literals, lit_off, n_lit,
                          window_size: int = 0, stream=None):
     """``replay_batch`` with the window's rules (see :func:`sliding_replay_host`).  -> (out_len, status)"""
-    import torch
-
-    L = _lib.load()
-    assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous() and literals.dtype == torch.uint8
-    assert win_off.dtype == torch.int64 and lit_off.dtype == torch.int64
-    assert all(t.dtype == torch.int32 for t in (have, literal_count, match_length, match_offset, n_seq, n_lit))
-    dev, n_streams = win.device, int(have.numel())
-    assert win_off.numel() == n_streams + 1 and literal_count.dim() == 2 and literal_count.is_contiguous()
-    assert match_length.is_contiguous() and match_offset.is_contiguous()
-    assert match_length.shape == literal_count.shape == match_offset.shape and literal_count.shape[0] == n_streams
-    out_len = torch.zeros(n_streams, dtype=torch.int32, device=dev)
-    status = torch.zeros(n_streams, dtype=torch.int32, device=dev)
-    a = _lib.Lz77SlidingReplayArgs(win.data_ptr(), win_off.data_ptr(), have.data_ptr(), n_streams, int(win.numel()),
-                                   int(literal_count.shape[1]), int(window_size), literal_count.data_ptr(),
-                                   match_length.data_ptr(), match_offset.data_ptr(), n_seq.data_ptr(), literals.data_ptr(),
-                                   int(literals.numel()), lit_off.data_ptr(), n_lit.data_ptr(), out_len.data_ptr(),
-                                   status.data_ptr())
-    with torch.cuda.device(dev):
-        rc = L.scl_lz77_sliding_replay_batch(C.byref(a), _stream_handle(stream, dev))
-    _lib.check(rc, "scl_lz77_sliding_replay_batch")
-    return out_len, status
+    return _replay_batch("scl_lz77_sliding_replay_batch", _lib.Lz77SlidingReplayArgs, window_size, win, win_off, have,
+                         literal_count, match_length, match_offset, n_seq, literals, lit_off, n_lit, stream)
 
 
 def sliding_compress_batch(win, win_off, start, params: SlidingParams = SlidingParams(), seq_cap: Optional[int] = None,
                            binned_offset: int = DEFAULT_BINNED_OFFSET, out_stride: Optional[int] = None, scratch=None,
                            stream=None):
     """``compress_batch`` for the sliding-window coder: parse + encode -> (:class:`EncodedBatch`, :class:`ParsedBatch`)"""
-    import torch
-
-    if seq_cap is None or out_stride is None:
-        lens = win_off[1:] - win_off[:-1] - start.to(torch.int64).bitwise_and(0xFFFFFFFF)
-        longest = max(int(lens.max().item()), 0) if start.numel() else 0
-        if seq_cap is None:
-            seq_cap = sliding_seq_cap(longest, params.min_match_length)
-        if out_stride is None:
-            out_stride = entropy_slot_bytes(seq_cap, longest, binned_offset)
+    seq_cap, out_stride = _default_caps(win_off, start, seq_cap, out_stride, binned_offset,
+                                        lambda longest: sliding_seq_cap(longest, params.min_match_length))
     parsed = sliding_parse_batch(win, win_off, start, params, seq_cap, scratch=scratch, stream=stream)
     return encode_batch(parsed, binned_offset, out_stride, stream=stream), parsed
 
@@ -757,13 +741,5 @@ def sliding_compress_batch(win, win_off, start, params: SlidingParams = SlidingP
 def sliding_decompress_batch(bits, bit_offset, nbits, win, win_off, have, seq_cap: int, window_size: int = 0,
                              binned_offset: int = DEFAULT_BINNED_OFFSET, stream=None):
     """``decompress_batch`` for the sliding-window coder: decode + windowed replay -> (out_len, status, consumed)"""
-    import torch
-
-    room = (win_off[1:] - win_off[:-1] - have.to(torch.int64).bitwise_and(0xFFFFFFFF)).clamp(min=0, max=0xFFFFFFFF)
-    lit_off = torch.cumsum(room, 0) - room
-    lit_cap = torch.where(room >= 1 << 31, room - (1 << 32), room).to(torch.int32)
-    decoded = decode_batch(bits, bit_offset, nbits, seq_cap, lit_off, lit_cap, binned_offset, stream=stream)
-    out_len, status = sliding_replay_batch(win, win_off, have, decoded.literal_count, decoded.match_length,
-                                           decoded.match_offset, decoded.n_seq, decoded.literals, lit_off, decoded.n_lit,
-                                           window_size, stream=stream)
-    return out_len, status | decoded.status, decoded.consumed
+    replay = lambda *rows, stream: sliding_replay_batch(*rows, window_size, stream=stream)  # noqa: E731
+    return _decompress_batch(replay, bits, bit_offset, nbits, win, win_off, have, seq_cap, binned_offset, stream)

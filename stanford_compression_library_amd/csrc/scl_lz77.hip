@@ -11,8 +11,8 @@
 //           candidates 64 at a time (lane j = the j-th most recent), longest wins, lowest lane on ties.
 // One LARGE stream has kernels of its own, scl_lz77_wide.hip; the *_host calls below choose.  The device code they share --
 // and share with the sliding-window coder, scl_lz77_sliding.hip: the sort's histogram and scatter kernels, templates on
-// the digit source, and the replay's copy loop -- is in scl_lz77_internal.h; the scans of the sort are here, behind
-// lz77_scan_exclusive.
+// the digit source, the replay kernels' body, the entry points' checks and the frame of the *_host calls -- is in
+// scl_lz77_internal.h; the scans of the sort are here, behind lz77_scan_exclusive.
 // No workgroup waits on another (every dependency between workgroups is a kernel boundary), every loop is bounded by the
 // data, and reads and writes are checked against the buffers' sizes on any input.
 #include "scl_lz77_internal.h"
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_parse(const u8 *win, u
                                                                 u32 seq_cap, u32 *lit_count, u32 *match_len,
                                                                 u32 *match_off, u8 *literals, u32 *n_seq_out,
                                                                 u32 *n_lit_out, u32 *status_out) {
-    const u32 s = blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE;
+    const u32 s = lz_wave_stream();
     if (s >= n_streams) return;
     const u32 lane = lz_lane();
     const u64 base = win_off[s], end = win_off[s + 1];
@@ -149,33 +149,16 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_parse(const u8 *win, u
 }
 
 // ---- replay ----------------------------------------------------------------------------------------------------------
-// One wavefront per stream appends to the stream's window: lz_replay_stream (scl_lz77_internal.h).  `win` is deliberately
-// neither const nor __restrict__, see there.
+// One wavefront per stream appends to the stream's window: lz_replay_frame (scl_lz77_internal.h).  `win` is deliberately
+// neither const nor __restrict__, see lz_replay_stream there.
 __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_replay(u8 *win, u64 N, const u64 *win_off, const u32 *have_in,
                                                                  u32 n_streams, u32 seq_cap, const u32 *lit_count,
                                                                  const u32 *match_len, const u32 *match_off,
                                                                  const u32 *n_seq_in, const u8 *literals, u64 lit_bytes,
                                                                  const u64 *lit_off, const u32 *n_lit_in, u32 *out_len,
                                                                  u32 *status_out) {
-    const u32 s = blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE;
-    if (s >= n_streams) return;
-    const u32 lane = lz_lane();
-    const u64 base = win_off[s], end = win_off[s + 1];
-    const u32 have = have_in[s], n_seq = n_seq_in[s], n_lit = n_lit_in[s];
-    const u64 l_at = lit_off[s];
-    u32 status = 0, d = have;
-    if (base > end || end > N || end - base >= (1ull << 32) || have > end - base || n_seq > seq_cap ||
-        l_at > lit_bytes || n_lit > lit_bytes - l_at) {
-        status = SCL_ST_SIZE;
-    } else {
-        const u32 *lc = lit_count + (u64)s * seq_cap, *ml = match_len + (u64)s * seq_cap,
-                  *mo = match_off + (u64)s * seq_cap;
-        status = lz_replay_stream<false>(win + base, (u32)(end - base), &d, lc, ml, mo, n_seq, literals + l_at, n_lit, 0);
-    }
-    if (lane == 0) {
-        out_len[s] = d - have;
-        status_out[s] = status;
-    }
+    lz_replay_frame<false>(win, N, win_off, have_in, n_streams, seq_cap, 0, lit_count, match_len, match_off, n_seq_in,
+                           literals, lit_bytes, lit_off, n_lit_in, out_len, status_out);
 }
 
 }  // namespace
@@ -206,74 +189,41 @@ extern "C" int scl_lz77_kernel_names(char *index, char *parse, char *replay, uin
 
 extern "C" int scl_lz77_parse_batch(const scl_lz77_parse_args *a, void *stream) {
     const char *what = "lz77_parse_batch";
-    SCL_REQUIRE(a, "%s: null pointer argument", what);
-    SCL_REQUIRE(a->d_win_off && a->d_start && a->d_n_seq && a->d_n_lit && a->d_status && a->d_scratch &&
-                    (a->total_bytes == 0 || (a->d_win && a->d_literals)) &&
-                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
-                "%s: null pointer argument", what);
-    SCL_REQUIRE(a->min_match_length >= 1 && a->min_match_length <= 8,
-                "%s: min_match_length %u: an L-gram is one 64-bit key, 1 <= L <= 8", what, a->min_match_length);
-    SCL_REQUIRE(a->total_bytes < (1ull << 32) && a->n_streams < (1ull << 32),
-                "%s: a batch holds less than 2^32 bytes and 2^32 streams", what);
-    SCL_REQUIRE(a->phases <= 3, "%s: phases is a mask of SCL_LZ77_INDEX | SCL_LZ77_PARSE", what);
-    const Lz77Scratch lay = lz77_scratch_layout(a->total_bytes);
-    SCL_REQUIRE(((uintptr_t)a->d_scratch & 255) == 0 && a->scratch_bytes >= lay.total,
-                "%s: d_scratch must be 256-byte aligned and hold scl_lz77_scratch_bytes = %llu bytes", what,
-                (unsigned long long)lay.total);
+    const auto params = [&]() -> int {
+        SCL_REQUIRE(a->min_match_length >= 1 && a->min_match_length <= 8,
+                    "%s: min_match_length %u: an L-gram is one 64-bit key, 1 <= L <= 8", what, a->min_match_length);
+        return SCL_OK;
+    };
+    if (int rc = lz77_parse_check(what, a, params, scl_lz77_scratch_bytes, "scl_lz77_scratch_bytes")) return rc;
     if (a->n_streams == 0) return SCL_OK;
     hipStream_t st = (hipStream_t)stream;
     const u64 N = a->total_bytes;
     const u32 L = a->min_match_length, n_streams = (u32)a->n_streams;
-    u8 *scr = (u8 *)a->d_scratch;
-    u32 *order_a = (u32 *)(scr + lay.order_a), *order_b = (u32 *)(scr + lay.order_b), *rank = (u32 *)(scr + lay.rank);
-    u64 *bitmap = (u64 *)(scr + lay.bitmap);
-    u32 *hist = (u32 *)(scr + lay.hist), *sums = (u32 *)(scr + lay.block_sums);
+    const Lz77Scratch lay = lz77_scratch_layout(N);
+    const Lz77ScratchPtrs p = lz77_scratch_carve(a->d_scratch, lay);
     const u32 phases = a->phases ? a->phases : 3u;
     const u32 passes = L + lz_stream_passes(a->n_streams);
     if ((phases & SCL_LZ77_INDEX) && N) {
-        lz77_sort_positions(LzGramDigit{a->d_win, N, a->d_win_off, n_streams, L}, N, passes, lay, order_a, order_b, rank,
-                            hist, sums, st);
+        lz77_sort_positions(LzGramDigit{a->d_win, N, a->d_win_off, n_streams, L}, N, passes, lay, p, st);
         hipLaunchKernelGGL(lz77_candidate_bitmap, dim3((u32)((N + 255) / 256)), dim3(256), 0, st, a->d_win, N,
-                           a->d_win_off, n_streams, L, order_a, rank, bitmap);
+                           a->d_win_off, n_streams, L, p.order_a, p.rank, p.bitmap);
     }
     if (phases & SCL_LZ77_PARSE) {
         const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
         hipLaunchKernelGGL(lz77_parse, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, st, a->d_win, N, a->d_win_off,
-                           a->d_start, n_streams, L, a->max_matches, order_a, rank, bitmap, a->seq_cap, a->d_lit_count,
-                           a->d_match_len, a->d_match_off, a->d_literals, a->d_n_seq, a->d_n_lit, a->d_status);
+                           a->d_start, n_streams, L, a->max_matches, p.order_a, p.rank, p.bitmap, a->seq_cap,
+                           a->d_lit_count, a->d_match_len, a->d_match_off, a->d_literals, a->d_n_seq, a->d_n_lit,
+                           a->d_status);
     }
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
 }
 
 extern "C" int scl_lz77_replay_batch(const scl_lz77_replay_args *a, void *stream) {
-    const char *what = "lz77_replay_batch";
-    SCL_REQUIRE(a, "%s: null pointer argument", what);
-    SCL_REQUIRE(a->d_win_off && a->d_have && a->d_n_seq && a->d_lit_off && a->d_n_lit && a->d_out_len && a->d_status &&
-                    (a->total_bytes == 0 || a->d_win) && (a->lit_bytes == 0 || a->d_literals) &&
-                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
-                "%s: null pointer argument", what);
-    SCL_REQUIRE(a->n_streams < (1ull << 32), "%s: a batch holds less than 2^32 streams", what);
-    if (a->n_streams == 0) return SCL_OK;
-    const u32 n_streams = (u32)a->n_streams;
-    const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
-    hipLaunchKernelGGL(lz77_replay, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, (hipStream_t)stream, a->d_win,
-                       a->total_bytes, a->d_win_off, a->d_have, n_streams, a->seq_cap, a->d_lit_count, a->d_match_len,
-                       a->d_match_off, a->d_n_seq, a->d_literals, a->lit_bytes, a->d_lit_off, a->d_n_lit, a->d_out_len,
-                       a->d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return lz77_replay_launch("lz77_replay_batch", a, stream, lz77_replay);  // `reserved` is not a window: none is passed
 }
 
-// ---- one stream in host memory -----------------------------------------------------------------------------------------
-namespace {
-struct LzMeta {  // the small per-stream words of a batch of one, in one allocation
-    u64 win_off[2];
-    u64 lit_off;
-    u32 start, n_seq, n_lit, status, have, out_len;
-};
-}  // namespace
-
+// ---- one stream in host memory (LzHostFrame, scl_lz77_internal.h) -------------------------------------------------------
 extern "C" int scl_lz77_parse_host(const uint8_t *h_window, uint64_t n, uint64_t start, uint32_t min_match_length,
                                    uint32_t max_matches, uint32_t *h_lit_count, uint32_t *h_match_len,
                                    uint32_t *h_match_off, uint64_t seq_cap, uint64_t *n_seq, uint8_t *h_literals,
@@ -290,35 +240,12 @@ extern "C" int scl_lz77_parse_host(const uint8_t *h_window, uint64_t n, uint64_t
     // a large block goes across the whole GPU (scl_lz77_wide.hip); the results are the same either way
     const bool wide = n - start >= scl_lz77_wide_threshold() && max_matches >= 1 && max_matches <= 64;
     const u64 scratch_bytes = wide ? scl_lz77_wide_scratch_bytes(n) : scl_lz77_scratch_bytes(n, 1);
-    ScratchDev d_win, d_lit, d_seq, d_meta, d_scr;
-    int rc;
-    if ((rc = d_win.alloc(n)) || (rc = d_lit.alloc(n)) || (rc = d_seq.alloc(3 * seq_cap * 4)) ||
-        (rc = d_meta.alloc(sizeof(LzMeta))) || (rc = d_scr.alloc(scratch_bytes)))
-        return rc;
-    LzMeta meta = {};
-    meta.win_off[1] = n;
-    meta.start = (u32)start;
-    if (n) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, n, hipMemcpyHostToDevice));
-    SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
-    LzMeta *dm = (LzMeta *)d_meta.p;
+    LzHostFrame f;
     scl_lz77_parse_args a = {};
-    a.d_win = (const u8 *)d_win.p;
-    a.d_win_off = dm->win_off;
-    a.d_start = &dm->start;
-    a.n_streams = 1;
-    a.total_bytes = n;
+    int rc = f.parse_open(a, h_window, n, start, seq_cap, scratch_bytes);
+    if (rc) return rc;
     a.min_match_length = min_match_length;
     a.max_matches = max_matches;
-    a.seq_cap = (u32)seq_cap;
-    a.d_lit_count = (u32 *)d_seq.p;
-    a.d_match_len = a.d_lit_count + seq_cap;
-    a.d_match_off = a.d_match_len + seq_cap;
-    a.d_literals = (u8 *)d_lit.p;
-    a.d_n_seq = &dm->n_seq;
-    a.d_n_lit = &dm->n_lit;
-    a.d_status = &dm->status;
-    a.d_scratch = d_scr.p;
-    a.scratch_bytes = scratch_bytes;
     if (wide) {
         scl_lz77_wide_parse_args w = {};
         w.d_win = a.d_win;
@@ -340,19 +267,7 @@ extern "C" int scl_lz77_parse_host(const uint8_t *h_window, uint64_t n, uint64_t
     } else {
         rc = scl_lz77_parse_batch(&a, nullptr);
     }
-    if (rc) return rc;
-    SCL_HIP_TRY(hipDeviceSynchronize());
-    SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
-    *n_seq = meta.n_seq;
-    *n_lit = meta.n_lit;
-    if (meta.status) return scl_status_to_error(meta.status, what);
-    if (meta.n_seq) {
-        SCL_HIP_TRY(hipMemcpy(h_lit_count, a.d_lit_count, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
-        SCL_HIP_TRY(hipMemcpy(h_match_len, a.d_match_len, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
-        SCL_HIP_TRY(hipMemcpy(h_match_off, a.d_match_off, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
-    }
-    if (meta.n_lit) SCL_HIP_TRY(hipMemcpy(h_literals, a.d_literals + start, meta.n_lit, hipMemcpyDeviceToHost));
-    return SCL_OK;
+    return rc ? rc : f.parse_close(what, start, h_lit_count, h_match_len, h_match_off, n_seq, h_literals, n_lit);
 }
 
 extern "C" int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, const uint32_t *h_lit_count,
@@ -366,66 +281,29 @@ extern "C" int scl_lz77_replay_host(uint8_t *h_window, uint64_t have, uint64_t c
                 "%s: have <= cap < 2^32, n_seq and n_lit < 2^32", what);
     const bool wide = cap - have >= scl_lz77_wide_threshold();  // as in scl_lz77_parse_host
     const u64 scratch_bytes = wide ? scl_lz77_wide_replay_scratch_bytes(n_seq, cap - have) : 0;
-    ScratchDev d_win, d_lit, d_seq, d_meta, d_scr;
-    int rc;
-    if ((rc = d_win.alloc(cap)) || (rc = d_lit.alloc(n_lit)) || (rc = d_seq.alloc(3 * n_seq * 4)) ||
-        (rc = d_meta.alloc(sizeof(LzMeta))) || (rc = d_scr.alloc(scratch_bytes)))
-        return rc;
-    LzMeta meta = {};
-    meta.win_off[1] = cap;
-    meta.have = (u32)have;
-    meta.n_seq = (u32)n_seq;
-    meta.n_lit = (u32)n_lit;
-    u32 *d_lc = (u32 *)d_seq.p, *d_ml = d_lc + n_seq, *d_mo = d_ml + n_seq;
-    if (have) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, have, hipMemcpyHostToDevice));
-    if (n_lit) SCL_HIP_TRY(hipMemcpy(d_lit.p, h_literals, n_lit, hipMemcpyHostToDevice));
-    if (n_seq) {
-        SCL_HIP_TRY(hipMemcpy(d_lc, h_lit_count, n_seq * 4, hipMemcpyHostToDevice));
-        SCL_HIP_TRY(hipMemcpy(d_ml, h_match_len, n_seq * 4, hipMemcpyHostToDevice));
-        SCL_HIP_TRY(hipMemcpy(d_mo, h_match_off, n_seq * 4, hipMemcpyHostToDevice));
-    }
-    SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
-    LzMeta *dm = (LzMeta *)d_meta.p;
+    LzHostFrame f;
     scl_lz77_replay_args a = {};
-    a.d_win = (u8 *)d_win.p;
-    a.d_win_off = dm->win_off;
-    a.d_have = &dm->have;
-    a.n_streams = 1;
-    a.total_bytes = cap;
-    a.seq_cap = (u32)n_seq;
-    a.d_lit_count = d_lc;
-    a.d_match_len = d_ml;
-    a.d_match_off = d_mo;
-    a.d_n_seq = &dm->n_seq;
-    a.d_literals = (const u8 *)d_lit.p;
-    a.lit_bytes = n_lit;
-    a.d_lit_off = &dm->lit_off;
-    a.d_n_lit = &dm->n_lit;
-    a.d_out_len = &dm->out_len;
-    a.d_status = &dm->status;
+    int rc = f.replay_open(a, h_window, have, cap, h_lit_count, h_match_len, h_match_off, n_seq, h_literals, n_lit,
+                           scratch_bytes);
+    if (rc) return rc;
     if (wide) {
         scl_lz77_wide_replay_args w = {};
         w.d_win = a.d_win;
         w.have = have;
         w.cap = cap;
-        w.d_lit_count = d_lc;
-        w.d_match_len = d_ml;
-        w.d_match_off = d_mo;
+        w.d_lit_count = a.d_lit_count;
+        w.d_match_len = a.d_match_len;
+        w.d_match_off = a.d_match_off;
         w.n_seq = n_seq;
         w.d_literals = a.d_literals;
         w.n_lit = n_lit;
         w.d_out_len = a.d_out_len;
         w.d_status = a.d_status;
-        w.d_scratch = d_scr.p;
+        w.d_scratch = f.d_scr.p;
         w.scratch_bytes = scratch_bytes;
         rc = scl_lz77_replay_wide(&w, nullptr);
     } else {
         rc = scl_lz77_replay_batch(&a, nullptr);
     }
-    if (rc) return rc;
-    SCL_HIP_TRY(hipDeviceSynchronize());
-    SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
-    *out_len = meta.out_len;
-    if (meta.out_len) SCL_HIP_TRY(hipMemcpy(h_window + have, (u8 *)d_win.p + have, meta.out_len, hipMemcpyDeviceToHost));
-    return scl_status_to_error(meta.status, what);
+    return rc ? rc : f.replay_close(what, h_window, have, out_len);
 }

@@ -1,6 +1,14 @@
 // scl_lz77_internal.h -- shapes, scratch layout and shared device code of the LZ77 kernels (scl_lz77.hip: batches, one
 // wavefront per stream; scl_lz77_wide.hip: one stream across the whole GPU; scl_lz77_sliding.hip: the sliding-window coder,
 // one wavefront per stream).  Internal to csrc/.
+//
+// Written once for the greedy and the sliding-window coder, which differ in their match rule and in two replay rules:
+//   device  lz_replay_frame<WINDOWED> (all of a replay kernel), the index sort, lz_score / lz_extend,
+//           lz_replay_stream<WINDOWED>.  NOT what stands around the match rule of the two parse kernels (prologue, emit
+//           step, epilogue): a frame around them left lz77_sliding_parse its registers but measured slower
+//           (profiles/lz77_frame_codegen.txt, profiles/lz77_frame_timing.txt), so both kernels keep their own lines
+//   entry   lz77_parse_check, lz77_scratch_carve, lz77_replay_launch
+//   host    LzMeta, LzHostFrame (parse_open / parse_close, replay_open / replay_close)
 #pragma once
 
 #include "scl_common.h"
@@ -50,6 +58,156 @@ static inline Lz77Scratch lz77_scratch_layout(u64 N) {
 // block_sums: ceil(n / LZ_SCAN_BLOCK) values.  V: u32 or u64.
 template <class V>
 void lz77_scan_exclusive(V *data, u64 n, V *block_sums, hipStream_t st);
+
+// ---- the entry points' shared parts ------------------------------------------------------------------------------------
+// the index part of a scratch buffer as pointers (the sliding-window coder adds its keys behind it)
+struct Lz77ScratchPtrs {
+    u32 *order_a, *order_b, *rank;
+    u64 *bitmap;
+    u32 *hist, *sums;
+};
+
+static inline Lz77ScratchPtrs lz77_scratch_carve(void *d_scratch, const Lz77Scratch &lay) {
+    u8 *scr = (u8 *)d_scratch;
+    return {(u32 *)(scr + lay.order_a), (u32 *)(scr + lay.order_b), (u32 *)(scr + lay.rank),
+            (u64 *)(scr + lay.bitmap),  (u32 *)(scr + lay.hist),    (u32 *)(scr + lay.block_sums)};
+}
+
+// What scl_lz77_parse_batch and scl_lz77_sliding_parse_batch refuse alike, in one order: null pointers, the coder's own
+// parameters (`params`: int() -> SCL_OK or the error), sizes, phases, the scratch buffer against `scratch_fn`.
+template <class A, class Params>
+static inline int lz77_parse_check(const char *what, const A *a, Params params,
+                                   uint64_t (*scratch_fn)(uint64_t, uint64_t), const char *scratch_name) {
+    SCL_REQUIRE(a, "%s: null pointer argument", what);
+    SCL_REQUIRE(a->d_win_off && a->d_start && a->d_n_seq && a->d_n_lit && a->d_status && a->d_scratch &&
+                    (a->total_bytes == 0 || (a->d_win && a->d_literals)) &&
+                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
+                "%s: null pointer argument", what);
+    if (int rc = params()) return rc;
+    SCL_REQUIRE(a->total_bytes < (1ull << 32) && a->n_streams < (1ull << 32),
+                "%s: a batch holds less than 2^32 bytes and 2^32 streams", what);
+    SCL_REQUIRE(a->phases <= 3, "%s: phases is a mask of SCL_LZ77_INDEX | SCL_LZ77_PARSE", what);
+    const u64 need = scratch_fn(a->total_bytes, a->n_streams);
+    SCL_REQUIRE(((uintptr_t)a->d_scratch & 255) == 0 && a->scratch_bytes >= need,
+                "%s: d_scratch must be 256-byte aligned and hold %s = %llu bytes", what, scratch_name,
+                (unsigned long long)need);
+    return SCL_OK;
+}
+
+// ---- one stream in host memory: a batch of one around any of the parse / replay calls ------------------------------------
+struct LzMeta {  // the small per-stream words of a batch of one, in one allocation
+    u64 win_off[2];
+    u64 lit_off;
+    u32 start, n_seq, n_lit, status, have, out_len;
+};
+
+// Owns the device buffers of one host call.  *_open allocates, uploads and fills the fields every argument struct of its
+// kind has (A: scl_lz77_parse_args / scl_lz77_sliding_parse_args, or the two replay structs); the caller adds its own
+// fields, makes the call, and *_close synchronises, reads the meta words back and downloads.
+struct LzHostFrame {
+    ScratchDev d_win, d_lit, d_seq, d_meta, d_scr;
+    LzMeta meta = {};
+    u32 *d_lc = nullptr, *d_ml = nullptr, *d_mo = nullptr;  // the three rows in d_seq
+
+    int alloc(u64 win_bytes, u64 lit_bytes, u64 seq_cap, u64 scratch_bytes) {
+        int rc;
+        if ((rc = d_win.alloc(win_bytes)) || (rc = d_lit.alloc(lit_bytes)) || (rc = d_seq.alloc(3 * seq_cap * 4)) ||
+            (rc = d_meta.alloc(sizeof(LzMeta))) || (rc = d_scr.alloc(scratch_bytes)))
+            return rc;
+        d_lc = (u32 *)d_seq.p;
+        d_ml = d_lc + seq_cap;
+        d_mo = d_ml + seq_cap;
+        return SCL_OK;
+    }
+
+    template <class A>
+    int parse_open(A &a, const u8 *h_window, u64 n, u64 start, u64 seq_cap, u64 scratch_bytes) {
+        if (int rc = alloc(n, n, seq_cap, scratch_bytes)) return rc;
+        meta.win_off[1] = n;
+        meta.start = (u32)start;
+        if (n) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, n, hipMemcpyHostToDevice));
+        SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
+        LzMeta *dm = (LzMeta *)d_meta.p;
+        a.d_win = (const u8 *)d_win.p;
+        a.d_win_off = dm->win_off;
+        a.d_start = &dm->start;
+        a.n_streams = 1;
+        a.total_bytes = n;
+        a.seq_cap = (u32)seq_cap;
+        a.d_lit_count = d_lc;
+        a.d_match_len = d_ml;
+        a.d_match_off = d_mo;
+        a.d_literals = (u8 *)d_lit.p;
+        a.d_n_seq = &dm->n_seq;
+        a.d_n_lit = &dm->n_lit;
+        a.d_status = &dm->status;
+        a.d_scratch = d_scr.p;
+        a.scratch_bytes = scratch_bytes;
+        return SCL_OK;
+    }
+
+    // a stream the parse gave up on reports its status and downloads nothing
+    int parse_close(const char *what, u64 start, u32 *h_lit_count, u32 *h_match_len, u32 *h_match_off, u64 *n_seq,
+                    u8 *h_literals, u64 *n_lit) {
+        SCL_HIP_TRY(hipDeviceSynchronize());
+        SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+        *n_seq = meta.n_seq;
+        *n_lit = meta.n_lit;
+        if (meta.status) return scl_status_to_error(meta.status, what);
+        if (meta.n_seq) {
+            SCL_HIP_TRY(hipMemcpy(h_lit_count, d_lc, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+            SCL_HIP_TRY(hipMemcpy(h_match_len, d_ml, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+            SCL_HIP_TRY(hipMemcpy(h_match_off, d_mo, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
+        }
+        if (meta.n_lit) SCL_HIP_TRY(hipMemcpy(h_literals, (u8 *)d_lit.p + start, meta.n_lit, hipMemcpyDeviceToHost));
+        return SCL_OK;
+    }
+
+    template <class A>
+    int replay_open(A &a, const u8 *h_window, u64 have, u64 cap, const u32 *h_lit_count, const u32 *h_match_len,
+                    const u32 *h_match_off, u64 n_seq, const u8 *h_literals, u64 n_lit, u64 scratch_bytes) {
+        if (int rc = alloc(cap, n_lit, n_seq, scratch_bytes)) return rc;
+        meta.win_off[1] = cap;
+        meta.have = (u32)have;
+        meta.n_seq = (u32)n_seq;
+        meta.n_lit = (u32)n_lit;
+        if (have) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, have, hipMemcpyHostToDevice));
+        if (n_lit) SCL_HIP_TRY(hipMemcpy(d_lit.p, h_literals, n_lit, hipMemcpyHostToDevice));
+        if (n_seq) {
+            SCL_HIP_TRY(hipMemcpy(d_lc, h_lit_count, n_seq * 4, hipMemcpyHostToDevice));
+            SCL_HIP_TRY(hipMemcpy(d_ml, h_match_len, n_seq * 4, hipMemcpyHostToDevice));
+            SCL_HIP_TRY(hipMemcpy(d_mo, h_match_off, n_seq * 4, hipMemcpyHostToDevice));
+        }
+        SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
+        LzMeta *dm = (LzMeta *)d_meta.p;
+        a.d_win = (u8 *)d_win.p;
+        a.d_win_off = dm->win_off;
+        a.d_have = &dm->have;
+        a.n_streams = 1;
+        a.total_bytes = cap;
+        a.seq_cap = (u32)n_seq;
+        a.d_lit_count = d_lc;
+        a.d_match_len = d_ml;
+        a.d_match_off = d_mo;
+        a.d_n_seq = &dm->n_seq;
+        a.d_literals = (const u8 *)d_lit.p;
+        a.lit_bytes = n_lit;
+        a.d_lit_off = &dm->lit_off;
+        a.d_n_lit = &dm->n_lit;
+        a.d_out_len = &dm->out_len;
+        a.d_status = &dm->status;
+        return SCL_OK;
+    }
+
+    // what a faulted stream appended in front of the fault comes back with the error: the download is first
+    int replay_close(const char *what, u8 *h_window, u64 have, u64 *out_len) {
+        SCL_HIP_TRY(hipDeviceSynchronize());
+        SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
+        *out_len = meta.out_len;
+        if (meta.out_len) SCL_HIP_TRY(hipMemcpy(h_window + have, (u8 *)d_win.p + have, meta.out_len, hipMemcpyDeviceToHost));
+        return scl_status_to_error(meta.status, what);
+    }
+};
 
 #ifdef __HIPCC__
 // ---- device code shared by the one-wave kernels and the wide ones ----------------------------------------------------
@@ -289,21 +447,21 @@ __global__ __launch_bounds__(LZ_SORT_THREADS) void lz77_sort_scatter(Digit digit
     }
 }
 
-// The stable LSD sort of the N positions over `passes` digits of `digit`, on `st`: order_a / order_b ping-pong and the
+// The stable LSD sort of the N positions over `passes` digits of `digit`, on `st`: p.order_a / p.order_b ping-pong and the
 // result ends in order_a, its inverse in rank.  passes >= 1.
 template <class Digit>
-static inline void lz77_sort_positions(Digit digit, u64 N, u32 passes, const Lz77Scratch &lay, u32 *order_a, u32 *order_b,
-                                       u32 *rank, u32 *hist, u32 *sums, hipStream_t st) {
-    u32 *out = (passes & 1) ? order_a : order_b;
+static inline void lz77_sort_positions(Digit digit, u64 N, u32 passes, const Lz77Scratch &lay, const Lz77ScratchPtrs &p,
+                                       hipStream_t st) {
+    u32 *out = (passes & 1) ? p.order_a : p.order_b;
     const u32 *in = nullptr;
     for (u32 pass = 0; pass < passes; ++pass) {
         hipLaunchKernelGGL(lz77_sort_histogram<Digit>, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, digit, N, pass,
-                           in, hist, lay.n_tiles);
-        lz77_scan_exclusive(hist, lay.n_hist, sums, st);
+                           in, p.hist, lay.n_tiles);
+        lz77_scan_exclusive(p.hist, lay.n_hist, p.sums, st);
         hipLaunchKernelGGL(lz77_sort_scatter<Digit>, dim3((u32)lay.n_tiles), dim3(LZ_SORT_THREADS), 0, st, digit, N, pass, in,
-                           out, pass + 1 == passes ? rank : nullptr, hist, lay.n_tiles);
+                           out, pass + 1 == passes ? p.rank : nullptr, p.hist, lay.n_tiles);
         in = out;
-        out = out == order_a ? order_b : order_a;
+        out = out == p.order_a ? p.order_b : p.order_a;
     }
 }
 
@@ -372,5 +530,59 @@ __device__ __forceinline__ u32 lz_replay_stream(u8 *out, u32 cap, u32 *d_io, con
     }
     *d_io = d;
     return status;
+}
+
+// ---- the per-stream frame of the one-wave kernels ------------------------------------------------------------------------
+// the stream of this wavefront (>= n_streams: none, the wave returns)
+__device__ __forceinline__ u32 lz_wave_stream() { return blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE; }
+
+// All of a replay kernel but its name: the bounds of stream s against the buffers, its rows, lz_replay_stream, the results.
+template <bool WINDOWED>
+__device__ __forceinline__ void lz_replay_frame(u8 *win, u64 N, const u64 *win_off, const u32 *have_in, u32 n_streams,
+                                                u32 seq_cap, u32 window, const u32 *lit_count, const u32 *match_len,
+                                                const u32 *match_off, const u32 *n_seq_in, const u8 *literals,
+                                                u64 lit_bytes, const u64 *lit_off, const u32 *n_lit_in, u32 *out_len,
+                                                u32 *status_out) {
+    const u32 s = lz_wave_stream();
+    if (s >= n_streams) return;
+    const u32 lane = lz_lane();
+    const u64 base = win_off[s], end = win_off[s + 1];
+    const u32 have = have_in[s], n_seq = n_seq_in[s], n_lit = n_lit_in[s];
+    const u64 l_at = lit_off[s];
+    u32 status = 0, d = have;
+    if (base > end || end > N || end - base >= (1ull << 32) || have > end - base || n_seq > seq_cap ||
+        l_at > lit_bytes || n_lit > lit_bytes - l_at) {
+        status = SCL_ST_SIZE;
+    } else {
+        const u32 *lc = lit_count + (u64)s * seq_cap, *ml = match_len + (u64)s * seq_cap,
+                  *mo = match_off + (u64)s * seq_cap;
+        status = lz_replay_stream<WINDOWED>(win + base, (u32)(end - base), &d, lc, ml, mo, n_seq, literals + l_at, n_lit,
+                                            window);
+    }
+    if (lane == 0) {
+        out_len[s] = d - have;
+        status_out[s] = status;
+    }
+}
+
+// Both *_replay_batch entry points: A is scl_lz77_replay_args or scl_lz77_sliding_replay_args, `kernel` the unit's own
+// __global__ around lz_replay_frame, `window` the sliding one's extra kernel argument (the greedy call passes none).
+template <class A, class Kernel, class... Window>
+static inline int lz77_replay_launch(const char *what, const A *a, void *stream, Kernel kernel, Window... window) {
+    SCL_REQUIRE(a, "%s: null pointer argument", what);
+    SCL_REQUIRE(a->d_win_off && a->d_have && a->d_n_seq && a->d_lit_off && a->d_n_lit && a->d_out_len && a->d_status &&
+                    (a->total_bytes == 0 || a->d_win) && (a->lit_bytes == 0 || a->d_literals) &&
+                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
+                "%s: null pointer argument", what);
+    SCL_REQUIRE(a->n_streams < (1ull << 32), "%s: a batch holds less than 2^32 streams", what);
+    if (a->n_streams == 0) return SCL_OK;
+    const u32 n_streams = (u32)a->n_streams;
+    const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, (hipStream_t)stream, a->d_win, a->total_bytes,
+                       a->d_win_off, a->d_have, n_streams, a->seq_cap, window..., a->d_lit_count, a->d_match_len,
+                       a->d_match_off, a->d_n_seq, a->d_literals, a->lit_bytes, a->d_lit_off, a->d_n_lit, a->d_out_len,
+                       a->d_status);
+    SCL_HIP_TRY(hipGetLastError());
+    return SCL_OK;
 }
 #endif  // __HIPCC__

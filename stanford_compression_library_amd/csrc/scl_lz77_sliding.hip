@@ -146,7 +146,7 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_parse(const u8
                                                                         u32 seq_cap, u32 *lit_count, u32 *match_len,
                                                                         u32 *match_off, u8 *literals, u32 *n_seq_out,
                                                                         u32 *n_lit_out, u32 *status_out) {
-    const u32 s = blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE;
+    const u32 s = lz_wave_stream();
     if (s >= n_streams) return;
     const u32 lane = lz_lane();
     const u64 base = win_off[s], end = win_off[s + 1];
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_parse(const u8
     }
 }
 
-// lz77_replay of scl_lz77.hip with the window's two rules (lz_replay_stream<true>)
+// lz77_replay of scl_lz77.hip with the window's two rules (lz_replay_frame<true>)
 __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_replay(u8 *win, u64 N, const u64 *win_off,
                                                                          const u32 *have_in, u32 n_streams, u32 seq_cap,
                                                                          u32 window, const u32 *lit_count,
@@ -221,25 +221,8 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_replay(u8 *win
                                                                          const u32 *n_seq_in, const u8 *literals,
                                                                          u64 lit_bytes, const u64 *lit_off,
                                                                          const u32 *n_lit_in, u32 *out_len, u32 *status_out) {
-    const u32 s = blockIdx.x * LZ_STREAMS_PER_BLOCK + threadIdx.x / SCL_WAVE;
-    if (s >= n_streams) return;
-    const u32 lane = lz_lane();
-    const u64 base = win_off[s], end = win_off[s + 1];
-    const u32 have = have_in[s], n_seq = n_seq_in[s], n_lit = n_lit_in[s];
-    const u64 l_at = lit_off[s];
-    u32 status = 0, d = have;
-    if (base > end || end > N || end - base >= (1ull << 32) || have > end - base || n_seq > seq_cap ||
-        l_at > lit_bytes || n_lit > lit_bytes - l_at) {
-        status = SCL_ST_SIZE;
-    } else {
-        const u32 *lc = lit_count + (u64)s * seq_cap, *ml = match_len + (u64)s * seq_cap,
-                  *mo = match_off + (u64)s * seq_cap;
-        status = lz_replay_stream<true>(win + base, (u32)(end - base), &d, lc, ml, mo, n_seq, literals + l_at, n_lit, window);
-    }
-    if (lane == 0) {
-        out_len[s] = d - have;
-        status_out[s] = status;
-    }
+    lz_replay_frame<true>(win, N, win_off, have_in, n_streams, seq_cap, window, lit_count, match_len, match_off, n_seq_in,
+                          literals, lit_bytes, lit_off, n_lit_in, out_len, status_out);
 }
 
 struct SlidingScratch {
@@ -270,12 +253,6 @@ int sliding_check_params(const char *what, u32 hl, u64 m, u32 C, u32 mml) {
     return SCL_OK;
 }
 
-struct LzMeta {  // the small per-stream words of a batch of one, in one allocation
-    u64 win_off[2];
-    u64 lit_off;
-    u32 start, n_seq, n_lit, status, have, out_len;
-};
-
 }  // namespace
 
 extern "C" uint64_t scl_lz77_sliding_scratch_bytes(uint64_t total_bytes, uint64_t n_streams) {
@@ -298,30 +275,19 @@ extern "C" uint32_t scl_lz77_sliding_bucket_host(const uint8_t *gram, uint32_t h
 
 extern "C" int scl_lz77_sliding_parse_batch(const scl_lz77_sliding_parse_args *a, void *stream) {
     const char *what = "lz77_sliding_parse_batch";
-    SCL_REQUIRE(a, "%s: null pointer argument", what);
-    SCL_REQUIRE(a->d_win_off && a->d_start && a->d_n_seq && a->d_n_lit && a->d_status && a->d_scratch &&
-                    (a->total_bytes == 0 || (a->d_win && a->d_literals)) &&
-                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
-                "%s: null pointer argument", what);
-    if (int rc = sliding_check_params(what, a->hash_length, a->hash_table_size, a->max_chain_length, a->min_match_length))
+    const auto params = [&] {
+        return sliding_check_params(what, a->hash_length, a->hash_table_size, a->max_chain_length, a->min_match_length);
+    };
+    if (int rc = lz77_parse_check(what, a, params, scl_lz77_sliding_scratch_bytes, "scl_lz77_sliding_scratch_bytes"))
         return rc;
-    SCL_REQUIRE(a->total_bytes < (1ull << 32) && a->n_streams < (1ull << 32),
-                "%s: a batch holds less than 2^32 bytes and 2^32 streams", what);
-    SCL_REQUIRE(a->phases <= 3, "%s: phases is a mask of SCL_LZ77_INDEX | SCL_LZ77_PARSE", what);
-    const SlidingScratch lay = sliding_scratch_layout(a->total_bytes);
-    SCL_REQUIRE(((uintptr_t)a->d_scratch & 255) == 0 && a->scratch_bytes >= lay.total,
-                "%s: d_scratch must be 256-byte aligned and hold scl_lz77_sliding_scratch_bytes = %llu bytes", what,
-                (unsigned long long)lay.total);
     if (a->n_streams == 0) return SCL_OK;
     hipStream_t st = (hipStream_t)stream;
     const u64 N = a->total_bytes;
     const u32 n_streams = (u32)a->n_streams;
     const u32 W = a->window_size ? a->window_size : 0xFFFFFFFFu;
-    u8 *scr = (u8 *)a->d_scratch;
-    u32 *order_a = (u32 *)(scr + lay.index.order_a), *order_b = (u32 *)(scr + lay.index.order_b);
-    u32 *rank = (u32 *)(scr + lay.index.rank), *key = (u32 *)(scr + lay.key);
-    u64 *bitmap = (u64 *)(scr + lay.index.bitmap);
-    u32 *hist = (u32 *)(scr + lay.index.hist), *sums = (u32 *)(scr + lay.index.block_sums);
+    const SlidingScratch lay = sliding_scratch_layout(N);
+    const Lz77ScratchPtrs p = lz77_scratch_carve(a->d_scratch, lay.index);
+    u32 *key = (u32 *)((u8 *)a->d_scratch + lay.key);
     const u32 phases = a->phases ? a->phases : 3u;
     if ((phases & SCL_LZ77_INDEX) && N) {
         const u32 blocks = (u32)((N + 255) / 256);
@@ -329,15 +295,15 @@ extern "C" int scl_lz77_sliding_parse_batch(const scl_lz77_sliding_parse_args *a
                            a->hash_length, a->hash_table_size, key);
         const u32 kp = key_passes(a->hash_table_size);
         lz77_sort_positions(LzKeyDigit{key, a->d_win_off, n_streams, kp}, N, kp + lz_stream_passes(a->n_streams), lay.index,
-                            order_a, order_b, rank, hist, sums, st);
-        hipLaunchKernelGGL(lz77_sliding_bitmap, dim3(blocks), dim3(256), 0, st, N, a->d_win_off, n_streams, W, order_a, rank,
-                           key, bitmap);
+                            p, st);
+        hipLaunchKernelGGL(lz77_sliding_bitmap, dim3(blocks), dim3(256), 0, st, N, a->d_win_off, n_streams, W, p.order_a,
+                           p.rank, key, p.bitmap);
     }
     if (phases & SCL_LZ77_PARSE) {
         const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
         hipLaunchKernelGGL(lz77_sliding_parse, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, st, a->d_win, N, a->d_win_off,
                            a->d_start, n_streams, a->hash_length, a->max_chain_length, a->lazy, a->min_match_length, W,
-                           order_a, rank, key, bitmap, a->seq_cap, a->d_lit_count, a->d_match_len, a->d_match_off,
+                           p.order_a, p.rank, key, p.bitmap, a->seq_cap, a->d_lit_count, a->d_match_len, a->d_match_off,
                            a->d_literals, a->d_n_seq, a->d_n_lit, a->d_status);
     }
     SCL_HIP_TRY(hipGetLastError());
@@ -345,25 +311,10 @@ extern "C" int scl_lz77_sliding_parse_batch(const scl_lz77_sliding_parse_args *a
 }
 
 extern "C" int scl_lz77_sliding_replay_batch(const scl_lz77_sliding_replay_args *a, void *stream) {
-    const char *what = "lz77_sliding_replay_batch";
-    SCL_REQUIRE(a, "%s: null pointer argument", what);
-    SCL_REQUIRE(a->d_win_off && a->d_have && a->d_n_seq && a->d_lit_off && a->d_n_lit && a->d_out_len && a->d_status &&
-                    (a->total_bytes == 0 || a->d_win) && (a->lit_bytes == 0 || a->d_literals) &&
-                    (a->seq_cap == 0 || (a->d_lit_count && a->d_match_len && a->d_match_off)),
-                "%s: null pointer argument", what);
-    SCL_REQUIRE(a->n_streams < (1ull << 32), "%s: a batch holds less than 2^32 streams", what);
-    if (a->n_streams == 0) return SCL_OK;
-    const u32 n_streams = (u32)a->n_streams;
-    const u32 blocks = (n_streams + LZ_STREAMS_PER_BLOCK - 1) / LZ_STREAMS_PER_BLOCK;
-    hipLaunchKernelGGL(lz77_sliding_replay, dim3(blocks), dim3(LZ_STREAM_THREADS), 0, (hipStream_t)stream, a->d_win,
-                       a->total_bytes, a->d_win_off, a->d_have, n_streams, a->seq_cap, a->window_size, a->d_lit_count,
-                       a->d_match_len, a->d_match_off, a->d_n_seq, a->d_literals, a->lit_bytes, a->d_lit_off, a->d_n_lit,
-                       a->d_out_len, a->d_status);
-    SCL_HIP_TRY(hipGetLastError());
-    return SCL_OK;
+    return lz77_replay_launch("lz77_sliding_replay_batch", a, stream, lz77_sliding_replay, a ? a->window_size : 0u);
 }
 
-// ---- one stream in host memory -----------------------------------------------------------------------------------------
+// ---- one stream in host memory (LzHostFrame, scl_lz77_internal.h) -------------------------------------------------------
 extern "C" int scl_lz77_sliding_parse_host(const uint8_t *h_window, uint64_t n, uint64_t start, uint32_t hash_length,
                                            uint64_t hash_table_size, uint32_t max_chain_length, uint32_t lazy,
                                            uint32_t min_match_length, uint32_t window_size, uint32_t *h_lit_count,
@@ -378,52 +329,18 @@ extern "C" int scl_lz77_sliding_parse_host(const uint8_t *h_window, uint64_t n, 
     SCL_REQUIRE(lit_cap >= n - start, "%s: h_literals must hold the block (%llu bytes)", what,
                 (unsigned long long)(n - start));
     const u64 scratch_bytes = scl_lz77_sliding_scratch_bytes(n, 1);
-    ScratchDev d_win, d_lit, d_seq, d_meta, d_scr;
-    int rc;
-    if ((rc = d_win.alloc(n)) || (rc = d_lit.alloc(n)) || (rc = d_seq.alloc(3 * seq_cap * 4)) ||
-        (rc = d_meta.alloc(sizeof(LzMeta))) || (rc = d_scr.alloc(scratch_bytes)))
-        return rc;
-    LzMeta meta = {};
-    meta.win_off[1] = n;
-    meta.start = (u32)start;
-    if (n) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, n, hipMemcpyHostToDevice));
-    SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
-    LzMeta *dm = (LzMeta *)d_meta.p;
+    LzHostFrame f;
     scl_lz77_sliding_parse_args a = {};
-    a.d_win = (const u8 *)d_win.p;
-    a.d_win_off = dm->win_off;
-    a.d_start = &dm->start;
-    a.n_streams = 1;
-    a.total_bytes = n;
+    int rc = f.parse_open(a, h_window, n, start, seq_cap, scratch_bytes);
+    if (rc) return rc;
     a.hash_length = hash_length;
     a.hash_table_size = hash_table_size;
     a.max_chain_length = max_chain_length;
     a.lazy = lazy;
     a.min_match_length = min_match_length;
     a.window_size = window_size;
-    a.seq_cap = (u32)seq_cap;
-    a.d_lit_count = (u32 *)d_seq.p;
-    a.d_match_len = a.d_lit_count + seq_cap;
-    a.d_match_off = a.d_match_len + seq_cap;
-    a.d_literals = (u8 *)d_lit.p;
-    a.d_n_seq = &dm->n_seq;
-    a.d_n_lit = &dm->n_lit;
-    a.d_status = &dm->status;
-    a.d_scratch = d_scr.p;
-    a.scratch_bytes = scratch_bytes;
-    if ((rc = scl_lz77_sliding_parse_batch(&a, nullptr))) return rc;
-    SCL_HIP_TRY(hipDeviceSynchronize());
-    SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
-    *n_seq = meta.n_seq;
-    *n_lit = meta.n_lit;
-    if (meta.status) return scl_status_to_error(meta.status, what);
-    if (meta.n_seq) {
-        SCL_HIP_TRY(hipMemcpy(h_lit_count, a.d_lit_count, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
-        SCL_HIP_TRY(hipMemcpy(h_match_len, a.d_match_len, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
-        SCL_HIP_TRY(hipMemcpy(h_match_off, a.d_match_off, meta.n_seq * 4ull, hipMemcpyDeviceToHost));
-    }
-    if (meta.n_lit) SCL_HIP_TRY(hipMemcpy(h_literals, a.d_literals + start, meta.n_lit, hipMemcpyDeviceToHost));
-    return SCL_OK;
+    rc = scl_lz77_sliding_parse_batch(&a, nullptr);
+    return rc ? rc : f.parse_close(what, start, h_lit_count, h_match_len, h_match_off, n_seq, h_literals, n_lit);
 }
 
 extern "C" int scl_lz77_sliding_replay_host(uint8_t *h_window, uint64_t have, uint64_t cap, uint32_t window_size,
@@ -436,48 +353,11 @@ extern "C" int scl_lz77_sliding_replay_host(uint8_t *h_window, uint64_t have, ui
                 "%s: null pointer argument", what);
     SCL_REQUIRE(cap < (1ull << 32) && have <= cap && n_seq < (1ull << 32) && n_lit < (1ull << 32),
                 "%s: have <= cap < 2^32, n_seq and n_lit < 2^32", what);
-    ScratchDev d_win, d_lit, d_seq, d_meta;
-    int rc;
-    if ((rc = d_win.alloc(cap)) || (rc = d_lit.alloc(n_lit)) || (rc = d_seq.alloc(3 * n_seq * 4)) ||
-        (rc = d_meta.alloc(sizeof(LzMeta))))
-        return rc;
-    LzMeta meta = {};
-    meta.win_off[1] = cap;
-    meta.have = (u32)have;
-    meta.n_seq = (u32)n_seq;
-    meta.n_lit = (u32)n_lit;
-    u32 *d_lc = (u32 *)d_seq.p, *d_ml = d_lc + n_seq, *d_mo = d_ml + n_seq;
-    if (have) SCL_HIP_TRY(hipMemcpy(d_win.p, h_window, have, hipMemcpyHostToDevice));
-    if (n_lit) SCL_HIP_TRY(hipMemcpy(d_lit.p, h_literals, n_lit, hipMemcpyHostToDevice));
-    if (n_seq) {
-        SCL_HIP_TRY(hipMemcpy(d_lc, h_lit_count, n_seq * 4, hipMemcpyHostToDevice));
-        SCL_HIP_TRY(hipMemcpy(d_ml, h_match_len, n_seq * 4, hipMemcpyHostToDevice));
-        SCL_HIP_TRY(hipMemcpy(d_mo, h_match_off, n_seq * 4, hipMemcpyHostToDevice));
-    }
-    SCL_HIP_TRY(hipMemcpy(d_meta.p, &meta, sizeof(meta), hipMemcpyHostToDevice));
-    LzMeta *dm = (LzMeta *)d_meta.p;
+    LzHostFrame f;
     scl_lz77_sliding_replay_args a = {};
-    a.d_win = (u8 *)d_win.p;
-    a.d_win_off = dm->win_off;
-    a.d_have = &dm->have;
-    a.n_streams = 1;
-    a.total_bytes = cap;
-    a.seq_cap = (u32)n_seq;
+    int rc = f.replay_open(a, h_window, have, cap, h_lit_count, h_match_len, h_match_off, n_seq, h_literals, n_lit, 0);
+    if (rc) return rc;
     a.window_size = window_size;
-    a.d_lit_count = d_lc;
-    a.d_match_len = d_ml;
-    a.d_match_off = d_mo;
-    a.d_n_seq = &dm->n_seq;
-    a.d_literals = (const u8 *)d_lit.p;
-    a.lit_bytes = n_lit;
-    a.d_lit_off = &dm->lit_off;
-    a.d_n_lit = &dm->n_lit;
-    a.d_out_len = &dm->out_len;
-    a.d_status = &dm->status;
-    if ((rc = scl_lz77_sliding_replay_batch(&a, nullptr))) return rc;
-    SCL_HIP_TRY(hipDeviceSynchronize());
-    SCL_HIP_TRY(hipMemcpy(&meta, d_meta.p, sizeof(meta), hipMemcpyDeviceToHost));
-    *out_len = meta.out_len;
-    if (meta.out_len) SCL_HIP_TRY(hipMemcpy(h_window + have, (u8 *)d_win.p + have, meta.out_len, hipMemcpyDeviceToHost));
-    return scl_status_to_error(meta.status, what);
+    rc = scl_lz77_sliding_replay_batch(&a, nullptr);
+    return rc ? rc : f.replay_close(what, h_window, have, out_len);
 }

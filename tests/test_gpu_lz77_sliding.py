@@ -5,10 +5,14 @@ The batch is lz77_helpers.ragged_batch(): 130 streams (four to a workgroup, the 
 odd offsets; the five parameter sets take every path of the parse: one bucket for everything (m = 1) and one per gram,
 chains shorter and longer than the candidates there are, windows shorter than the streams, lazy and not, hash_length 1
 and 8, minimum_match_length below and above hash_length."""
+import ctypes
+
 import numpy as np
 import pytest
 
 from lz77_helpers import ST_CAPACITY, ST_STATE, ST_TRUNCATED, edge_batch, pack_windows, ragged_batch, with_garbage
+from lz77_helpers import parse_restated as greedy_parse_restated
+from lz77_helpers import replay_restated as greedy_replay_restated
 from lz77_sliding_helpers import case_params, golden_blocks, goldens, parse_restated, ragged_reference, replay_restated
 from stanford_compression_library_amd.backend import lib as backend_lib
 from stanford_compression_library_amd.backend import lz77 as dev_lz77
@@ -202,8 +206,10 @@ def test_scratch_of_a_larger_batch_is_reused(dev):
 
 
 # ---- replay statuses ---------------------------------------------------------------------------------------------------------
-def replay_device(dev, histories, caps, seqs, lits, window_size):
-    """slots of caps[s] bytes holding histories[s], between sentinel bytes -> (slot contents, out_len, status)"""
+def replay_device(dev, histories, caps, seqs, lits, window_size, call=None):
+    """slots of caps[s] bytes holding histories[s], between sentinel bytes -> (slot contents, out_len, status).  ``call``:
+    what replays the tensors, ``sliding_replay_batch`` with ``window_size`` unless given"""
+    call = call or (lambda *tensors: dev_lz77.sliding_replay_batch(*tensors, window_size=window_size))
     n = len(histories)
     slots = pack_windows([np.concatenate([h, np.full(c - len(h), FILL, np.uint8)]) for h, c in zip(histories, caps)],
                          [len(h) for h in histories], lead=np.full(3, 0x77, np.uint8), tail=np.full(5, 0x77, np.uint8))
@@ -215,10 +221,10 @@ def replay_device(dev, histories, caps, seqs, lits, window_size):
     literals = np.concatenate([np.asarray(x, np.uint8) for x in lits] + [np.zeros(1, np.uint8)])
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(dev)  # noqa: E731
     win = t(slots["buf"], np.uint8)
-    out_len, status = dev_lz77.sliding_replay_batch(
+    out_len, status = call(
         win, t(slots["win_off"], np.int64), t(slots["start"], np.int32), t(rows[0], np.int32), t(rows[1], np.int32),
         t(rows[2], np.int32), t(np.array([len(q) for q in seqs]), np.int32), t(literals, np.uint8), t(lit_off[:-1], np.int64),
-        t(np.array([len(x) for x in lits]), np.int32), window_size=window_size)
+        t(np.array([len(x) for x in lits]), np.int32))
     torch.cuda.synchronize()
     return win.cpu().numpy(), slots, out_len.cpu().numpy(), status.cpu().numpy()
 
@@ -252,3 +258,89 @@ def test_replay_statuses_and_sentinels(dev):
     # no window bound: the first case passes
     _, _, out_len, status = replay_device(dev, [hist], [40], [[(2, 3, W + 1)]], [[1, 2]], 0)
     assert status[0] == 0 and out_len[0] == 5
+
+
+# ---- the two coders share their replay frame and their host frame: what must still differ, and what must not ------------------
+TWO_RULES = [[(2, 0, 0), (0, 4, 2)], [(1, 0, 77), (0, 3, 1)], [(2, 3, 9)], [(2, 3, 8)]]
+TWO_RULES_LITS = [[1, 2], [3], [4, 5], [6, 7]]
+
+
+def test_same_sequences_under_the_two_replay_rules(dev):
+    """a match length of 0 ends a greedy stream (offset 0, or beyond the bytes so far) and is skipped by the windowed rule;
+    offset 9 is fine without a window and ST_STATE at window_size 8, offset 8 is fine under both"""
+    hist = np.arange(20, dtype=np.uint8)
+    args = (dev, [hist] * 4, [64] * 4, TWO_RULES, TWO_RULES_LITS)
+    for name, restated, call, want_status, want_len in (
+            ("greedy", greedy_replay_restated, dev_lz77.replay_batch, [ST_STATE, ST_STATE, 0, 0], [2, 1, 5, 5]),
+            ("sliding", lambda h, q, x, cap: replay_restated(h, q, x, window_size=8, cap=cap), None, [0, 0, ST_STATE, 0],
+             [6, 4, 2, 5])):
+        got, slots, out_len, status = replay_device(*args, 8, call=call)
+        assert status.tolist() == want_status and out_len.tolist() == want_len, name
+        expect = slots["buf"].copy()
+        for s in range(4):
+            new, st = restated(hist, TWO_RULES[s], TWO_RULES_LITS[s], cap=64)
+            assert st == want_status[s] and len(new) == want_len[s], f"{name} stream {s}"
+            at = int(slots["win_off"][s]) + len(hist)
+            expect[at: at + len(new)] = new
+        assert np.array_equal(got, expect), name
+
+
+def test_reserved_of_the_greedy_replay_is_not_a_window(dev):
+    def raw(reserved):
+        def call(win, win_off, have, lc, ml, mo, n_seq, literals, lit_off, n_lit):
+            out_len, status = (torch.zeros(have.numel(), dtype=torch.int32, device=dev) for _ in range(2))
+            a = backend_lib.Lz77ReplayArgs(win.data_ptr(), win_off.data_ptr(), have.data_ptr(), int(have.numel()),
+                                           int(win.numel()), int(lc.shape[1]), reserved, lc.data_ptr(), ml.data_ptr(),
+                                           mo.data_ptr(), n_seq.data_ptr(), literals.data_ptr(), int(literals.numel()),
+                                           lit_off.data_ptr(), n_lit.data_ptr(), out_len.data_ptr(), status.data_ptr())
+            rc = backend_lib.load().scl_lz77_replay_batch(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream)
+            backend_lib.check(rc, "scl_lz77_replay_batch")
+            return out_len, status
+        return call
+
+    hist = np.arange(20, dtype=np.uint8)
+    got5, _, out_len5, status5 = replay_device(dev, [hist], [40], [[(2, 3, 9)]], [[1, 2]], 0, call=raw(5))
+    got0, _, out_len0, status0 = replay_device(dev, [hist], [40], [[(2, 3, 9)]], [[1, 2]], 0, call=raw(0))
+    assert status5[0] == 0 and status0[0] == 0 and out_len5[0] == 5 and out_len0[0] == 5
+    assert np.array_equal(got5, got0)
+    new, _ = greedy_replay_restated(hist, [(2, 3, 9)], [1, 2], cap=40)
+    assert got5[3 + 20: 3 + 25].tolist() == new.tolist() == [1, 2, 13, 14, 15]
+
+
+HOST_SLIDING = (4, 1000, 64, 1, 4, 64)  # (hl, m, C, lazy, mml, W) as lz77_sliding_helpers takes them
+HOST_PAIRS = {
+    "greedy": (lambda w, s: dev_lz77.parse_host(w, s, 4, 64), dev_lz77.replay_host,
+               lambda w, s: greedy_parse_restated(w, s, 4, 64), greedy_replay_restated, "scl_lz77_replay_host", ()),
+    "sliding": (lambda w, s: dev_lz77.sliding_parse_host(w, s, dev_lz77.SlidingParams(4, 1000, 64, True, 4, 64)),
+                lambda *a: dev_lz77.sliding_replay_host(*a, window_size=64),
+                lambda w, s: parse_restated(w, s, HOST_SLIDING),
+                lambda h, q, x, cap: replay_restated(h, q, x, window_size=64, cap=cap), "scl_lz77_sliding_replay_host", (64,)),
+}
+
+
+@pytest.mark.parametrize("coder", sorted(HOST_PAIRS))
+def test_one_host_frame_both_directions(coder, dev):
+    parse, replay, parse_ref, replay_ref, entry, extra = HOST_PAIRS[coder]
+    data = np.random.default_rng(11).integers(0, 4, 400).astype(np.uint8)
+    for window, start in ((data[:300], 0), (data, 100), (data[:100], 100)):  # no history, history, the empty block
+        lc, ml, mo, lits = parse(window, start)
+        ref_seq, ref_lit = parse_ref(window, start)
+        assert np.stack([lc, ml, mo], axis=1).astype(np.int64).tolist() == ref_seq.tolist(), (coder, start)
+        assert lits.tolist() == ref_lit.tolist(), (coder, start)
+        assert len(lits) + int(ml.sum()) == len(window) - start, (coder, start)
+        assert replay(window[:start], lc, ml, mo, lits).tolist() == window[start:].tolist(), (coder, start)
+    # a replay that faults at sequence 2: the bytes in front of the fault come back with SCL_E_CHUNK
+    hist = np.arange(20, dtype=np.uint8)
+    seqs, lits = np.array([(1, 2, 1), (1, 2, 1), (0, 3, 0)], np.uint32), np.array([5, 6], np.uint8)
+    new, st = replay_ref(hist, seqs, lits, cap=29)
+    assert st == ST_STATE and len(new) == 6
+    with pytest.raises(backend_lib.SclHipError) as err:
+        replay(hist, seqs[:, 0], seqs[:, 1], seqs[:, 2], lits)
+    assert err.value.code == backend_lib.E_CHUNK
+    buf = np.concatenate([hist, np.full(9, FILL, np.uint8)])
+    rows = [np.ascontiguousarray(seqs[:, k]) for k in range(3)]
+    out_len = ctypes.c_uint64(0)
+    rc = getattr(backend_lib.load(), entry)(backend_lib.u8_ptr(buf), 20, 29, *extra, *(backend_lib.u32_ptr(r) for r in rows), 3,
+                                            backend_lib.u8_ptr(lits), 2, ctypes.byref(out_len))
+    assert rc == backend_lib.E_CHUNK and out_len.value == 6
+    assert buf.tolist() == hist.tolist() + new.tolist() + [FILL] * 3
