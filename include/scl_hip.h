@@ -553,6 +553,82 @@ int scl_fixed_decode_host(const uint8_t *h_in, uint64_t in_bit_offset, uint64_t 
                           uint64_t K, uint32_t *h_out_idx, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed,
                           uint32_t *status);
 
+/* ---- typical-set code: tables built on the device, ONE block coded by the whole grid (scl_typical.hip; added to ABI 8 as above)
+ * The reference's TypicalSetEncoder / TypicalSetDecoder (typical_set_coder.py).  A block is cut into chunks of n symbols; chunk
+ * x_0..x_{n-1} is tuple t = sum x_i * K^(n-1-i) of the N = K^n tuples in itertools.product order.  Tuple t is typical iff
+ * fabs(s / (double)n - entropy) <= eps with s = nlp[x_0] + nlp[x_1] + ... + nlp[x_{n-1}] summed in that order in float64
+ * (csrc/scl_typical_rule.h: the one function, compiled for the host and the device).  The `count` typical tuples are numbered
+ * in the order of t.  A typical chunk is coded as bit 0 and its number in bt = ceil(log2 count) bits, any other as bit 1 and t
+ * in bo = ceil(log2 N) bits, most significant first.  The stream is the codewords back to back, nothing else.
+ *   scl_typical_model_create: h_nlp = -log2 p of the K symbols (host, float64), uploaded; rank[N] (the number of a typical
+ *           tuple, SCL_TYPICAL_NONE otherwise) and inv[count] (its inverse) are built by three kernels on the current
+ *           device, whose buffers are filled with 0xA5 in front of them.  SCL_E_PARAM before any device call, the message
+ *           naming the limit: a null pointer, K = 0, n = 0, K > 65536, n > 2^24, K^n > 2^24 (SCL_TYPICAL_MAX_TUPLES: the
+ *           longest codeword is then 25 bits and rank[] 64 MiB), a non-finite nlp, entropy or eps.  A negative eps is legal:
+ *           no tuple is typical.
+ *   scl_typical_model_info: bt = SCL_TYPICAL_NONE for an empty typical set (0: one member).
+ *   scl_typical_model_tables: rank[N] and inv[count] copied to the host (either may be NULL).
+ *   scl_typical_table_host: the same table on the CPU, no device: h_rank[N] (may be NULL: the count alone), *count.
+ *   scl_typical_index_bits_host: ceil(log2 x) in integers as the model computes bt and bo; x = 0 gives SCL_TYPICAL_NONE.
+ *   encode: as scl_prefix_encode_block over n_symbols symbol indices (uint8: K <= 256; _u16: any K); n_symbols is a multiple
+ *           of n.  *d_status: SCL_ST_SYMBOL = an index >= K (coded as index 0), SCL_ST_CAPACITY as there.
+ *   decode: as scl_prefix_decode_block; out_cap, n_out count SYMBOLS (whole chunks are delivered: out_cap / n of them at the
+ *           most).  status, at the sequentially first codeword that has one: SCL_ST_TRUNCATED = in_nbits ends inside a
+ *           codeword; SCL_ST_STATE = flag 0 with an empty typical set, a typical number >= count, or flag 1 with t >= N;
+ *           SCL_ST_CAPACITY = bits are left after out_cap / n chunks.  consumed = the bits of the whole chunks in front.
+ *   the *_block_host calls report the status word as scl_uint_*_block_host do.
+ * SCL_E_PARAM (message = the entry point's name + ':'), before any device call: a null pointer, a model of another device, a
+ * model of more than 256 symbols through a uint8 entry point, n_symbols % n != 0, the misalignments, scratch and size limits of
+ * scl_prefix_*_block (d_sym / d_out_sym: the symbol size; the scratch: scl_typical_block_scratch_bytes). */
+#define SCL_TYPICAL_MAX_TUPLES (1u << 24)
+#define SCL_TYPICAL_NONE 0xFFFFFFFFu
+
+typedef struct scl_typical_model scl_typical_model;
+typedef struct scl_typical_info {
+    uint32_t N, count; /* tuples, typical tuples                              */
+    uint32_t bt, bo;   /* index widths (bt: SCL_TYPICAL_NONE for count = 0)   */
+    uint32_t K, n;
+    int32_t device;
+    uint32_t reserved;
+} scl_typical_info;
+
+typedef struct scl_typical_block_result {
+    uint64_t n_out, consumed;
+    uint32_t status, sync_passes;
+} scl_typical_block_result;
+
+int scl_typical_model_create(const double *h_nlp, uint32_t K, uint32_t n, double entropy, double eps,
+                             scl_typical_model **out);
+void scl_typical_model_destroy(scl_typical_model *m);
+int scl_typical_model_info(const scl_typical_model *m, scl_typical_info *info);
+int scl_typical_model_tables(const scl_typical_model *m, uint32_t *h_rank, uint32_t *h_inv);
+int scl_typical_table_host(const double *h_nlp, uint32_t K, uint32_t n, double entropy, double eps, uint32_t *h_rank,
+                           uint32_t *count);
+uint32_t scl_typical_index_bits_host(uint64_t x);
+/* device scratch that serves an encode of n_symbols and a decode of in_nbits with this model */
+uint64_t scl_typical_block_scratch_bytes(const scl_typical_model *m, uint64_t n_symbols, uint64_t in_nbits);
+int scl_typical_encode_block(const scl_typical_model *m, const uint8_t *d_sym, uint64_t n_symbols, uint8_t *d_out,
+                             uint64_t out_cap_bytes, uint64_t *d_nbits, uint32_t *d_status, void *d_scratch,
+                             uint64_t scratch_bytes, void *stream);
+int scl_typical_encode_block_u16(const scl_typical_model *m, const uint16_t *d_sym, uint64_t n_symbols, uint8_t *d_out,
+                                 uint64_t out_cap_bytes, uint64_t *d_nbits, uint32_t *d_status, void *d_scratch,
+                                 uint64_t scratch_bytes, void *stream);
+int scl_typical_decode_block(const scl_typical_model *m, const uint8_t *d_in, uint64_t in_size_bytes, uint64_t in_bit_offset,
+                             uint64_t in_nbits, uint8_t *d_out_sym, uint64_t out_cap, scl_typical_block_result *d_result,
+                             void *d_scratch, uint64_t scratch_bytes, void *stream);
+int scl_typical_decode_block_u16(const scl_typical_model *m, const uint8_t *d_in, uint64_t in_size_bytes,
+                                 uint64_t in_bit_offset, uint64_t in_nbits, uint16_t *d_out_sym, uint64_t out_cap,
+                                 scl_typical_block_result *d_result, void *d_scratch, uint64_t scratch_bytes, void *stream);
+int scl_typical_encode_block_host(const scl_typical_model *m, const uint8_t *h_sym, uint64_t n_symbols, uint8_t *h_out,
+                                  uint64_t out_cap_bytes, uint64_t *nbits, uint32_t *status);
+int scl_typical_encode_block_host_u16(const scl_typical_model *m, const uint16_t *h_sym, uint64_t n_symbols, uint8_t *h_out,
+                                      uint64_t out_cap_bytes, uint64_t *nbits, uint32_t *status);
+int scl_typical_decode_block_host(const scl_typical_model *m, const uint8_t *h_in, uint64_t in_nbits, uint8_t *h_out_sym,
+                                  uint64_t out_cap, uint64_t *n_out, uint64_t *consumed, uint32_t *status);
+int scl_typical_decode_block_host_u16(const scl_typical_model *m, const uint8_t *h_in, uint64_t in_nbits,
+                                      uint16_t *h_out_sym, uint64_t out_cap, uint64_t *n_out, uint64_t *consumed,
+                                      uint32_t *status);
+
 /* ---- LZ77: match index, greedy parse and sequence replay (scl_lz77.hip; added to ABI 8 as above) -----------------------
  * The LZ layer of the reference's LZ77 coder, for a batch of independent streams, one wavefront per stream:
  *   scl_lz77_parse_batch   <->  LZ77Encoder.lz77_parse_and_generate_sequences   scl/compressors/lz77.py:525-603

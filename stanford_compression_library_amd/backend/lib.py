@@ -57,6 +57,16 @@ class UintCodeStruct(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("M", C.c_uint32)]
 
 
+class TypicalInfo(C.Structure):
+    """scl_typical_info"""
+    _fields_ = [("N", C.c_uint32), ("count", C.c_uint32), ("bt", C.c_uint32), ("bo", C.c_uint32), ("K", C.c_uint32),
+                ("n", C.c_uint32), ("device", C.c_int32), ("reserved", C.c_uint32)]
+
+
+TYPICAL_NONE = 0xFFFFFFFF        # SCL_TYPICAL_NONE: no rank (an atypical tuple), no width (an empty typical set)
+TYPICAL_MAX_TUPLES = 1 << 24     # SCL_TYPICAL_MAX_TUPLES
+
+
 class Lz77ParseArgs(C.Structure):
     """scl_lz77_parse_args: device pointers travel as integers"""
     _fields_ = [("d_win", C.c_void_p), ("d_win_off", C.c_void_p), ("d_start", C.c_void_p), ("n_streams", C.c_uint64),
@@ -156,6 +166,7 @@ LZ77_INDEX, LZ77_PARSE = 1, 2
 LZ77_WIDE_INDEX, LZ77_WIDE_SCORE, LZ77_WIDE_WALK, LZ77_WIDE_EMIT = 1, 2, 4, 8
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+_f64p = C.POINTER(C.c_double)
 _vp, _u32, _u64, _int = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 
 # name -> (restype, argtypes); device pointers travel as void* (integers from tensor.data_ptr())
@@ -239,6 +250,18 @@ _SIGNATURES = {
     "scl_fixed_kernel_names": (_int, [_u32, _u64, C.c_char_p, C.c_char_p, _u64]),
     "scl_fixed_encode_host": (_int, [_u32p, _u64, _u32, _u64, _u8p, _u64, _u64p, _u32p]),
     "scl_fixed_decode_host": (_int, [_u8p, _u64, _u64, _u64, _u32, _u64, _u32p, _u64, _u64p, _u64p, _u32p]),
+    # typical-set code: tables built on the device, one block coded by the whole grid (scl_typical.hip)
+    "scl_typical_model_create": (_int, [_f64p, _u32, _u32, C.c_double, C.c_double, C.POINTER(_vp)]),
+    "scl_typical_model_destroy": (None, [_vp]),
+    "scl_typical_model_info": (_int, [_vp, C.POINTER(TypicalInfo)]),
+    "scl_typical_model_tables": (_int, [_vp, _u32p, _u32p]),
+    "scl_typical_table_host": (_int, [_f64p, _u32, _u32, C.c_double, C.c_double, _u32p, _u32p]),
+    "scl_typical_index_bits_host": (_u32, [_u64]),
+    "scl_typical_block_scratch_bytes": (_u64, [_vp, _u64, _u64]),
+    "scl_typical_encode_block": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "scl_typical_decode_block": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "scl_typical_encode_block_host": (_int, [_vp, _vp, _u64, _u8p, _u64, _u64p, _u32p]),
+    "scl_typical_decode_block_host": (_int, [_vp, _u8p, _u64, _vp, _u64, _u64p, _u64p, _u32p]),
     # LZ77: match index, greedy parse, sequence replay (scl_lz77.hip)
     "scl_lz77_scratch_bytes": (_u64, [_u64, _u64]),
     "scl_lz77_parse_batch": (_int, [C.POINTER(Lz77ParseArgs), _vp]),
@@ -339,6 +362,8 @@ for _op, _host in (("encode", _ENC_HOST16), ("decode", _DEC_HOST16)):
 for _op, _host in (("encode", _ENC_HOST16), ("decode", _DEC_HOST16)):
     _SIGNATURES[f"scl_prefix_{_op}_block_u16"] = _SIGNATURES[f"scl_prefix_{_op}_block"]
     _SIGNATURES[f"scl_prefix_{_op}_block_host_u16"] = (_int, _host)
+    _SIGNATURES[f"scl_typical_{_op}_block_u16"] = _SIGNATURES[f"scl_typical_{_op}_block"]
+    _SIGNATURES[f"scl_typical_{_op}_block_host_u16"] = _SIGNATURES[f"scl_typical_{_op}_block_host"]
 
 
 def any_parameter_forced() -> bool:

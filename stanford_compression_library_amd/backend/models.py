@@ -817,6 +817,123 @@ class UintCode:
         return tuple(names)
 
 
+class TypicalSetModel(_DeviceModel):
+    """the typical-set code of ``n``-symbol chunks over ``K`` symbols (csrc/scl_typical.hip): ``nlp[i]`` = -log2 p of symbol
+    ``i`` as float64, ``entropy`` and ``eps`` as the reference's ``is_typical`` takes them.  The constructor builds the tables
+    on the current device -- ``rank[t]`` (the number of typical tuple ``t``, ``NONE`` otherwise) and its inverse ``inv`` -- and
+    refuses what the device does not enumerate with ``SclHipError(E_PARAM)`` before it touches one.  Blocks are arrays of symbol
+    indices (``sym_dtype``), a whole number of chunks; the streams carry no header."""
+
+    _prefix = "typical"
+    size_bits = 0
+    NONE = _lib.TYPICAL_NONE
+    MAX_TUPLES = _lib.TYPICAL_MAX_TUPLES
+
+    def __init__(self, nlp, n: int, entropy: float, eps: float):
+        super().__init__()
+        v = np.ascontiguousarray(nlp, dtype=np.float64)
+        assert v.ndim == 1, "one value per symbol"
+        rc = self._L.scl_typical_model_create(v.ctypes.data_as(_lib._f64p), v.size, int(n), float(entropy), float(eps),
+                                              C.byref(self._h))
+        _lib.check(rc, "scl_typical_model_create")
+        self.K = int(v.size)
+        info = self.info()
+        self.n, self.N, self.count, self.bo = int(info.n), int(info.N), int(info.count), int(info.bo)
+        self.bt = None if info.bt == self.NONE else int(info.bt)  # None: an empty typical set
+        self.min_len = 1 + (self.bo if self.bt is None else min(self.bt, self.bo))
+        self.max_len = 1 + self.bo
+
+    @staticmethod
+    def table_host(nlp, n: int, entropy: float, eps: float, want_rank: bool = True):
+        """the rule on the CPU, no device -> (rank[N] or None, count): what the device tables are held against"""
+        L = _lib.load()
+        v = np.ascontiguousarray(nlp, dtype=np.float64)
+        count = C.c_uint32(0)
+        args = (v.ctypes.data_as(_lib._f64p), v.size, int(n), float(entropy), float(eps))
+        # (a table the call refuses is not allocated: K^n is only computed where it is small)
+        taken = want_rank and 0 < int(n) <= 24 and 0 < v.size ** int(n) <= TypicalSetModel.MAX_TUPLES
+        rank = np.zeros(v.size ** int(n), np.uint32) if taken else None
+        _lib.check(L.scl_typical_table_host(*args, _lib.u32_ptr(rank) if taken else None, C.byref(count)),
+                   "scl_typical_table_host")
+        return rank, int(count.value)
+
+    def info(self) -> _lib.TypicalInfo:
+        info = _lib.TypicalInfo()
+        _lib.check(self._L.scl_typical_model_info(self._h, C.byref(info)), "scl_typical_model_info")
+        return info
+
+    def tables(self):
+        """the device-built tables as numpy arrays -> (rank[N], inv[count])"""
+        rank, inv = np.zeros(self.N, np.uint32), np.zeros(max(self.count, 1), np.uint32)
+        _lib.check(self._L.scl_typical_model_tables(self._h, _lib.u32_ptr(rank), _lib.u32_ptr(inv)), "scl_typical_model_tables")
+        return rank, inv[: self.count]
+
+    def slot_bytes(self, n_symbols: int) -> int:
+        """bytes that hold the stream of any ``n_symbols`` symbols, in whole words"""
+        return ((int(n_symbols) // self.n) * self.max_len + 31) // 32 * 4 + 4
+
+    def max_symbols(self, nbits: int) -> int:
+        """an output capacity no stream of ``nbits`` reaches: one chunk more than its bits can hold, so that bits left behind
+        the last whole chunk are reported as what they are (a cut or a bad codeword), never as ``ST_CAPACITY``"""
+        return (int(nbits) // self.min_len + 1) * self.n
+
+    # -- one block, host memory ----------------------------------------------------------------------------------------
+    def encode_host(self, sym: np.ndarray):
+        """index array -> (packed MSB-first bytes, nbits, status); ``ST_SYMBOL``: an index >= K (coded as index 0)"""
+        sym = np.ascontiguousarray(sym, dtype=self.sym_dtype)
+        cap = self.slot_bytes(sym.size)
+        out = np.zeros(cap, dtype=np.uint8)
+        nbits, status = C.c_uint64(0), C.c_uint32(0)
+        rc = self._sym_fn("encode_block_host")(self._h, C.c_void_p(sym.ctypes.data), sym.size, _lib.u8_ptr(out), cap,
+                                               C.byref(nbits), C.byref(status))
+        _lib.check(rc, "scl_typical_encode_block_host")
+        return out[: (nbits.value + 7) // 8], int(nbits.value), int(status.value)
+
+    def decode_host(self, packed: np.ndarray, nbits: int, out_cap: Optional[int] = None):
+        """(packed bytes, EXACT stream bits) -> (index array, num_bits_consumed, status); the whole chunks in front of a fault
+        are delivered.  ``out_cap`` (symbols) defaults to :meth:`max_symbols`."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        cap = self.max_symbols(nbits) if out_cap is None else int(out_cap)
+        if packed.size == 0:
+            packed = np.zeros(1, dtype=np.uint8)
+        out = np.zeros(max(cap, 1), dtype=self.sym_dtype)
+        n_out, used, status = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        rc = self._sym_fn("decode_block_host")(self._h, _lib.u8_ptr(packed), int(nbits), C.c_void_p(out.ctypes.data), cap,
+                                               C.byref(n_out), C.byref(used), C.byref(status))
+        _lib.check(rc, "scl_typical_decode_block_host")
+        return out[: n_out.value], int(used.value), int(status.value)
+
+    # -- one block, device memory (torch tensors) ----------------------------------------------------------------------
+    def block_scratch(self, n_symbols: int, nbits: int, device):
+        import torch
+
+        nbytes = int(self._L.scl_typical_block_scratch_bytes(self._h, int(n_symbols), int(nbits)))
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    def encode_block_into(self, sym, out, out_cap_bytes: Optional[int] = None, scratch=None):
+        """1-D symbol tensor (a whole number of chunks) -> its stream at the front of the uint8 tensor ``out``, asynchronously
+        on the current stream.  -> int64 tensor ``[nbits, status]`` on the device."""
+        return _encode_block_into(functools.partial(self._sym_fn("encode_block"), self._h), "scl_typical_encode_block", sym,
+                                  self._torch_sym_dtypes(), out, out_cap_bytes, None,
+                                  lambda dev, st: scratch if scratch is not None else self.block_scratch(sym.numel(), 0, dev))
+
+    def encode_block_device(self, sym):
+        """1-D symbol tensor on the device -> (uint8 tensor holding the stream, nbits, status).  Waits for the result."""
+        import torch
+
+        out = torch.empty(self.slot_bytes(sym.numel()), dtype=torch.uint8, device=sym.device)
+        nbits, status = (int(v) for v in self.encode_block_into(sym, out).cpu())
+        return out[: (nbits + 7) // 8], nbits, status & 0xFFFFFFFF
+
+    def decode_block_device(self, data, nbits: int, bit_offset: int = 0, out_cap: Optional[int] = None, out=None, scratch=None):
+        """the ``nbits`` bits from bit ``bit_offset`` of the uint8 device tensor ``data`` -> (symbols, n_out, consumed, status,
+        sync_passes); ``out_cap`` and ``n_out`` count symbols.  The call synchronises the current stream."""
+        cap = self.max_symbols(nbits) if out_cap is None else int(out_cap)
+        return _decode_block_device(functools.partial(self._sym_fn("decode_block"), self._h), "scl_typical_decode_block", data,
+                                    nbits, bit_offset, cap, out, self._torch_sym_dtypes(), self.min_len, None,
+                                    lambda dev, st: scratch if scratch is not None else self.block_scratch(0, nbits, dev))
+
+
 class FixedWidthCode:
     """fixed-width codes of symbol indices: index ``i`` of a stream of width ``w`` is the stream's bits ``[i * w, (i + 1) * w)``
     (csrc/scl_fixed.hip).  There is no table and no device handle, not even a parameter: every stream of a batch brings its own
