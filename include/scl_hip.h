@@ -770,7 +770,8 @@ int scl_lz77_sliding_replay_batch(const scl_lz77_sliding_replay_args *args, void
 int scl_lz77_sliding_kernel_names(char *index, char *parse, char *replay, uint64_t cap);
 /* bucket of the gram gram[0..hl): the function the kernels use, on the host.  0 for a null gram, hl outside 1..8 or m = 0 */
 uint32_t scl_lz77_sliding_bucket_host(const uint8_t *gram, uint32_t hl, uint32_t m);
-/* one stream in host memory, as scl_lz77_parse_host / scl_lz77_replay_host (always on one wavefront) */
+/* one stream in host memory, as scl_lz77_parse_host / scl_lz77_replay_host: on one wavefront below
+   scl_lz77_sliding_wide_threshold() block bytes, across the whole GPU from there on (scl_lz77_sliding_*_wide below) */
 int scl_lz77_sliding_parse_host(const uint8_t *h_window, uint64_t n, uint64_t start, uint32_t hash_length,
                                 uint64_t hash_table_size, uint32_t max_chain_length, uint32_t lazy,
                                 uint32_t min_match_length, uint32_t window_size, uint32_t *h_lit_count,
@@ -839,6 +840,77 @@ void scl_lz77_wide_shape(uint32_t *tile, uint32_t *cap);
 uint64_t scl_lz77_wide_threshold(void);
 /* the kernels that carry the scoring, the walk and the replay's pointer doubling, as scl_lz77_kernel_names */
 int scl_lz77_wide_kernel_names(char *score, char *walk, char *resolve, uint64_t cap);
+
+/* ---- LZ77 with a sliding window: one large stream across the whole GPU (scl_lz77_sliding_wide.hip; added to ABI 8) --------
+ * scl_lz77_sliding_parse_batch / scl_lz77_sliding_replay_batch give every stream one wavefront.  These two calls take ONE
+ * stream and use the whole chip; what they store is what the batch calls store for a batch of that one stream, bit for
+ * bit: sequences, literals, d_n_seq, d_n_lit, d_out_len, d_status.  DESIGN.md 3.6.5 has the scheme and why it is exact.
+ *   parse : the window is d_win[0..n), the block starts at `start` (host values: they size the launches); the parameters
+ *           are scl_lz77_sliding_parse_args'.  The sequence that starts at E is a function of E and the window alone, so
+ *           the parse is the orbit of that function from `start`.  After the batch call's index phase: every
+ *           candidate bit that can lead to no match under any E is cleared (the filtered bitmap); one wavefront per
+ *           segment of `segment` positions follows the orbit from the segment's first position and stores every sequence
+ *           in a table addressed by its E, right extensions capped at `cap` bytes and the search for a first match bounded
+ *           by the end of the next segment (a sequence that reaches either is stored as OPEN and ends the segment's orbit);
+ *           ONE wavefront then walks from `start`: a stored sequence is followed (a speculated one straight to its
+ *           segment's exit), any other position is computed by the one-wave kernel's own code; one wavefront per segment
+ *           writes rows and its own segment's literal bytes after scans over the segments.  scl_lz77_sliding_wide_shape.
+ *           d_literals is laid out like d_win: d_n_lit bytes at d_literals + start.  d_status: SCL_ST_CAPACITY as in the
+ *           batch call.
+ *   replay: scl_lz77_replay_wide's kernels with the window's two rules: a sequence with match_length 0 copies nothing and
+ *           its offset is not looked at, and an offset above min(W, bytes so far) is SCL_ST_STATE (W = 0: no bound).  Its
+ *           scratch is scl_lz77_wide_replay_scratch_bytes(n_seq, cap - have).
+ * Both are asynchronous on `stream` and read their scratch until they finish.  SCL_E_PARAM before any device call: a null
+ * pointer, hl outside 1..8, m = 0 or m >= 2^32, C outside 1..64, mml = 0, n or cap >= 2^32, start > n, have > cap, phases
+ * above 15, scratch misaligned (256 bytes) or smaller than scl_lz77_sliding_wide_scratch_bytes(n) /
+ * scl_lz77_wide_replay_scratch_bytes(n_seq, cap - have). */
+#define SCL_LZ77_SLIDING_WIDE_INDEX 1u
+#define SCL_LZ77_SLIDING_WIDE_SPECULATE 2u
+#define SCL_LZ77_SLIDING_WIDE_WALK 4u
+#define SCL_LZ77_SLIDING_WIDE_EMIT 8u
+
+typedef struct scl_lz77_sliding_wide_parse_args {
+    const uint8_t *d_win;
+    uint64_t n, start;
+    uint64_t hash_table_size;
+    uint32_t hash_length, max_chain_length;
+    uint32_t lazy, min_match_length;
+    uint32_t window_size, seq_cap;
+    uint32_t phases, reserved; /* phases: 0 = all, else a mask of SCL_LZ77_SLIDING_WIDE_* run on the same scratch, in this
+                                  order (for measurements; a walk that is repeated follows what the first one stored) */
+    uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [seq_cap] each */
+    uint8_t *d_literals;                               /* n bytes */
+    uint32_t *d_n_seq, *d_n_lit, *d_status;            /* one word each */
+    void *d_scratch;
+    uint64_t scratch_bytes;
+} scl_lz77_sliding_wide_parse_args;
+
+typedef struct scl_lz77_sliding_wide_replay_args {
+    uint8_t *d_win;
+    uint64_t have, cap;
+    const uint32_t *d_lit_count, *d_match_len, *d_match_off; /* [n_seq] each */
+    uint64_t n_seq;
+    const uint8_t *d_literals;
+    uint64_t n_lit;
+    uint32_t *d_out_len, *d_status; /* one word each */
+    void *d_scratch;
+    uint64_t scratch_bytes;
+    uint32_t window_size, reserved;
+} scl_lz77_sliding_wide_replay_args;
+
+/* about 29.6 bytes per window byte: the batch call's index (12 for the sort's two permutations and its inverse, 4 for the
+   keys, 0.4 for the bitmap and the histograms), 12 for the sequence table, 1 for its marks, 0.125 for the filtered bitmap,
+   and 24 per segment */
+uint64_t scl_lz77_sliding_wide_scratch_bytes(uint64_t n);
+int scl_lz77_sliding_parse_wide(const scl_lz77_sliding_wide_parse_args *args, void *stream);
+int scl_lz77_sliding_replay_wide(const scl_lz77_sliding_wide_replay_args *args, void *stream);
+/* the compile-time shape: positions per segment and the cap of a speculated right extension; either may be NULL */
+void scl_lz77_sliding_wide_shape(uint32_t *segment, uint32_t *cap);
+/* scl_lz77_sliding_parse_host takes the wide path for a block of at least this many bytes, scl_lz77_sliding_replay_host
+   for cap - have of at least this many; below it the one-wave path.  Same results either way. */
+uint64_t scl_lz77_sliding_wide_threshold(void);
+/* the kernels that carry the speculation, the walk and the emission, as scl_lz77_kernel_names */
+int scl_lz77_sliding_wide_kernel_names(char *speculate, char *walk, char *emit, uint64_t cap);
 
 /* ---- LZ77: the entropy stage, sequences and literals <-> block bits (scl_lz77_entropy.hip; added to ABI 8 as above) -------
  *   scl_lz77_entropy_encode_batch  <->  LZ77StreamsEncoder.encode_block   scl/compressors/lz77.py:301-361

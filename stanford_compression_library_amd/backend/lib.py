@@ -122,6 +122,21 @@ class Lz77WideReplayArgs(C.Structure):
                 ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
 
 
+class Lz77SlidingWideParseArgs(C.Structure):
+    """scl_lz77_sliding_wide_parse_args"""
+    _fields_ = [("d_win", C.c_void_p), ("n", C.c_uint64), ("start", C.c_uint64), ("hash_table_size", C.c_uint64),
+                ("hash_length", C.c_uint32), ("max_chain_length", C.c_uint32), ("lazy", C.c_uint32),
+                ("min_match_length", C.c_uint32), ("window_size", C.c_uint32), ("seq_cap", C.c_uint32),
+                ("phases", C.c_uint32), ("reserved", C.c_uint32), ("d_lit_count", C.c_void_p), ("d_match_len", C.c_void_p),
+                ("d_match_off", C.c_void_p), ("d_literals", C.c_void_p), ("d_n_seq", C.c_void_p), ("d_n_lit", C.c_void_p),
+                ("d_status", C.c_void_p), ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_uint64)]
+
+
+class Lz77SlidingWideReplayArgs(C.Structure):
+    """scl_lz77_sliding_wide_replay_args"""
+    _fields_ = Lz77WideReplayArgs._fields_ + [("window_size", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Lz77EntropyEncodeArgs(C.Structure):
     """scl_lz77_entropy_encode_args"""
     _fields_ = [("n_streams", C.c_uint64), ("seq_cap", C.c_uint32), ("binned_offset", C.c_uint32),
@@ -164,6 +179,7 @@ class Lz77EntropyWideDecodeArgs(C.Structure):
 
 LZ77_INDEX, LZ77_PARSE = 1, 2
 LZ77_WIDE_INDEX, LZ77_WIDE_SCORE, LZ77_WIDE_WALK, LZ77_WIDE_EMIT = 1, 2, 4, 8
+LZ77_SLIDING_WIDE_INDEX, LZ77_SLIDING_WIDE_SPECULATE, LZ77_SLIDING_WIDE_WALK, LZ77_SLIDING_WIDE_EMIT = 1, 2, 4, 8
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 _f64p = C.POINTER(C.c_double)
@@ -286,6 +302,13 @@ _SIGNATURES = {
     "scl_lz77_wide_shape": (None, [_u32p, _u32p]),
     "scl_lz77_wide_threshold": (_u64, []),
     "scl_lz77_wide_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
+    # LZ77 with a sliding window: one large stream across the whole GPU (scl_lz77_sliding_wide.hip)
+    "scl_lz77_sliding_wide_scratch_bytes": (_u64, [_u64]),
+    "scl_lz77_sliding_parse_wide": (_int, [C.POINTER(Lz77SlidingWideParseArgs), _vp]),
+    "scl_lz77_sliding_replay_wide": (_int, [C.POINTER(Lz77SlidingWideReplayArgs), _vp]),
+    "scl_lz77_sliding_wide_shape": (None, [_u32p, _u32p]),
+    "scl_lz77_sliding_wide_threshold": (_u64, []),
+    "scl_lz77_sliding_wide_kernel_names": (_int, [C.c_char_p, C.c_char_p, C.c_char_p, _u64]),
     # LZ77: the entropy stage (scl_lz77_entropy.hip)
     "scl_lz77_entropy_encode_batch": (_int, [C.POINTER(Lz77EntropyEncodeArgs), _vp]),
     "scl_lz77_entropy_decode_batch": (_int, [C.POINTER(Lz77EntropyDecodeArgs), _vp]),

@@ -15,7 +15,9 @@ Two call shapes, as in :mod:`.models`:
 * ``sliding_parse_host`` / ``sliding_replay_host`` / ``sliding_parse_batch`` / ``sliding_replay_batch`` /
   ``sliding_compress_batch`` / ``sliding_decompress_batch`` -- the same shapes for the sliding-window coder
   (csrc/scl_lz77_sliding.hip: hash-bucket index, lazy parse, windowed replay); its :class:`ParsedBatch` goes through the
-  same ``encode_batch``.
+  same ``encode_batch``.  From ``sliding_wide_threshold()`` bytes on the host calls spread the stream over the whole GPU;
+* ``sliding_parse_wide`` / ``sliding_replay_wide`` / ``sliding_compress_wide`` / ``sliding_decompress_wide`` -- that wide
+  path of the sliding-window coder on ONE stream resident in HBM (csrc/scl_lz77_sliding_wide.hip), the same results.
 
 A batch is ``n_streams`` windows laid out one after another in one uint8 tensor; ``win_off`` (int64, ``n_streams + 1``
 entries) says where each starts.  uint32 / uint64 arrays of the C ABI travel as int32 / int64 tensors (the bit patterns).
@@ -684,8 +686,9 @@ def sliding_bucket(gram, hash_table_size: int) -> int:
 
 
 def sliding_parse_host(window: np.ndarray, start: int, params: SlidingParams = SlidingParams()):
-    """``parse_host`` for the sliding-window coder (always one wavefront).  window: uint8 array = history + block, the block
-    starts at ``start``.  -> (literal_count, match_length, match_offset: uint32 arrays; literals: uint8 array)"""
+    """``parse_host`` for the sliding-window coder (from ``sliding_wide_threshold()`` block bytes on: the wide path).
+    window: uint8 array = history + block, the block starts at ``start``.
+    -> (literal_count, match_length, match_offset: uint32 arrays; literals: uint8 array)"""
     _lib.load()
     hl, m, chain, lazy, mml, W = params._c()
     if not (0 <= hl < 1 << 32 and 0 <= m < 1 << 64 and 0 <= chain < 1 << 32 and 0 <= mml < 1 << 32 and 0 <= W < 1 << 32):
@@ -743,3 +746,110 @@ def sliding_decompress_batch(bits, bit_offset, nbits, win, win_off, have, seq_ca
     """``decompress_batch`` for the sliding-window coder: decode + windowed replay -> (out_len, status, consumed)"""
     replay = lambda *rows, stream: sliding_replay_batch(*rows, window_size, stream=stream)  # noqa: E731
     return _decompress_batch(replay, bits, bit_offset, nbits, win, win_off, have, seq_cap, binned_offset, stream)
+
+
+# ---- sliding window, one large stream across the whole GPU (csrc/scl_lz77_sliding_wide.hip) -----------------------------------
+def sliding_wide_shape():
+    """-> (segment, cap): positions per speculated segment and the cap of a speculated right extension, compile-time"""
+    segment, cap = C.c_uint32(0), C.c_uint32(0)
+    _lib.load().scl_lz77_sliding_wide_shape(C.byref(segment), C.byref(cap))
+    return segment.value, cap.value
+
+
+def sliding_wide_threshold() -> int:
+    """block bytes from which ``sliding_parse_host`` / ``sliding_replay_host`` take the wide path"""
+    return int(_lib.load().scl_lz77_sliding_wide_threshold())
+
+
+def sliding_wide_scratch_bytes(n: int) -> int:
+    return int(_lib.load().scl_lz77_sliding_wide_scratch_bytes(int(n)))
+
+
+def sliding_wide_kernel_names():
+    """-> (speculate, walk, emit) kernel names as a kernel trace prints them"""
+    return _kernel_names("scl_lz77_sliding_wide_kernel_names")
+
+
+def sliding_parse_wide(win, start: int, params: SlidingParams = SlidingParams(), seq_cap: Optional[int] = None,
+                       scratch=None, stream=None, out: Optional[ParsedBatch] = None, phases: int = 0) -> ParsedBatch:
+    """``parse_wide`` for the sliding-window coder: ONE window whose block starts at ``start`` -> what
+    ``sliding_parse_batch`` returns for a batch of this one stream.  ``seq_cap`` defaults to ``sliding_seq_cap`` of the
+    block; ``scratch``: a uint8 tensor of at least ``sliding_wide_scratch_bytes(win.numel())`` bytes to reuse across calls;
+    ``phases``: 0 = everything, else a mask of ``lib.LZ77_SLIDING_WIDE_INDEX`` / ``_SPECULATE`` / ``_WALK`` / ``_EMIT`` run
+    on the same scratch (for measurements)."""
+    import torch
+
+    L = _lib.load()
+    assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous() and win.dim() == 1
+    dev, n, start = win.device, int(win.numel()), int(start)
+    hl, m, chain, lazy, mml, W = params._c()
+    if out is not None:
+        seq_cap = out.seq_cap
+    if seq_cap is None:
+        seq_cap = sliding_seq_cap(n - start, mml)
+    need = sliding_wide_scratch_bytes(n)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert scratch.numel() >= need
+    if out is None:
+        out = _new_parsed(1, seq_cap, n, torch.full((1,), start, dtype=torch.int64, device=dev), dev)
+    assert out.literal_count.shape == (1, out.seq_cap) and out.literals.numel() >= n
+    a = _lib.Lz77SlidingWideParseArgs(win.data_ptr(), n, start, m, hl, chain, lazy, mml, W, out.seq_cap, int(phases), 0,
+                                      out.literal_count.data_ptr(), out.match_length.data_ptr(),
+                                      out.match_offset.data_ptr(), out.literals.data_ptr(), out.n_seq.data_ptr(),
+                                      out.n_lit.data_ptr(), out.status.data_ptr(), scratch.data_ptr(), int(scratch.numel()))
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_sliding_parse_wide(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_sliding_parse_wide")
+    out._scratch = scratch  # the kernels read it asynchronously: it lives as long as the result
+    return out
+
+
+def sliding_replay_wide(win, have: int, literal_count, match_length, match_offset, n_seq: int, literals, n_lit: int,
+                        window_size: int = 0, cap=None, scratch=None, stream=None):
+    """``replay_wide`` with the window's rules (see :func:`sliding_replay_host`).  ``scratch``: at least
+    ``wide_replay_scratch_bytes(n_seq, cap - have)`` bytes.  -> (out_len, status): int32 [1] each."""
+    import torch
+
+    L = _lib.load()
+    assert win.is_cuda and win.dtype == torch.uint8 and win.is_contiguous() and literals.dtype == torch.uint8
+    rows = tuple(t.reshape(-1) for t in (literal_count, match_length, match_offset))
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= int(n_seq) for t in rows)
+    assert literals.numel() >= int(n_lit)
+    dev, have, cap = win.device, int(have), int(win.numel() if cap is None else cap)
+    assert cap <= win.numel()
+    need = wide_replay_scratch_bytes(n_seq, max(cap - have, 0))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert scratch.numel() >= need
+    out_len = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    a = _lib.Lz77SlidingWideReplayArgs(win.data_ptr(), have, cap, rows[0].data_ptr(), rows[1].data_ptr(),
+                                       rows[2].data_ptr(), int(n_seq), literals.data_ptr(), int(n_lit), out_len.data_ptr(),
+                                       status.data_ptr(), scratch.data_ptr(), int(scratch.numel()), int(window_size), 0)
+    with torch.cuda.device(dev):
+        rc = L.scl_lz77_sliding_replay_wide(C.byref(a), _stream_handle(stream, dev))
+    _lib.check(rc, "scl_lz77_sliding_replay_wide")
+    out_len._inputs = (rows, literals, scratch)  # read asynchronously: they live as long as the result
+    return out_len, status
+
+
+def sliding_compress_wide(win, start: int, params: SlidingParams = SlidingParams(), seq_cap: Optional[int] = None,
+                          binned_offset: int = DEFAULT_BINNED_OFFSET, out_stride: Optional[int] = None, scratch=None,
+                          stream=None, out: Optional[EncodedBatch] = None):
+    """``sliding_parse_wide`` + ``encode_wide``: the bits of ``sliding_compress_batch`` for a batch of this one stream ->
+    (:class:`EncodedBatch` of one slot, :class:`ParsedBatch`).  ``scratch`` serves both steps, one after the other."""
+    parsed = sliding_parse_wide(win, start, params, seq_cap=seq_cap, scratch=scratch, stream=stream)
+    return encode_wide(parsed, binned_offset, out_stride, lit_off=int(start), scratch=scratch, stream=stream, out=out), parsed
+
+
+def sliding_decompress_wide(bits, bit_offset: int, nbits: int, win, have: int, seq_cap: int, window_size: int = 0,
+                            binned_offset: int = DEFAULT_BINNED_OFFSET, scratch=None, stream=None):
+    """``decode_wide`` + ``sliding_replay_wide``: appends the block to ``win``, which holds ``have`` bytes already.
+    -> (out_len, status, consumed): status = the decoder's | the replay's."""
+    lit_cap = max(int(win.numel()) - int(have), 0)
+    decoded = decode_wide(bits, bit_offset, nbits, seq_cap, lit_cap, binned_offset, scratch=scratch, stream=stream)
+    n_seq, n_lit = (int(x) & 0xFFFFFFFF for x in decoded._inputs[2][2:4].cpu().tolist())
+    out_len, status = sliding_replay_wide(win, have, decoded.literal_count, decoded.match_length, decoded.match_offset, n_seq,
+                                          decoded.literals, n_lit, window_size, stream=stream)
+    return out_len, status | decoded.status, decoded.consumed

@@ -9,11 +9,13 @@ Drop-in for reference scl/compressors/lz77_sliding_window.py: ``LZ77Window``, ``
   ``window_size`` bytes of its history plus the block to ``backend.lz77.sliding_parse_host`` (csrc/scl_lz77_sliding.hip,
   DESIGN.md 3.6.4), which indexes them anew and implements the finder's rule bit for bit: hash buckets, capped chains, the
   window test, right and left extension, lazy matching at the horizon of the first match.  Older bytes cannot change the
-  outcome.  A block is parsed on ONE wavefront at any size (``backend.lz77.sliding_parse_batch`` is the call for many
-  streams; there is no whole-GPU path for one large stream of this coder).
+  outcome.  A block below ``backend.lz77.sliding_wide_threshold()`` bytes is parsed on ONE wavefront; from there on the
+  host call spreads it over the whole GPU (csrc/scl_lz77_sliding_wide.hip), with the same sequences and
+  literals.  ``backend.lz77.sliding_parse_batch`` is the call for many streams.
 * Any other ``MatchFinderBase`` runs the reference's host loop over ``find_best_match``, so a user's own finder works; it
   is as slow as Python is.
 * The decoder replays on the device with the window's rules: an offset beyond ``min(window_size, bytes so far)`` raises.
+  A block of ``sliding_wide_threshold()`` bytes or more is replayed across the whole GPU, with the same bytes and errors.
 
 Parameters the device refuses raise ``NotImplementedError``: ``hash_length`` outside 1..8, ``hash_table_size`` of 2^32 or
 more, ``max_chain_length`` outside 1..64, and ``minimum_match_length`` 0, with which the reference loops forever.

@@ -1,13 +1,15 @@
 // scl_lz77_internal.h -- shapes, scratch layout and shared device code of the LZ77 kernels (scl_lz77.hip: batches, one
 // wavefront per stream; scl_lz77_wide.hip: one stream across the whole GPU; scl_lz77_sliding.hip: the sliding-window coder,
-// one wavefront per stream).  Internal to csrc/.
+// one wavefront per stream; scl_lz77_sliding_wide.hip: that coder's one stream across the whole GPU).  Internal to csrc/.
 //
 // Written once for the greedy and the sliding-window coder, which differ in their match rule and in two replay rules:
 //   device  lz_replay_frame<WINDOWED> (all of a replay kernel), the index sort, lz_score / lz_extend,
 //           lz_replay_stream<WINDOWED>.  NOT what stands around the match rule of the two parse kernels (prologue, emit
 //           step, epilogue): a frame around them left lz77_sliding_parse its registers but measured slower
 //           (profiles/lz77_frame_codegen.txt, profiles/lz77_frame_timing.txt), so both kernels keep their own lines
-//   entry   lz77_parse_check, lz77_scratch_carve, lz77_replay_launch
+//           lz_sliding_sequence / lz_sliding_best: the sliding-window coder's match rule, one sequence from E, for its
+//           one-wave parse and its wide kernels alike (as lz_score serves both greedy parses)
+//   entry   lz77_parse_check, lz77_scratch_carve, lz77_replay_launch, sliding_scratch_layout, sliding_check_params
 //   host    LzMeta, LzHostFrame (parse_open / parse_close, replay_open / replay_close)
 #pragma once
 
@@ -91,6 +93,31 @@ static inline int lz77_parse_check(const char *what, const A *a, Params params,
     SCL_REQUIRE(((uintptr_t)a->d_scratch & 255) == 0 && a->scratch_bytes >= need,
                 "%s: d_scratch must be 256-byte aligned and hold %s = %llu bytes", what, scratch_name,
                 (unsigned long long)need);
+    return SCL_OK;
+}
+
+// ---- the sliding-window coder's scratch and parameters (scl_lz77_sliding.hip, scl_lz77_sliding_wide.hip) ------------------
+#define LZ_NO_KEY 0xFFFFFFFFu  // m < 2^32, so no bucket has this number
+
+struct SlidingScratch {
+    Lz77Scratch index;  // order_a, order_b, rank, bitmap, hist, block_sums as in the greedy index
+    u64 key, total;
+};
+
+static inline SlidingScratch sliding_scratch_layout(u64 N) {
+    SlidingScratch s;
+    s.index = lz77_scratch_layout(N);
+    s.key = s.index.total;
+    s.total = s.key + scl_round_up(N * 4 ? N * 4 : 1, 256);
+    return s;
+}
+
+static inline int sliding_check_params(const char *what, u32 hl, u64 m, u32 C, u32 mml) {
+    SCL_REQUIRE(hl >= 1 && hl <= 8, "%s: hash_length %u: 1 <= hash_length <= 8", what, hl);
+    SCL_REQUIRE(m >= 1 && m < (1ull << 32), "%s: hash_table_size %llu: a bucket number is 32-bit, 1 <= hash_table_size < 2^32",
+                what, (unsigned long long)m);
+    SCL_REQUIRE(C >= 1 && C <= 64, "%s: max_chain_length %u: one candidate per lane, 1 <= max_chain_length <= 64", what, C);
+    SCL_REQUIRE(mml >= 1, "%s: min_match_length 0: a match has at least one byte", what);
     return SCL_OK;
 }
 
@@ -340,6 +367,141 @@ __device__ __forceinline__ u32 lz_score(const u8 *win, u64 base, u64 gp, u32 lim
     }
     *best_q_out = best_q;
     return best_len;
+}
+
+// ---- the sliding-window coder's match rule: the one-wave parse and the wide kernels -------------
+// The best match for position p of the stream at `base` (n bytes) at horizon T <= p, the lookahead starting at E <= T; all
+// arguments are wave-uniform and p + hl <= n.  The entries in front of rank[p] are p's older bucket-mates, newest first;
+// those at or past T come first and are skipped (at most p - T), then lane k < C takes the k-th.  A candidate more than W
+// back is not scored but keeps its lane.  -> the length after both extensions (0: none), *lits_out = where the match
+// starts, counted from E, *off_out = its offset.  CAPPED: no right extension reads more than `cap` bytes, and *capped
+// says that a scored candidate reached the cap with bytes left in the window (the lengths are then lower bounds only;
+// with *capped false every number is the uncapped call's).  FAR: lz_extend_far, for a caller whose matches run far (the same
+// numbers).
+template <bool CAPPED, bool FAR = false>
+__device__ __forceinline__ u32 lz_sliding_best(const u8 *win, u64 N, u64 base, u32 n, u32 E, u32 p, u32 T, u32 C, u32 W,
+                                               const u32 *order, const u32 *rank, const u32 *key, u32 cap, bool *capped,
+                                               u32 *lits_out, u32 *off_out) {
+    const u32 lane = lz_lane();
+    const u64 gp = base + p, gT = base + T;
+    const u32 i = rank[gp], kp = key[gp];
+    if (CAPPED) *capped = false;
+    if (i >= N) return 0;  // not an index of this buffer: nothing to look at
+    u32 skip = 0;
+    if (T < p) {
+        while (true) {
+            const u64 back = (u64)skip + lane;
+            bool late = false;
+            if (back < i) {
+                const u32 c = order[i - 1 - back];
+                late = c >= gT && c < gp && key[c] == kp;
+            }
+            const u64 mask = __ballot(late);
+            if (mask != ~0ull) {
+                skip += (u32)__builtin_ctzll(~mask);
+                break;
+            }
+            skip += SCL_WAVE;
+        }
+    }
+    const u64 back = (u64)skip + lane;
+    u32 c = 0, start = p;
+    u64 score = 0;  // (length, 63 - lane): the maximum is the longest match, the newest on ties
+    bool ok = lane < C && back < i, reached = false;
+    if (ok) {
+        c = order[i - 1 - back];
+        ok = c >= base && c < gT && key[c] == kp && gp - c <= W;
+    }
+    if (ok) {
+        const u8 *w = win + base;
+        u32 q = (u32)(c - base);
+        const u32 limit = CAPPED && cap < n - p ? cap : n - p;
+        u32 len = FAR ? lz_extend_far(win + c, win + gp, 0, limit) : lz_extend(win + c, win + gp, 0, limit);
+        if (CAPPED) reached = cap < n - p && len >= cap;
+        const u32 first = E > W ? E - W : 0;  // the oldest byte the coder's window still holds
+        while (start > E && q > first && w[start - 1] == w[q - 1]) {
+            --start;
+            --q;
+            ++len;
+        }
+        score = ((u64)len << 6) | (63u - lane);
+    }
+    if (CAPPED) *capped = __ballot(reached) != 0;
+    for (u32 d = 32; d; d >>= 1) {
+        const u32 lo = __shfl_xor((u32)score, d), hi = __shfl_xor((u32)(score >> 32), d);
+        const u64 other = ((u64)hi << 32) | lo;
+        score = other > score ? other : score;
+    }
+    const u32 best_len = (u32)(score >> 6);
+    if (best_len == 0) return 0;
+    const u32 winner = 63u - (u32)(score & 63);
+    *lits_out = (u32)__builtin_amdgcn_readlane((int)(start - E), (int)winner);
+    *off_out = (u32)__builtin_amdgcn_readlane((int)(u32)(gp - c), (int)winner);
+    return best_len;
+}
+
+// ONE SEQUENCE FROM E < n: f(E) of DESIGN.md 3.6.5, the whole wave together, all arguments wave-uniform.  From E the first
+// position whose best match has mml bytes or more is taken (the bitmap says where a candidate exists at all); if `lazy`,
+// the positions behind it are tried at the same horizon while each beats the best so far.  -> (*lits, *len, *off); the
+// next sequence starts at E + *lits + *len.  It reads E, the index and the bytes, and nothing else.
+// BOUNDED (the wide parse's speculation): right extensions are capped at `cap` bytes and the search for the first match
+// stops in front of position `bound`; returns true -- OPEN, the outputs mean nothing -- if any scored candidate reached
+// the cap or the search reached the bound with positions left.  Returning false, every number is the unbounded call's.
+// Unbounded, the return value is false.  FAR: as in lz_sliding_best (the walk of the wide parse, where one wavefront extends
+// the long matches alone).
+template <bool BOUNDED, bool FAR = false>
+__device__ __forceinline__ bool lz_sliding_sequence(const u8 *win, u64 N, u64 base, u32 n, u32 E, u32 hl, u32 C, u32 lazy,
+                                                    u32 mml, u32 W, const u32 *order, const u32 *rank, const u32 *key,
+                                                    const u64 *bitmap, u32 cap, u32 bound, u32 *lits_out, u32 *len_out,
+                                                    u32 *off_out) {
+    u32 lits = n - E, len = 0, off = 0;  // fewer than hl bytes left: all literals
+    bool open = false, capped = false;
+    if (n - E >= hl) {
+        const u32 stop = n - hl + 1;  // the positions [E, stop) have a whole gram
+        const u32 search_end = BOUNDED && bound < stop ? bound : stop;
+        lits = stop - E;
+        u32 from = E;
+        while (true) {
+            const u64 g = lz_next_bit(bitmap, base + from, base + search_end);
+            if (g >= base + search_end) {
+                open = search_end < stop;
+                break;
+            }
+            const u32 p = (u32)(g - base);
+            u32 b_lits = 0, b_off = 0;
+            const u32 b_len =
+                lz_sliding_best<BOUNDED, FAR>(win, N, base, n, E, p, p, C, W, order, rank, key, cap, &capped, &b_lits, &b_off);
+            if (BOUNDED && capped) {
+                open = true;
+                break;
+            }
+            if (b_len >= mml) {
+                len = b_len;
+                lits = b_lits;
+                off = b_off;
+                if (lazy) {  // the positions behind p, at p's horizon, while each beats the best so far
+                    for (u32 pj = p + 1; pj < stop; ++pj) {
+                        const u32 l = lz_sliding_best<BOUNDED, FAR>(win, N, base, n, E, pj, p, C, W, order, rank, key, cap, &capped,
+                                                               &b_lits, &b_off);
+                        if (BOUNDED && capped) {
+                            open = true;
+                            break;
+                        }
+                        if (l <= len) break;
+                        len = l;
+                        lits = b_lits;
+                        off = b_off;
+                    }
+                }
+                break;
+            }
+            from = p + 1;
+        }
+    }
+    *lits_out = lits;
+    *len_out = len;
+    *off_out = off;
+    return open;
 }
 
 // ---- the index sort's kernels, shared by the greedy index (scl_lz77.hip) and the hash-bucket index (scl_lz77_sliding.hip)

@@ -12,12 +12,12 @@
 //   bitmap: one bit per position: the newest older position of its bucket lies within W.  Every candidate at every
 //           horizon is such a position, so a clear bit means "no match here" for the walk that looks for the first match;
 //   parse : ONE WAVEFRONT PER STREAM; at p, lane k < C takes the k-th newest bucket-mate below the horizon, extends right
-//           and left, and a wave maximum over (length, 63 - lane) picks the longest, the newest on ties.
+//           and left, and a wave maximum over (length, 63 - lane) picks the longest, the newest on ties.  The rule itself --
+//           one sequence from E -- is lz_sliding_sequence of scl_lz77_internal.h, which the kernels for ONE large stream
+//           (scl_lz77_sliding_wide.hip) call too; the *_host calls below choose between the two.
 // No workgroup waits on another, every loop is bounded by the data, and reads and writes are checked against the buffers'
 // sizes on any input.
 #include "scl_lz77_internal.h"
-
-#define LZ_NO_KEY 0xFFFFFFFFu  // m < 2^32, so no bucket has this number
 
 // CPython's hash(tuple(bytes)) % m (Objects/tupleobject.c, 64-bit build; the hash of a small int is the int itself)
 __host__ __device__ static inline u32 lz_sliding_bucket(const u8 *gram, u32 hl, u64 m) {
@@ -77,68 +77,6 @@ __global__ __launch_bounds__(256) void lz77_sliding_bitmap(u64 N, const u64 *win
     if (lz_lane() == 0 && (g >> 6) < (N + 63) / 64) bitmap[g >> 6] = word;
 }
 
-// The best match for position p of the stream at `base` (n bytes) at horizon T <= p, the lookahead starting at E <= T; all
-// arguments are wave-uniform and p + hl <= n.  The entries in front of rank[p] are p's older bucket-mates, newest first;
-// those at or past T come first and are skipped (at most p - T), then lane k < C takes the k-th.  A candidate more than W
-// back is not scored but keeps its lane.  -> the length after both extensions (0: none), *lits_out = where the match
-// starts, counted from E, *off_out = its offset.
-__device__ __forceinline__ u32 lz_sliding_best(const u8 *win, u64 N, u64 base, u32 n, u32 E, u32 p, u32 T, u32 C, u32 W,
-                                               const u32 *order, const u32 *rank, const u32 *key, u32 *lits_out,
-                                               u32 *off_out) {
-    const u32 lane = lz_lane();
-    const u64 gp = base + p, gT = base + T;
-    const u32 i = rank[gp], kp = key[gp];
-    if (i >= N) return 0;  // not an index of this buffer: nothing to look at
-    u32 skip = 0;
-    if (T < p) {
-        while (true) {
-            const u64 back = (u64)skip + lane;
-            bool late = false;
-            if (back < i) {
-                const u32 c = order[i - 1 - back];
-                late = c >= gT && c < gp && key[c] == kp;
-            }
-            const u64 mask = __ballot(late);
-            if (mask != ~0ull) {
-                skip += (u32)__builtin_ctzll(~mask);
-                break;
-            }
-            skip += SCL_WAVE;
-        }
-    }
-    const u64 back = (u64)skip + lane;
-    u32 c = 0, start = p;
-    u64 score = 0;  // (length, 63 - lane): the maximum is the longest match, the newest on ties
-    bool ok = lane < C && back < i;
-    if (ok) {
-        c = order[i - 1 - back];
-        ok = c >= base && c < gT && key[c] == kp && gp - c <= W;
-    }
-    if (ok) {
-        const u8 *w = win + base;
-        u32 q = (u32)(c - base);
-        u32 len = lz_extend(win + c, win + gp, 0, n - p);
-        const u32 first = E > W ? E - W : 0;  // the oldest byte the coder's window still holds
-        while (start > E && q > first && w[start - 1] == w[q - 1]) {
-            --start;
-            --q;
-            ++len;
-        }
-        score = ((u64)len << 6) | (63u - lane);
-    }
-    for (u32 d = 32; d; d >>= 1) {
-        const u32 lo = __shfl_xor((u32)score, d), hi = __shfl_xor((u32)(score >> 32), d);
-        const u64 other = ((u64)hi << 32) | lo;
-        score = other > score ? other : score;
-    }
-    const u32 best_len = (u32)(score >> 6);
-    if (best_len == 0) return 0;
-    const u32 winner = 63u - (u32)(score & 63);
-    *lits_out = (u32)__builtin_amdgcn_readlane((int)(start - E), (int)winner);
-    *off_out = (u32)__builtin_amdgcn_readlane((int)(u32)(gp - c), (int)winner);
-    return best_len;
-}
-
 __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_parse(const u8 *win, u64 N, const u64 *win_off,
                                                                         const u32 *start, u32 n_streams, u32 hl, u32 C,
                                                                         u32 lazy, u32 mml, u32 W, const u32 *order,
@@ -166,35 +104,9 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_parse(const u8
                 status |= SCL_ST_CAPACITY;
                 break;
             }
-            u32 lits = n - E, len = 0, off = 0;  // fewer than hl bytes left: all literals
-            if (n - E >= hl) {
-                const u32 stop = n - hl + 1;  // the positions [E, stop) have a whole gram
-                lits = stop - E;
-                u32 from = E;
-                while (true) {
-                    const u64 g = lz_next_bit(bitmap, base + from, base + stop);
-                    if (g >= base + stop) break;
-                    const u32 p = (u32)(g - base);
-                    u32 b_lits = 0, b_off = 0;
-                    const u32 b_len = lz_sliding_best(win, N, base, n, E, p, p, C, W, order, rank, key, &b_lits, &b_off);
-                    if (b_len >= mml) {
-                        len = b_len;
-                        lits = b_lits;
-                        off = b_off;
-                        if (lazy) {  // the positions behind p, at p's horizon, while each beats the best so far
-                            for (u32 pj = p + 1; pj < stop; ++pj) {
-                                const u32 l = lz_sliding_best(win, N, base, n, E, pj, p, C, W, order, rank, key, &b_lits, &b_off);
-                                if (l <= len) break;
-                                len = l;
-                                lits = b_lits;
-                                off = b_off;
-                            }
-                        }
-                        break;
-                    }
-                    from = p + 1;
-                }
-            }
+            u32 lits, len, off;  // one sequence from E: the rule itself is lz_sliding_sequence (scl_lz77_internal.h)
+            (void)lz_sliding_sequence<false>(win, N, base, n, E, hl, C, lazy, mml, W, order, rank, key, bitmap, 0, 0, &lits,
+                                             &len, &off);
             for (u32 k = lane; k < lits; k += SCL_WAVE) lit[n_lit + k] = w[E + k];
             if (lane == 0) {
                 out_lc[n_seq] = lits;
@@ -225,32 +137,10 @@ __global__ __launch_bounds__(LZ_STREAM_THREADS) void lz77_sliding_replay(u8 *win
                           literals, lit_bytes, lit_off, n_lit_in, out_len, status_out);
 }
 
-struct SlidingScratch {
-    Lz77Scratch index;  // order_a, order_b, rank, bitmap, hist, block_sums as in the greedy index
-    u64 key, total;
-};
-
-SlidingScratch sliding_scratch_layout(u64 N) {
-    SlidingScratch s;
-    s.index = lz77_scratch_layout(N);
-    s.key = s.index.total;
-    s.total = s.key + scl_round_up(N * 4 ? N * 4 : 1, 256);
-    return s;
-}
-
 u32 key_passes(u64 m) {  // bytes of the largest bucket number, at least one pass
     u32 passes = 1;
     while (passes < 4 && ((m - 1) >> (8 * passes))) ++passes;
     return passes;
-}
-
-int sliding_check_params(const char *what, u32 hl, u64 m, u32 C, u32 mml) {
-    SCL_REQUIRE(hl >= 1 && hl <= 8, "%s: hash_length %u: 1 <= hash_length <= 8", what, hl);
-    SCL_REQUIRE(m >= 1 && m < (1ull << 32), "%s: hash_table_size %llu: a bucket number is 32-bit, 1 <= hash_table_size < 2^32",
-                what, (unsigned long long)m);
-    SCL_REQUIRE(C >= 1 && C <= 64, "%s: max_chain_length %u: one candidate per lane, 1 <= max_chain_length <= 64", what, C);
-    SCL_REQUIRE(mml >= 1, "%s: min_match_length 0: a match has at least one byte", what);
-    return SCL_OK;
 }
 
 }  // namespace
@@ -328,7 +218,9 @@ extern "C" int scl_lz77_sliding_parse_host(const uint8_t *h_window, uint64_t n, 
     SCL_REQUIRE(n < (1ull << 32) && start <= n && seq_cap < (1ull << 32), "%s: start <= n < 2^32 and seq_cap < 2^32", what);
     SCL_REQUIRE(lit_cap >= n - start, "%s: h_literals must hold the block (%llu bytes)", what,
                 (unsigned long long)(n - start));
-    const u64 scratch_bytes = scl_lz77_sliding_scratch_bytes(n, 1);
+    // a large block goes across the whole GPU (scl_lz77_sliding_wide.hip); the results are the same either way
+    const bool wide = n - start >= scl_lz77_sliding_wide_threshold();
+    const u64 scratch_bytes = wide ? scl_lz77_sliding_wide_scratch_bytes(n) : scl_lz77_sliding_scratch_bytes(n, 1);
     LzHostFrame f;
     scl_lz77_sliding_parse_args a = {};
     int rc = f.parse_open(a, h_window, n, start, seq_cap, scratch_bytes);
@@ -339,7 +231,31 @@ extern "C" int scl_lz77_sliding_parse_host(const uint8_t *h_window, uint64_t n, 
     a.lazy = lazy;
     a.min_match_length = min_match_length;
     a.window_size = window_size;
-    rc = scl_lz77_sliding_parse_batch(&a, nullptr);
+    if (wide) {
+        scl_lz77_sliding_wide_parse_args w = {};
+        w.d_win = a.d_win;
+        w.n = n;
+        w.start = start;
+        w.hash_table_size = hash_table_size;
+        w.hash_length = hash_length;
+        w.max_chain_length = max_chain_length;
+        w.lazy = lazy;
+        w.min_match_length = min_match_length;
+        w.window_size = window_size;
+        w.seq_cap = a.seq_cap;
+        w.d_lit_count = a.d_lit_count;
+        w.d_match_len = a.d_match_len;
+        w.d_match_off = a.d_match_off;
+        w.d_literals = a.d_literals;
+        w.d_n_seq = a.d_n_seq;
+        w.d_n_lit = a.d_n_lit;
+        w.d_status = a.d_status;
+        w.d_scratch = a.d_scratch;
+        w.scratch_bytes = scratch_bytes;
+        rc = scl_lz77_sliding_parse_wide(&w, nullptr);
+    } else {
+        rc = scl_lz77_sliding_parse_batch(&a, nullptr);
+    }
     return rc ? rc : f.parse_close(what, start, h_lit_count, h_match_len, h_match_off, n_seq, h_literals, n_lit);
 }
 
@@ -353,11 +269,33 @@ extern "C" int scl_lz77_sliding_replay_host(uint8_t *h_window, uint64_t have, ui
                 "%s: null pointer argument", what);
     SCL_REQUIRE(cap < (1ull << 32) && have <= cap && n_seq < (1ull << 32) && n_lit < (1ull << 32),
                 "%s: have <= cap < 2^32, n_seq and n_lit < 2^32", what);
+    const bool wide = cap - have >= scl_lz77_sliding_wide_threshold();  // as in scl_lz77_sliding_parse_host
+    const u64 scratch_bytes = wide ? scl_lz77_wide_replay_scratch_bytes(n_seq, cap - have) : 0;
     LzHostFrame f;
     scl_lz77_sliding_replay_args a = {};
-    int rc = f.replay_open(a, h_window, have, cap, h_lit_count, h_match_len, h_match_off, n_seq, h_literals, n_lit, 0);
+    int rc = f.replay_open(a, h_window, have, cap, h_lit_count, h_match_len, h_match_off, n_seq, h_literals, n_lit,
+                           scratch_bytes);
     if (rc) return rc;
     a.window_size = window_size;
-    rc = scl_lz77_sliding_replay_batch(&a, nullptr);
+    if (wide) {
+        scl_lz77_sliding_wide_replay_args w = {};
+        w.d_win = a.d_win;
+        w.have = have;
+        w.cap = cap;
+        w.d_lit_count = a.d_lit_count;
+        w.d_match_len = a.d_match_len;
+        w.d_match_off = a.d_match_off;
+        w.n_seq = n_seq;
+        w.d_literals = a.d_literals;
+        w.n_lit = n_lit;
+        w.d_out_len = a.d_out_len;
+        w.d_status = a.d_status;
+        w.d_scratch = f.d_scr.p;
+        w.scratch_bytes = scratch_bytes;
+        w.window_size = window_size;
+        rc = scl_lz77_sliding_replay_wide(&w, nullptr);
+    } else {
+        rc = scl_lz77_sliding_replay_batch(&a, nullptr);
+    }
     return rc ? rc : f.replay_close(what, h_window, have, out_len);
 }

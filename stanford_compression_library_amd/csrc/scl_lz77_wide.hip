@@ -307,41 +307,49 @@ __global__ __launch_bounds__(256) void lz77w_replay_sums(const u32 *lit_count, c
 }
 
 // the checks of sequence k in the one-wave kernel's order; d = output position and lp = literal position in front of it.
-// -> 0, or the status; *with_literals: the literal run is produced all the same (the fault is in the match)
-__device__ __forceinline__ u32 lz77w_check(u64 d, u64 lp, u32 run, u32 len, u32 off, u64 cap, u64 n_lit,
+// -> 0, or the status; *with_literals: the literal run is produced all the same (the fault is in the match).  The one
+// place that decides statuses, for both coders: WINDOWED (the sliding-window coder, lz_replay_stream<true>) a sequence
+// with match length 0 copies nothing and its offset is not looked at, and an offset above `window` (0: no bound) is
+// SCL_ST_STATE.
+template <bool WINDOWED>
+__device__ __forceinline__ u32 lz77w_check(u64 d, u64 lp, u32 run, u32 len, u32 off, u64 cap, u64 n_lit, u32 window,
                                            bool *with_literals) {
     *with_literals = false;
     if (lp > n_lit || run > n_lit - lp) return SCL_ST_TRUNCATED;
     if (d > cap || run > cap - d) return SCL_ST_CAPACITY;
     *with_literals = true;
     d += run;
-    if (off == 0 || off > d) return SCL_ST_STATE;
+    if (WINDOWED && len == 0) return 0;
+    if (off == 0 || off > d || (WINDOWED && window && off > window)) return SCL_ST_STATE;
     if (len > cap - d) return SCL_ST_CAPACITY;
     return 0;
 }
 
+template <bool WINDOWED>
 __global__ __launch_bounds__(256) void lz77w_replay_validate(const u32 *lit_count, const u32 *match_len,
                                                              const u32 *match_off, u64 n_seq, const u64 *lit_sum,
                                                              const u64 *all_sum, u64 have, u64 cap, u64 n_lit,
-                                                             ReplayMeta *meta) {
+                                                             u32 window, ReplayMeta *meta) {
     const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_seq) return;
     bool with_literals;
-    if (lz77w_check(have + all_sum[k], lit_sum[k], lit_count[k], match_len[k], match_off[k], cap, n_lit, &with_literals))
+    if (lz77w_check<WINDOWED>(have + all_sum[k], lit_sum[k], lit_count[k], match_len[k], match_off[k], cap, n_lit, window,
+                              &with_literals))
         atomicMin(&meta->first, (u32)k);
 }
 
 // one thread: what the stream produces up to its first fault -> meta->out_end, out_len, status
+template <bool WINDOWED>
 __global__ void lz77w_replay_plan(const u32 *lit_count, const u32 *match_len, const u32 *match_off, u64 n_seq,
-                                  const u64 *lit_sum, const u64 *all_sum, u64 have, u64 cap, u64 n_lit, ReplayMeta *meta,
-                                  u32 *out_len, u32 *status_out) {
+                                  const u64 *lit_sum, const u64 *all_sum, u64 have, u64 cap, u64 n_lit, u32 window,
+                                  ReplayMeta *meta, u32 *out_len, u32 *status_out) {
     const u64 f = meta->first;
     const u64 d = have + all_sum[f], lp = lit_sum[f];
     u64 end = d;
     u32 status = 0;
     if (f < n_seq) {
         bool with_literals;
-        status = lz77w_check(d, lp, lit_count[f], match_len[f], match_off[f], cap, n_lit, &with_literals);
+        status = lz77w_check<WINDOWED>(d, lp, lit_count[f], match_len[f], match_off[f], cap, n_lit, window, &with_literals);
         if (with_literals) end = d + lit_count[f];
     } else {  // the literals left over
         const u64 rest = n_lit - lp;
@@ -358,6 +366,8 @@ __global__ void lz77w_replay_plan(const u32 *lit_count, const u32 *match_len, co
 
 // One thread per produced byte i: its sequence k is the last with have + all_sum[k] <= i (k = n_seq: the literals left
 // over).  A literal byte is stored and is its own root; a match byte's root is the earlier byte it copies.
+// A sequence without a match has no match byte, whatever its offset says: the remainder is taken of a validated offset
+// only (an offset of 0 on a byte that no input reaches makes the byte its own root).
 __global__ __launch_bounds__(256) void lz77w_resolve_init(u8 *out, u64 have, const u32 *lit_count, const u32 *match_off,
                                                           u64 n_seq, const u64 *lit_sum, const u64 *all_sum,
                                                           const u8 *literals, const ReplayMeta *meta, u32 *root) {
@@ -379,7 +389,7 @@ __global__ __launch_bounds__(256) void lz77w_resolve_init(u8 *out, u64 have, con
         root[at] = (u32)i;
     } else {
         const u64 m = d + run, off = match_off[lo];
-        root[at] = (u32)(m - off + (i - m) % off);
+        root[at] = off ? (u32)(m - off + (i - m) % off) : (u32)i;
     }
 }
 
@@ -521,8 +531,10 @@ extern "C" int scl_lz77_parse_wide(const scl_lz77_wide_parse_args *a, void *stre
     return SCL_OK;
 }
 
-extern "C" int scl_lz77_replay_wide(const scl_lz77_wide_replay_args *a, void *stream) {
-    const char *what = "lz77_replay_wide";
+// Both *_replay_wide entry points: A is scl_lz77_wide_replay_args or scl_lz77_sliding_wide_replay_args (the same fields,
+// the second with a window_size behind them), WINDOWED and `window` the sliding-window coder's two rules.
+template <bool WINDOWED, class A>
+static int replay_wide_run(const char *what, const A *a, u32 window, void *stream) {
     SCL_REQUIRE(a, "%s: null pointer argument", what);
     SCL_REQUIRE(a->d_out_len && a->d_status && a->d_scratch && (a->cap == 0 || a->d_win) &&
                     (a->n_lit == 0 || a->d_literals) &&
@@ -546,10 +558,10 @@ extern "C" int scl_lz77_replay_wide(const scl_lz77_wide_replay_args *a, void *st
     lz77_scan_exclusive(lit_sum, n_seq + 1, sums, st);
     lz77_scan_exclusive(all_sum, n_seq + 1, sums, st);
     if (n_seq)
-        hipLaunchKernelGGL(lz77w_replay_validate, dim3((u32)((n_seq + 255) / 256)), dim3(256), 0, st, a->d_lit_count,
-                           a->d_match_len, a->d_match_off, n_seq, lit_sum, all_sum, a->have, a->cap, a->n_lit, meta);
-    hipLaunchKernelGGL(lz77w_replay_plan, dim3(1), dim3(1), 0, st, a->d_lit_count, a->d_match_len, a->d_match_off, n_seq,
-                       lit_sum, all_sum, a->have, a->cap, a->n_lit, meta, a->d_out_len, a->d_status);
+        hipLaunchKernelGGL(lz77w_replay_validate<WINDOWED>, dim3((u32)((n_seq + 255) / 256)), dim3(256), 0, st, a->d_lit_count,
+                           a->d_match_len, a->d_match_off, n_seq, lit_sum, all_sum, a->have, a->cap, a->n_lit, window, meta);
+    hipLaunchKernelGGL(lz77w_replay_plan<WINDOWED>, dim3(1), dim3(1), 0, st, a->d_lit_count, a->d_match_len, a->d_match_off,
+                       n_seq, lit_sum, all_sum, a->have, a->cap, a->n_lit, window, meta, a->d_out_len, a->d_status);
     if (grow) {
         const u32 blocks = (u32)((grow + 255) / 256);
         hipLaunchKernelGGL(lz77w_resolve_init, dim3(blocks), dim3(256), 0, st, a->d_win, a->have, a->d_lit_count,
@@ -561,4 +573,13 @@ extern "C" int scl_lz77_replay_wide(const scl_lz77_wide_replay_args *a, void *st
     }
     SCL_HIP_TRY(hipGetLastError());
     return SCL_OK;
+}
+
+extern "C" int scl_lz77_replay_wide(const scl_lz77_wide_replay_args *a, void *stream) {
+    return replay_wide_run<false>("lz77_replay_wide", a, 0u, stream);
+}
+
+// the sliding-window coder's replay of one stream (scl_lz77_sliding_wide.hip has its parse): these kernels, WINDOWED
+extern "C" int scl_lz77_sliding_replay_wide(const scl_lz77_sliding_wide_replay_args *a, void *stream) {
+    return replay_wide_run<true>("lz77_sliding_replay_wide", a, a ? a->window_size : 0u, stream);
 }
