@@ -26,6 +26,69 @@
 #include "scl_ans_fast_io.h"
 
 #ifdef __HIPCC__
+// ---- issue priority of the waves of a SIMD (profiles/wave_progress_timing.txt) -------------------------
+// The headline batch puts four waves with the same work on every SIMD.  VALU issue between them goes by priority, then by
+// age: at equal priority the oldest wave wins every contested slot, runs ahead and leaves; the SIMD then ends the kernel
+// with three, two and one wave, which cannot cover the state chain's latency (measured: the oldest wave of a SIMD lived 0.59
+// of the SIMD's span in the striped encoder, 0.69 in the 1024-lane decoder).  The line loops of those two kernels therefore
+// set the priority anew for every 128-symbol line:
+//   priority = (slot + lines still to go) & 3,  slot = HW_ID.wave_id, the wave's place on its SIMD -- not threadIdx: a
+//   workgroup's waves start at a varying SIMD, and the striped encoder's four waves of a SIMD belong to four workgroups.
+// Every wave is the winner a quarter of the time, and the count FALLS with progress: a wave that gets a line ahead of the
+// others drops a step (three times out of four) and is caught up with.  Counting upwards measured 1.2 % slower in the
+// encoder: there a wave that is ahead rises, ties with its neighbour and wins the tie by age.
+//   SCL_WAVE_PRIO_ENC / _DEC = 1 that rotation (the default), 0 nothing (device code as before the rotation existed: the
+//   "before" build of tools/wave_lifetimes.py), 2 priority 3 - slot set once (the other candidate of the timing note: it
+//   hands the oldest wave what it takes anyway and changes nothing).
+// Priority only steers the scheduler: behind the table-staging barrier neither kernel has a cross-wave dependency.
+#ifndef SCL_WAVE_PRIO_ENC
+#define SCL_WAVE_PRIO_ENC 1
+#endif
+#ifndef SCL_WAVE_PRIO_DEC
+#define SCL_WAVE_PRIO_DEC 1
+#endif
+__device__ __forceinline__ u32 scl_wave_slot() { return __builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 3u; }  // HW_ID[3:0]
+// p: the same in every active lane.  s_setprio takes an immediate and ignores EXEC, so the branches must be scalar ones.
+__device__ __forceinline__ void scl_wave_prio(u32 p) {
+    const u32 u = (u32)__builtin_amdgcn_readfirstlane((int)p) & 3u;
+    if (u == 0) __builtin_amdgcn_s_setprio(0);
+    else if (u == 1) __builtin_amdgcn_s_setprio(1);
+    else if (u == 2) __builtin_amdgcn_s_setprio(2);
+    else __builtin_amdgcn_s_setprio(3);
+}
+template <int MODE>
+__device__ __forceinline__ u32 scl_wave_prio_enter() {  // once, behind the table staging; returns the rank for the line loop
+    if constexpr (MODE == 0) return 0u;
+    const u32 r = scl_wave_slot();
+    if constexpr (MODE == 2) scl_wave_prio(3u - r);
+    return r;
+}
+template <int MODE>
+__device__ __forceinline__ void scl_wave_prio_line(u32 rank, u32 lines_left) {  // at the top of every line
+    if constexpr (MODE == 1) scl_wave_prio(rank + lines_left);
+}
+
+#ifdef SCL_WAVE_TRACE
+// tools/wave_lifetimes.py only: lane 0 of every wave records where it ran and when its main work began and ended.  The tool
+// sets the two symbols (scl_wave_trace_set, scl_rans_fast.hip); without the macro nothing of this exists.
+static __device__ unsigned long long *scl_wave_trace_buf;
+static __device__ unsigned scl_wave_trace_cap;  // waves the buffer has room for
+__device__ __forceinline__ u64 scl_wave_trace_now() { return __builtin_amdgcn_s_memtime(); }
+__device__ __forceinline__ void scl_wave_trace_put(u64 t0) {
+    const u64 t1 = __builtin_amdgcn_s_memtime();
+    const u32 hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));   // HW_ID
+    const u32 xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));  // XCC_ID[3:0]
+    const u32 w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if ((threadIdx.x & 63u) == 0 && scl_wave_trace_buf && w < scl_wave_trace_cap) {
+        unsigned long long *p = scl_wave_trace_buf + 4ull * w;
+        p[0] = hw | ((u64)xcc << 32);
+        p[1] = t0;
+        p[2] = t1;
+        p[3] = 1ull + w;
+    }
+}
+#endif
+
 // True: the header does not fit in the chunk's `avail` bits; the chunk's three results are written and the lane is done.
 // (Its own function, `if (ans_decode_refuse(..)) return;` in the kernel: as the false branch of a bool ans_decode_open the
 // exit cost every decoder registers -- profiles/ans_frame_codegen.txt.)
@@ -59,9 +122,11 @@ __device__ __forceinline__ void ans_decode_open(const DEV &P, DecIn &r, char *ld
 }
 
 // (the step comes by value: by reference every decoder of scl_rans_fast.hip drifted further from its own loops)
-template <class STEP, class DecIn>
+// PRIO: the wave-priority mode of the line loop (scl_wave_prio_*, above); 0 for every decoder but the 1024-lane rANS / tANS one.
+template <int PRIO = 0, class STEP, class DecIn>
 __device__ __forceinline__ void ans_decode_rows(const STEP s, u32 &x, DecIn &r, char *lds, u32 n, u8 *out_sym, u64 c,
                                                 u64 out_stride) {
+    [[maybe_unused]] const u32 rank = scl_wave_prio_enter<PRIO>();
     u8 *dst = out_sym + c * out_stride;
     // symbols come out last-first (rANS.py:291): the ragged head of the last 16-byte block ...
     u32 i = n;
@@ -81,6 +146,7 @@ __device__ __forceinline__ void ans_decode_rows(const STEP s, u32 &x, DecIn &r, 
     cs.init(out_sym, c, out_stride, i);
 #pragma nounroll
     while (i) {
+        scl_wave_prio_line<PRIO>(rank, i >> 7);  // (the first active lane's count)
         uint4 a[8];
 #pragma unroll
         for (int b = 7; b >= 0; --b)

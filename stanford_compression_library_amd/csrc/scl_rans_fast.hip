@@ -205,6 +205,12 @@ __global__ void __launch_bounds__(RF_THREADS, (EncOut::STRIPED && CHECK_SYM) ? 3
     static_assert(RF_RING_OFF == 256 * sizeof(uint4), "the rings start right behind the symbol table");
     reinterpret_cast<uint4 *>(s_lds)[threadIdx.x & 255] = P.d_enc_tab[threadIdx.x & 255];
     __syncthreads();
+#ifdef SCL_WAVE_TRACE
+    const u64 trace_t0 = scl_wave_trace_now();
+#endif
+    // four workgroups per CU put four waves on every SIMD: only the striped writer's kernels steer their issue priority
+    constexpr int PRIO = EncOut::STRIPED ? SCL_WAVE_PRIO_ENC : 0;
+    [[maybe_unused]] const u32 rank = scl_wave_prio_enter<PRIO>();
     const u64 c = (u64)blockIdx.x * RF_THREADS + threadIdx.x;
     if (c >= n_chunks) return;
     const u32 n = lens ? lens[c] : chunk_len;
@@ -263,6 +269,7 @@ __global__ void __launch_bounds__(RF_THREADS, (EncOut::STRIPED && CHECK_SYM) ? 3
     u32 t = 0;
 #pragma nounroll
     for (; t < n_lines; ++t) {
+        scl_wave_prio_line<PRIO>(rank, n_lines - t);
         RF_LOAD_LINE(nxt, t + 1);
         RF_ENCODE_LINE(cur)
         cur = nxt;
@@ -294,6 +301,9 @@ __global__ void __launch_bounds__(RF_THREADS, (EncOut::STRIPED && CHECK_SYM) ? 3
     if (P.size_bits < 32 && (n >> P.size_bits)) st |= SCL_ST_SIZE;
     o.template put32<RF_RING_OFF>(lds, n, P.size_bits);
     ans_encode_results(o.finish(lds, wg_out), st, c, out_stride, out_bit_off, out_nbits, status);
+#ifdef SCL_WAVE_TRACE
+    scl_wave_trace_put(trace_t0);
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -474,6 +484,9 @@ __global__ void __launch_bounds__(THREADS) rans_decode_fast_kernel(RansFastDev P
         reinterpret_cast<uint2 *>(s_lds)[i] = v;
     }
     __syncthreads();
+#ifdef SCL_WAVE_TRACE
+    const u64 trace_t0 = scl_wave_trace_now();
+#endif
     const u64 c = (u64)blockIdx.x * THREADS + threadIdx.x;
     if (c >= n_chunks) return;
     const u32 avail = in_nbits[c];
@@ -488,9 +501,22 @@ __global__ void __launch_bounds__(THREADS) rans_decode_fast_kernel(RansFastDev P
     rf_gen.m = NB_T != 1 ? P.dec_sadd : P.M;   // NUM_BITS_OUT > 1: b - 1 - cbl and ~(b - 1), see rf_decode_symbol
     rf_gen.l = NB_T != 1 ? P.dec_notb : P.L;
     const Step step = {tab, P.m_log2, (ML_T == 0 && CB_T == 3) ? 3u - (32 - P.nsb) : 32 - P.nsb, rf_gen};
-    ans_decode_rows(step, x, r, lds, n, out_sym, c, out_stride);
+    // one workgroup of 1024 lanes per CU is four waves per SIMD: only that form steers its waves' issue priority
+    ans_decode_rows<THREADS == ANS_THREADS_WIDE ? SCL_WAVE_PRIO_DEC : 0>(step, x, r, lds, n, out_sym, c, out_stride);
     ans_decode_close(r.consumed(), avail, st, x >> Step::XSH, P.L, c, consumed, status);
+#ifdef SCL_WAVE_TRACE
+    scl_wave_trace_put(trace_t0);
+#endif
 }
+
+#ifdef SCL_WAVE_TRACE
+// tools/wave_lifetimes.py: where the next launches of this file's kernels record their waves (null: nowhere)
+extern "C" int scl_wave_trace_set(void *buf, unsigned cap_waves) {
+    unsigned long long *p = static_cast<unsigned long long *>(buf);
+    if (hipMemcpyToSymbol(HIP_SYMBOL(scl_wave_trace_cap), &cap_waves, sizeof cap_waves) != hipSuccess) return SCL_E_HIP;
+    return hipMemcpyToSymbol(HIP_SYMBOL(scl_wave_trace_buf), &p, sizeof p) == hipSuccess ? SCL_OK : SCL_E_HIP;
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------------
 // host side
